@@ -13,16 +13,22 @@ more GPUs than the box has, or a WORLD_SIZE that differs from --gpus, ends with 
 line -- never an N = 1 line for an N > 1 request.
 
 Prints ONE JSON line (rank 0).  `roofline` is for the count kernel: algorithmic bytes = (L + 8) / L per base
- over the HIP-event launch time; `cpu_baseline` is the reference's CPU path timed on a bounded sample of
-the same reads.  At N = 1 the line also carries `other_configs`: BASELINE.json configs[2] (long reads, with and
-without -m 10), configs[4] (1 M sites), the host-fed path on its PCIe roofline (`feed`) and the file -> counts.txt path through build/ntsmCount, each with its own
-correctness check; `n10_full` is the same measurement at the upper bound of the real sites file's size
-(2.5 M site k-mers).
+ over the HIP-event launch time of the timed steps.
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints the line; nothing
+else.  `--dump-outputs DIR` then writes what the timed path computed (see dump_outputs).  `--full` adds everything else
+the line used to carry: the full-size check of the timed counts against the generic kernel (and, at N > 1, the proof of
+the merge), `cpu_baseline` (the reference's CPU path timed on a bounded sample of the same reads) and, at N = 1,
+`other_configs`: BASELINE.json configs[2] (long reads, with and without -m 10), configs[4] (1 M sites), the host-fed path
+on its PCIe roofline (`feed`) and the file -> counts.txt path through build/ntsmCount, each with its own correctness check
+(DESIGN.md section 7); `n10_full` is the same measurement at the upper bound of the real sites file's size (2.5 M site
+k-mers).
 """
 import argparse
 import hashlib
 import json
 import os
+import shutil
 import socket
 import subprocess
 import sys
@@ -67,7 +73,15 @@ def parse_args(argv=None):
     ap.add_argument("--e2e-qual-model", type=int, default=1, help="quality lines of the CLI legs' FASTQ: 1 Illumina-like 8-level binned, 0 constant 'I' (rounds 1-4)")
     ap.add_argument("--dry-launch", action="store_true",
                     help="launch test: every rank prints its rank environment as one JSON line and exits before touching the GPU")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks and secondary measurements (generic-kernel check, merge proof, CPU baseline, "
+                         "other configs); a plain run only times the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed as DIR/<name>.npy (rank 0)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # -----------------------------------------------------------------------------------------------------------------
@@ -671,6 +685,20 @@ def config_feed(local, args):
     return out
 
 
+def dump_outputs(out_dir, counts, totals, reps):
+    """--dump-outputs: what one step of the timed path computed, as a caller of the count path receives it --
+      counts.npy  per-k-mer counts in the order of the site keys (ntsm_counts), float64
+      totals.npy  [total_kmers, total_hits, total_bases, reads_consumed] (ntsm_sync), float64
+    The timed context accumulates over its warm-up and timed steps, all of them the same pass over the same resident reads, so
+    one step's result is what it holds divided by their number (exact: the quotients are integers, far below 2^53).  At N > 1
+    it is the merged, job-wide view.  About 12 MB for the default site set; the inputs are seeded, so equal arguments give equal
+    inputs from run to run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "counts.npy"), np.asarray(counts, dtype=np.uint64).astype(np.float64) / reps)
+    np.save(os.path.join(out_dir, "totals.npy"), np.array(totals, dtype=np.float64) / reps)
+
+
 def run_rank(args):
     rank = int(os.environ.get("RANK", 0))
     world = int(os.environ.get("WORLD_SIZE", 1))
@@ -748,7 +776,7 @@ def run_rank(args):
     gloo = None
     if use_dist:
         gloo = dist.new_group(backend="gloo")
-    if not args.no_check:
+    if args.full and not args.no_check:
         ref = ntsm_amd.Context(sites.keys, k=K, device=local)
         if args.kernel != 1:
             ref.set_kernel(1)
@@ -792,11 +820,17 @@ def run_rank(args):
             merged_checked = check_merged(rank, world, reps, (merged_totals.total_kmers, merged_totals.total_hits, merged_totals.total_bases, merged_totals.reads_consumed),
                                           merged_counts, expect_job, n_reads, bases_per_step)
         ctx.set_max_hits(0, armed=False)                   # drop the merged view: this context's own counts again
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, merged_counts, (merged_totals.total_kmers, merged_totals.total_hits,
+                                                            merged_totals.total_bases, merged_totals.reads_consumed), reps)
     totals = ctx.sync()
+    own_counts = ctx.counts() if expect is not None or (args.dump_outputs and not use_dist) else None
+    if args.dump_outputs and not use_dist:
+        dump_outputs(args.dump_outputs, own_counts, (totals.total_kmers, totals.total_hits, totals.total_bases, totals.reads_consumed), reps)
     if expect is not None:
         assert (totals.total_kmers, totals.total_hits) == (reps * expect[0], reps * expect[1]), \
             "timed launches disagree with the generic kernel's sum over < 2 GiB pieces: %r vs %d x %r" % ((totals.total_kmers, totals.total_hits), reps, expect[:2])
-        assert (ctx.counts() == expect[2] * np.uint64(reps)).all(), "per-k-mer counts of the timed launches differ from the generic kernel's sum over pieces"
+        assert (own_counts == expect[2] * np.uint64(reps)).all(), "per-k-mer counts of the timed launches differ from the generic kernel's sum over pieces"
         checked = True
 
     per_rank = None
@@ -881,7 +915,7 @@ def run_rank(args):
                                  "import_ms_per_step": max(r["import_ms_per_step"] for r in per_rank),
                                  "check_route": "gloo (host TCP) all_reduce of the generic kernel's per-rank vectors + all_gather_object of totals / SHA-256"}
             out["per_rank"] = per_rank
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cb = cpu_baseline(synth, sites_path, args.cpu_sample_reads)
             main_kind = "reference" if "reference" in cb else ("port" if "port" in cb else None)
             if main_kind:
@@ -896,7 +930,7 @@ def run_rank(args):
                     mt = cpu_baseline(synth, sites_path, max(1, args.cpu_sample_reads // n_thr), n_thr).get("reference")
                     if mt:
                         out["cpu_baseline_threads"] = mt
-        which = [w for w in args.other_configs.split(",") if w and w != "none"] if world == 1 and not use_dist else []
+        which = [w for w in args.other_configs.split(",") if w and w != "none"] if args.full and world == 1 and not use_dist else []
         if which:
             other = {}
             single = None
@@ -938,6 +972,7 @@ def run_rank(args):
         print(json.dumps(out), flush=True)
     if use_dist:
         dist.destroy_process_group()
+    shutil.rmtree(tmp, ignore_errors=True)
     return 0
 
 

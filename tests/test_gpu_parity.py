@@ -805,7 +805,7 @@ def test_bench_two_ranks_over_rccl(nt):
     the merged totals of both shards."""
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--reads", "2e6", "--no-cpu-baseline", "--other-configs", "none"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600,
+                        "--reads", "2e6", "--full", "--no-cpu-baseline", "--other-configs", "none"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600,
                        env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads([l for l in p.stdout.decode().split("\n") if l.startswith("{")][-1])
@@ -840,7 +840,7 @@ def test_bench_gpus_flag_launches_or_refuses(nt):
     itself.  On a box with fewer than N devices it must end non-zero with a message and NO JSON line -- never an N = 1 result
     under an N > 1 request; where N devices exist the self-launched job must report n_gpus = N."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--reads", "2e6",
-           "--no-cpu-baseline", "--other-configs", "none"]
+           "--full", "--no-cpu-baseline", "--other-configs", "none"]
     p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     out = [l for l in p.stdout.decode().split("\n") if l.startswith("{")]
     if _n_gpus() < 2:
@@ -862,11 +862,11 @@ def test_bench_rccl_path_on_one_rank(nt):
     the barriers and the MAX over ranks.  Merging a vector with itself over one rank must leave the totals of a plain run."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", NTSM_FORCE_DIST="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", "29541",
-           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--reads", "2e6", "--no-cpu-baseline", "--other-configs", "none"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--reads", "2e6", "--full", "--no-cpu-baseline", "--other-configs", "none"]
     p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, env=env)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     d = json.loads([l for l in p.stdout.decode().split("\n") if l.startswith("{")][-1])
-    q = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--reads", "2e6", "--no-cpu-baseline", "--other-configs", "none"],
+    q = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--reads", "2e6", "--full", "--no-cpu-baseline", "--other-configs", "none"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert q.returncode == 0, q.stderr.decode()[-2000:]
     e = json.loads([l for l in q.stdout.decode().split("\n") if l.startswith("{")][-1])
@@ -1871,10 +1871,10 @@ def test_randomised_cli_soak(nt):
 
 
 def test_bench_contract_line(nt):
-    """bench.py at a small size: exactly one JSON line with the contract's keys (metric/value/unit/..., roofline,
+    """bench.py --full at a small size: exactly one JSON line with the contract's keys (metric/value/unit/..., roofline,
     cpu_baseline from the CPU reference or its port), and the per-step totals it reports are the oracle-checked ones
     scaled: value = bases / time, frac = achieved / peak."""
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--reads", "2e6", "--steps", "2", "--warmup", "1", "--cpu-sample-reads", "20000",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--reads", "2e6", "--steps", "2", "--warmup", "1", "--cpu-sample-reads", "20000",
                         "--long-reads", "2e4", "--stress-sites", "2e4", "--stress-reads", "1e6", "--n10-full-sites", "2e4", "--n10-full-reads", "1e6",
                         "--e2e-reads", "2e5", "--e2e-gz-single-reads", "5e4", "--e2e-threads", "4", "--feed-reads", "2e6"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE)
@@ -1929,6 +1929,45 @@ def test_bench_contract_line(nt):
     assert o["long"]["m10"]["early_stop"] in (True, False) and o["long"]["m10"]["stop_read"] <= o["long"]["reads"]
     assert o["stress"]["check"]["equals_generic_kernel_on_the_whole_stream"] and o["stress"]["gbases_per_s"] > 0
     assert o["e2e_cli"]["check"]["counts_txt_equals_resident_path"] and o["e2e_cli"]["wall_s"] > 0 and len(o["e2e_cli"]["counts_sha256"]) == 64
+
+
+def test_bench_plain_run_and_dump_outputs(nt, tmp_path):
+    """A plain bench.py run (no --full) times exactly --steps steps and prints the contract line without the secondary
+    measurements; --dump-outputs writes one step's per-k-mer counts and totals, equal to what the generic kernel counts on the
+    same seeded reads."""
+    import torch
+    out_dir = str(tmp_path / "out")
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--reads", "2e6", "--steps", "3", "--warmup", "2",
+                        "--dump-outputs", out_dir], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert p.returncode == 0, p.stderr.decode()[-1500:]
+    lines = [l for l in p.stdout.decode().split("\n") if l.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["unit"] == "bases/s" and d["higher_is_better"] is True and d["dtype"] == "u64" and d["steps"] == 3 and d["warmup"] == 2
+    assert d["roofline"]["launches"] == 3 and abs(d["value"] - 2e6 * 150 * 3 / (d["ms_per_step"] * 3e-3)) / d["value"] < 1e-6
+    assert "cpu_baseline" not in d and "other_configs" not in d and d["check"]["equals_generic_kernel_sum_of_pieces_below_2GiB"] is False
+    counts, totals = np.load(os.path.join(out_dir, "counts.npy")), np.load(os.path.join(out_dir, "totals.npy"))
+    assert counts.dtype == np.float64 and totals.dtype == np.float64 and counts.nbytes + totals.nbytes < 64 << 20
+    sys.path.insert(0, ROOT)
+    import bench
+    sp = str(tmp_path / "sites.fa")
+    s = nt.SynthShort(bench.SITES_SEED, bench.N_SITES, k=bench.K, read_seed=bench.READ_SEED, read_len=bench.READ_LEN, sites_path=sp)
+    sites = nt.Sites(sp, k=bench.K)
+    n = 2_000_000
+    d_win = torch.from_numpy(s.windows).cuda()
+    d_bases = torch.empty(n * s.stride, dtype=torch.uint8, device="cuda")
+    s.device_fill(d_win.data_ptr(), 0, n, d_bases.data_ptr())
+    torch.cuda.synchronize()
+    ref = nt.Context(sites.keys, k=bench.K)
+    ref.set_kernel(1)
+    ref.count_resident(d_bases.data_ptr(), d_bases.numel(), 0, n)
+    t = ref.sync()
+    exp = ref.counts()
+    ref.close()
+    assert counts.shape == exp.shape and np.array_equal(counts, exp.astype(np.float64))
+    assert list(totals[:2]) == [t.total_kmers, t.total_hits] and totals[0] == d["check"]["total_kmers_per_step"] and totals[1] > 0
 
 
 def test_counts_at_and_beyond_2_32_print_like_the_reference(nt):

@@ -10,6 +10,6 @@ python3 tools/ablate.py grid $R
 NTSM_HIP_LIB=libntsm_hip_abl.so python3 tools/ablate.py switches $R
 for lib in ntsm_amd/libntsm_hip.so build/lib/libntsm_hip*.so; do
   case $lib in *abl*) chk=--no-check;; *) chk=;; esac
-  NTSM_HIP_LIB=$(basename $lib) timeout 600 python3 bench.py --no-cpu-baseline $chk --other-configs none --reads 3e8 2>/dev/null |
+  NTSM_HIP_LIB=$(basename $lib) timeout 600 python3 bench.py --full --no-cpu-baseline $chk --other-configs none --reads 3e8 2>/dev/null |
     python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('$lib', round(d['value']/1e9,1), 'Gbases/s', round(d['ms_per_step'],2), 'ms', d['check'].get('equals_generic_kernel_sum_of_pieces_below_2GiB'))"
 done

@@ -67,10 +67,11 @@ xlib:
 	$(call hiplib,build/lib/libntsm_hip_$(XNAME).so,$(XFLAGS),build/obj_$(XNAME))
 
 # ntsmEval all-pairs scoring: own library, own CLI
-ntsm_amd/libntsm_eval_hip.so: $(CSRC)/ntsm_eval.hip include/ntsm_eval_hip.h
-	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -shared -o $@ $(CSRC)/ntsm_eval.hip
+# + the PCA-guided pair search (-p / -n): ntsm_eval_pca.hip with the x87 add of xprec.h
+ntsm_amd/libntsm_eval_hip.so: $(CSRC)/ntsm_eval.hip $(CSRC)/ntsm_eval_pca.hip $(CSRC)/xprec.h include/ntsm_eval_hip.h
+	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -shared -o $@ $(CSRC)/ntsm_eval.hip $(CSRC)/ntsm_eval_pca.hip
 
-build/ntsmEval: $(HOST)/ntsm_eval_main.cpp include/ntsm_eval_hip.h ntsm_amd/libntsm_eval_hip.so
+build/ntsmEval: $(HOST)/ntsm_eval_main.cpp $(CSRC)/xprec.h include/ntsm_eval_hip.h ntsm_amd/libntsm_eval_hip.so
 	@mkdir -p build
 	$(CXX) $(CXXFLAGS) -ffp-contract=off -o $@ $(HOST)/ntsm_eval_main.cpp -Lntsm_amd -lntsm_eval_hip \
 	    -Wl,-rpath,'$$ORIGIN/../ntsm_amd' -Wl,-rpath,/opt/rocm/lib

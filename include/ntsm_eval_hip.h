@@ -39,6 +39,53 @@ static inline uint64_t ntsm_eval_pair_index(uint32_t i, uint32_t j, uint32_t n)
 int ntsm_eval_pairs(int device, const uint32_t *counts, uint32_t n_samples, uint32_t n_sites, uint32_t min_cov,
 		ntsm_eval_record *out, double *kernel_ms);
 
+/* ---- PCA-guided pair search (the reference's -p / -n mode: CompareCounts::projectPCs, :116-211, and computeScorePCA,
+ * :285-398), in ntsm_amd/csrc/ntsm_eval_pca.hip.  A session holds one run's counts on the device; the caller loads the
+ * files, forms the summaries and radii and prints (ntsm_amd/csrc/host/ntsm_eval_main.cpp).
+ *
+ * ntsm_eval_project: m_cloud[i][d] = inner_product(vals_i, rot[d], 0.0) (:166-211), bit for bit: per site
+ *   cAT = countAT > min_cov ? countAT : 0 (cCG alike); a site with cAT + cCG == 0 gives v = +0.0 (not centred), else
+ *   g = double(cAT) / double(cAT + cCG), c = g < 0.25 ? 0 : g < 0.75 ? 0.5 : 1, v = double(c - norm[j]) (x87 subtraction);
+ *   each step acc = RN53(RN64(acc + RN64(v * rot[d][j]))), sites in order from +0.0 (x87 products and sums, a double
+ *   accumulator).  The library's host code forms the products with real long double (a [site][dim][4] table: c = 0, 1/2,
+ *   1 and the missing site's +0.0 * rot) and the device runs the sequential x87 add in integers (ntsm_amd/csrc/xprec.h),
+ *   one lane per (sample, component).
+ *
+ * ntsm_eval_candidates: the pairs that computeScorePCA scores (:311-398), in its one-thread print order.  Rows i
+ * ascending; a row with radius[i] < DBL_MAX takes every k with evalMetric(cloud[i], cloud[k]) < radius[i] (nanoflann's
+ * L2_Adaptor, vendor/nanoflann.hpp:452-486: groups of four as result += ((d0^2 + d1^2) + d2^2) + d3^2, then the last 0-3
+ * terms one by one; RadiusResultSet keeps dist < radius, :305-307), skips k when radius[k] == radius[i] and k <= i, or
+ * when radius[i] < radius[k], and orders the row by ascending evalMetric (the reference sorts the matches); a row with
+ * radius DBL_MAX ("search all") takes every k ascending except k <= i of radius DBL_MAX.  dist[p] is calcDistance (:926-932,
+ * a sequential sum of squared differences: a different rounding order from evalMetric).  The search is brute force over
+ * all N^2 pairs in IEEE double without contraction.  Two deviations from the kd-tree, both intended: (1) ties in evalMetric
+ * are ordered by ascending k (the reference's order among exact ties is that of its kd-tree leaves); (2) nanoflann prunes
+ * nodes with an incrementally rounded bound, which could in principle drop a point one ulp inside the radius; brute force
+ * keeps it.
+ *
+ * ntsm_eval_score_pairs: for each (pi[p], pk[p]), any order (pi > pk included), the record ntsm_eval_pairs gives for that
+ * pair with sample pi[p] as sample 1, i.e. bit-identical to ntsm_eval_pairs' record of (min, max) with the 1 / 2 fields
+ * swapped when pi[p] > pk[p].  Device memory is O(samples * sites + pairs), never O(samples^2). */
+typedef struct ntsm_eval_session ntsm_eval_session;
+
+#define NTSM_EVAL_E_CAPACITY (-3)   /* ntsm_eval_candidates: the caller's buffers are too small; *n_pairs = the size needed */
+
+/* counts: host [n_samples][n_sites][2] (as for ntsm_eval_pairs), uploaded once.  Returns 0, -1 bad argument, -2 HIP error. */
+int ntsm_eval_open(int device, const uint32_t *counts, uint32_t n_samples, uint32_t n_sites, uint32_t min_cov, ntsm_eval_session **h);
+void ntsm_eval_close(ntsm_eval_session *h);
+/* norm: [n_sites], rot: [dim][n_sites] (the first dim components), cloud: out [n_samples][dim].  kernel_ms (may be NULL):
+ * HIP-event time of the projection kernel.  Returns 0, -1, -2. */
+int ntsm_eval_project(ntsm_eval_session *h, const long double *norm, const long double *rot, uint32_t dim, double *cloud,
+		double *kernel_ms);
+/* cloud: [n_samples][dim], radius: [n_samples] (squared radii, DBL_MAX = search all).  Writes up to capacity pairs to
+ * pi / pk / dist (any may be NULL when capacity is 0) and their number to *n_pairs.  kernel_ms: the two search kernels.
+ * Returns 0, -1, -2, or NTSM_EVAL_E_CAPACITY with *n_pairs = the number of pairs (nothing written). */
+int ntsm_eval_candidates(ntsm_eval_session *h, const double *cloud, uint32_t dim, const double *radius, uint32_t *pi, uint32_t *pk,
+		double *dist, uint64_t capacity, uint64_t *n_pairs, double *kernel_ms);
+/* out: [n_pairs] records.  kernel_ms: the scoring kernel.  Returns 0, -1 (an index out of range, or pi[p] == pk[p]), -2. */
+int ntsm_eval_score_pairs(ntsm_eval_session *h, const uint32_t *pi, const uint32_t *pk, uint64_t n_pairs, ntsm_eval_record *out,
+		double *kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

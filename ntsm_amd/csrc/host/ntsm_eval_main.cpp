@@ -1,10 +1,12 @@
 /*
- * ntsm_eval_main.cpp -- host mirror of the reference's ntsmEval for its all-to-all path (src/ntSeqMatchEval.cpp:86-349,
- * src/CompareCounts.hpp): same flags, same stdout bytes; the pair loop of CompareCounts::computeScore (:591-624) is one
- * call into the HIP library (include/ntsm_eval_hip.h).  A single input file prints the QC table (computeScoreSingle,
- * :541-585) without touching the GPU; -e FILE writes the merged counts (mergeCounts, :626-674), -o skips the analysis.
- * Not built: the PCA / kd-tree search (-p, -n and its radii); asking for it is an error instead of a silent all-to-all run.  Parity with the reference is unpinned (DESIGN.md
- * section 9): the reference's scoring class cannot be compiled in this image.
+ * ntsm_eval_main.cpp -- host mirror of the reference's ntsmEval (src/ntSeqMatchEval.cpp:86-349, src/CompareCounts.hpp):
+ * same flags, same stdout bytes; the pair loop of CompareCounts::computeScore (:591-624) is one call into the HIP library
+ * (include/ntsm_eval_hip.h).  A single input file prints the QC table (computeScoreSingle, :541-585) without touching the
+ * GPU unless -p asks for its PC columns; -e FILE writes the merged counts (mergeCounts, :626-674), -o skips the analysis.
+ * -p ROT -n NORM is the PCA-guided search (projectPCs, :116-211, computeScorePCA, :285-398): projection, candidate pairs
+ * and their scoring in the library's session calls, printed in the one-thread order.  Not built: -b (the debug
+ * ground-truth mode) and -p without a normalization file (the reference dies in an assert); both are refused.  Parity with
+ * the reference is unpinned: the reference's scoring class cannot be compiled in this image.
  */
 #include <getopt.h>
 
@@ -32,8 +34,10 @@ struct Opt {                                 /* src/Options.h:44-55 */
 	unsigned minCov = 1, threads = 1;
 	uint64_t genomeSize = 6200000000ull;
 	int verbose = 0, device = 0;
-	std::string pca, merge;
+	std::string pca, merge, norm, debug;
 	bool onlyMerge = false;
+	unsigned dim = 20;                       /* src/Options.h:22, 35-39: the PCA search */
+	double pcSearchRadius1 = 2, pcSearchRadius2 = 15, pcErrorThresh = 0.01, pcMissSite1 = 0.01, pcMissSite2 = 0.3;
 };
 
 struct Counts {                              /* the members of CompareCounts the all-to-all path reads */
@@ -107,7 +111,7 @@ void load(Counts &c)
 	}
 }
 
-struct Genotype { unsigned hets = 0, homs = 0, miss = 0; double errorRate = 0, cov = 0; };
+struct Genotype { unsigned hets = 0, homs = 0, miss = 0; double errorRate = 0, cov = 0, radius = DBL_MAX; };
 
 /* calcHomHetMiss (:742-767), computeErrorRate (:1198-1216), cov (:597-598) */
 std::vector<Genotype> summaries(const Counts &c, const Opt &opt)
@@ -150,17 +154,180 @@ void printHelpDialog()
 	    "  -c, --min_cov = INT        Keep only sites with this coverage and above.[" << std::to_string(d.minCov) << "]\n"
 	    "  -g, --genome_size = INT    Diploid genome size for error rate estimation.\n"
 	    "                             [" << std::to_string(d.genomeSize) << "]\n"
-	    "  -G, --gpu = INT            HIP device [0] (this build only)\n"
-	    "  -h, --help                 Display this dialog.\n"
-	    "  -v, --verbose              Display verbose output.\n"
 	    "  -e, --merge = STR          After analysis merge counts and output to file.\n"
 	    "  -o, --only_merge           Do not perform an analysis. Only functions when\n"
 	    "                             -e (--merge) option is specified.\n"
-	    "Not in this build: -p/-n/-d/-r/-1/-2/-S/-l (PCA search).\n" << std::endl;
+	    "  -p, --pca = STR            Use PCA information to speed up analysis. Input is a\n"
+	    "                             set of rotational values from a PCA.\n"
+	    "  -d, --dim = INT            Number of dimensions to consider in PCA. [" << std::to_string(d.dim) << "]\n"
+	    "  -n, --norm = STR           Set of values use to center the data before rotation\n"
+	    "                             during PCA. [Required if -p is enabled]\n"
+	    "  -r, --error_rate = FLOAT   Error rate threshold for PCA based search [" << std::to_string(d.pcErrorThresh) << "]\n"
+	    "  -1, --miss_small = FLOAT   Missing site threshold small for PCA based search [" << std::to_string(d.pcMissSite1) << "]\n"
+	    "  -2, --miss_large = FLOAT   Missing site threshold large PCA based search [" << std::to_string(d.pcMissSite2) << "]\n"
+	    "  -S, --small = FLOAT        Search radius for small PCA based search [" << std::to_string(d.pcSearchRadius1) << "]\n"
+	    "  -l, --large = FLOAT        Search radius for large PCA based search [" << std::to_string(d.pcSearchRadius2) << "]\n"
+	    "  -G, --gpu = INT            HIP device [0] (this build only)\n"
+	    "  -h, --help                 Display this dialog.\n"
+	    "  -v, --verbose              Display verbose output.\n"
+	    "Not in this build: -b (debug mode of the PCA search).\n" << std::endl;
 	exit(EXIT_SUCCESS);
 }
 
 template <typename T> bool parse(const char *s, T &out) { std::stringstream c(s); return bool(c >> out); }
+
+/* skew (:1081-1083) and computeLogLikelihood (:1093-1099) over a pair's record: sample i is sample 1 */
+double pairScore(const ntsm_eval_record &r, const Genotype &gi, const Genotype &gj, const Opt &opt)
+{
+	double score = DBL_MAX;
+	if (r.n_valid > 0) {
+		score = -2.0 * (r.sum_joint - (r.sum_single1 + r.sum_single2));
+		score = score / std::pow(gi.cov * gj.cov, opt.covSkew);
+		score /= double(r.n_valid);
+	}
+	return score;
+}
+
+/* resultsStr (:843-905) + "\n" for pair (i, j), sample i as sample 1 */
+void appendRow(std::string &temp, const Counts &c, const std::vector<Genotype> &g, const Opt &opt, const ntsm_eval_record &r,
+		double score, const std::string &dist, uint32_t i, uint32_t j)
+{
+	const double homConcord = (double(r.shared_homs) - 2.0 * double(r.ibs0)) / double(r.homs1 < r.homs2 ? r.homs1 : r.homs2);
+	const double relate = (double(r.shared_hets) - 2.0 * double(r.ibs0)) / double(r.hets1 < r.hets2 ? r.hets1 : r.hets2);
+	temp.clear();
+	temp += c.files[i]; temp += "\t"; temp += c.files[j]; temp += "\t"; temp += std::to_string(score);
+	temp += opt.all ? (score < opt.scoreThresh ? "\t1\t" : "\t0\t") : "\t1\t";
+	temp += dist; temp += "\t"; temp += std::to_string(relate);
+	temp += "\t"; temp += std::to_string(r.ibs0); temp += "\t"; temp += std::to_string(r.ibs2);
+	temp += "\t"; temp += std::to_string(homConcord);
+	temp += "\t"; temp += std::to_string(r.hets1); temp += "\t"; temp += std::to_string(r.hets2); temp += "\t"; temp += std::to_string(r.shared_hets);
+	temp += "\t"; temp += std::to_string(r.homs1); temp += "\t"; temp += std::to_string(r.homs2); temp += "\t"; temp += std::to_string(r.shared_homs);
+	temp += "\t"; temp += std::to_string((uint64_t) r.n_valid);
+	temp += "\t"; temp += std::to_string(g[i].cov); temp += "\t"; temp += std::to_string(g[j].cov);
+	temp += "\t"; temp += std::to_string(g[i].errorRate); temp += "\t"; temp += std::to_string(g[j].errorRate);
+	temp += "\t"; temp += std::to_string(g[i].miss); temp += "\t"; temp += std::to_string(g[j].miss);
+	temp += "\t"; temp += std::to_string(g[i].homs); temp += "\t"; temp += std::to_string(g[j].homs);
+	temp += "\t"; temp += std::to_string(g[i].hets); temp += "\t"; temp += std::to_string(g[j].hets);
+	temp += "\n";
+}
+
+const char *kHeader = "sample1\tsample2\tscore\tsame\tdist\trelate\tibs0\tibs2\thomConcord\thet1\thet2\tsharedHet\thom1\thom2\tsharedHom\tn"
+                      "\tcov1\tcov2\terrorRate1\terrorRate2\tmiss1\tmiss2\tallHom1\tallHom2\tallHet1\tallHet2";
+
+/* projectPCs' input files (:120-165): norm values (one long double per line, 0 where a line does not parse) and the first
+ * opt.dim components of the rotation rows, matched to sites by position.  Stops the program where the reference asserts
+ * (dim > components, rows != norm values) and where it would read past its arrays (fewer values than sites). */
+void loadPCA(const Opt &opt, size_t nSites, std::vector<long double> &norm, std::vector<long double> &rot /*[dim][nSites]*/)
+{
+	if (opt.verbose > 0) std::cerr << "Projecting samples onto PCA" << std::endl;
+	std::vector<long double> normVals;
+	{
+		std::ifstream fh(opt.norm);
+		std::string line;
+		while (fh.is_open() && std::getline(fh, line)) {
+			std::stringstream ss(line);
+			long double value = 0;
+			ss >> value;
+			normVals.push_back(value);
+		}
+	}
+	unsigned compNum = 0;
+	std::ifstream fh(opt.pca);
+	std::string line;
+	std::getline(fh, line);
+	{
+		std::stringstream ss(line);
+		std::string val;
+		ss >> val;
+		while (ss >> val) ++compNum;
+	}
+	if (opt.verbose > 0) std::cerr << "Detected " << compNum << " components for " << normVals.size() << " sites" << std::endl;
+	if (opt.dim > compNum) {                                 /* assert(opt::dim <= compNum), :153 */
+		std::cerr << PROGRAM ": -d " << opt.dim << " exceeds the " << compNum << " components of " << opt.pca << std::endl;
+		abort();
+	}
+	std::vector<std::vector<long double>> rows;             /* [row][dim] */
+	while (std::getline(fh, line)) {
+		std::stringstream ss(line);
+		std::string rsID;
+		ss >> rsID;
+		std::vector<long double> v(opt.dim, 0.0L);
+		for (unsigned d = 0; d < opt.dim; ++d) ss >> v[d];  /* after a failed read the rest stay 0, as in the reference */
+		rows.push_back(std::move(v));
+	}
+	if (rows.size() != normVals.size()) {                   /* assert(index == normVals.size()), :165 */
+		std::cerr << PROGRAM ": " << rows.size() << " rotation rows but " << normVals.size() << " normalization values" << std::endl;
+		abort();
+	}
+	if (normVals.size() < nSites) {
+		std::cerr << "Error: " << normVals.size() << " normalization values and rotation rows for " << nSites
+		          << " sites; a PCA search with fewer values than sites is not part of this build" << std::endl;
+		exit(EXIT_FAILURE);
+	}
+	norm.assign(normVals.begin(), normVals.begin() + nSites);
+	rot.assign((size_t) opt.dim * nSites, 0.0L);
+	for (size_t j = 0; j < nSites; ++j)
+		for (unsigned d = 0; d < opt.dim; ++d) rot[(size_t) d * nSites + j] = rows[j][d];
+}
+
+int gpuFail(const char *what, int rc)
+{
+	std::cerr << PROGRAM ": " << what << " on the GPU failed (" << rc << "); there is no CPU path" << std::endl;
+	return 3;
+}
+
+/* projectPCs (:166-211) on the device: cloud [n][dim] */
+int project(const Counts &c, const Opt &opt, ntsm_eval_session *h, const std::vector<long double> &norm, const std::vector<long double> &rot,
+		std::vector<double> &cloud)
+{
+	cloud.assign(c.files.size() * (size_t) opt.dim, 0.0);
+	double ms = 0;
+	const int rc = ntsm_eval_project(h, norm.data(), rot.data(), opt.dim, cloud.data(), &ms);
+	if (rc) return gpuFail("projection", rc);
+	if (opt.verbose > 2)
+		for (const std::string &f : c.files) std::cerr << "Normalizing " << f << std::endl;
+	if (opt.verbose > 1) std::cerr << "projection kernel: " << ms << " ms" << std::endl << "Finished Normalization " << std::endl;
+	return 0;
+}
+
+/* computeScorePCA (:285-398), the one-thread order of its rows */
+int scorePCA(const Counts &c, std::vector<Genotype> &g, const Opt &opt, ntsm_eval_session *h, const std::vector<double> &cloud)
+{
+	if (opt.verbose > 1) std::cerr << "Generating kd-tree" << std::endl;
+	const size_t n = c.files.size(), m = c.nSites();
+	std::vector<double> radius(n);
+	for (size_t i = 0; i < n; ++i) {                    /* :297-305; pow(x, 2) = x * x */
+		const double propMissing = double(g[i].miss) / double(m);
+		g[i].radius = DBL_MAX;
+		if (g[i].errorRate < opt.pcErrorThresh && propMissing < opt.pcMissSite1) g[i].radius = opt.pcSearchRadius1 * opt.pcSearchRadius1;
+		else if (propMissing < opt.pcMissSite2) g[i].radius = opt.pcSearchRadius2 * opt.pcSearchRadius2;
+		radius[i] = g[i].radius;
+	}
+	if (opt.verbose > 1) std::cerr << "Starting Score Computation with PCA" << std::endl;
+	uint64_t np = 0;
+	double msSearch = 0, msScore = 0;
+	int rc = ntsm_eval_candidates(h, cloud.data(), opt.dim, radius.data(), nullptr, nullptr, nullptr, 0, &np, &msSearch);
+	if (rc && rc != NTSM_EVAL_E_CAPACITY) return gpuFail("candidate search", rc);
+	std::vector<uint32_t> pi(np), pk(np);
+	std::vector<double> dist(np);
+	if (np) {
+		rc = ntsm_eval_candidates(h, cloud.data(), opt.dim, radius.data(), pi.data(), pk.data(), dist.data(), np, &np, &msSearch);
+		if (rc) return gpuFail("candidate search", rc);
+	}
+	std::vector<ntsm_eval_record> rec(np);
+	rc = ntsm_eval_score_pairs(h, pi.data(), pk.data(), np, rec.data(), &msScore);
+	if (rc) return gpuFail("scoring", rc);
+	if (opt.verbose > 1) std::cerr << "search kernels: " << msSearch << " ms, scoring kernel: " << msScore << " ms for " << np << " pairs" << std::endl;
+	std::cout << kHeader << "\n";
+	std::string temp;
+	for (uint64_t p = 0; p < np; ++p) {
+		const double score = pairScore(rec[p], g[pi[p]], g[pk[p]], opt);
+		if (!(opt.all || score < opt.scoreThresh)) continue;
+		appendRow(temp, c, g, opt, rec[p], score, std::to_string(dist[p]), pi[p], pk[p]);
+		std::cout << temp;
+	}
+	return 0;
+}
 
 }  // namespace
 
@@ -174,6 +341,9 @@ int main(int argc, char **argv)
 		{ "genome_size", required_argument, nullptr, 'g' }, { "threads", required_argument, nullptr, 't' },
 		{ "merge", required_argument, nullptr, 'e' }, { "only_merge", required_argument, nullptr, 'o' },
 		{ "help", no_argument, nullptr, 'h' }, { "pca", required_argument, nullptr, 'p' }, { "norm", required_argument, nullptr, 'n' },
+		{ "error_rate", required_argument, nullptr, 'r' }, { "miss_small", required_argument, nullptr, '1' },
+		{ "miss_large", required_argument, nullptr, '2' }, { "small", required_argument, nullptr, 'k' },   /* 'k': as in the reference's table, no effect */
+		{ "large", required_argument, nullptr, 'l' }, { "debug", required_argument, nullptr, 'b' },
 		{ "gpu", required_argument, nullptr, 'G' }, { "verbose", no_argument, nullptr, 'v' }, { nullptr, 0, nullptr, 0 } };
 	int ch;
 	while ((ch = getopt_long(argc, argv, "t:vhs:c:m:aw:g:p:n:d:r:e:o1:2:S:l:b:G:", long_options, nullptr)) != -1) {
@@ -188,10 +358,18 @@ int main(int argc, char **argv)
 		case 'G': if (!parse(optarg, opt.device)) { std::cerr << "Error - Invalid parameter G: " << optarg << std::endl; return 0; } break;
 		case 'e': opt.merge = optarg; break;
 		case 'o': opt.onlyMerge = true; break;
-		case 'p': opt.pca = optarg; break;
+		case 'p': if (!parse(optarg, opt.pca)) { std::cerr << "Error - Invalid parameter p: " << optarg << std::endl; return 0; } break;
+		case 'n': if (!parse(optarg, opt.norm)) { std::cerr << "Error - Invalid parameter n: " << optarg << std::endl; return 0; } break;
+		case 'd': if (!parse(optarg, opt.dim)) { std::cerr << "Error - Invalid parameter d: " << optarg << std::endl; return 0; } break;
+		case 'r': if (!parse(optarg, opt.pcErrorThresh)) { std::cerr << "Error - Invalid parameter r: " << optarg << std::endl; return 0; } break;
+		case '1': if (!parse(optarg, opt.pcMissSite1)) { std::cerr << "Error - Invalid parameter 1: " << optarg << std::endl; return 0; } break;
+		case '2': if (!parse(optarg, opt.pcMissSite2)) { std::cerr << "Error - Invalid parameter 2: " << optarg << std::endl; return 0; } break;
+		case 'S': if (!parse(optarg, opt.pcSearchRadius1)) { std::cerr << "Error - Invalid parameter S: " << optarg << std::endl; return 0; } break;
+		case 'l': if (!parse(optarg, opt.pcSearchRadius2)) { std::cerr << "Error - Invalid parameter l: " << optarg << std::endl; return 0; } break;
+		case 'b': if (!parse(optarg, opt.debug)) { std::cerr << "Error - Invalid parameter b: " << optarg << std::endl; return 0; } break;
 		case 'v': opt.verbose++; break;
 		case '?': die = true; break;
-		default: break;                              /* m n d r 1 2 S l b: read by the reference, without effect on this path */
+		default: break;                              /* m: read by the reference, without effect */
 		}
 	}
 	Counts c;
@@ -202,24 +380,59 @@ int main(int argc, char **argv)
 			abort();
 		}
 	if (c.files.empty()) { std::cerr << "Error: Need Input File" << std::endl; die = true; }
-	if (!opt.pca.empty()) {
-		std::cerr << "Error: the PCA search (-p) is not part of this build" << std::endl;
-		die = true;
+	/* the PCA path runs for one file (its PC columns) and for an analysis (not -o); refusals before any GPU work */
+	const bool pcaRuns = !opt.pca.empty() && !c.files.empty() && (c.files.size() == 1 || !opt.onlyMerge);
+	if (pcaRuns && !die) {
+		if (!std::ifstream(opt.norm).good()) {           /* src/ntSeqMatchEval.cpp:335-338; the reference then dies in an assert */
+			std::cerr << "Error: Need normalization file" << std::endl;
+			std::cerr << "Error: a PCA search (-p) without a normalization file (-n) is not part of this build" << std::endl;
+			die = true;
+		} else if (!opt.debug.empty()) {
+			std::cerr << "Error: the debug mode of the PCA search (-b) is not part of this build" << std::endl;
+			die = true;
+		} else if (opt.dim == 0) {
+			std::cerr << "Error: a PCA search with -d 0 is not part of this build" << std::endl;
+			die = true;
+		}
 	}
 	if (die) { std::cerr << "Try '--help' for more information.\n"; exit(EXIT_FAILURE); }
 	const auto t0 = std::chrono::steady_clock::now();
 	if (opt.verbose > 0) std::cerr << "Reading count files" << std::endl;
 	load(c);
-	const std::vector<Genotype> g = summaries(c, opt);
+	std::vector<Genotype> g = summaries(c, opt);
+	std::vector<long double> norm, rot;
+	if (pcaRuns) loadPCA(opt, c.nSites(), norm, rot);     /* every refusal and abort of the PCA inputs comes before the GPU */
 	if (c.files.size() == 1) {                           /* computeScoreSingle, :541-585 */
 		if (opt.verbose > 1) std::cerr << "Detected only 1 file, providing only QC information." << std::endl;
-		std::cout << "sample\tcov\terrorRate\tmiss\thom\thet" << std::endl;
+		std::string head = "sample\tcov\terrorRate\tmiss\thom\thet";
+		std::vector<double> cloud;
+		if (pcaRuns) {                                   /* projectPCs + the PC columns */
+			ntsm_eval_session *h = nullptr;
+			int rc = ntsm_eval_open(opt.device, c.counts.data(), 1, (uint32_t) c.nSites(), opt.minCov, &h);
+			if (rc) return gpuFail("session", rc);
+			rc = project(c, opt, h, norm, rot, cloud);
+			ntsm_eval_close(h);
+			if (rc) return rc;
+			for (unsigned d = 1; d <= opt.dim; ++d) { head += "\tPC"; head += std::to_string(d); }
+		}
+		std::cout << head << std::endl;
 		std::cout << c.files[0] << "\t" << std::to_string(g[0].cov) << "\t" << std::to_string(g[0].errorRate) << "\t" << std::to_string(g[0].miss)
 		          << "\t" << std::to_string(g[0].homs) << "\t" << std::to_string(g[0].hets);
+		for (double v : cloud) std::cout << "\t" << std::to_string(v);
 	} else if (opt.onlyMerge) {                          /* src/ntSeqMatchEval.cpp:314-322 */
 		if (opt.verbose > 1) std::cerr << "Finished loading files. Now comparing all samples." << std::endl;
 		if (opt.merge.empty()) { std::cerr << "(-l) cannot be used without --merge (-e) option." << std::endl; exit(EXIT_FAILURE); }
 		std::cerr << " (-l) option detected. Not performing analysis, only merging." << std::endl;
+	} else if (pcaRuns) {                                /* projectPCs + computeScorePCA, src/ntSeqMatchEval.cpp:333-341 */
+		if (opt.verbose > 1) std::cerr << "Finished loading files. Now comparing all samples." << std::endl;
+		ntsm_eval_session *h = nullptr;
+		int rc = ntsm_eval_open(opt.device, c.counts.data(), (uint32_t) c.files.size(), (uint32_t) c.nSites(), opt.minCov, &h);
+		if (rc) return gpuFail("session", rc);
+		std::vector<double> cloud;
+		rc = project(c, opt, h, norm, rot, cloud);
+		if (!rc) rc = scorePCA(c, g, opt, h, cloud);
+		ntsm_eval_close(h);
+		if (rc) return rc;
 	} else {                                             /* computeScore, :591-624 */
 		if (opt.verbose > 1) std::cerr << "Finished loading files. Now comparing all samples." << std::endl;
 		std::cerr << "Performing all-to-all score computation.\nSpecify -p (--pca) to enable faster comparisons." << std::endl;
@@ -229,37 +442,15 @@ int main(int argc, char **argv)
 		const int rc = ntsm_eval_pairs(opt.device, c.counts.data(), n, (uint32_t) c.nSites(), opt.minCov, rec.data(), &ms);
 		if (rc) { std::cerr << PROGRAM ": scoring on the GPU failed (" << rc << "); there is no CPU path" << std::endl; return 3; }
 		if (opt.verbose > 1) std::cerr << "pair kernel: " << ms << " ms for " << rec.size() << " pairs" << std::endl;
-		std::cout << "sample1\tsample2\tscore\tsame\tdist\trelate\tibs0\tibs2\thomConcord\thet1\thet2\tsharedHet\thom1\thom2\tsharedHom\tn"
-		             "\tcov1\tcov2\terrorRate1\terrorRate2\tmiss1\tmiss2\tallHom1\tallHom2\tallHet1\tallHet2";
+		std::cout << kHeader;
 		std::cout << "\n";
 		std::string temp;
 		for (uint32_t i = 0; i < n; ++i)
 			for (uint32_t j = i + 1; j < n; ++j) {
 				const ntsm_eval_record &r = rec[ntsm_eval_pair_index(i, j, n)];
-				double score = DBL_MAX;
-				if (r.n_valid > 0) {
-					score = -2.0 * (r.sum_joint - (r.sum_single1 + r.sum_single2));            /* :1093-1099 */
-					score = score / std::pow(g[i].cov * g[j].cov, opt.covSkew);                 /* :1081-1083 */
-					score /= double(r.n_valid);
-				}
+				const double score = pairScore(r, g[i], g[j], opt);
 				if (!(opt.all || score < opt.scoreThresh)) continue;
-				const double homConcord = (double(r.shared_homs) - 2.0 * double(r.ibs0)) / double(r.homs1 < r.homs2 ? r.homs1 : r.homs2);
-				const double relate = (double(r.shared_hets) - 2.0 * double(r.ibs0)) / double(r.hets1 < r.hets2 ? r.hets1 : r.hets2);
-				temp.clear();                                /* resultsStr, :843-905 */
-				temp += c.files[i]; temp += "\t"; temp += c.files[j]; temp += "\t"; temp += std::to_string(score);
-				temp += opt.all ? (score < opt.scoreThresh ? "\t1\t" : "\t0\t") : "\t1\t";
-				temp += "-1"; temp += "\t"; temp += std::to_string(relate);
-				temp += "\t"; temp += std::to_string(r.ibs0); temp += "\t"; temp += std::to_string(r.ibs2);
-				temp += "\t"; temp += std::to_string(homConcord);
-				temp += "\t"; temp += std::to_string(r.hets1); temp += "\t"; temp += std::to_string(r.hets2); temp += "\t"; temp += std::to_string(r.shared_hets);
-				temp += "\t"; temp += std::to_string(r.homs1); temp += "\t"; temp += std::to_string(r.homs2); temp += "\t"; temp += std::to_string(r.shared_homs);
-				temp += "\t"; temp += std::to_string((uint64_t) r.n_valid);
-				temp += "\t"; temp += std::to_string(g[i].cov); temp += "\t"; temp += std::to_string(g[j].cov);
-				temp += "\t"; temp += std::to_string(g[i].errorRate); temp += "\t"; temp += std::to_string(g[j].errorRate);
-				temp += "\t"; temp += std::to_string(g[i].miss); temp += "\t"; temp += std::to_string(g[j].miss);
-				temp += "\t"; temp += std::to_string(g[i].homs); temp += "\t"; temp += std::to_string(g[j].homs);
-				temp += "\t"; temp += std::to_string(g[i].hets); temp += "\t"; temp += std::to_string(g[j].hets);
-				temp += "\n";
+				appendRow(temp, c, g, opt, r, score, "-1", i, j);
 				std::cout << temp;
 			}
 	}

@@ -35,3 +35,119 @@ def pairs(counts, min_cov=1, device=0):
     if rc:
         raise RuntimeError("ntsm_eval_pairs failed: %d" % rc)
     return out, ms.value
+
+
+# ---- PCA-guided pair search (the reference's -p / -n mode; include/ntsm_eval_hip.h: ntsm_eval_open ... ntsm_eval_score_pairs)
+E_CAPACITY = -3
+lib.ntsm_eval_open.restype = C.c_int
+lib.ntsm_eval_open.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+lib.ntsm_eval_close.restype = None
+lib.ntsm_eval_close.argtypes = [C.c_void_p]
+lib.ntsm_eval_project.restype = C.c_int
+lib.ntsm_eval_project.argtypes = [C.c_void_p, C.POINTER(C.c_longdouble), C.POINTER(C.c_longdouble), C.c_uint32, C.c_void_p,
+                                  C.POINTER(C.c_double)]
+lib.ntsm_eval_candidates.restype = C.c_int
+lib.ntsm_eval_candidates.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                     C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+lib.ntsm_eval_score_pairs.restype = C.c_int
+lib.ntsm_eval_score_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_double)]
+assert np.dtype(np.longdouble).itemsize == C.sizeof(C.c_longdouble)
+
+
+def _ld_ptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_longdouble))
+
+
+class Session:
+    """One run's counts on the device (ntsm_eval_open): uint32 [n_samples][n_sites][2], uploaded once."""
+
+    def __init__(self, counts, min_cov=1, device=0):
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        self.n, self.m = counts.shape[0], counts.shape[1]
+        self.h = C.c_void_p()
+        rc = lib.ntsm_eval_open(device, counts.ctypes.data, self.n, self.m, min_cov, C.byref(self.h))
+        if rc:
+            raise RuntimeError("ntsm_eval_open failed: %d" % rc)
+
+    def project(self, norm, rot):
+        """norm: long double [n_sites]; rot: long double [dim][n_sites] (np.longdouble, the x87 format).  Returns
+        (cloud double [n_samples][dim], kernel ms)."""
+        norm = np.ascontiguousarray(norm, dtype=np.longdouble)
+        rot = np.ascontiguousarray(rot, dtype=np.longdouble).reshape(-1, self.m)
+        dim = rot.shape[0]
+        cloud = np.zeros((self.n, dim), dtype=np.float64)
+        ms = C.c_double()
+        rc = lib.ntsm_eval_project(self.h, _ld_ptr(norm), _ld_ptr(rot), dim, cloud.ctypes.data, C.byref(ms))
+        if rc:
+            raise RuntimeError("ntsm_eval_project failed: %d" % rc)
+        return cloud, ms.value
+
+    def candidates(self, cloud, radius, capacity=None):
+        """cloud: double [n_samples][dim]; radius: double [n_samples] (squared, DBL_MAX = search all).  Returns
+        (pi, pk, calcDistance, kernel ms) in the reference's one-thread print order.  capacity: buffer size to offer
+        (default: ask for the size first); too small raises ValueError carrying the size needed."""
+        cloud = np.ascontiguousarray(cloud, dtype=np.float64)
+        radius = np.ascontiguousarray(radius, dtype=np.float64)
+        dim = cloud.shape[1] if cloud.ndim == 2 else 0
+        ms, n = C.c_double(), C.c_uint64()
+        if capacity is None:
+            rc = lib.ntsm_eval_candidates(self.h, cloud.ctypes.data, dim, radius.ctypes.data, None, None, None, 0, C.byref(n), C.byref(ms))
+            if rc not in (0, E_CAPACITY):
+                raise RuntimeError("ntsm_eval_candidates failed: %d" % rc)
+            capacity = n.value
+        pi, pk = np.zeros(capacity, dtype=np.uint32), np.zeros(capacity, dtype=np.uint32)
+        dist = np.zeros(capacity, dtype=np.float64)
+        rc = lib.ntsm_eval_candidates(self.h, cloud.ctypes.data, dim, radius.ctypes.data, pi.ctypes.data, pk.ctypes.data, dist.ctypes.data,
+                                      capacity, C.byref(n), C.byref(ms))
+        if rc == E_CAPACITY:
+            raise ValueError("capacity %d < %d candidate pairs" % (capacity, n.value), n.value)
+        if rc:
+            raise RuntimeError("ntsm_eval_candidates failed: %d" % rc)
+        k = n.value
+        return pi[:k], pk[:k], dist[:k], ms.value
+
+    def score_pairs(self, pi, pk):
+        """Records (RECORD) for the listed pairs, sample pi as sample 1; (records, kernel ms)."""
+        pi = np.ascontiguousarray(pi, dtype=np.uint32)
+        pk = np.ascontiguousarray(pk, dtype=np.uint32)
+        out = np.zeros(len(pi), dtype=RECORD)
+        ms = C.c_double()
+        rc = lib.ntsm_eval_score_pairs(self.h, pi.ctypes.data, pk.ctypes.data, len(pi), out.ctypes.data, C.byref(ms))
+        if rc:
+            raise RuntimeError("ntsm_eval_score_pairs failed: %d" % rc)
+        return out, ms.value
+
+    def close(self):
+        if self.h:
+            lib.ntsm_eval_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
+def project(counts, norm, rot, min_cov=1, device=0):
+    """m_cloud of the reference's projectPCs: (cloud [n_samples][dim], kernel ms)."""
+    s = Session(counts, min_cov, device)
+    try:
+        return s.project(norm, rot)
+    finally:
+        s.close()
+
+
+def candidates(counts, cloud, radius, min_cov=1, device=0):
+    """computeScorePCA's pairs: (pi, pk, calcDistance, kernel ms)."""
+    s = Session(counts, min_cov, device)
+    try:
+        return s.candidates(cloud, radius)
+    finally:
+        s.close()
+
+
+def score_pairs(counts, pi, pk, min_cov=1, device=0):
+    """Records of arbitrary pairs (pi as sample 1): (records, kernel ms)."""
+    s = Session(counts, min_cov, device)
+    try:
+        return s.score_pairs(pi, pk)
+    finally:
+        s.close()

@@ -5,6 +5,7 @@
 #   build/ntsm_synth          generator CLI
 #   build/ntsm_host_test      host-logic test driver (no GPU calls)
 #   ntsm_amd/libntsm_eval_hip.so, build/ntsmEval   all-pairs scoring of ntsmEval (HIP library + CLI mirror)
+#   ntsm_amd/libntsm_vcf_hip.so, build/ntsmVCF     multi-sample VCF to PCA matrix + centre file (HIP library + CLI mirror)
 #   oracle/                   CPU checker (+ oracle/_ref when /root/reference is present)
 HIPCC    ?= /opt/rocm/bin/hipcc
 CXX      ?= g++
@@ -18,7 +19,7 @@ HOSTSRC  := $(HOST)/seq_reader.cpp $(HOST)/site_set.cpp $(HOST)/report.cpp $(HOS
             $(HOST)/inflate.cpp $(HOST)/inflate_spec.cpp $(HOST)/gz_stream.cpp $(HOST)/gz_parallel.cpp $(HOST)/crc32_fast.cpp $(HOST)/pack2.cpp
 HOSTHDR  := $(wildcard $(HOST)/*.hpp) include/ntsm_host.h include/ntsm_hip.h
 
-all: oracle_all build/ntsm_synth build/gather_bench build/ntsm_feed_bench build/ubench/inflate_wave ntsm_amd/libntsm_hip.so ntsm_amd/libntsm_synth.so ntsm_amd/libntsm_host.so build/ntsmCount ntsm_amd/libntsm_eval_hip.so build/ntsmEval ref_gpu_binding
+all: oracle_all build/ntsm_synth build/gather_bench build/ntsm_feed_bench build/ubench/inflate_wave ntsm_amd/libntsm_hip.so ntsm_amd/libntsm_synth.so ntsm_amd/libntsm_host.so build/ntsmCount ntsm_amd/libntsm_eval_hip.so build/ntsmEval ntsm_amd/libntsm_vcf_hip.so build/ntsmVCF ref_gpu_binding
 
 # host-only pieces (reader, site loader, report formatting): no HIP dependency
 ntsm_amd/libntsm_host.so: $(HOSTSRC) $(HOST)/early_ingest.cpp $(HOST)/host_capi.cpp $(HOSTHDR)
@@ -74,6 +75,17 @@ ntsm_amd/libntsm_eval_hip.so: $(CSRC)/ntsm_eval.hip $(CSRC)/ntsm_eval_pca.hip $(
 build/ntsmEval: $(HOST)/ntsm_eval_main.cpp $(CSRC)/xprec.h include/ntsm_eval_hip.h ntsm_amd/libntsm_eval_hip.so
 	@mkdir -p build
 	$(CXX) $(CXXFLAGS) -ffp-contract=off -o $@ $(HOST)/ntsm_eval_main.cpp -Lntsm_amd -lntsm_eval_hip \
+	    -Wl,-rpath,'$$ORIGIN/../ntsm_amd' -Wl,-rpath,/opt/rocm/lib
+
+# ntsmVCF (multi-sample VCF -> PCA matrix and centre file): own library, own CLI
+ntsm_amd/libntsm_vcf_hip.so: $(CSRC)/ntsm_vcf.hip include/ntsm_vcf_hip.h
+	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -shared -o $@ $(CSRC)/ntsm_vcf.hip
+
+VCFSRC := $(HOST)/seq_reader.cpp $(HOST)/site_set.cpp $(HOST)/inflate.cpp $(HOST)/inflate_spec.cpp $(HOST)/gz_stream.cpp \
+          $(HOST)/gz_parallel.cpp $(HOST)/crc32_fast.cpp
+build/ntsmVCF: $(VCFSRC) $(HOST)/ntsm_vcf_main.cpp $(HOSTHDR) include/ntsm_vcf_hip.h ntsm_amd/libntsm_vcf_hip.so
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) -ffp-contract=off -o $@ $(VCFSRC) $(HOST)/ntsm_vcf_main.cpp -Lntsm_amd -lntsm_vcf_hip -lz -pthread \
 	    -Wl,-rpath,'$$ORIGIN/../ntsm_amd' -Wl,-rpath,/opt/rocm/lib
 
 # ablation builds (never shipped: wrong counts by construction).  `make ablation`: the default kernels with the switches of

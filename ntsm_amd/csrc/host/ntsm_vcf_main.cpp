@@ -1,0 +1,633 @@
+/*
+ * ntsm_vcf_main.cpp -- host mirror of the reference's ntsmVCF (src/ntSeqMatchVCF.cpp:54-216, src/VCFConvert.hpp,
+ * src/MultiCount.hpp): a multi-sample VCF and a reference genome to the PCA matrix NAME_matrix.tsv and the centre file
+ * NAME_center.txt that ntsmEval -n reads.  Same flags (plus -G, the HIP device), same output and stderr bytes as ONE
+ * thread of the reference with one correction: the sample x k-mer matrix is sized for the header's samples (the reference
+ * sizes it before reading the header, VCFConvert.hpp:42 / MultiCount.hpp:278, and crashes at the first insert).
+ *
+ *   sites        ntsm::SiteSet (MultiCount::initCountsHash, :214-288: the same loader as FingerPrint's)
+ *   genome       every record of -r through ntsm::SeqReader (VCFConvert.hpp:43-58; a later duplicate name wins)
+ *   VCF          parsed here on -t threads (VCFConvert::count, :63-172): per line the REF / VAR windows
+ *                (getSeqFromSite, :207-218), the genotype codes and the window k-mers that are keys (the EVENTS)
+ *   inserts      + maxima + sums: one call into the HIP library (include/ntsm_vcf_hip.h), which replaces the
+ *                insertCount calls (:151-170) and printNormMatrix's walk of the matrix (MultiCount.hpp:156-187)
+ *   matrix       formatted here on -t threads (printNormMatrix, :148-201; iostream's %.*g / %.*Lg, the precision 19
+ *                that sticks to the stream after the first undefined cell)
+ * Whatever -t is, the result is the one-thread result.  Inputs where the reference throws, asserts or has undefined
+ * behaviour are refused with "Error: ..." and exit status 1.  A VCF that starts with the gzip
+ * magic is decoded (ntsm::GzStream); the reference reads it as text and finds no samples.
+ */
+#include <fcntl.h>
+#include <getopt.h>
+#include <sys/mman.h>
+#include <sys/resource.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <iostream>
+#include <sstream>
+#include <stdexcept>
+#include <string>
+#include <thread>
+#include <unordered_map>
+#include <vector>
+
+#include "../../../include/ntsm_vcf_hip.h"
+#include "gz_stream.hpp"
+#include "kmer.hpp"
+#include "seq_reader.hpp"
+#include "site_set.hpp"
+
+#define PROGRAM "ntsmVCF"
+
+namespace {
+
+struct Opt {                                 /* src/Options.h: the members ntsmVCF reads */
+	int verbose = 0, device = 0;
+	unsigned threads = 1, k = 19, window = 31, multi = 20;
+	bool dupes = false;
+	std::string snp, ref, pca;
+};
+
+constexpr unsigned kMaxWindow = 1u << 20;    /* getSeqFromSite keeps two window + 1 byte arrays on the stack */
+
+[[noreturn]] void refuse(const std::string &msg)
+{
+	std::cerr << "Error: " << msg << std::endl;
+	exit(EXIT_FAILURE);
+}
+
+void printVersion()
+{
+	std::cerr << PROGRAM " (ntsm-mi355x)\n"
+	          << "MI355X-native implementation of ntsmVCF (multi-sample VCF to PCA matrix)\n" << std::endl;
+	exit(EXIT_SUCCESS);
+}
+
+void printHelpDialog()
+{
+	const Opt d;
+	std::cerr << "Usage: " PROGRAM " -s [FASTA] -r [FASTA] [VCF]\n"
+	    "Converts a multi vcf file to a set of counts files.\n"
+	    "Alternatively, you may also create a matrix to be used for PCA.\n"
+	    "  -t, --threads = INT    Number of threads to run.[1]\n"
+	    "  -d, --dupes            Allow shared k-mers between sites to\n"
+	    "                         be counted.\n"
+	    "  -s, --snp = STR        Interleaved fasta of SNP sites to\n"
+	    "                         k-merize. [required]\n"
+	    "  -p, --pca = STR        With multivcf generate rotation and\n"
+	    "                         centering files with this prefix.\n"
+	    "  -k, --kmer = INT       k-mer size used. [19]\n"
+	    "  -m, --multi = INT      Value to multiply base counts [" << std::to_string(d.multi) << "]\n"
+	    "  -w, --window = INT     Window size used. [" << std::to_string(d.window) << "]\n"
+	    "  -r, --ref = STR        Reference fasta. [required]\n"
+	    "  -G, --gpu = INT        HIP device [0] (this build only)\n"
+	    "  -h, --help             Display this dialog.\n"
+	    "  -v, --verbose          Display verbose output.\n"
+	    "      --version          Print version information.\n" << std::endl;
+	exit(EXIT_SUCCESS);
+}
+
+template <typename T> bool parse(const char *s, T &out) { std::stringstream c(s); return bool(c >> out); }
+
+bool fexists(const std::string &f) { return std::ifstream(f).good(); }       /* src/Util.h:22-27 */
+
+/* key lookup: canonical code -> key index (open addressing; the reference's m_kmerToHash) */
+class KeyTable {
+public:
+	explicit KeyTable(const std::vector<uint64_t> &keys)
+	{
+		size_t cap = 16;
+		while (cap < keys.size() * 2 + 16) cap <<= 1;
+		mask_ = cap - 1;
+		slot_.assign(cap, kEmpty);
+		idx_.assign(cap, 0);
+		for (size_t i = 0; i < keys.size(); ++i) {
+			size_t h = hash(keys[i]);
+			while (slot_[h] != kEmpty) h = (h + 1) & mask_;
+			slot_[h] = keys[i];
+			idx_[h] = (uint32_t) i;
+		}
+	}
+	int64_t find(uint64_t code) const
+	{
+		for (size_t h = hash(code);; h = (h + 1) & mask_) {
+			if (slot_[h] == code) return idx_[h];
+			if (slot_[h] == kEmpty) return -1;
+		}
+	}
+private:
+	static constexpr uint64_t kEmpty = ~0ull;                    /* no canonical code of k <= 31 */
+	size_t hash(uint64_t c) const { return (size_t) ((c * 0x9E3779B97F4A7C15ull) >> 20) & mask_; }
+	size_t mask_ = 0;
+	std::vector<uint64_t> slot_;
+	std::vector<uint32_t> idx_;
+};
+
+struct Genome {                              /* VCFConvert::m_ref / m_chrIDs */
+	std::vector<std::string> seq;
+	std::unordered_map<std::string, uint32_t> id;
+};
+
+/* The VCF as bytes (plain: mapped; gzip / BGZF: decoded) */
+struct VcfBytes {
+	const char *data = nullptr;
+	size_t size = 0;
+	std::vector<char> owned;
+	void *map = nullptr;
+	~VcfBytes() { if (map) munmap(map, size); }
+	bool load(const std::string &path, unsigned threads)
+	{
+		if (ntsm::GzStream::is_gzip(path)) {
+			ntsm::GzStream::set_decoder_threads(threads);
+			ntsm::GzStream gz;
+			if (!gz.open(path)) return false;
+			std::vector<char> buf(1 << 22);
+			for (;;) {
+				const int n = gz.read(buf.data(), (unsigned) buf.size());
+				if (n < 0) return false;
+				if (n == 0) break;
+				owned.insert(owned.end(), buf.data(), buf.data() + n);
+			}
+			data = owned.data();
+			size = owned.size();
+			return true;
+		}
+		const int fd = open(path.c_str(), O_RDONLY);
+		if (fd < 0) return false;
+		struct stat st;
+		if (fstat(fd, &st) != 0) { close(fd); return false; }
+		if (S_ISREG(st.st_mode) && st.st_size > 0) {
+			size = (size_t) st.st_size;
+			map = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
+			close(fd);
+			if (map == MAP_FAILED) { map = nullptr; return false; }
+			data = (const char *) map;
+			return true;
+		}
+		std::vector<char> buf(1 << 20);                         /* not a regular file: read it through */
+		for (ssize_t n; (n = read(fd, buf.data(), buf.size())) > 0;) owned.insert(owned.end(), buf.data(), buf.data() + n);
+		close(fd);
+		data = owned.data();
+		size = owned.size();
+		return true;
+	}
+};
+
+/* What one body line of the VCF contributes (VCFConvert::count, :102-171) */
+struct Part {                                /* the lines [lo, hi) of one thread, in order */
+	std::vector<uint32_t> ev_key;            /* events: key index */
+	std::vector<uint8_t> ev_side;
+	std::vector<uint32_t> ev_line;           /* used line, local numbering */
+	std::vector<uint8_t> geno;               /* [used line][stride] */
+	uint32_t used = 0;
+	bool failed = false;
+	std::string error;
+	std::vector<std::string> rs_id;          /* -v -v -v: per line */
+	std::vector<uint64_t> line_events;       /* -v -v -v: events per line */
+};
+
+struct Ctx {
+	const Opt &opt;
+	const Genome &genome;
+	const KeyTable &table;
+	uint32_t n_samples, stride;
+};
+
+/* std::getline(ss, item, '\t') repeated on one line: the i-th call gives field i, and once the fields are used up the
+ * item keeps its last value (a failed getline does not touch it).  A call that reaches the end of the line without
+ * extracting anything fails, so an empty last field -- the one after a trailing tab, or an empty line -- is not counted by
+ * the reference's `while (getline(ss, item, '\t'))` loops (VCFConvert.hpp:86, :139), although it leaves item empty */
+struct Fields {
+	std::vector<std::pair<const char *, const char *>> f;
+	void split(const char *b, const char *e)
+	{
+		f.clear();
+		for (const char *p = b;;) {
+			const char *t = (const char *) memchr(p, '\t', (size_t) (e - p));
+			if (!t) { f.emplace_back(p, e); return; }
+			f.emplace_back(p, t);
+			p = t + 1;
+		}
+	}
+	std::string get(size_t i) const { const auto &x = f[std::min(i, f.size() - 1)]; return std::string(x.first, x.second); }
+	/* successful getline calls: every field but an empty last one */
+	size_t n_read() const { return f.size() - (f.back().first == f.back().second ? 1 : 0); }
+};
+
+int genotype_code(const char *b, const char *e)              /* :140-146; anything else stays hom1 */
+{
+	if (e - b != 3 || b[1] != '|') return NTSM_VCF_HOM1;
+	if (b[0] == '0' && b[2] == '0') return NTSM_VCF_HOM1;
+	if ((b[0] == '0' && b[2] == '1') || (b[0] == '1' && b[2] == '0')) return NTSM_VCF_HET;
+	if (b[0] == '1' && b[2] == '1') return NTSM_VCF_HOM2;
+	return NTSM_VCF_HOM1;
+}
+
+void parse_lines(const Ctx &c, const char *lo, const char *hi, uint64_t first_line, Part &out)
+{
+	Fields fl;
+	const unsigned W = c.opt.window, half = W / 2;
+	std::vector<char> refStr(W + 1), varStr(W + 1);
+	uint64_t line_no = first_line;
+	for (const char *p = lo; p < hi; ++line_no) {
+		const char *nl = (const char *) memchr(p, '\n', (size_t) (hi - p));
+		const char *b = p, *e = nl;                              /* every line here ends in '\n' */
+		p = nl + 1;
+		auto fail = [&](const std::string &why) {
+			out.failed = true;
+			out.error = "line " + std::to_string(line_no) + " of the VCF: " + why;
+		};
+		if (b == e) { fail("empty line"); return; }             /* stoi("") throws */
+		fl.split(b, e);
+		const std::string chr = fl.get(0), pos_s = fl.get(1);
+		long pos;
+		try {
+			pos = std::stoi(pos_s);                              /* :114 */
+		} catch (const std::exception &) {
+			fail("POS '" + pos_s + "' is not an int"); return;
+		}
+		const size_t n_before = out.ev_key.size();
+		if (c.opt.verbose > 2) out.rs_id.push_back(fl.get(2));
+		auto done_line = [&]() { if (c.opt.verbose > 2) out.line_events.push_back(out.ev_key.size() - n_before); };
+		if (fl.get(3) == ".") { done_line(); continue; }         /* :121-124 */
+		const std::string alt = fl.get(4);
+		if (alt.size() != 1) { done_line(); continue; }          /* :125-128 */
+		/* getSeqFromSite (:207-218) */
+		const auto chr_it = c.genome.id.find(chr);
+		if (chr_it == c.genome.id.end()) { fail("unknown chromosome '" + chr + "'"); return; }
+		const std::string &g = c.genome.seq[chr_it->second];
+		if (pos <= (long) half) { fail("POS " + std::to_string(pos) + " is not greater than half the window"); return; }
+		const size_t offset = (size_t) pos - half - 1;
+		if (g.empty() || offset > g.size()) { fail("the window at POS " + std::to_string(pos) + " starts past the end of " + chr); return; }
+		strncpy(refStr.data(), g.c_str() + offset, W);
+		strncpy(varStr.data(), g.c_str() + offset, W);
+		varStr[half] = alt[0];
+		varStr[W] = '\0';
+		refStr[W] = '\0';
+		/* genotypes (:137-149): fields 9 on; their number must be the header's */
+		const size_t n_gt = fl.n_read() > 9 ? fl.n_read() - 9 : 0;
+		if (n_gt != c.n_samples) {
+			fail(std::to_string(n_gt) + " genotype fields, the header has " + std::to_string(c.n_samples) + " samples"); return;
+		}
+		const size_t n_ref_before = out.ev_key.size();
+		for (int side = 0; side < 2 && c.n_samples; ++side) {     /* without samples no insert happens */
+			const char *s = side ? varStr.data() : refStr.data();
+			ntsm::for_each_kmer(s, strlen(s), c.opt.k, [&](uint64_t code, uint64_t) {
+				const int64_t q = c.table.find(code);
+				if (q < 0) return;                                   /* insertCount: not a key, nothing happens */
+				out.ev_key.push_back((uint32_t) q);
+				out.ev_side.push_back((uint8_t) side);
+				out.ev_line.push_back(out.used);
+			});
+		}
+		if (out.ev_key.size() > n_ref_before && c.n_samples) {
+			const size_t at = out.geno.size();
+			out.geno.resize(at + c.stride, (uint8_t) NTSM_VCF_PAD);
+			for (uint32_t s = 0; s < c.n_samples; ++s) out.geno[at + s] = (uint8_t) genotype_code(fl.f[9 + s].first, fl.f[9 + s].second);
+		}
+		if (out.ev_key.size() > n_ref_before) ++out.used;
+		done_line();
+	}
+}
+
+long rss_kbytes()                            /* Util::getRSS: only in the Time line, which is not compared */
+{
+	struct rusage ru;
+	getrusage(RUSAGE_SELF, &ru);
+	return ru.ru_maxrss;
+}
+
+double seconds_since(std::chrono::steady_clock::time_point t)
+{
+	return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
+}
+
+template <class F> void on_threads(unsigned n, F f)
+{
+	std::vector<std::thread> pool;
+	for (unsigned t = 1; t < n; ++t) pool.emplace_back(f, t);
+	f(0u);
+	for (auto &th : pool) th.join();
+}
+
+} // namespace
+
+int main(int argc, char **argv)
+{
+	Opt opt;
+	bool die = false;
+	int OPT_VERSION = 0;
+	static struct option long_options[] = {
+		{ "threads", required_argument, nullptr, 't' }, { "dupes", no_argument, nullptr, 'd' },
+		{ "snp", required_argument, nullptr, 's' }, { "pca", required_argument, nullptr, 'p' },
+		{ "kmer", required_argument, nullptr, 'k' }, { "multi", required_argument, nullptr, 'm' },
+		{ "window", required_argument, nullptr, 'w' }, { "ref", required_argument, nullptr, 'r' },
+		{ "help", no_argument, nullptr, 'h' }, { "version", no_argument, &OPT_VERSION, 1 },
+		{ "verbose", no_argument, nullptr, 'v' }, { "gpu", required_argument, nullptr, 'G' }, { nullptr, 0, nullptr, 0 } };
+	int ch;
+	while ((ch = getopt_long(argc, argv, "s:t:vhk:dr:w:m:p:G:", long_options, nullptr)) != -1) {
+		switch (ch) {                            /* src/ntSeqMatchVCF.cpp:82-156 */
+		case 'h': printHelpDialog(); break;
+		case 'd': opt.dupes = true; break;
+		case 's': if (!parse(optarg, opt.snp)) { std::cerr << "Error - Invalid parameter s: " << optarg << std::endl; return 0; } break;
+		case 'p': if (!parse(optarg, opt.pca)) { std::cerr << "Error - Invalid parameter p: " << optarg << std::endl; return 0; } break;
+		case 'k': if (!parse(optarg, opt.k)) { std::cerr << "Error - Invalid parameter k: " << optarg << std::endl; return 0; } break;
+		case 'w': if (!parse(optarg, opt.window)) { std::cerr << "Error - Invalid parameter w: " << optarg << std::endl; return 0; } break;
+		case 'm': if (!parse(optarg, opt.multi)) { std::cerr << "Error - Invalid parameter m: " << optarg << std::endl; return 0; } break;
+		case 't': if (!parse(optarg, opt.threads)) { std::cerr << "Error - Invalid parameter t: " << optarg << std::endl; return 0; } break;
+		case 'r': if (!parse(optarg, opt.ref)) { std::cerr << "Error - Invalid parameter r: " << optarg << std::endl; return 0; } break;
+		case 'G': if (!parse(optarg, opt.device)) { std::cerr << "Error - Invalid parameter G: " << optarg << std::endl; return 0; } break;
+		case 'v': opt.verbose++; break;
+		case '?': die = true; break;
+		default: break;
+		}
+	}
+	if (OPT_VERSION) printVersion();
+	if (opt.k > 32) {                                                /* :168-171 */
+		die = true;
+		std::cerr << "k cannot be greater than 32" << std::endl;
+	}
+	std::vector<std::string> inputs;
+	while (optind < argc) {
+		inputs.emplace_back(argv[optind++]);
+		if (!fexists(inputs.back())) refuse("input file " + inputs.back() + " does not exist");   /* :176 asserts */
+	}
+	if (inputs.empty()) {
+		std::cerr << "Error: Need Input File" << std::endl;
+		die = true;
+	}
+	if (!fexists(opt.ref)) {
+		std::cerr << "Error: Unable to load reference file" << std::endl;
+		die = true;
+	}
+	if (die) {
+		std::cerr << "Try '--help' for more information.\n";
+		exit(EXIT_FAILURE);
+	}
+	if (inputs.size() > 1) refuse("ntsmVCF takes one VCF file, " + std::to_string(inputs.size()) + " were given");   /* :199 asserts */
+	if (opt.k == 0 || opt.k == 32) refuse("-k " + std::to_string(opt.k) + " is not supported (k must be 1 to 31)");
+	if (opt.window >= kMaxWindow) refuse("-w " + std::to_string(opt.window) + " is too large (at most " + std::to_string(kMaxWindow - 1) + ")");
+	const unsigned T = opt.threads ? std::min(opt.threads, 256u) : std::max(1u, std::min(64u, std::thread::hardware_concurrency()));
+	const auto t_start = std::chrono::steady_clock::now();
+	const bool prof = getenv("NTSM_VCF_PROF") != nullptr;      /* phase times on stderr (tools/vcf_bench.py) */
+	auto t_lap = t_start;
+	auto lap = [&](const char *what) {
+		if (!prof) return;
+		const auto t = std::chrono::steady_clock::now();
+		fprintf(stderr, "[vcf] %s: %.4f s\n", what, std::chrono::duration<double>(t - t_lap).count());
+		t_lap = t;
+	};
+
+	/* VCFConvert's constructor: the sites (MultiCount's, initialised first), then the genome */
+	ntsm::SiteSet sites;
+	{
+		if (!fexists(opt.snp)) {                                    /* MultiCount.hpp:218-221 */
+			std::cerr << "file " << opt.snp << " cannot be opened" << std::endl;
+			exit(1);
+		}
+		if (opt.verbose) std::cerr << "Opening " << opt.snp << std::endl;
+		if (!sites.load(opt.snp, opt.k, opt.dupes, std::cerr)) {
+			std::cerr << "file " << opt.snp << " cannot be opened" << std::endl;
+			exit(1);
+		}
+	}
+	const size_t n_sites = sites.ids.size();
+	if (sites.ref.size() != sites.var.size())
+		refuse("the sites file has an odd number of records (" + std::to_string(sites.ref.size() + sites.var.size()) + "): site " +
+		    sites.ids.back() + " has no VAR record");
+	if (!opt.pca.empty() && !opt.dupes && sites.n_erased) {
+		/* without -d a shared k-mer is erased from the keys but stays in its first allele list: the reference's
+		 * printNormMatrix throws at that site (m_kmerToHash.at), after rows that overlap the next sample's */
+		size_t s = 0;
+		auto has = [](const std::vector<int64_t> &l) { return std::find(l.begin(), l.end(), ntsm::SiteSet::kErased) != l.end(); };
+		while (s < n_sites && !has(sites.ref[s]) && !has(sites.var[s])) ++s;
+		refuse("the sites file has k-mers shared between sites (first at site " + sites.ids[std::min(s, n_sites - 1)] +
+		    "); -p needs -d for such a file");
+	}
+	lap("sites");
+	if (opt.verbose > 1) std::cerr << "Loading Reference " << opt.ref << std::endl;
+	Genome genome;
+	{
+		ntsm::SeqReader rd;
+		if (!rd.open(opt.ref)) refuse("cannot read the reference file " + opt.ref);
+		for (int64_t l = rd.next(); l >= 0; l = rd.next()) {
+			genome.id[rd.name()] = (uint32_t) genome.seq.size();
+			genome.seq.emplace_back(rd.seq_data(), (size_t) l);
+		}
+	}
+	lap("genome");
+
+	/* VCFConvert::count (:63-172) */
+	if (opt.verbose > 1) std::cerr << "Reading VCF file: " << inputs[0] << std::endl;
+	VcfBytes vcf;
+	if (!vcf.load(inputs[0], T)) refuse("cannot read the VCF file " + inputs[0]);
+	const char *p = vcf.data, *const end = vcf.data + vcf.size;
+	std::vector<std::string> samples;
+	for (uint64_t line_no = 1; p < end; ++line_no) {            /* the header (:70-93) */
+		const char *nl = (const char *) memchr(p, '\n', (size_t) (end - p));
+		const char *b = p, *e = nl ? nl : end;
+		p = nl ? nl + 1 : end;
+		if (b == e) refuse("line " + std::to_string(line_no) + " of the VCF: empty line");   /* line.at(0) throws */
+		if (*b != '#') continue;
+		const char *t = (const char *) memchr(b, '\t', (size_t) (e - b));
+		if (std::string(b, t ? t : e) != "#CHROM") continue;
+		Fields fl;
+		fl.split(b, e);
+		for (size_t i = 9; i < fl.n_read(); ++i) samples.emplace_back(fl.f[i].first, fl.f[i].second);
+		break;
+	}
+	const uint64_t header_lines = (uint64_t) std::count(vcf.data, p, '\n');
+	const uint32_t n_samples = (uint32_t) samples.size();
+	if (opt.verbose > 1) std::cerr << "Starting multicount of each rsID for " << n_samples << " samples." << std::endl;
+	/* body: complete lines only (a last line without '\n' fails fh.good(), :108) */
+	const char *body_end = p;
+	for (const char *q = end; q > p; --q)
+		if (q[-1] == '\n') { body_end = q; break; }
+	const uint32_t stride = (n_samples + 15) / 16 * 16;
+	KeyTable table(sites.keys);
+	const Ctx ctx { opt, genome, table, n_samples, stride };
+	std::vector<Part> parts(T);
+	std::vector<const char *> cut(T + 1, body_end);
+	cut[0] = p;
+	for (unsigned t = 1; t < T; ++t) {
+		const char *q = std::max(cut[t - 1], p + (size_t) (body_end - p) / T * t);
+		while (q < body_end && q > p && q[-1] != '\n') ++q;
+		cut[t] = q;
+	}
+	std::vector<uint64_t> first_line(T + 1, header_lines + 1);
+	on_threads(T, [&](unsigned t) {                              /* line numbers of the cuts (for messages) */
+		first_line[t + 1] = (uint64_t) std::count(cut[t], cut[t + 1], '\n');
+	});
+	for (unsigned t = 0; t < T; ++t) first_line[t + 1] += first_line[t];
+	on_threads(T, [&](unsigned t) { parse_lines(ctx, cut[t], cut[t + 1], first_line[t], parts[t]); });
+	for (const Part &pt : parts)
+		if (pt.failed) refuse(pt.error);
+	lap("parse");
+	/* events in one-thread order -> per-key lists (CSR), ascending ordinals */
+	uint64_t n_events = 0, n_used = 0;
+	for (const Part &pt : parts) { n_events += pt.ev_key.size(); n_used += pt.used; }
+	if (n_events > 0xFFFFFFFFull || n_used > 0x7FFFFFFFull) refuse("too many window k-mers in the VCF");
+	const uint64_t n_keys = sites.keys.size();
+	std::vector<uint64_t> key_off(n_keys + 1, 0);
+	for (const Part &pt : parts)
+		for (uint32_t q : pt.ev_key) key_off[q + 1]++;
+	for (uint64_t q = 0; q < n_keys; ++q) key_off[q + 1] += key_off[q];
+	std::vector<uint32_t> ev_ord(n_events), ev_ls(n_events);
+	std::vector<uint8_t> geno((size_t) n_used * stride);
+	{
+		std::vector<uint64_t> fill(key_off.begin(), key_off.end() - 1);
+		uint64_t ord = 0, line_base = 0;
+		std::vector<uint64_t> geno_at(T + 1, 0);
+		for (unsigned t = 0; t < T; ++t) {
+			const Part &pt = parts[t];
+			for (size_t i = 0; i < pt.ev_key.size(); ++i, ++ord) {
+				const uint64_t at = fill[pt.ev_key[i]]++;
+				ev_ord[at] = (uint32_t) ord;
+				ev_ls[at] = (uint32_t) ((line_base + pt.ev_line[i]) * 2 + pt.ev_side[i]);
+			}
+			line_base += pt.used;
+			geno_at[t + 1] = geno_at[t] + pt.geno.size();
+		}
+		on_threads(T, [&](unsigned t) {
+			if (!parts[t].geno.empty()) memcpy(geno.data() + geno_at[t], parts[t].geno.data(), parts[t].geno.size());
+			std::vector<uint8_t>().swap(parts[t].geno);
+		});
+	}
+	/* per-site key lists (erased k-mers -- only without -d, and then without -p -- have no events: left out) */
+	std::vector<uint64_t> site_off(2 * n_sites + 1, 0);
+	std::vector<uint32_t> site_keys;
+	for (size_t s = 0; s < n_sites; ++s)
+		for (int side = 0; side < 2; ++side) {
+			for (int64_t q : side ? sites.var[s] : sites.ref[s])
+				if (q >= 0) site_keys.push_back((uint32_t) q);
+			site_off[2 * s + side + 1] = site_keys.size();
+		}
+	lap("events");
+
+	/* the device step: inserts, maxima, sums (include/ntsm_vcf_hip.h) */
+	std::vector<uint16_t> cells((size_t) n_sites * n_samples);
+	std::vector<double> sums(n_sites);
+	std::vector<uint32_t> first_undef(n_sites);
+	std::vector<ntsm_vcf_warning> warn(1 << 20);                  /* 16 MB: more warnings cost a second call */
+	uint64_t n_warn = 0;
+	ntsm_vcf_times tm {};
+	for (;;) {
+		const int rc = ntsm_vcf_run(opt.device, n_samples, opt.multi, n_used, geno.data(), stride, n_keys, key_off.data(), n_events,
+		    ev_ord.data(), ev_ls.data(), n_sites, site_off.data(), site_keys.data(), cells.data(), sums.data(), first_undef.data(),
+		    warn.data(), warn.size(), &n_warn, &tm);
+		if (rc == NTSM_VCF_E_CAPACITY) { warn.resize(n_warn); continue; }
+		if (rc) refuse("the HIP device step failed (" + std::to_string(rc) + ")");
+		break;
+	}
+	if (prof) fprintf(stderr, "[vcf] device: upload %.4f s, state kernel %.4f s, sum kernel %.4f s, download %.4f s, kernel bytes %llu, "
+	    "state launches %llu\n", tm.upload_ms / 1e3, tm.state_kernel_ms / 1e3, tm.sum_kernel_ms / 1e3, tm.download_ms / 1e3,
+	    (unsigned long long) tm.kernel_bytes, (unsigned long long) tm.state_launches);
+	lap("device step (total)");
+	warn.resize(n_warn);
+	std::sort(warn.begin(), warn.end(), [](const ntsm_vcf_warning &a, const ntsm_vcf_warning &b) {
+		return a.event != b.event ? a.event < b.event : a.sample < b.sample;
+	});
+	{
+		std::string text;
+		auto put = [&](const ntsm_vcf_warning &w) {             /* MultiCount.hpp:59-60 */
+			text += "Warning: Inconsistent k-mer counts, check for overlapping sites: ";
+			text += (char) (uint8_t) w.old;
+			text += " vs ";
+			text += std::to_string(w.value);
+			text += "\n";
+		};
+		if (opt.verbose > 2) {                                   /* "Processing site" per line, its warnings after it */
+			size_t wi = 0;
+			uint64_t ev_end = 0;
+			for (const Part &pt : parts)
+				for (size_t i = 0; i < pt.rs_id.size(); ++i) {
+					text += "Processing site: " + pt.rs_id[i] + "\n";
+					ev_end += pt.line_events[i];
+					for (; wi < warn.size() && warn[wi].event < ev_end; ++wi) put(warn[wi]);
+				}
+		} else {
+			for (const ntsm_vcf_warning &w : warn) put(w);
+		}
+		std::cerr << text << std::flush;
+	}
+	if (opt.pca.empty()) {
+		if (opt.verbose > 1) std::cerr << "Outputting counts" << std::endl;
+	} else {
+		if (opt.verbose > 1) {
+			std::cerr << "Outputting matrix and normalization values for PCA" << std::endl;
+			std::cerr << "Outputting matrix and normalization values for PCA" << std::endl;
+		}
+		/* printNormMatrix (:148-201) */
+		FILE *out = fopen((opt.pca + "_matrix.tsv").c_str(), "wb");
+		FILE *cf = fopen((opt.pca + "_center.txt").c_str(), "wb");
+		if (!out || !cf) refuse("cannot write " + opt.pca + "_matrix.tsv / _center.txt");
+		uint64_t first_undef_cell = ~0ull;                       /* row-major: precision 19 from here on */
+		for (size_t s = 0; s < n_sites && first_undef_cell == ~0ull; ++s)
+			if (first_undef[s] < n_samples) first_undef_cell = (uint64_t) s * n_samples + first_undef[s];
+		std::vector<std::string> centre(n_sites);
+		std::string ctext;
+		char buf[128];
+		for (size_t s = 0; s < n_sites; ++s) {
+			const long double sizeFloat = n_samples;
+			const long double center = sums[s] / sizeFloat;
+			snprintf(buf, sizeof buf, "%.19Lg", center);
+			centre[s] = buf;
+			ctext += centre[s];
+			ctext += "\n";
+		}
+		/* the cell text of every (maxREF, maxVAR) pair that can occur: bytes 0, (uint8_t) m, (uint8_t) 2m */
+		std::vector<std::string> tab[2];
+		tab[0].resize(65536);
+		tab[1].resize(65536);
+		const unsigned bv[3] = { 0u, opt.multi & 255u, (opt.multi * 2u) & 255u };
+		auto cell_text = [](unsigned r, unsigned v, int prec) {
+			char b[64];
+			snprintf(b, sizeof b, "%.*g", prec, double(r) / double(r + v));
+			return std::string(b);
+		};
+		for (unsigned r : bv)
+			for (unsigned v : bv)
+				if (r + v) { tab[0][r | v << 8] = cell_text(r, v, 6); tab[1][r | v << 8] = cell_text(r, v, 19); }
+		std::string head = "alleleID";
+		for (const std::string &sm : samples) { head += "\t"; head += sm; }
+		head += "\n";
+		fwrite(head.data(), 1, head.size(), out);
+		const size_t batch = std::max<size_t>(1, (size_t) (64u << 20) / ((size_t) n_samples * 8 + 64));   /* ~64 MB of text per thread */
+		std::vector<std::string> text(T);
+		for (size_t s0 = 0; s0 < n_sites; s0 += batch * T) {
+			on_threads(T, [&](unsigned t) {
+				std::string &o = text[t];
+				o.clear();
+				const size_t lo = std::min(n_sites, s0 + batch * t), hi = std::min(n_sites, s0 + batch * (t + 1));
+				for (size_t s = lo; s < hi; ++s) {
+					o += sites.ids[s];
+					const uint16_t *row = cells.data() + s * n_samples;
+					for (uint32_t j = 0; j < n_samples; ++j) {
+						o += '\t';
+						const unsigned c = row[j];
+						if ((c & 255u) + (c >> 8) == 0) { o += centre[s]; continue; }
+						const int hi19 = (uint64_t) s * n_samples + j > first_undef_cell;
+						const std::string &x = tab[hi19][c];
+						if (!x.empty()) o += x;
+						else o += cell_text(c & 255u, c >> 8, hi19 ? 19 : 6);
+					}
+					o += '\n';
+				}
+			});
+			for (unsigned t = 0; t < T; ++t) fwrite(text[t].data(), 1, text[t].size(), out);
+		}
+		fwrite(ctext.data(), 1, ctext.size(), cf);
+		const bool ok = fclose(out) == 0;
+		if (fclose(cf) != 0 || !ok) refuse("writing " + opt.pca + "_matrix.tsv / _center.txt failed");
+		lap("format + write");
+	}
+	std::cerr << "Time: " << seconds_since(t_start) << " s Memory: " << rss_kbytes() << " kbytes" << std::endl;
+	return 0;
+}

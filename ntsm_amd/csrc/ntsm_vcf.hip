@@ -1,0 +1,231 @@
+/*
+ * ntsm_vcf.hip -- the device step of ntsmVCF on one MI355X (include/ntsm_vcf_hip.h; reference: MultiCount::insertCount,
+ * src/MultiCount.hpp:51-68, as VCFConvert::count calls it, src/VCFConvert.hpp:151-170, and the maxima and sums of
+ * MultiCount::printNormMatrix, :156-187).
+ *
+ * State kernel: one workgroup per site, each lane 16 consecutive samples (one 128-bit load of a G row per event).  For
+ * every key of the site's REF list, then of its VAR list, the lane walks the key's events in ordinal order with the 16
+ * bytes of state in registers, applies insertCount's rule, and folds the final bytes into maxREF / maxVAR.  All lanes of
+ * a workgroup walk the same events, so the loops are uniform; the G row of a line is shared by the ~2 x (W - k + 1)
+ * keys of its site and comes from L2 after the first.  Warnings take a slot through one atomic counter; their content
+ * does not depend on the slot, and the host sorts them into the one-thread order.
+ * Sum kernel: one lane per site, the reference's sequential double sum over the samples (correctly rounded division,
+ * built with -ffp-contract=off), plus the first sample with a zero denominator.
+ */
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+
+#include "../../include/ntsm_vcf_hip.h"
+
+namespace {
+
+constexpr int kLane = 16;                    /* samples per lane */
+constexpr uint64_t kWarnInit = 1u << 16;     /* warning records the device buffer starts with; grown (and the kernels re-run) on overflow */
+
+__device__ __forceinline__ void apply(uint8_t (&st)[kLane], uint4 g, uint32_t side, uint32_t v1, uint32_t v2, uint32_t ord,
+		uint32_t s0, uint32_t n_samples, ntsm_vcf_warning *warn, unsigned long long warn_cap, unsigned long long *n_warn)
+{
+	const uint32_t w[4] = { g.x, g.y, g.z, g.w };
+	/* REF side: hom1 -> 2m, het -> m; VAR side: hom2 -> 2m, het -> m (VCFConvert.hpp:151-170) */
+	const uint32_t full = side ? NTSM_VCF_HOM2 : NTSM_VCF_HOM1;
+#pragma unroll
+	for (int j = 0; j < kLane; ++j) {
+		const uint32_t code = (w[j >> 2] >> ((j & 3) * 8)) & 0xFFu;
+		if (code != full && code != NTSM_VCF_HET) continue;       /* no insert (also the padding) */
+		const uint32_t value = code == full ? v2 : v1;
+		const uint32_t old = st[j];
+		if (old != 0) {                                            /* MultiCount.hpp:57-62 */
+			if (old != value && s0 + j < n_samples) {
+				const unsigned long long slot = atomicAdd(n_warn, 1ull);
+				if (slot < warn_cap) warn[slot] = ntsm_vcf_warning { ord, s0 + (uint32_t) j, old, value };
+			}
+		} else {
+			st[j] = (uint8_t) value;                               /* the CAS stores the truncated value */
+		}
+	}
+}
+
+__global__ __launch_bounds__(256) void ntsm_vcf_state(uint32_t n_samples, uint32_t v1, uint32_t v2, const uint8_t *geno, uint32_t g_stride,
+		const uint64_t *key_off, const uint32_t *ev_ord, const uint32_t *ev_ls, const uint64_t *site_off, const uint32_t *site_keys,
+		uint16_t *cells, ntsm_vcf_warning *warn, unsigned long long warn_cap, unsigned long long *n_warn)
+{
+	const uint64_t site = blockIdx.x;
+	const uint32_t n_chunks = (n_samples + kLane - 1) / kLane;
+	for (uint32_t chunk = threadIdx.x; chunk < n_chunks; chunk += blockDim.x) {
+		const uint32_t s0 = chunk * kLane;
+		uint8_t mx[2][kLane];
+#pragma unroll
+		for (int j = 0; j < kLane; ++j) mx[0][j] = mx[1][j] = 0;
+		for (uint32_t side = 0; side < 2; ++side) {
+			for (uint64_t ki = site_off[2 * site + side]; ki < site_off[2 * site + side + 1]; ++ki) {
+				const uint32_t key = site_keys[ki];
+				uint8_t st[kLane];
+#pragma unroll
+				for (int j = 0; j < kLane; ++j) st[j] = 0;
+				for (uint64_t e = key_off[key]; e < key_off[key + 1]; ++e) {
+					const uint32_t ls = ev_ls[e];
+					const uint4 g = *reinterpret_cast<const uint4 *>(geno + (uint64_t) (ls >> 1) * g_stride + s0);
+					apply(st, g, ls & 1u, v1, v2, ev_ord[e], s0, n_samples, warn, warn_cap, n_warn);
+				}
+#pragma unroll
+				for (int j = 0; j < kLane; ++j) mx[side][j] = st[j] > mx[side][j] ? st[j] : mx[side][j];
+			}
+		}
+		uint16_t *row = cells + site * n_samples;
+#pragma unroll
+		for (int j = 0; j < kLane; ++j)
+			if (s0 + j < n_samples) row[s0 + j] = (uint16_t) (mx[0][j] | (mx[1][j] << 8));
+	}
+}
+
+/* printNormMatrix's per-row loop (:162-187): sum += double(maxREF) / double(denom) in sample order */
+__global__ __launch_bounds__(256) void ntsm_vcf_sums(uint64_t n_sites, uint32_t n_samples, const uint16_t *cells, double *sums, uint32_t *first_undef)
+{
+	const uint64_t site = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
+	if (site >= n_sites) return;
+	const uint16_t *row = cells + site * n_samples;
+	double sum = 0.0;
+	uint32_t first = n_samples;
+	for (uint32_t j = 0; j < n_samples; ++j) {
+		const uint32_t c = row[j], r = c & 0xFFu, denom = r + (c >> 8);
+		if (denom == 0) {
+			if (first == n_samples) first = j;
+		} else {
+			sum = __dadd_rn(sum, __ddiv_rn((double) r, (double) denom));
+		}
+	}
+	sums[site] = sum;
+	first_undef[site] = first;
+}
+
+#define VCFCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
+	fprintf(stderr, "ntsm_vcf: %s failed: %s\n", #x, hipGetErrorString(e_)); rc = -2; goto done; } } while (0)
+
+double now_ms()
+{
+	return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+} // namespace
+
+extern "C" int ntsm_vcf_run(int device, uint32_t n_samples, uint32_t multi,
+		uint64_t n_lines, const uint8_t *geno, uint32_t g_stride,
+		uint64_t n_keys, const uint64_t *key_off, uint64_t n_events, const uint32_t *ev_ord, const uint32_t *ev_ls,
+		uint64_t n_sites, const uint64_t *site_off, const uint32_t *site_keys,
+		uint16_t *cells, double *sums, uint32_t *first_undef,
+		ntsm_vcf_warning *warn, uint64_t warn_cap, uint64_t *n_warn, ntsm_vcf_times *times)
+{
+	if (!n_warn || (n_sites && (!site_off || !sums || !first_undef)) || (n_sites && n_samples && !cells)) return -1;
+	if (g_stride % kLane != 0 || g_stride < n_samples || (n_lines && !geno) || !key_off || (n_events && (!ev_ord || !ev_ls))) return -1;
+	if (n_lines > 0x7FFFFFFFull || n_keys >= 0xFFFFFFFFull || n_sites > 0x7FFFFFFFull) return -1;
+	/* every index the kernels follow is checked here, on the host: nothing on the device reads out of bounds */
+	if (key_off[0] != 0 || key_off[n_keys] != n_events) return -1;
+	for (uint64_t q = 0; q < n_keys; ++q)
+		if (key_off[q + 1] < key_off[q]) return -1;
+	for (uint64_t e = 0; e < n_events; ++e)
+		if ((ev_ls[e] >> 1) >= n_lines) return -1;
+	const uint64_t n_site_keys = n_sites ? site_off[2 * n_sites] : 0;
+	if (n_sites) {
+		if (site_off[0] != 0 || (n_site_keys && !site_keys)) return -1;
+		for (uint64_t i = 0; i < 2 * n_sites; ++i)
+			if (site_off[i + 1] < site_off[i]) return -1;
+		for (uint64_t i = 0; i < n_site_keys; ++i)
+			if (site_keys[i] >= n_keys) return -1;
+	}
+	const uint32_t v1 = multi, v2 = multi * 2u;               /* opt::multi, opt::multi * 2 (unsigned) */
+	const uint64_t n_cells = n_sites * (uint64_t) n_samples;
+	int rc = 0;
+	uint8_t *d_geno = nullptr;
+	uint64_t *d_key_off = nullptr, *d_site_off = nullptr;
+	uint32_t *d_ev_ord = nullptr, *d_ev_ls = nullptr, *d_site_keys = nullptr, *d_first = nullptr;
+	uint16_t *d_cells = nullptr;
+	double *d_sums = nullptr;
+	ntsm_vcf_warning *d_warn = nullptr;
+	unsigned long long *d_n_warn = nullptr, h_n_warn = 0, d_cap = std::min<uint64_t>(std::max<uint64_t>(warn_cap, 1), kWarnInit);
+	uint64_t launches = 0;
+	hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
+	float ms_state = 0, ms_sum = 0;
+	double t0 = now_ms(), t_up = 0, t_down = 0;
+	*n_warn = 0;
+	if (n_sites == 0) goto done;
+	VCFCHK(hipSetDevice(device));
+	VCFCHK(hipEventCreate(&e0));
+	VCFCHK(hipEventCreate(&e1));
+	VCFCHK(hipEventCreate(&e2));
+	/* +1 element everywhere: no zero-byte allocations */
+	VCFCHK(hipMalloc(&d_geno, n_lines * g_stride + kLane));
+	VCFCHK(hipMalloc(&d_key_off, (n_keys + 1) * sizeof(uint64_t)));
+	VCFCHK(hipMalloc(&d_ev_ord, (n_events + 1) * sizeof(uint32_t)));
+	VCFCHK(hipMalloc(&d_ev_ls, (n_events + 1) * sizeof(uint32_t)));
+	VCFCHK(hipMalloc(&d_site_off, (2 * n_sites + 1) * sizeof(uint64_t)));
+	VCFCHK(hipMalloc(&d_site_keys, (n_site_keys + 1) * sizeof(uint32_t)));
+	VCFCHK(hipMalloc(&d_cells, (n_cells + 1) * sizeof(uint16_t)));
+	VCFCHK(hipMalloc(&d_sums, n_sites * sizeof(double)));
+	VCFCHK(hipMalloc(&d_first, n_sites * sizeof(uint32_t)));
+	VCFCHK(hipMalloc(&d_warn, d_cap * sizeof(ntsm_vcf_warning)));
+	VCFCHK(hipMalloc(&d_n_warn, sizeof(unsigned long long)));
+	if (n_lines) VCFCHK(hipMemcpy(d_geno, geno, n_lines * g_stride, hipMemcpyHostToDevice));
+	VCFCHK(hipMemcpy(d_key_off, key_off, (n_keys + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
+	if (n_events) {
+		VCFCHK(hipMemcpy(d_ev_ord, ev_ord, n_events * sizeof(uint32_t), hipMemcpyHostToDevice));
+		VCFCHK(hipMemcpy(d_ev_ls, ev_ls, n_events * sizeof(uint32_t), hipMemcpyHostToDevice));
+	}
+	VCFCHK(hipMemcpy(d_site_off, site_off, (2 * n_sites + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
+	if (n_site_keys) VCFCHK(hipMemcpy(d_site_keys, site_keys, n_site_keys * sizeof(uint32_t), hipMemcpyHostToDevice));
+	t_up = now_ms() - t0;
+	for (;;) {                                                 /* a second pass only if the warning buffer overflowed */
+		VCFCHK(hipMemset(d_n_warn, 0, sizeof(unsigned long long)));
+		VCFCHK(hipEventRecord(e0, 0));
+		if (n_samples) {
+			const uint32_t n_chunks = (n_samples + kLane - 1) / kLane;
+			const uint32_t block = std::min<uint32_t>(256, (n_chunks + 63) / 64 * 64);
+			hipLaunchKernelGGL(ntsm_vcf_state, dim3((uint32_t) n_sites), dim3(block), 0, 0, n_samples, v1, v2, d_geno, g_stride,
+			    d_key_off, d_ev_ord, d_ev_ls, d_site_off, d_site_keys, d_cells, d_warn, d_cap, d_n_warn);
+			VCFCHK(hipGetLastError());
+			++launches;
+		}
+		VCFCHK(hipEventRecord(e1, 0));
+		hipLaunchKernelGGL(ntsm_vcf_sums, dim3((uint32_t) ((n_sites + 255) / 256)), dim3(256), 0, 0, n_sites, n_samples, d_cells, d_sums, d_first);
+		VCFCHK(hipGetLastError());
+		VCFCHK(hipEventRecord(e2, 0));
+		VCFCHK(hipEventSynchronize(e2));
+		VCFCHK(hipMemcpy(&h_n_warn, d_n_warn, sizeof(h_n_warn), hipMemcpyDeviceToHost));
+		if (h_n_warn <= d_cap) break;
+		VCFCHK(hipFree(d_warn));
+		d_warn = nullptr;
+		d_cap = h_n_warn;
+		VCFCHK(hipMalloc(&d_warn, d_cap * sizeof(ntsm_vcf_warning)));
+	}
+	VCFCHK(hipEventElapsedTime(&ms_state, e0, e1));
+	VCFCHK(hipEventElapsedTime(&ms_sum, e1, e2));
+	*n_warn = h_n_warn;
+	t0 = now_ms();
+	if (n_cells) VCFCHK(hipMemcpy(cells, d_cells, n_cells * sizeof(uint16_t), hipMemcpyDeviceToHost));
+	VCFCHK(hipMemcpy(sums, d_sums, n_sites * sizeof(double), hipMemcpyDeviceToHost));
+	VCFCHK(hipMemcpy(first_undef, d_first, n_sites * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	if (h_n_warn > warn_cap) rc = NTSM_VCF_E_CAPACITY;
+	else if (h_n_warn) VCFCHK(hipMemcpy(warn, d_warn, h_n_warn * sizeof(ntsm_vcf_warning), hipMemcpyDeviceToHost));
+	t_down = now_ms() - t0;
+done:
+	if (times) {
+		times->upload_ms = t_up;
+		times->state_kernel_ms = ms_state;
+		times->sum_kernel_ms = ms_sum;
+		times->download_ms = t_down;
+		/* G rows of the used lines, the event and key lists once, and the cells written */
+		times->kernel_bytes = n_lines * (uint64_t) g_stride + n_events * 8 + (n_keys + 1) * 8 + n_site_keys * 4 + n_cells * 2;
+		times->state_launches = launches;
+	}
+	if (e0) (void) hipEventDestroy(e0);
+	if (e1) (void) hipEventDestroy(e1);
+	if (e2) (void) hipEventDestroy(e2);
+	(void) hipFree(d_geno); (void) hipFree(d_key_off); (void) hipFree(d_ev_ord); (void) hipFree(d_ev_ls);
+	(void) hipFree(d_site_off); (void) hipFree(d_site_keys); (void) hipFree(d_cells); (void) hipFree(d_sums);
+	(void) hipFree(d_first); (void) hipFree(d_warn); (void) hipFree(d_n_warn);
+	return rc;
+}

@@ -1,0 +1,68 @@
+/*
+ * include/ntsm_pca_hip.h -- C ABI of the MI355X (gfx950) device steps of ntsmPCA: the exact PCA of the matrix that
+ * `ntsmVCF -p NAME` writes (NAME_matrix.tsv), i.e. the rotation that `ntsmEval -p` reads.
+ *
+ * With A the p x n matrix of the file (p sites, n samples; host, row-major, IEEE double), c_j the mean of row j and
+ * Ac = A - c:
+ *   G = Ac^T Ac (n x n);  (l_i, u_i) its D largest eigenpairs, descending;  s_i = sqrt(l_i);
+ *   rotation column i:  v_i = Ac u_i / s_i (length p);   scores of the samples:  t_i = s_i u_i (length n);
+ *   sign: the entry of v_i with the largest absolute value (the first one on a tie) is positive, t_i follows.
+ * This is what sklearn.decomposition.PCA(n_components=D, svd_solver="full") computes on A^T (components_ transposed and
+ * the transformed samples), up to rounding.
+ *
+ * Device steps: (1) row means in a fixed order, Ac written once over the uploaded copy of A (zero padded to the tile
+ * sizes); (2) the Gram product with v_mfma_f64_16x16x4_f64, upper 128 x 128 tiles only, the site dimension split over
+ * workgroups and the partial tiles summed by a second kernel in split order, mirrored into the lower triangle; (3) the
+ * eigenpairs of G with rocSOLVER's dsyevd (bound with dlopen on first use); (4) V = Ac U_D / s and T = U_D s.
+ * No floating-point atomics anywhere: every result is a pure function of the input and of `split`.
+ */
+#ifndef NTSM_PCA_HIP_H
+#define NTSM_PCA_HIP_H
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct ntsm_pca_times {     /* milliseconds; upload / download wall clock, device steps from HIP events */
+	double upload_ms, centre_ms, gram_ms, eigen_ms, project_ms, download_ms;
+	uint64_t gram_flops;             /* n (n + 1) p: the multiply-adds of the triangle, counted as two operations each */
+	uint64_t gram_bytes;             /* bytes the Gram kernels read and write at least once (panels, partial tiles, G) */
+	uint32_t gram_tiles, gram_split; /* upper 128 x 128 tiles; pieces the site dimension was cut into */
+} ntsm_pca_times;
+
+enum {
+	NTSM_PCA_E_ARG = -1,             /* bad argument */
+	NTSM_PCA_E_HIP = -2,             /* HIP error (text on stderr) */
+	NTSM_PCA_E_SOLVER_MISSING = -3,  /* librocsolver.so.0 / librocsolver.so could not be loaded or lacks a symbol */
+	NTSM_PCA_E_SOLVER = -4,          /* rocSOLVER returned an error or dsyevd did not converge */
+	NTSM_PCA_E_RANK = -5             /* a requested component's eigenvalue is <= n * eps * l_1; *bad_component says which */
+};
+
+/*
+ * The Gram step on its own.
+ * a:       host [p][n] row-major.
+ * centre:  non-zero: G = Ac^T Ac; 0: G = A^T A (the row means are still computed when `means` is given).
+ * split:   pieces of the site dimension; 0 = chosen from p, n and the device's compute units.  Clamped to the number
+ *          of 16-site chunks.
+ * gram:    host out [n][n], symmetric (the lower triangle is the mirror of the upper one, bit for bit).
+ * means:   host out [p], may be NULL.
+ * times:   may be NULL.
+ */
+int ntsm_pca_gram(int device, uint64_t p, uint32_t n, const double *a, int centre, uint32_t split,
+		double *gram, double *means, ntsm_pca_times *times);
+
+/*
+ * The whole PCA.  1 <= d <= min(n, p), n >= 2.
+ * eigval:  host out [d], descending.
+ * rot:     host out [p][d] (row = site, the layout of NAME_rotationalMatrix.tsv).
+ * comp:    host out [n][d] (row = sample, the layout of NAME_components.tsv).
+ * bad_component: out, set with NTSM_PCA_E_RANK; may be NULL.
+ */
+int ntsm_pca_run(int device, uint64_t p, uint32_t n, const double *a, uint32_t d, uint32_t split,
+		double *eigval, double *rot, double *comp, uint32_t *bad_component, ntsm_pca_times *times);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -4,7 +4,9 @@ build/ntsmEval.
 PARITY WITH THE REFERENCE IS UNPINNED: src/CompareCounts.hpp cannot be compiled in this image (it includes
 vendor/kfunc.c, which needs autoconf's config.h) and the reference holds no fixtures for this path.  What these tests
 pin is (CPU) the oracle against an independent statement of the formulas written here from the reference text and
-against hand-checkable cases, and (GPU) the HIP library and the CLI against the oracle, bit for bit."""
+against hand-checkable cases, and (GPU) the HIP library and the CLI against the oracle, bit for bit: every record of
+all pairs (not samples of them) against vec_pairs, a numpy model of all pairs that a CPU test pins to that statement
+and to the oracle, also on cohorts past 1,024 samples, where the pair kernel runs 256-thread workgroups."""
 import math
 import os
 import subprocess
@@ -84,6 +86,51 @@ def same_bits(x, y):
     return np.float64(x).tobytes() == np.float64(y).tobytes()
 
 
+def vec_pairs(samples, c):
+    """py_pair for every pair i < j at once, in the order of np.triu_indices(n, 1) (the order of the HIP records): the
+    sites are walked in order, and at each site the joint term and the two single terms are computed for all pairs with
+    uint32 sums and elementwise float64 a / d, a * f + b * g, acc + x.  Elementwise numpy float64 is IEEE without
+    contraction and the order over the sites is py_pair's, so every field is bit-identical to py_pair
+    (test_vec_pairs_equal_py_pair_and_oracle pins that).  Returns {field: array over the pairs}."""
+    s = np.ascontiguousarray(samples, dtype=np.uint32)
+    n, m = s.shape[0], s.shape[1]
+    ii, jj = np.triu_indices(n, 1)
+    c = np.uint32(c)
+
+    def term(x0, x1):
+        d = (x0 + x1).astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            f0 = np.where(x0 > c, x0.astype(np.float64) / d, 0.0)
+            f1 = np.where(x1 > c, x1.astype(np.float64) / d, 0.0)
+        return x0.astype(np.float64) * f0 + x1.astype(np.float64) * f1
+    acc = {f: np.zeros(len(ii), dtype=np.float64 if f.startswith("sum") else np.int64) for f in FIELDS}
+    for site in range(m):
+        a0, a1 = s[:, site, 0], s[:, site, 1]
+        covered, het, single = (a0 > c) | (a1 > c), (a0 > c) & (a1 > c), term(a0, a1)
+        valid = covered[ii] & covered[jj]
+        acc["sum_joint"] = np.where(valid, acc["sum_joint"] + term(a0[ii] + a0[jj], a1[ii] + a1[jj]), acc["sum_joint"])
+        acc["sum_single1"] = np.where(valid, acc["sum_single1"] + single[ii], acc["sum_single1"])
+        acc["sum_single2"] = np.where(valid, acc["sum_single2"] + single[jj], acc["sum_single2"])
+        h1, h2 = het[ii], het[jj]
+        both_hom = valid & ~h1 & ~h2
+        same_allele = (a0 > c)[ii] == (a0 > c)[jj]
+        for f, x in (("n_valid", valid), ("hets1", valid & h1), ("homs1", valid & ~h1), ("hets2", valid & h2), ("homs2", valid & ~h2),
+                     ("shared_hets", valid & h1 & h2), ("shared_homs", both_hom & same_allele), ("ibs0", both_hom & ~same_allele)):
+            acc[f] += x
+    acc["ibs2"] = acc["shared_hets"] + acc["shared_homs"]
+    return acc
+
+
+def mismatches(rec, model):
+    """(field, pair position) of every HIP record field that differs from the model's: doubles by their bits"""
+    out = []
+    for f in FIELDS:
+        g, w = np.ascontiguousarray(rec[f]), model[f]
+        ne = g.view(np.uint64) != w.view(np.uint64) if f.startswith("sum") else g.astype(np.int64) != w
+        out += [(f, int(p)) for p in np.flatnonzero(ne)[:5]]
+    return out
+
+
 def files_for(tmp_path, samples, **kw):
     paths = []
     for i in range(samples.shape[0]):
@@ -158,6 +205,30 @@ def test_oracle_pairs_match_an_independent_statement_of_the_formulas(tmp_path):
     assert o.L.ntsm_eval_oracle_score(o.pair(0, 2, 1), 1.0, 1.0, 0.2) == 1.7976931348623157e308
     assert o.genotype(0, 1) == (1, 2, 1) and o.genotype(2, 1) == (1, 0, 3)  # hets, homs, miss (calcHomHetMiss, :742-767)
     o.close()
+
+
+def test_vec_pairs_equal_py_pair_and_oracle(tmp_path):
+    """vec_pairs, the all-pairs model of the GPU tests, against py_pair and against the oracle: every pair, every field,
+    doubles by their bits, min_cov 0 / 1 / 3, with a sample without coverage and a duplicated sample."""
+    rng = np.random.default_rng(4)
+    for n, m, c in ((9, 300, 0), (9, 300, 1), (12, 500, 3)):
+        samples = random_samples(rng, n, m)
+        samples[3] = 0
+        samples[4] = samples[1]
+        model = vec_pairs(samples, c)
+        o = EvalOracle(files_for(tmp_path, samples))
+        ii, jj = np.triu_indices(n, 1)
+        assert len(model["n_valid"]) == n * (n - 1) // 2
+        for p, (i, j) in enumerate(zip(ii.tolist(), jj.tolist())):
+            w, r = py_pair(samples[i], samples[j], c), o.pair(i, j, c)
+            for f in FIELDS:
+                g = model[f][p]
+                if f.startswith("sum"):
+                    assert same_bits(g, w[f]) and same_bits(g, getattr(r, f)), (n, m, c, i, j, f, g, w[f])
+                else:
+                    assert int(g) == w[f] == int(getattr(r, f)), (n, m, c, i, j, f, g, w[f])
+        o.close()
+        assert model["n_valid"].max() > 0 and (model["n_valid"] == 0).sum() == n - 1      # the pairs of the empty sample
 
 
 def test_eval_library_exports_and_cli_without_gpu(tmp_path):
@@ -251,8 +322,12 @@ def test_oracle_reproduces_the_readme_example_rows(tmp_path):
 # ---------------------------------------------------------------------------------------------------- GPU
 @pytest.mark.gpu
 def test_hip_pairs_equal_oracle_bit_for_bit(tmp_path):
-    """The HIP library against the oracle on the same counts: every record field of every pair, doubles compared by
-    their bits.  Shapes around the tile sizes (256 lanes of j, 4 rows of i), min_cov 0 / 1 / 3, empty samples."""
+    """The HIP library on the same counts as the models: every record field of every pair against vec_pairs (all but the
+    96,287-site case, where 400 sampled pairs and four fixed ones are checked), and as before against the oracle
+    (n <= 65) or py_pair on the fixed and sampled pairs; doubles compared by their bits.  min_cov 0 / 1 / 3, an empty
+    sample, a duplicate.  Every cohort here has at most 1,024 samples, so these are 64-thread workgroups: 64 lanes of j
+    (n = 65, 257 and 300 cross one, four and four tile edges) by 4 rows of i.  The 256-lane tiles of larger cohorts are
+    test_hip_wide_tiles_equal_the_model_on_every_pair's."""
     import ntsm_amd.eval as ev
     rng = np.random.default_rng(11)
     for n, m, c in ((2, 1, 1), (3, 7, 0), (5, 300, 1), (65, 1000, 1), (257, 200, 3), (300, 500, 1), (40, 96287, 1)):
@@ -261,6 +336,10 @@ def test_hip_pairs_equal_oracle_bit_for_bit(tmp_path):
             samples[3] = 0                                                   # a sample without any coverage
             samples[4] = samples[1]
         rec, ms = ev.pairs(samples, min_cov=c)
+        assert len(rec) == n * (n - 1) // 2
+        if m <= 2000:
+            bad = mismatches(rec, vec_pairs(samples, c))
+            assert not bad, (n, m, c, bad[:10])
         o = EvalOracle(files_for(tmp_path, samples)) if n <= 65 else None
         pairs = [(i, j) for i in range(n) for j in range(i + 1, n)]
         if len(pairs) > 400:
@@ -277,6 +356,33 @@ def test_hip_pairs_equal_oracle_bit_for_bit(tmp_path):
                 assert same_bits(g[f], w[f]) if f.startswith("sum") else int(g[f]) == int(w[f]), (n, m, c, i, j, f, g[f], w[f])
         if o:
             o.close()
+
+
+WIDE_SITES = 24
+WIDE = [(1024, 1), (1025, 1), (1027, 1), (1280, 1), (1283, 1), (1025, 0), (1283, 3)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,c", WIDE, ids=["n%d_c%d" % w for w in WIDE])
+def test_hip_wide_tiles_equal_the_model_on_every_pair(n, c):
+    """Cohorts around the switch from 64-thread to 256-thread workgroups (n_samples <= 1024: the last 64-wide launch;
+    1,025: the first 256-wide one, whose fifth tile of j has one live lane; 1,027: n mod 4 = 3, the i clamp of the last
+    row group; 1,280: a multiple of 256; 1,283), 24 sites: every field of every record against vec_pairs, doubles by
+    their bits.  No sample is empty and the model's n_valid is positive for every pair, so a record that was never
+    written (fresh device memory tends to be zero) cannot pass; a duplicated sample stays in."""
+    import ntsm_amd.eval as ev
+    rng = np.random.default_rng(1000 * n + c)
+    samples = random_samples(rng, n, WIDE_SITES, depth=30.0)
+    samples[4] = samples[1]
+    model = vec_pairs(samples, c)
+    assert model["n_valid"].min() > 0
+    rec, ms = ev.pairs(samples, min_cov=c)
+    assert len(rec) == n * (n - 1) // 2
+    bad = mismatches(rec, model)
+    if bad:
+        ii, jj = np.triu_indices(n, 1)
+        where = [(f, int(ii[p]), int(jj[p]), rec[f][p], model[f][p]) for f, p in bad[:10]]
+        raise AssertionError((n, c, where))
 
 
 @pytest.mark.gpu
@@ -309,3 +415,23 @@ def test_cli_equals_oracle_cli_bytes(tmp_path):
     p = subprocess.run([EVAL, "-a"] + outs, capture_output=True)
     q = subprocess.run([ORACLE_CLI, "-a"] + outs, capture_output=True)
     assert p.returncode == 0 and p.stdout == q.stdout and p.stdout.count(b"\n") == 4
+
+
+@pytest.mark.gpu
+def test_cli_wide_cohort_equals_oracle_cli_bytes(tmp_path):
+    """build/ntsmEval -a on 1,030 counts files of 30 sites (256-thread workgroups, five tiles of j) against the oracle's
+    printer: one line per pair, stdout equal in length and SHA-256."""
+    import hashlib
+    n = 1030
+    rng = np.random.default_rng(13)
+    files = [os.path.basename(f) for f in files_for(tmp_path, random_samples(rng, n, 30, depth=30.0))]
+    seen = []
+    for exe in (EVAL, ORACLE_CLI):
+        out = str(tmp_path / (os.path.basename(exe) + ".out"))
+        with open(out, "wb") as fh:
+            p = subprocess.run([exe, "-a"] + files, stdout=fh, stderr=subprocess.PIPE, cwd=str(tmp_path))
+        assert p.returncode == 0, (exe, p.stderr[-300:])
+        data = open(out, "rb").read()
+        seen.append((len(data), data.count(b"\n"), hashlib.sha256(data).hexdigest()))
+    assert seen[0] == seen[1]
+    assert seen[0][1] == 1 + n * (n - 1) // 2

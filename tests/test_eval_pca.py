@@ -219,13 +219,15 @@ def test_pca_cli_refusals_and_flag_errors(tmp_path):
 # ---------------------------------------------------------------------------------------------------- GPU
 @pytest.mark.gpu
 def test_projection_equals_restatement_bits(tmp_path, restatement):
-    """m_cloud from ntsm_eval_project against the restatement's long double projection, compared by bits: N 2 / 65 / 300,
-    up to 96,287 sites, D 1 / 3 / 4 / 5 / 20, min_cov 0 / 1 / 3, samples without coverage, duplicated samples, centre and
-    rotation values with 19-20 significant digits, a centre file longer than the site list and a line that does not parse."""
+    """m_cloud from ntsm_eval_project against the restatement's long double projection, compared by bits: N 2 / 65 / 300
+    and 1,030 (five workgroups per component, the last with six live lanes), up to 96,287 sites, D 1 / 3 / 4 / 5 / 20,
+    min_cov 0 / 1 / 3, samples without coverage, duplicated samples, centre and rotation values with 19-20 significant
+    digits, a centre file longer than the site list and a line that does not parse."""
     import ntsm_amd.eval as ev
     rng = np.random.default_rng(21)
     for n, m, dim, c, extra, bad in ((2, 7, 1, 1, 0, False), (65, 1000, 3, 0, 5, True), (300, 2000, 20, 3, 0, False),
-                                      (65, 3000, 5, 1, 0, False), (300, 500, 4, 1, 2, False), (65, 96287, 20, 1, 0, False)):
+                                      (65, 3000, 5, 1, 0, False), (300, 500, 4, 1, 2, False), (65, 96287, 20, 1, 0, False),
+                                      (1030, 60, 3, 1, 0, False)):
         d = tmp_path / ("p%d_%d_%d" % (n, m, dim))
         d.mkdir()
         s = cohort(rng, n, m)
@@ -246,10 +248,11 @@ def test_projection_equals_restatement_bits(tmp_path, restatement):
 def test_candidates_equal_restatement(tmp_path, restatement):
     """ntsm_eval_candidates against the restatement's brute-force evalMetric selection: order, k and calcDistance bits,
     for radii that mix small, large and search-all samples (several radius scales and seeds); a buffer that is too small
-    gets NTSM_EVAL_E_CAPACITY with the size needed."""
+    gets NTSM_EVAL_E_CAPACITY with the size needed.  N = 1,030: every row takes five passes of 256 partners, the last
+    with six live lanes."""
     import ntsm_amd.eval as ev
     rng = np.random.default_rng(22)
-    for n, m, dim in ((2, 50, 1), (65, 800, 5), (300, 1500, 20), (257, 400, 4), (120, 600, 3)):
+    for n, m, dim in ((2, 50, 1), (65, 800, 5), (300, 1500, 20), (257, 400, 4), (120, 600, 3), (1030, 60, 3)):
         d = tmp_path / ("c%d" % n)
         d.mkdir()
         s = cohort(rng, n, m)
@@ -276,10 +279,12 @@ def test_candidates_equal_restatement(tmp_path, restatement):
 @pytest.mark.gpu
 def test_score_pairs_equal_all_pairs_records(tmp_path):
     """ntsm_eval_score_pairs on every pair in both orientations and on a random list with repeats: each record bit-equal
-    to ntsm_eval_pairs' record of (min, max), with the 1 / 2 fields swapped when the first sample is the larger."""
+    to ntsm_eval_pairs' record of (min, max), with the 1 / 2 fields swapped when the first sample is the larger.  At
+    N = 1,025 ntsm_eval_pairs runs its 256-thread tiles: the gather kernel (one lane per listed pair) and the tile kernel
+    are two independent paths to the same record."""
     import ntsm_amd.eval as ev
     rng = np.random.default_rng(23)
-    for n, m, c in ((2, 5, 1), (65, 3000, 1), (150, 1000, 3), (40, 96287, 0)):
+    for n, m, c in ((2, 5, 1), (65, 3000, 1), (150, 1000, 3), (40, 96287, 0), (1025, 24, 1)):
         s = cohort(rng, n, m)
         rec, _ = ev.pairs(s, min_cov=c)
         sess = ev.Session(s, c)
@@ -288,12 +293,14 @@ def test_score_pairs_equal_all_pairs_records(tmp_path):
         rnd_k = (rnd_i + rng.integers(1, n, size=3000)) % n
         for pi, pk in ((ii, kk), (kk, ii), (rnd_i, rnd_k)):
             got, _ = sess.score_pairs(pi, pk)
-            for p in range(len(pi)):
-                i, k = int(pi[p]), int(pk[p])
-                w = rec[ev.pair_index(min(i, k), max(i, k), n)]
-                for f in FIELDS:
-                    g2 = SWAP.get(f, f) if i > k else f
-                    assert same_bits(got[p][f], w[g2]) if f.startswith("sum") else int(got[p][f]) == int(w[g2]), (n, c, i, k, f)
+            lo, hi = np.minimum(pi, pk).astype(np.int64), np.maximum(pi, pk).astype(np.int64)
+            w = rec[ev.pair_index(lo, hi, n)]
+            assert len(got) == len(pi)
+            for f in FIELDS:
+                want = np.where(pi > pk, w[SWAP.get(f, f)], w[f])
+                bits = np.uint64 if f.startswith("sum") else want.dtype
+                ne = np.flatnonzero(np.ascontiguousarray(got[f]).view(bits) != want.view(bits))
+                assert ne.size == 0, (n, c, f, [(int(pi[p]), int(pk[p]), got[f][p], want[p]) for p in ne[:5]])
         sess.close()
 
 

@@ -296,7 +296,7 @@ def mirrored_integers(rng, p, n):
 
 
 GRAM_SHAPES = [(5, 3, 0), (16, 128, 1), (33, 16, 0), (40, 127, 0), (40, 128, 0), (40, 129, 0), (1000, 300, 0), (1001, 200, 8),
-               (333, 513, 3), (4099, 131, 0), (2, 2, 5)]
+               (333, 513, 3), (4099, 131, 0), (2, 2, 5), (48, 513, 0), (17, 640, 3)]
 
 
 @pytest.mark.gpu
@@ -304,7 +304,9 @@ GRAM_SHAPES = [(5, 3, 0), (16, 128, 1), (33, 16, 0), (40, 127, 0), (40, 128, 0),
 def test_gram_is_exact_on_integers(built, p, n, split):
     """ntsm_pca_gram on integer matrices equals numpy's int64 product bit for bit, with the centring off (A^T A) and on
     (row means exactly 4): padding, one tile, a tile edge +/- 1, many tiles (the off-diagonal ones are not symmetric, so
-    a transposed or wrongly mapped accumulator shows), a site split with a short last piece."""
+    a transposed or wrongly mapped accumulator shows), a site split with a short last piece; 513 samples: a 5 x 5 tile
+    grid (15 upper tiles) whose last tile has one live column; 640: five full tiles with p no multiple of 16 and a forced
+    split."""
     import ntsm_amd.pca as pca
     rng = np.random.default_rng(1000 * p + n)
     a = mirrored_integers(rng, p, n)

@@ -5,8 +5,8 @@ The contract of steps 1 and 3 is upstream's two scripts; the fixtures under test
 unmodified scripts (README there).  The contract of step 2 is the definition of H in the header;
 tests/sitegen_restatement.cpp states it as a brute force.  CPU: the program with -H and the restatement both reproduce
 every fixture, every refusal, the flags.  GPU: the C ABI against the brute force value for value (k = 11 .. 31, x = 0 / 1,
-one piece and many chunks, duplicates, an empty set, a dense set), the program without -H against the fixtures, and the
-chain into ntsmCount and ntsmVCF."""
+one piece and many chunks, duplicates, an empty set, a dense set, a genome longer than one staging buffer), the program
+without -H against the fixtures, and the chain into ntsmCount and ntsmVCF."""
 import gzip
 import json
 import os
@@ -427,6 +427,70 @@ def test_device_counts_on_a_dense_candidate_set(built, restatement, tmp_path):
     assert t.probes > t.windows and (want > 1).sum() > 1000 and (want == 0).sum() > 1000
     again, _ = device_hits(cands, k, 1, records, 65536)
     assert np.array_equal(again, want)
+
+
+STAGE = 1 << 27                                                # kStageCap of ntsm_sitegen.hip: bytes per full launch
+SEAMS = ["straddles", "ends_at", "in_the_carry", "starts_at", "two_records"]
+
+
+def mutate(rng, q, subs):
+    q = list(q)
+    for o in rng.choice(len(q), size=subs, replace=False):
+        q[o] = rng.choice([b for b in "ACGT" if b != q[o]])
+    return "".join(q)
+
+
+def seam_case(rng, k, seam):
+    """(record text as uint8, record ends, islands, candidates, number of candidates cut from the islands): a text of 'N'
+    a little longer than STAGE with islands of random ACGT near offset 0, at the tail and at the seam.  Offsets are those
+    of the text; for "two_records" the first record is text[:STAGE - 1], so that its separator is byte STAGE - 1 of the
+    staged stream and the second record starts at byte STAGE of it."""
+    total = STAGE + 5000
+    at_seam = {"straddles": [(STAGE - 150, STAGE + 150)], "ends_at": [(STAGE - 300, STAGE), (STAGE + 1, STAGE + 200)],
+               "in_the_carry": [(STAGE - (k - 1), STAGE + 280)], "starts_at": [(STAGE - 250, STAGE - 1), (STAGE, STAGE + 300)],
+               "two_records": [(STAGE - 151, STAGE - 1), (STAGE - 1, STAGE + 149)]}[seam]
+    spans = [(5, 305)] + at_seam + [(total - 400, total)]
+    islands = ["".join(rng.choice(list("ACGT"), size=b - a)) for a, b in spans]
+    text = np.full(total, ord("N"), dtype=np.uint8)
+    for (a, b), isl in zip(spans, islands):
+        text[a:b] = np.frombuffer(isl.encode(), dtype=np.uint8)
+    cands = []
+    for n_isl, isl in enumerate(islands):
+        for at in range(0, len(isl) - k + 1, 1 if 0 < n_isl < len(islands) - 1 else 7):
+            q, kind = isl[at:at + k], len(cands) % 4            # exact, one substitution, two, reverse strand
+            q = mutate(rng, q, kind) if kind in (1, 2) else q
+            cands.append("".join(COMP[c] for c in reversed(q)) if kind == 3 else q)
+    cut = len(cands)
+    if seam == "two_records":                                   # the window that a scan without the separator would see
+        cands.append(islands[1][-(k // 2):] + islands[2][:k - k // 2])
+    return text, [STAGE - 1, total] if seam == "two_records" else [total], islands, cands, cut
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", [19, 31])
+@pytest.mark.parametrize("seam", SEAMS)
+def test_device_counts_across_a_full_staging_buffer(built, restatement, tmp_path, k, seam):
+    """More than one staging buffer (2^27 bytes) through a single submit call: the first launch is full, has no 'N'
+    padding behind it, and hands its last k - 1 bytes to the second.  The genome is 'N' except for islands of random
+    ACGT: near offset 0, at the tail, and at the seam -- straddling byte 2^27; ending exactly at 2^27 (its last window
+    ends on the last byte of the full launch); starting at 2^27 - (k - 1) (its part before the seam is exactly the
+    carry: every window ends in the second launch and must be counted once); starting exactly at 2^27; or one island
+    cut at 2^27 - 1 into two records, so that the separator is the last byte of the full launch and no window may bridge
+    it.  No window crosses an 'N', so the expected counts are the brute force's on a small FASTA of the islands alone.
+    Candidates are every window of the seam islands and some of the others: exact, one and two substitutions, reverse
+    strand.  full_launches == 1 and launches == 2: if the buffer size ever changes, this fails instead of silently
+    missing the seam."""
+    import ntsm_amd.sitegen as S
+    rng = np.random.default_rng(k * 10 + SEAMS.index(seam))
+    text, ends, islands, cands, cut = seam_case(rng, k, seam)
+    want = brute(restatement, tmp_path, islands, cands, k, 1)
+    assert (want[0:cut:4] >= 1).all() and (want[1:cut:4] >= 1).all() and (want[3:cut:4] >= 1).all() and (want[cut:] == 0).all()
+    with S.Session(cands, k, 1) as sess:
+        sess.submit(text, ends)
+        got, t = sess.hits().astype(np.int64), sess.times()
+    assert (t.full_launches, t.launches) == (1, 2)
+    assert t.windows == sum(len(isl) - k + 1 for isl in islands)
+    assert np.array_equal(got, want), [(int(c), cands[c], int(got[c]), int(want[c])) for c in np.flatnonzero(got != want)[:10]]
 
 
 # ------------------------------------------------------------------------------------------------ GPU: the program

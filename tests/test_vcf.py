@@ -5,8 +5,9 @@ The contract is one thread of the reference with the sample x k-mer matrix sized
 fixtures under tests/golden/vcf/ were recorded from the reference classes with only that change (README there);
 tests/vcf_restatement.cpp is an independent restatement written from the reference text.  CPU: the restatement
 reproduces every fixture, and the CLI's refusals and flag errors.  GPU: the CLI against the fixtures and against the
-restatement on seeded cohorts, -t 1 against -t 16, gzip / BGZF input, the device step against a numpy model, and the
-chain into ntsmEval -p / -n."""
+restatement on seeded cohorts, -t 1 against -t 16, gzip / BGZF input, the device step against a numpy model (also on
+cohorts past 1,024 and 4,096 samples, where the state kernel widens its workgroup and then loops a lane over chunks),
+and the chain into ntsmEval -p / -n."""
 import gzip
 import json
 import os
@@ -340,6 +341,59 @@ def test_device_step_matches_numpy_model(built, multi):
     assert np.array_equal(first, ef)
     assert [tuple(int(x) for x in w) for w in warn] == ew
     assert len(ew) > 4
+
+
+def wide_lists(rng, n, n_lines, n_sites, events_on_key0):
+    """Small lists for a wide cohort (numpy_model walks warnings and sums in Python): key 0 takes events_on_key0 events
+    of both sides, the other events spread over the next keys, the last key of the plain layout has no event and its
+    last site no key.  n_sites > 5: one key per site (the sum kernel then needs a second block of 256 sites)."""
+    geno = rng.integers(0, 3 if events_on_key0 > 10 else 4, size=(n_lines, n)).astype(np.uint8)
+    if n_sites > 5:
+        n_keys, n_ev = n_sites, 300
+        keys = np.sort(rng.integers(0, n_keys, size=n_ev))
+        site_ref = [[q] if q % 2 == 0 else [] for q in range(n_keys)]
+        site_var = [[q] if q % 2 == 1 else [] for q in range(n_keys)]
+    else:
+        n_keys, n_ev = 12, 40
+        keys = np.sort(np.concatenate([np.zeros(events_on_key0, dtype=np.int64), rng.integers(1, n_keys - 1, size=n_ev - events_on_key0)]))
+        site_ref = [[0, 1, 2], [5], [7, 8], [11], []]                           # key 11: no events; site 4: no keys
+        site_var = [[3, 4], [6], [], [9, 10], []]
+    lines = rng.integers(0, n_lines, size=n_ev)
+    sides = rng.integers(0, 2, size=n_ev)
+    sides[:2] = (0, 1)                                                          # both sides on key 0
+    key_events = [[(int(o), int(lines[o]), int(sides[o])) for o in np.flatnonzero(keys == q)] for q in range(n_keys)]
+    return geno, key_events, site_ref, site_var
+
+
+WIDE_STEPS = [(1024, 20, 5, 4), (1025, 20, 5, 4), (3073, 20, 5, 4), (4096, 20, 5, 4), (4097, 20, 5, 4), (4113, 128, 5, 4), (8200, 20, 5, 30),
+              (1025, 20, 257, 4)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,multi,n_sites,on_key0", WIDE_STEPS, ids=["n%d_m%d_sites%d" % w[:3] for w in WIDE_STEPS])
+def test_device_step_matches_numpy_model_on_wide_cohorts(built, n, multi, n_sites, on_key0):
+    """ntsm_vcf_run where the state kernel changes its launch: a lane holds 16 samples and a workgroup 64 to 256 lanes.
+    1,024 samples: 64 lanes, all full; 1,025: 128 lanes, the last chunk one live sample and 15 padding bytes; 3,073: 256
+    lanes; 4,096: every lane one chunk; 4,097: lane 0 alone loops to a second chunk of one live sample; 4,113: a second
+    pass with a ragged chunk (multi 128: 2 * multi truncates to 0); 8,200: three passes, and more than 65,536 warnings,
+    so the buffer regrow runs together with the lane loop; 257 sites: the sum kernel's second block.  Cells, sums by
+    their bits, first_undef and the sorted warnings against numpy_model."""
+    import ntsm_amd.vcf as V
+    rng = np.random.default_rng(n + multi + n_sites)
+    geno, key_events, site_ref, site_var = wide_lists(rng, n, 10, n_sites, on_key0)
+    ec, es, ef, ew = numpy_model(geno, multi, key_events, site_ref, site_var)
+    assert any(len(e) == 0 for e in key_events) and len(ew) > n // 4
+    if n == 8200:
+        assert len(ew) > 65536
+    cells, sums, first, warn, times = V.run(geno, multi, key_events, site_ref, site_var, warn_cap=1 << 18)
+    assert times.state_launches == (2 if len(ew) > 65536 else 1)
+    bad = np.argwhere(cells != ec)
+    assert bad.size == 0, (n, bad[:10].tolist())                                # (site, sample): chunk = sample // 16, lane = chunk % block
+    assert np.array_equal(sums.view(np.uint64), es.view(np.uint64))
+    assert np.array_equal(first, ef)
+    assert len(warn) == len(ew)
+    assert np.array_equal(np.stack([warn[f] for f in ("event", "sample", "old", "value")], axis=1).astype(np.int64),
+                          np.array(ew, dtype=np.int64).reshape(-1, 4))
 
 
 @pytest.mark.gpu

@@ -71,7 +71,7 @@ xlib:
 
 # ntsmEval all-pairs scoring: own library, own CLI
 # + the PCA-guided pair search (-p / -n): ntsm_eval_pca.hip with the x87 add of xprec.h
-ntsm_amd/libntsm_eval_hip.so: $(CSRC)/ntsm_eval.hip $(CSRC)/ntsm_eval_pca.hip $(CSRC)/xprec.h include/ntsm_eval_hip.h
+ntsm_amd/libntsm_eval_hip.so: $(CSRC)/ntsm_eval.hip $(CSRC)/ntsm_eval_pca.hip $(CSRC)/ntsm_eval_score.h $(CSRC)/ntsm_hip_scope.h $(CSRC)/xprec.h include/ntsm_eval_hip.h
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -shared -o $@ $(CSRC)/ntsm_eval.hip $(CSRC)/ntsm_eval_pca.hip
 
 build/ntsmEval: $(HOST)/ntsm_eval_main.cpp $(CSRC)/xprec.h include/ntsm_eval_hip.h ntsm_amd/libntsm_eval_hip.so
@@ -80,7 +80,7 @@ build/ntsmEval: $(HOST)/ntsm_eval_main.cpp $(CSRC)/xprec.h include/ntsm_eval_hip
 	    -Wl,-rpath,'$$ORIGIN/../ntsm_amd' -Wl,-rpath,/opt/rocm/lib
 
 # ntsmVCF (multi-sample VCF -> PCA matrix and centre file): own library, own CLI
-ntsm_amd/libntsm_vcf_hip.so: $(CSRC)/ntsm_vcf.hip include/ntsm_vcf_hip.h
+ntsm_amd/libntsm_vcf_hip.so: $(CSRC)/ntsm_vcf.hip $(CSRC)/ntsm_hip_scope.h include/ntsm_vcf_hip.h
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -shared -o $@ $(CSRC)/ntsm_vcf.hip
 
 VCFSRC := $(HOST)/seq_reader.cpp $(HOST)/site_set.cpp $(HOST)/inflate.cpp $(HOST)/inflate_spec.cpp $(HOST)/gz_stream.cpp \
@@ -92,7 +92,7 @@ build/ntsmVCF: $(VCFSRC) $(HOST)/ntsm_vcf_main.cpp $(HOSTHDR) include/ntsm_vcf_h
 
 # ntsmPCA (NAME_matrix.tsv -> NAME_rotationalMatrix.tsv, NAME_components.tsv): own library, own CLI.  rocSOLVER is bound with
 # dlopen on first use (the rpath lets a bare `librocsolver.so.0` resolve), so nothing links against it
-ntsm_amd/libntsm_pca_hip.so: $(CSRC)/ntsm_pca.hip include/ntsm_pca_hip.h
+ntsm_amd/libntsm_pca_hip.so: $(CSRC)/ntsm_pca.hip $(CSRC)/ntsm_hip_scope.h include/ntsm_pca_hip.h
 	$(HIPCC) $(HIPFLAGS) -fvisibility=hidden -ffp-contract=off -shared -o $@ $(CSRC)/ntsm_pca.hip -ldl -Wl,-rpath,/opt/rocm/lib
 
 PCASRC := $(HOST)/inflate.cpp $(HOST)/inflate_spec.cpp $(HOST)/gz_stream.cpp $(HOST)/gz_parallel.cpp $(HOST)/crc32_fast.cpp
@@ -102,7 +102,7 @@ build/ntsmPCA: $(PCASRC) $(HOST)/ntsm_pca_main.cpp $(HOSTHDR) include/ntsm_pca_h
 	    -Wl,-rpath,'$$ORIGIN/../ntsm_amd' -Wl,-rpath,/opt/rocm/lib
 
 # ntsmSiteGen (genome + VCF of SNPs -> NAME_n{i}.fa sites files): own library, own CLI
-ntsm_amd/libntsm_sitegen_hip.so: $(CSRC)/ntsm_sitegen.hip include/ntsm_sitegen_hip.h
+ntsm_amd/libntsm_sitegen_hip.so: $(CSRC)/ntsm_sitegen.hip $(CSRC)/ntsm_hip_scope.h include/ntsm_sitegen_hip.h
 	$(HIPCC) $(HIPFLAGS) -fvisibility=hidden -shared -o $@ $(CSRC)/ntsm_sitegen.hip
 
 SITEGENSRC := $(HOST)/seq_reader.cpp $(HOST)/inflate.cpp $(HOST)/inflate_spec.cpp $(HOST)/gz_stream.cpp $(HOST)/gz_parallel.cpp \

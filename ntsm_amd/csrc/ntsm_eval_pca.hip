@@ -4,9 +4,10 @@
  * :285-398 computeScorePCA).
  *
  * Session.  The counts stay on the device in the files' layout, [sample][site][2], next to the single-sample term of
- * every (sample, site) (computeSumLogPSingle's  first * freqAT + second * freqCG, :971-987, the expression of
- * ntsm_eval.hip's prepare kernel).  Both kernels that read them give one lane one sample and walk its sites in order, so a
- * lane streams its own row and a 64-byte line serves it for 8 (counts) or 8 (terms) consecutive sites.
+ * every (sample, site) (computeSumLogPSingle's  first * freqAT + second * freqCG, :971-987: ntsm_eval_score.h's
+ * ntsm_eval_term, which ntsm_eval.hip's prepare kernel calls too).  Both kernels that read them give one lane one sample
+ * and walk its sites in order, so a lane streams its own row and a 64-byte line serves it for 8 (counts) or 8 (terms)
+ * consecutive sites.
  *
  * Projection.  One lane per (sample, component): the chain over the sites is sequential (the reference's inner_product),
  * so the parallelism is N * D chains.  A lane forms the genotype code of each site from its counts and adds the product
@@ -18,8 +19,8 @@
  * ballots + an LDS scan across the four waves).  The host sorts each radius row by evalMetric (stable: ties keep k order).
  * IEEE double with __dadd_rn / __dsub_rn / __dmul_rn: the reference is built without contraction.
  *
- * Scoring.  One lane per listed pair, both rows gathered; the same operations in the same order as ntsm_eval_pair_kernel,
- * so a record is bit-identical to the all-pairs one (sample pi as sample 1).
+ * Scoring.  One lane per listed pair, both rows gathered; the per-site update and the record are ntsm_eval_score.h's, the
+ * ones ntsm_eval_pair_kernel calls, so a record is bit-identical to the all-pairs one (sample pi as sample 1).
  */
 #include <hip/hip_runtime.h>
 
@@ -29,6 +30,9 @@
 #include <vector>
 
 #include "../../include/ntsm_eval_hip.h"
+#include "ntsm_eval_score.h"
+#define NTSM_HIP_TAG "ntsm_eval"
+#include "ntsm_hip_scope.h"
 #include "xprec.h"
 
 struct ntsm_eval_session {
@@ -46,11 +50,7 @@ __global__ __launch_bounds__(kThreads) void pca_term_kernel(const uint32_t *coun
 {
 	const uint64_t cell = (uint64_t) blockIdx.x * kThreads + threadIdx.x;
 	if (cell >= cells) return;
-	const uint32_t a0 = counts[cell * 2], a1 = counts[cell * 2 + 1];
-	double fAT = 0, fCG = 0;                                                   /* :971-987, as ntsm_eval_prepare */
-	if (a0 > min_cov) fAT = __ddiv_rn((double) a0, (double) (a0 + a1));
-	if (a1 > min_cov) fCG = __ddiv_rn((double) a1, (double) (a0 + a1));
-	term[cell] = __dadd_rn(__dmul_rn((double) a0, fAT), __dmul_rn((double) a1, fCG));
+	term[cell] = ntsm_eval_term(counts[cell * 2], counts[cell * 2 + 1], min_cov);
 }
 
 /* m_cloud[i][d] (:166-211); tab[(site * dim + d) * 4 + code], code 0 / 1 / 2 = genotype 0 / 0.5 / 1, 3 = missing */
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(kThreads) void pca_fill_kernel(const double *__rest
 	}
 }
 
-/* one record per listed pair, sample pi as sample 1: ntsm_eval_pair_kernel's operations in its order */
+/* one record per listed pair, sample pi as sample 1 */
 __global__ __launch_bounds__(kThreads) void pca_score_kernel(const uint32_t *__restrict__ counts, const double *__restrict__ term, uint32_t m, uint32_t min_cov,
 		const uint32_t *__restrict__ pi, const uint32_t *__restrict__ pk, uint64_t n_pairs, ntsm_eval_record *__restrict__ out)
 {
@@ -177,76 +177,35 @@ __global__ __launch_bounds__(kThreads) void pca_score_kernel(const uint32_t *__r
 	if (p >= n_pairs) return;
 	const uint32_t *ra = counts + (uint64_t) pi[p] * m * 2, *rb = counts + (uint64_t) pk[p] * m * 2;
 	const double *ta = term + (uint64_t) pi[p] * m, *tb = term + (uint64_t) pk[p] * m;
-	double joint = 0, s1 = 0, s2 = 0;
-	uint32_t nv = 0, hets1 = 0, homs1 = 0, hets2 = 0, homs2 = 0, sh_het = 0, sh_hom = 0, ibs0 = 0;
-	for (uint32_t site = 0; site < m; ++site) {
-		const uint32_t a0 = ra[2 * site], a1 = ra[2 * site + 1], b0 = rb[2 * site], b1 = rb[2 * site + 1];
-		const bool vi = a0 > min_cov || a1 > min_cov, vj = b0 > min_cov || b1 > min_cov;
-		if (!(vi && vj)) continue;                                              /* gatherValidEntries, :1057-1078 */
-		nv++;
-		const uint32_t cAT = a0 + b0, cCG = a1 + b1;                            /* computeSumLogPJoint, :1018-1031 */
-		const double den = (double) (cAT + cCG);
-		double fAT = 0, fCG = 0;
-		if (cAT > min_cov) fAT = __ddiv_rn((double) cAT, den);
-		if (cCG > min_cov) fCG = __ddiv_rn((double) cCG, den);
-		joint = __dadd_rn(joint, __dadd_rn(__dmul_rn((double) cAT, fAT), __dmul_rn((double) cCG, fCG)));
-		s1 = __dadd_rn(s1, ta[site]);
-		s2 = __dadd_rn(s2, tb[site]);
-		const bool heti = a0 > min_cov && a1 > min_cov, hetj = b0 > min_cov && b1 > min_cov;   /* calcRelatedness, :1151-1188 */
-		const bool i_at = a0 > min_cov, j_at = b0 > min_cov;
-		hets1 += heti; homs1 += !heti;
-		hets2 += hetj; homs2 += !hetj;
-		if (heti && hetj) sh_het++;
-		else if (!heti && !hetj) { if (i_at == j_at) sh_hom++; else ibs0++; }
-	}
-	ntsm_eval_record r;
-	r.sum_joint = joint; r.sum_single1 = s1; r.sum_single2 = s2;
-	r.n_valid = nv;
-	r.hets1 = hets1; r.homs1 = homs1; r.hets2 = hets2; r.homs2 = homs2;
-	r.shared_hets = sh_het; r.shared_homs = sh_hom; r.ibs0 = ibs0; r.ibs2 = sh_het + sh_hom;
-	out[p] = r;
+	ntsm_eval_acc acc;
+	for (uint32_t site = 0; site < m; ++site)
+		acc.add(ntsm_eval_side_of(ra[2 * site], ra[2 * site + 1], ta[site], min_cov),
+		        ntsm_eval_side_of(rb[2 * site], rb[2 * site + 1], tb[site], min_cov), min_cov);
+	out[p] = acc.record();
 }
 
-/* device buffers freed on every return path */
-struct DevBuf {
-	std::vector<void *> ptr;
-	~DevBuf() { for (void *p : ptr) (void) hipFree(p); }
-	template <typename T> hipError_t alloc(T **p, uint64_t count)
-	{
-		*p = nullptr;
-		if (count == 0) count = 1;
-		const hipError_t e = hipMalloc((void **) p, count * sizeof(T));
-		if (e == hipSuccess) ptr.push_back(*p);
-		return e;
-	}
-};
-
-struct Timer {
-	hipEvent_t e0 = nullptr, e1 = nullptr;
-	~Timer() { if (e0) (void) hipEventDestroy(e0); if (e1) (void) hipEventDestroy(e1); }
-	hipError_t init() { hipError_t e = hipEventCreate(&e0); return e != hipSuccess ? e : hipEventCreate(&e1); }
-};
+/* the session's device state: the upload and the term of every cell */
+int session_upload(ntsm_eval_session *s, const uint32_t *counts, uint64_t cells)
+{
+	HIPCHK(hipMalloc(&s->counts, (cells ? cells : 1) * 2 * sizeof(uint32_t)));
+	HIPCHK(hipMalloc(&s->term, (cells ? cells : 1) * sizeof(double)));
+	if (cells == 0) return 0;
+	HIPCHK(hipMemcpy(s->counts, counts, cells * 2 * sizeof(uint32_t), hipMemcpyHostToDevice));
+	hipLaunchKernelGGL(pca_term_kernel, dim3((unsigned) ((cells + kThreads - 1) / kThreads)), dim3(kThreads), 0, 0, s->counts, cells, s->min_cov, s->term);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipDeviceSynchronize());
+	return 0;
+}
 
 }  // namespace
-
-#define PCHK(x) do { if ((x) != hipSuccess) return -2; } while (0)
 
 extern "C" int ntsm_eval_open(int device, const uint32_t *counts, uint32_t n_samples, uint32_t n_sites, uint32_t min_cov, ntsm_eval_session **h)
 {
 	if (!h || (!counts && (uint64_t) n_samples * n_sites > 0)) return -1;
 	*h = nullptr;
+	HIPCHK(hipSetDevice(device));                                               /* before the session exists: ntsm_eval_close sets its device */
 	ntsm_eval_session *s = new ntsm_eval_session { device, n_samples, n_sites, min_cov, nullptr, nullptr };
-	const uint64_t cells = (uint64_t) n_samples * n_sites;
-	int rc = 0;
-	if (hipSetDevice(device) != hipSuccess || hipMalloc(&s->counts, (cells ? cells : 1) * 2 * sizeof(uint32_t)) != hipSuccess ||
-	    hipMalloc(&s->term, (cells ? cells : 1) * sizeof(double)) != hipSuccess) rc = -2;
-	if (!rc && cells) {
-		if (hipMemcpy(s->counts, counts, cells * 2 * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) rc = -2;
-		if (!rc) {
-			hipLaunchKernelGGL(pca_term_kernel, dim3((unsigned) ((cells + kThreads - 1) / kThreads)), dim3(kThreads), 0, 0, s->counts, cells, min_cov, s->term);
-			if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = -2;
-		}
-	}
+	const int rc = session_upload(s, counts, (uint64_t) n_samples * n_sites);
 	if (rc) { ntsm_eval_close(s); return rc; }
 	*h = s;
 	return 0;
@@ -286,22 +245,22 @@ extern "C" int ntsm_eval_project(ntsm_eval_session *h, const long double *norm, 
 		for (uint64_t t = 0; t < (uint64_t) n * dim; ++t) cloud[t] = 0.0;
 		return 0;
 	}
-	PCHK(hipSetDevice(h->device));
-	DevBuf b;
+	HIPCHK(hipSetDevice(h->device));
+	ntsm_hip::Buffers b;
 	ntsm_x64 *d_tab;
 	double *d_cloud;
-	PCHK(b.alloc(&d_tab, tab.size()));
-	PCHK(b.alloc(&d_cloud, (uint64_t) n * dim));
-	PCHK(hipMemcpy(d_tab, tab.data(), tab.size() * sizeof(ntsm_x64), hipMemcpyHostToDevice));
-	Timer t;
-	PCHK(t.init());
-	PCHK(hipEventRecord(t.e0, 0));
+	HIPCHK(b.alloc(&d_tab, tab.size()));
+	HIPCHK(b.alloc(&d_cloud, (uint64_t) n * dim));
+	HIPCHK(hipMemcpy(d_tab, tab.data(), tab.size() * sizeof(ntsm_x64), hipMemcpyHostToDevice));
+	ntsm_hip::Events<2> ev;
+	HIPCHK(ev.create());
+	HIPCHK(hipEventRecord(ev[0], 0));
 	hipLaunchKernelGGL(pca_project_kernel, dim3((n + kThreads - 1) / kThreads, dim), dim3(kThreads), 0, 0, h->counts, n, m, h->min_cov, d_tab, dim, d_cloud);
-	PCHK(hipGetLastError());
-	PCHK(hipEventRecord(t.e1, 0));
-	PCHK(hipMemcpy(cloud, d_cloud, (uint64_t) n * dim * sizeof(double), hipMemcpyDeviceToHost));
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(ev[1], 0));
+	HIPCHK(hipMemcpy(cloud, d_cloud, (uint64_t) n * dim * sizeof(double), hipMemcpyDeviceToHost));
 	float ms = 0;
-	PCHK(hipEventElapsedTime(&ms, t.e0, t.e1));
+	HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
 	if (kernel_ms) *kernel_ms = ms;
 	return 0;
 }
@@ -314,25 +273,25 @@ extern "C" int ntsm_eval_candidates(ntsm_eval_session *h, const double *cloud, u
 	*n_pairs = 0;
 	const uint32_t n = h->n;
 	if (n < 2) return 0;
-	PCHK(hipSetDevice(h->device));
-	DevBuf b;
+	HIPCHK(hipSetDevice(h->device));
+	ntsm_hip::Buffers b;
 	double *d_cloud, *d_radius;
 	uint32_t *d_count;
-	PCHK(b.alloc(&d_cloud, (uint64_t) n * dim));
-	PCHK(b.alloc(&d_radius, n));
-	PCHK(b.alloc(&d_count, n));
-	if (dim) PCHK(hipMemcpy(d_cloud, cloud, (uint64_t) n * dim * sizeof(double), hipMemcpyHostToDevice));
-	PCHK(hipMemcpy(d_radius, radius, n * sizeof(double), hipMemcpyHostToDevice));
-	Timer t;
-	PCHK(t.init());
-	PCHK(hipEventRecord(t.e0, 0));
+	HIPCHK(b.alloc(&d_cloud, (uint64_t) n * dim));
+	HIPCHK(b.alloc(&d_radius, n));
+	HIPCHK(b.alloc(&d_count, n));
+	if (dim) HIPCHK(hipMemcpy(d_cloud, cloud, (uint64_t) n * dim * sizeof(double), hipMemcpyHostToDevice));
+	HIPCHK(hipMemcpy(d_radius, radius, n * sizeof(double), hipMemcpyHostToDevice));
+	ntsm_hip::Events<2> ev;
+	HIPCHK(ev.create());
+	HIPCHK(hipEventRecord(ev[0], 0));
 	hipLaunchKernelGGL(pca_count_kernel, dim3(n), dim3(kThreads), 0, 0, d_cloud, d_radius, n, dim, d_count);
-	PCHK(hipGetLastError());
-	PCHK(hipEventRecord(t.e1, 0));
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(ev[1], 0));
 	std::vector<uint32_t> count(n);
-	PCHK(hipMemcpy(count.data(), d_count, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(count.data(), d_count, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
 	float ms0 = 0;
-	PCHK(hipEventElapsedTime(&ms0, t.e0, t.e1));
+	HIPCHK(hipEventElapsedTime(&ms0, ev[0], ev[1]));
 	std::vector<uint64_t> offset(n + 1, 0);
 	for (uint32_t i = 0; i < n; ++i) offset[i + 1] = offset[i] + count[i];
 	const uint64_t total = offset[n];
@@ -343,22 +302,22 @@ extern "C" int ntsm_eval_candidates(ntsm_eval_session *h, const double *cloud, u
 	uint64_t *d_offset;
 	uint32_t *d_pk;
 	double *d_metric, *d_dist;
-	PCHK(b.alloc(&d_offset, n + 1));
-	PCHK(b.alloc(&d_pk, total));
-	PCHK(b.alloc(&d_metric, total));
-	PCHK(b.alloc(&d_dist, total));
-	PCHK(hipMemcpy(d_offset, offset.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
-	PCHK(hipEventRecord(t.e0, 0));
+	HIPCHK(b.alloc(&d_offset, n + 1));
+	HIPCHK(b.alloc(&d_pk, total));
+	HIPCHK(b.alloc(&d_metric, total));
+	HIPCHK(b.alloc(&d_dist, total));
+	HIPCHK(hipMemcpy(d_offset, offset.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
+	HIPCHK(hipEventRecord(ev[0], 0));
 	hipLaunchKernelGGL(pca_fill_kernel, dim3(n), dim3(kThreads), 0, 0, d_cloud, d_radius, n, dim, d_offset, d_pk, d_metric, d_dist);
-	PCHK(hipGetLastError());
-	PCHK(hipEventRecord(t.e1, 0));
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(ev[1], 0));
 	std::vector<uint32_t> k(total);
 	std::vector<double> metric(total), dd(total);
-	PCHK(hipMemcpy(k.data(), d_pk, total * sizeof(uint32_t), hipMemcpyDeviceToHost));
-	PCHK(hipMemcpy(metric.data(), d_metric, total * sizeof(double), hipMemcpyDeviceToHost));
-	PCHK(hipMemcpy(dd.data(), d_dist, total * sizeof(double), hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(k.data(), d_pk, total * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(metric.data(), d_metric, total * sizeof(double), hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(dd.data(), d_dist, total * sizeof(double), hipMemcpyDeviceToHost));
 	float ms1 = 0;
-	PCHK(hipEventElapsedTime(&ms1, t.e0, t.e1));
+	HIPCHK(hipEventElapsedTime(&ms1, ev[0], ev[1]));
 	if (kernel_ms) *kernel_ms = (double) ms0 + ms1;
 	/* radius rows in ascending evalMetric (nanoflann sorts its matches); the fill wrote k ascending, so a stable sort
 	 * orders exact ties by k */
@@ -390,25 +349,25 @@ extern "C" int ntsm_eval_score_pairs(ntsm_eval_session *h, const uint32_t *pi, c
 		for (uint64_t p = 0; p < n_pairs; ++p) out[p] = ntsm_eval_record {};
 		return 0;
 	}
-	PCHK(hipSetDevice(h->device));
-	DevBuf b;
+	HIPCHK(hipSetDevice(h->device));
+	ntsm_hip::Buffers b;
 	uint32_t *d_pi, *d_pk;
 	ntsm_eval_record *d_out;
-	PCHK(b.alloc(&d_pi, n_pairs));
-	PCHK(b.alloc(&d_pk, n_pairs));
-	PCHK(b.alloc(&d_out, n_pairs));
-	PCHK(hipMemcpy(d_pi, pi, n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice));
-	PCHK(hipMemcpy(d_pk, pk, n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice));
-	Timer t;
-	PCHK(t.init());
-	PCHK(hipEventRecord(t.e0, 0));
+	HIPCHK(b.alloc(&d_pi, n_pairs));
+	HIPCHK(b.alloc(&d_pk, n_pairs));
+	HIPCHK(b.alloc(&d_out, n_pairs));
+	HIPCHK(hipMemcpy(d_pi, pi, n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice));
+	HIPCHK(hipMemcpy(d_pk, pk, n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice));
+	ntsm_hip::Events<2> ev;
+	HIPCHK(ev.create());
+	HIPCHK(hipEventRecord(ev[0], 0));
 	hipLaunchKernelGGL(pca_score_kernel, dim3((unsigned) ((n_pairs + kThreads - 1) / kThreads)), dim3(kThreads), 0, 0, h->counts, h->term, h->m, h->min_cov,
 			d_pi, d_pk, n_pairs, d_out);
-	PCHK(hipGetLastError());
-	PCHK(hipEventRecord(t.e1, 0));
-	PCHK(hipMemcpy(out, d_out, n_pairs * sizeof(ntsm_eval_record), hipMemcpyDeviceToHost));
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(ev[1], 0));
+	HIPCHK(hipMemcpy(out, d_out, n_pairs * sizeof(ntsm_eval_record), hipMemcpyDeviceToHost));
 	float ms = 0;
-	PCHK(hipEventElapsedTime(&ms, t.e0, t.e1));
+	HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
 	if (kernel_ms) *kernel_ms = ms;
 	return 0;
 }

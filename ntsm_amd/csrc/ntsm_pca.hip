@@ -26,6 +26,9 @@
 #include <vector>
 
 #include "../../include/ntsm_pca_hip.h"
+#define NTSM_HIP_TAG "ntsm_pca"
+#define NTSM_HIP_FAIL NTSM_PCA_E_HIP
+#include "ntsm_hip_scope.h"
 
 namespace {
 
@@ -223,29 +226,29 @@ const Solver &solver_bind()
 	return s;
 }
 
-#define PCACHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
-	fprintf(stderr, "ntsm_pca: %s failed: %s\n", #x, hipGetErrorString(e_)); rc = NTSM_PCA_E_HIP; goto done; } } while (0)
-
 double ms_since(std::chrono::steady_clock::time_point t)
 {
 	return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
 }
 
-/* everything both entry points share: the padded matrix on the device, the row means, G */
+/* everything both entry points share: the padded matrix on the device, the row means, G; released with the scope */
 struct Device {
+	ntsm_hip::Buffers buf;
+	ntsm_hip::Events<3> ev;
 	double *a = nullptr, *means = nullptr, *partial = nullptr, *g = nullptr;
 	double *w = nullptr, *e = nullptr, *s = nullptr, *ud = nullptr, *t = nullptr, *v = nullptr;
 	rocblas_int *info = nullptr;
-	hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
 	size_t ld = 0;
 	uint64_t p_pad = 0;
-	~Device()
-	{
-		for (void *q : { (void *) a, (void *) means, (void *) partial, (void *) g, (void *) w, (void *) e, (void *) s, (void *) ud,
-		         (void *) t, (void *) v, (void *) info })
-			if (q) (void) hipFree(q);
-		for (hipEvent_t x : ev) if (x) (void) hipEventDestroy(x);
-	}
+};
+
+/* the rocBLAS handle of one run, destroyed on every return path */
+struct Handle {
+	const Solver &sv;
+	rocblas_handle h = nullptr;
+	explicit Handle(const Solver &s) : sv(s) {}
+	Handle(const Handle &) = delete;
+	~Handle() { if (h) (void) sv.destroy_handle(h); }
 };
 
 bool args_ok(uint64_t p, uint32_t n, const double *a)
@@ -256,7 +259,6 @@ bool args_ok(uint64_t p, uint32_t n, const double *a)
 /* upload, centre, Gram: leaves Ac (or A) in dev.a, the means in dev.means and G in dev.g */
 int gram_on_device(Device &dev, int device, uint64_t p, uint32_t n, const double *a, int centre, uint32_t split, ntsm_pca_times &tm)
 {
-	int rc = 0;
 	float ms = 0;
 	const uint32_t edge = (n + kTile - 1) / kTile, n_tiles = edge * (edge + 1) / 2;
 	const uint32_t chunks = (uint32_t) ((p + kChunk - 1) / kChunk);
@@ -265,8 +267,8 @@ int gram_on_device(Device &dev, int device, uint64_t p, uint32_t n, const double
 	uint32_t pieces = split, cpp = 0;
 	hipDeviceProp_t prop;
 	auto t0 = std::chrono::steady_clock::now();
-	PCACHK(hipSetDevice(device));
-	PCACHK(hipGetDeviceProperties(&prop, device));
+	HIPCHK(hipSetDevice(device));
+	HIPCHK(hipGetDeviceProperties(&prop, device));
 	if (!pieces) {
 		/* about 32 workgroups per compute unit: two are resident at a time (128 accumulator registers per lane), so the
 		 * last, partly filled round of workgroups is a small share of the whole; at most 1 GiB of partial tiles */
@@ -276,37 +278,36 @@ int gram_on_device(Device &dev, int device, uint64_t p, uint32_t n, const double
 	pieces = std::max(1u, std::min(pieces, chunks));
 	cpp = (chunks + pieces - 1) / pieces;
 	pieces = (chunks + cpp - 1) / cpp;                          /* no empty piece; the last one may be short */
-	for (hipEvent_t &x : dev.ev) PCACHK(hipEventCreate(&x));
-	PCACHK(hipMalloc(&dev.a, dev.p_pad * dev.ld * sizeof(double)));
-	PCACHK(hipMalloc(&dev.means, dev.p_pad * sizeof(double)));
-	PCACHK(hipMalloc(&dev.partial, (size_t) pieces * n_tiles * kTile * kTile * sizeof(double)));
-	PCACHK(hipMalloc(&dev.g, (size_t) n * n * sizeof(double)));
-	PCACHK(hipMemset(dev.a, 0, dev.p_pad * dev.ld * sizeof(double)));
-	PCACHK(hipMemcpy2D(dev.a, dev.ld * sizeof(double), a, (size_t) n * sizeof(double), (size_t) n * sizeof(double), p, hipMemcpyHostToDevice));
-	PCACHK(hipDeviceSynchronize());
+	HIPCHK(dev.ev.create());
+	HIPCHK(dev.buf.alloc(&dev.a, dev.p_pad * dev.ld));
+	HIPCHK(dev.buf.alloc(&dev.means, dev.p_pad));
+	HIPCHK(dev.buf.alloc(&dev.partial, (size_t) pieces * n_tiles * kTile * kTile));
+	HIPCHK(dev.buf.alloc(&dev.g, (size_t) n * n));
+	HIPCHK(hipMemset(dev.a, 0, dev.p_pad * dev.ld * sizeof(double)));
+	HIPCHK(hipMemcpy2D(dev.a, dev.ld * sizeof(double), a, (size_t) n * sizeof(double), (size_t) n * sizeof(double), p, hipMemcpyHostToDevice));
+	HIPCHK(hipDeviceSynchronize());
 	tm.upload_ms = ms_since(t0);
 
-	PCACHK(hipEventRecord(dev.ev[0], 0));
+	HIPCHK(hipEventRecord(dev.ev[0], 0));
 	ntsm_pca_centre<<<dim3((unsigned) p), dim3(256)>>>(dev.a, dev.ld, n, dev.means, centre ? 1 : 0);
-	PCACHK(hipGetLastError());
-	PCACHK(hipEventRecord(dev.ev[1], 0));
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(dev.ev[1], 0));
 	ntsm_pca_gram_tiles<<<dim3(n_tiles, pieces), dim3(256)>>>(dev.a, dev.ld, edge, n_tiles, chunks, cpp, dev.partial);
-	PCACHK(hipGetLastError());
+	HIPCHK(hipGetLastError());
 	ntsm_pca_gram_reduce<<<dim3(n_tiles, kTile / 8), dim3(256)>>>(dev.partial, edge, n_tiles, pieces, n, dev.g);
-	PCACHK(hipGetLastError());
-	PCACHK(hipEventRecord(dev.ev[2], 0));
-	PCACHK(hipEventSynchronize(dev.ev[2]));
-	PCACHK(hipEventElapsedTime(&ms, dev.ev[0], dev.ev[1]));
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(dev.ev[2], 0));
+	HIPCHK(hipEventSynchronize(dev.ev[2]));
+	HIPCHK(hipEventElapsedTime(&ms, dev.ev[0], dev.ev[1]));
 	tm.centre_ms = ms;
-	PCACHK(hipEventElapsedTime(&ms, dev.ev[1], dev.ev[2]));
+	HIPCHK(hipEventElapsedTime(&ms, dev.ev[1], dev.ev[2]));
 	tm.gram_ms = ms;
 	tm.gram_flops = (uint64_t) n * (n + 1ull) * p;
 	tm.gram_bytes = (uint64_t) n_tiles * 2ull * kTile * dev.p_pad * 8ull            /* both panels of every tile */
 	    + 2ull * pieces * n_tiles * kTile * kTile * 8ull + (uint64_t) n * n * 8ull;  /* partial tiles out and in, G */
 	tm.gram_tiles = n_tiles;
 	tm.gram_split = pieces;
-done:
-	return rc;
+	return 0;
 }
 
 } // namespace
@@ -315,19 +316,15 @@ extern "C" __attribute__((visibility("default"))) int ntsm_pca_gram(int device, 
 		int centre, uint32_t split, double *gram, double *means, ntsm_pca_times *times)
 {
 	if (!args_ok(p, n, a) || !gram) return NTSM_PCA_E_ARG;
-	int rc = 0;
 	ntsm_pca_times tm = {};
 	Device dev;
-	if ((rc = gram_on_device(dev, device, p, n, a, centre, split, tm)) != 0) return rc;
-	{
-		auto t0 = std::chrono::steady_clock::now();
-		PCACHK(hipMemcpy(gram, dev.g, (size_t) n * n * sizeof(double), hipMemcpyDeviceToHost));
-		if (means) PCACHK(hipMemcpy(means, dev.means, p * sizeof(double), hipMemcpyDeviceToHost));
-		tm.download_ms = ms_since(t0);
-	}
+	if (const int rc = gram_on_device(dev, device, p, n, a, centre, split, tm)) return rc;
+	auto t0 = std::chrono::steady_clock::now();
+	HIPCHK(hipMemcpy(gram, dev.g, (size_t) n * n * sizeof(double), hipMemcpyDeviceToHost));
+	if (means) HIPCHK(hipMemcpy(means, dev.means, p * sizeof(double), hipMemcpyDeviceToHost));
+	tm.download_ms = ms_since(t0);
 	if (times) *times = tm;
-done:
-	return rc;
+	return 0;
 }
 
 extern "C" __attribute__((visibility("default"))) int ntsm_pca_run(int device, uint64_t p, uint32_t n, const double *a,
@@ -336,71 +333,67 @@ extern "C" __attribute__((visibility("default"))) int ntsm_pca_run(int device, u
 	if (!args_ok(p, n, a) || n < 2 || d < 1 || d > n || d > p || !eigval || !rot || !comp) return NTSM_PCA_E_ARG;
 	const Solver &sv = solver_bind();
 	if (!sv.ok) return NTSM_PCA_E_SOLVER_MISSING;
-	int rc = 0;
 	float ms = 0;
 	ntsm_pca_times tm = {};
 	Device dev;
-	rocblas_handle handle = nullptr;
+	Handle handle(sv);
 	rocblas_int info = 0;
 	const uint32_t d_pad = (d + kProjComp - 1) / kProjComp * kProjComp;
 	std::vector<double> w(n), s(d_pad, 1.0);
-	if ((rc = gram_on_device(dev, device, p, n, a, 1, split, tm)) != 0) return rc;
+	if (const int rc = gram_on_device(dev, device, p, n, a, 1, split, tm)) return rc;
 
 	/* eigenpairs of G: dsyevd overwrites G with the eigenvectors (column-major), eigenvalues ascending in w */
-	PCACHK(hipMalloc(&dev.w, n * sizeof(double)));
-	PCACHK(hipMalloc(&dev.e, n * sizeof(double)));
-	PCACHK(hipMalloc(&dev.info, sizeof(rocblas_int)));
+	HIPCHK(dev.buf.alloc(&dev.w, n));
+	HIPCHK(dev.buf.alloc(&dev.e, n));
+	HIPCHK(dev.buf.alloc(&dev.info, 1));
 	{
 		auto t0 = std::chrono::steady_clock::now();
-		if (sv.create_handle(&handle) != rocblas_status_success) { rc = NTSM_PCA_E_SOLVER; goto done; }
-		(void) sv.set_atomics_mode(handle, rocblas_atomics_not_allowed);    /* the same bits on every run */
-		const rocblas_status st = sv.dsyevd(handle, rocblas_evect_original, rocblas_fill_upper, (rocblas_int) n, dev.g, (rocblas_int) n,
+		if (sv.create_handle(&handle.h) != rocblas_status_success) return NTSM_PCA_E_SOLVER;
+		(void) sv.set_atomics_mode(handle.h, rocblas_atomics_not_allowed);    /* the same bits on every run */
+		const rocblas_status st = sv.dsyevd(handle.h, rocblas_evect_original, rocblas_fill_upper, (rocblas_int) n, dev.g, (rocblas_int) n,
 		    dev.w, dev.e, dev.info);
 		if (st != rocblas_status_success) {
 			fprintf(stderr, "ntsm_pca: rocsolver_dsyevd returned status %d\n", (int) st);
-			rc = NTSM_PCA_E_SOLVER;
-			goto done;
+			return NTSM_PCA_E_SOLVER;
 		}
-		PCACHK(hipDeviceSynchronize());
-		PCACHK(hipMemcpy(&info, dev.info, sizeof(info), hipMemcpyDeviceToHost));
-		PCACHK(hipMemcpy(w.data(), dev.w, n * sizeof(double), hipMemcpyDeviceToHost));
+		HIPCHK(hipDeviceSynchronize());
+		HIPCHK(hipMemcpy(&info, dev.info, sizeof(info), hipMemcpyDeviceToHost));
+		HIPCHK(hipMemcpy(w.data(), dev.w, n * sizeof(double), hipMemcpyDeviceToHost));
 		tm.eigen_ms = ms_since(t0);
 		if (info != 0) {
 			fprintf(stderr, "ntsm_pca: rocsolver_dsyevd did not converge (info = %d)\n", (int) info);
-			rc = NTSM_PCA_E_SOLVER;
-			goto done;
+			return NTSM_PCA_E_SOLVER;
 		}
 	}
 	for (uint32_t i = 0; i < d; ++i) {
 		const double l = w[n - 1 - i], l1 = w[n - 1];
 		if (!(l > (double) n * std::numeric_limits<double>::epsilon() * l1)) {
 			if (bad_component) *bad_component = i;
-			rc = NTSM_PCA_E_RANK;
-			goto done;
+			return NTSM_PCA_E_RANK;
 		}
 		eigval[i] = l;
 		s[i] = std::sqrt(l);
 	}
 
-	PCACHK(hipMalloc(&dev.s, d_pad * sizeof(double)));
-	PCACHK(hipMalloc(&dev.ud, (size_t) n * d_pad * sizeof(double)));
-	PCACHK(hipMalloc(&dev.t, (size_t) n * d * sizeof(double)));
-	PCACHK(hipMalloc(&dev.v, (size_t) p * d * sizeof(double)));
-	PCACHK(hipMemcpy(dev.s, s.data(), d_pad * sizeof(double), hipMemcpyHostToDevice));
-	PCACHK(hipEventRecord(dev.ev[0], 0));
+	HIPCHK(dev.buf.alloc(&dev.s, d_pad));
+	HIPCHK(dev.buf.alloc(&dev.ud, (size_t) n * d_pad));
+	HIPCHK(dev.buf.alloc(&dev.t, (size_t) n * d));
+	HIPCHK(dev.buf.alloc(&dev.v, (size_t) p * d));
+	HIPCHK(hipMemcpy(dev.s, s.data(), d_pad * sizeof(double), hipMemcpyHostToDevice));
+	HIPCHK(hipEventRecord(dev.ev[0], 0));
 	ntsm_pca_scores<<<dim3((unsigned) (((size_t) n * d_pad + 255) / 256)), dim3(256)>>>(dev.g, n, d, d_pad, dev.s, dev.ud, dev.t);
-	PCACHK(hipGetLastError());
+	HIPCHK(hipGetLastError());
 	ntsm_pca_project<<<dim3((unsigned) (dev.p_pad / (4 * kProjRows)), d_pad / kProjComp), dim3(256)>>>(dev.a, dev.ld, n, p, dev.ud, d_pad,
 	    dev.s, d, dev.v);
-	PCACHK(hipGetLastError());
-	PCACHK(hipEventRecord(dev.ev[1], 0));
-	PCACHK(hipEventSynchronize(dev.ev[1]));
-	PCACHK(hipEventElapsedTime(&ms, dev.ev[0], dev.ev[1]));
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(dev.ev[1], 0));
+	HIPCHK(hipEventSynchronize(dev.ev[1]));
+	HIPCHK(hipEventElapsedTime(&ms, dev.ev[0], dev.ev[1]));
 	tm.project_ms = ms;
 	{
 		auto t0 = std::chrono::steady_clock::now();
-		PCACHK(hipMemcpy(rot, dev.v, (size_t) p * d * sizeof(double), hipMemcpyDeviceToHost));
-		PCACHK(hipMemcpy(comp, dev.t, (size_t) n * d * sizeof(double), hipMemcpyDeviceToHost));
+		HIPCHK(hipMemcpy(rot, dev.v, (size_t) p * d * sizeof(double), hipMemcpyDeviceToHost));
+		HIPCHK(hipMemcpy(comp, dev.t, (size_t) n * d * sizeof(double), hipMemcpyDeviceToHost));
 		tm.download_ms = ms_since(t0);
 	}
 	/* sign (sklearn's svd_flip, v-based): the entry of v_i with the largest magnitude, the first on a tie, is positive */
@@ -416,7 +409,5 @@ extern "C" __attribute__((visibility("default"))) int ntsm_pca_run(int device, u
 		for (uint32_t j = 0; j < n; ++j) comp[(size_t) j * d + i] = -comp[(size_t) j * d + i];
 	}
 	if (times) *times = tm;
-done:
-	if (handle) (void) sv.destroy_handle(handle);
-	return rc;
+	return 0;
 }

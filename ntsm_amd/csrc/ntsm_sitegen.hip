@@ -25,6 +25,8 @@
 #include <vector>
 
 #include "../../include/ntsm_sitegen_hip.h"
+#define NTSM_HIP_TAG "ntsm_sitegen"
+#include "ntsm_hip_scope.h"
 
 #define NTSM_API extern "C" __attribute__((visibility("default")))
 
@@ -156,26 +158,24 @@ struct ntsm_sitegen {
 
 namespace {
 
-#define HIP_TRY(e) do { if ((e) != hipSuccess) return -2; } while (0)
-
 int launch(ntsm_sitegen *s)
 {
 	if (s->fresh && s->fill >= s->k) {
 		const uint64_t n = (s->fill + 15) & ~15ull;
 		memset(s->stage + s->fill, 'N', n - s->fill);
 		double t0 = now_ms();
-		HIP_TRY(hipMemcpyAsync(s->d_genome, s->stage, n, hipMemcpyHostToDevice, s->stream));
-		HIP_TRY(hipStreamSynchronize(s->stream));
+		HIPCHK(hipMemcpyAsync(s->d_genome, s->stage, n, hipMemcpyHostToDevice, s->stream));
+		HIPCHK(hipStreamSynchronize(s->stream));
 		s->times.upload_ms += now_ms() - t0;
 		const uint64_t lanes = (n + kStretch - 1) / kStretch;
 		const uint32_t blocks = (uint32_t)((lanes + kBlock - 1) / kBlock);
-		HIP_TRY(hipEventRecord(s->ev0, s->stream));
+		HIPCHK(hipEventRecord(s->ev0, s->stream));
 		hipLaunchKernelGGL(scan_kernel, dim3(blocks), dim3(kBlock), 0, s->stream, s->d_genome, n, s->t);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipEventRecord(s->ev1, s->stream));
-		HIP_TRY(hipEventSynchronize(s->ev1));
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipEventRecord(s->ev1, s->stream));
+		HIPCHK(hipEventSynchronize(s->ev1));
 		float ms = 0;
-		HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+		HIPCHK(hipEventElapsedTime(&ms, s->ev0, s->ev1));
 		s->times.kernel_ms += ms;
 		if (n == kStageCap) {                            /* full launches only: their spread is the measurement's noise */
 			if (!s->times.full_launches || ms < s->times.full_kernel_ms_min) s->times.full_kernel_ms_min = ms;
@@ -262,19 +262,19 @@ int build_tables(ntsm_sitegen *s, const uint64_t *cands)
 
 	t0 = now_ms();
 	const size_t hits_bytes = (s->n_cands ? s->n_cands : 1) * sizeof(uint32_t);
-	HIP_TRY(hipMalloc(&s->d_bitmap, bitmap.size() * 4));
-	HIP_TRY(hipMalloc(&s->d_off, off.size() * 4));
-	HIP_TRY(hipMalloc(&s->d_kmer, kmer.size() * 8));
-	HIP_TRY(hipMalloc(&s->d_idx, idx.size() * 4));
-	HIP_TRY(hipMalloc(&s->d_hits, hits_bytes));
-	HIP_TRY(hipMalloc(&s->d_counters, 2 * sizeof(unsigned long long)));
-	HIP_TRY(hipMemcpy(s->d_bitmap, bitmap.data(), bitmap.size() * 4, hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(s->d_off, off.data(), off.size() * 4, hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(s->d_kmer, kmer.data(), kmer.size() * 8, hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(s->d_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice));
-	HIP_TRY(hipMemset(s->d_hits, 0, hits_bytes));
-	HIP_TRY(hipMemset(s->d_counters, 0, 2 * sizeof(unsigned long long)));
-	HIP_TRY(hipDeviceSynchronize());
+	HIPCHK(hipMalloc(&s->d_bitmap, bitmap.size() * 4));
+	HIPCHK(hipMalloc(&s->d_off, off.size() * 4));
+	HIPCHK(hipMalloc(&s->d_kmer, kmer.size() * 8));
+	HIPCHK(hipMalloc(&s->d_idx, idx.size() * 4));
+	HIPCHK(hipMalloc(&s->d_hits, hits_bytes));
+	HIPCHK(hipMalloc(&s->d_counters, 2 * sizeof(unsigned long long)));
+	HIPCHK(hipMemcpy(s->d_bitmap, bitmap.data(), bitmap.size() * 4, hipMemcpyHostToDevice));
+	HIPCHK(hipMemcpy(s->d_off, off.data(), off.size() * 4, hipMemcpyHostToDevice));
+	HIPCHK(hipMemcpy(s->d_kmer, kmer.data(), kmer.size() * 8, hipMemcpyHostToDevice));
+	HIPCHK(hipMemcpy(s->d_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice));
+	HIPCHK(hipMemset(s->d_hits, 0, hits_bytes));
+	HIPCHK(hipMemset(s->d_counters, 0, 2 * sizeof(unsigned long long)));
+	HIPCHK(hipDeviceSynchronize());
 	s->times.table_upload_ms = now_ms() - t0;
 	s->times.table_bytes = bitmap.size() * 4 + off.size() * 4 + kmer.size() * 8 + idx.size() * 4;
 	t.bitmap = (const uint32_t *)s->d_bitmap;
@@ -283,6 +283,17 @@ int build_tables(ntsm_sitegen *s, const uint64_t *cands)
 	t.idx = (const uint32_t *)s->d_idx;
 	t.hits = (uint32_t *)s->d_hits;
 	t.counters = (unsigned long long *)s->d_counters;
+	return 0;
+}
+
+/* the stream, its two events and both ends of the staging buffer */
+int open_stage(ntsm_sitegen *s)
+{
+	HIPCHK(hipStreamCreate(&s->stream));
+	HIPCHK(hipEventCreate(&s->ev0));
+	HIPCHK(hipEventCreate(&s->ev1));
+	HIPCHK(hipHostMalloc((void **)&s->stage, kStageCap + 16, hipHostMallocDefault));
+	HIPCHK(hipMalloc((void **)&s->d_genome, kStageCap + 16));
 	return 0;
 }
 
@@ -308,8 +319,7 @@ NTSM_API int ntsm_sitegen_open(int device, uint32_t k, uint32_t x, uint64_t n_ca
 		return -1;
 	*out = nullptr;
 	static_assert(kPreheat >= 30 && kPreheat % 16 == 0 && kStretch % 16 == 0 && kStageCap % kStretch == 0, "stretch geometry");
-	if (hipSetDevice(device) != hipSuccess)
-		return -2;
+	HIPCHK(hipSetDevice(device));
 	ntsm_sitegen *s = new (std::nothrow) ntsm_sitegen;
 	if (!s)
 		return -2;
@@ -318,10 +328,8 @@ NTSM_API int ntsm_sitegen_open(int device, uint32_t k, uint32_t x, uint64_t n_ca
 	s->x = x;
 	s->n_cands = n_cands;
 	int rc = build_tables(s, cands);
-	if (!rc && (hipStreamCreate(&s->stream) != hipSuccess || hipEventCreate(&s->ev0) != hipSuccess || hipEventCreate(&s->ev1) != hipSuccess
-	            || hipHostMalloc((void **)&s->stage, kStageCap + 16, hipHostMallocDefault) != hipSuccess
-	            || hipMalloc((void **)&s->d_genome, kStageCap + 16) != hipSuccess))
-		rc = -2;
+	if (!rc)
+		rc = open_stage(s);
 	if (rc) {
 		ntsm_sitegen_close(s);
 		return rc;
@@ -340,8 +348,7 @@ NTSM_API int ntsm_sitegen_submit(ntsm_sitegen *s, const char *bases, uint64_t n,
 			return -1;
 		prev = ends[i];
 	}
-	if (hipSetDevice(s->device) != hipSuccess)
-		return -2;
+	HIPCHK(hipSetDevice(s->device));
 	double t0 = now_ms();
 	const double busy0 = s->times.upload_ms + s->times.kernel_ms;
 	uint64_t at = 0;
@@ -365,10 +372,9 @@ NTSM_API int ntsm_sitegen_hits(ntsm_sitegen *s, uint8_t *hits)
 {
 	if (!s || (s->n_cands && !hits))
 		return -1;
-	if (hipSetDevice(s->device) != hipSuccess)
-		return -2;
+	HIPCHK(hipSetDevice(s->device));
 	std::vector<uint32_t> h(s->n_cands ? s->n_cands : 1);
-	HIP_TRY(hipMemcpy(h.data(), s->d_hits, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(h.data(), s->d_hits, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
 	for (uint64_t i = 0; i < s->n_cands; i++)
 		hits[i] = (uint8_t)(h[i] < 255 ? h[i] : 255);
 	return 0;
@@ -378,10 +384,9 @@ NTSM_API int ntsm_sitegen_times_get(ntsm_sitegen *s, ntsm_sitegen_times *out)
 {
 	if (!s || !out)
 		return -1;
-	if (hipSetDevice(s->device) != hipSuccess)
-		return -2;
+	HIPCHK(hipSetDevice(s->device));
 	unsigned long long c[2];
-	HIP_TRY(hipMemcpy(c, s->d_counters, sizeof c, hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(c, s->d_counters, sizeof c, hipMemcpyDeviceToHost));
 	s->times.windows = c[0];
 	s->times.probes = c[1];
 	s->times.bitmap_tests = c[0] * (s->x ? 3 : 1);

@@ -17,10 +17,11 @@
 #include <algorithm>
 #include <chrono>
 #include <cstdint>
-#include <cstdio>
 #include <cstring>
 
 #include "../../include/ntsm_vcf_hip.h"
+#define NTSM_HIP_TAG "ntsm_vcf"
+#include "ntsm_hip_scope.h"
 
 namespace {
 
@@ -103,9 +104,6 @@ __global__ __launch_bounds__(256) void ntsm_vcf_sums(uint64_t n_sites, uint32_t 
 	first_undef[site] = first;
 }
 
-#define VCFCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
-	fprintf(stderr, "ntsm_vcf: %s failed: %s\n", #x, hipGetErrorString(e_)); rc = -2; goto done; } } while (0)
-
 double now_ms()
 {
 	return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -139,79 +137,81 @@ extern "C" int ntsm_vcf_run(int device, uint32_t n_samples, uint32_t multi,
 	}
 	const uint32_t v1 = multi, v2 = multi * 2u;               /* opt::multi, opt::multi * 2 (unsigned) */
 	const uint64_t n_cells = n_sites * (uint64_t) n_samples;
-	int rc = 0;
-	uint8_t *d_geno = nullptr;
-	uint64_t *d_key_off = nullptr, *d_site_off = nullptr;
-	uint32_t *d_ev_ord = nullptr, *d_ev_ls = nullptr, *d_site_keys = nullptr, *d_first = nullptr;
-	uint16_t *d_cells = nullptr;
-	double *d_sums = nullptr;
-	ntsm_vcf_warning *d_warn = nullptr;
-	unsigned long long *d_n_warn = nullptr, h_n_warn = 0, d_cap = std::min<uint64_t>(std::max<uint64_t>(warn_cap, 1), kWarnInit);
-	uint64_t launches = 0;
-	hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
+	double t_up = 0, t_down = 0;
 	float ms_state = 0, ms_sum = 0;
-	double t0 = now_ms(), t_up = 0, t_down = 0;
+	uint64_t launches = 0;
 	*n_warn = 0;
-	if (n_sites == 0) goto done;
-	VCFCHK(hipSetDevice(device));
-	VCFCHK(hipEventCreate(&e0));
-	VCFCHK(hipEventCreate(&e1));
-	VCFCHK(hipEventCreate(&e2));
-	/* +1 element everywhere: no zero-byte allocations */
-	VCFCHK(hipMalloc(&d_geno, n_lines * g_stride + kLane));
-	VCFCHK(hipMalloc(&d_key_off, (n_keys + 1) * sizeof(uint64_t)));
-	VCFCHK(hipMalloc(&d_ev_ord, (n_events + 1) * sizeof(uint32_t)));
-	VCFCHK(hipMalloc(&d_ev_ls, (n_events + 1) * sizeof(uint32_t)));
-	VCFCHK(hipMalloc(&d_site_off, (2 * n_sites + 1) * sizeof(uint64_t)));
-	VCFCHK(hipMalloc(&d_site_keys, (n_site_keys + 1) * sizeof(uint32_t)));
-	VCFCHK(hipMalloc(&d_cells, (n_cells + 1) * sizeof(uint16_t)));
-	VCFCHK(hipMalloc(&d_sums, n_sites * sizeof(double)));
-	VCFCHK(hipMalloc(&d_first, n_sites * sizeof(uint32_t)));
-	VCFCHK(hipMalloc(&d_warn, d_cap * sizeof(ntsm_vcf_warning)));
-	VCFCHK(hipMalloc(&d_n_warn, sizeof(unsigned long long)));
-	if (n_lines) VCFCHK(hipMemcpy(d_geno, geno, n_lines * g_stride, hipMemcpyHostToDevice));
-	VCFCHK(hipMemcpy(d_key_off, key_off, (n_keys + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
-	if (n_events) {
-		VCFCHK(hipMemcpy(d_ev_ord, ev_ord, n_events * sizeof(uint32_t), hipMemcpyHostToDevice));
-		VCFCHK(hipMemcpy(d_ev_ls, ev_ls, n_events * sizeof(uint32_t), hipMemcpyHostToDevice));
-	}
-	VCFCHK(hipMemcpy(d_site_off, site_off, (2 * n_sites + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
-	if (n_site_keys) VCFCHK(hipMemcpy(d_site_keys, site_keys, n_site_keys * sizeof(uint32_t), hipMemcpyHostToDevice));
-	t_up = now_ms() - t0;
-	for (;;) {                                                 /* a second pass only if the warning buffer overflowed */
-		VCFCHK(hipMemset(d_n_warn, 0, sizeof(unsigned long long)));
-		VCFCHK(hipEventRecord(e0, 0));
-		if (n_samples) {
-			const uint32_t n_chunks = (n_samples + kLane - 1) / kLane;
-			const uint32_t block = std::min<uint32_t>(256, (n_chunks + 63) / 64 * 64);
-			hipLaunchKernelGGL(ntsm_vcf_state, dim3((uint32_t) n_sites), dim3(block), 0, 0, n_samples, v1, v2, d_geno, g_stride,
-			    d_key_off, d_ev_ord, d_ev_ls, d_site_off, d_site_keys, d_cells, d_warn, d_cap, d_n_warn);
-			VCFCHK(hipGetLastError());
-			++launches;
+	/* the device part: a HIP failure leaves it at once, its buffers and events released, and the times below are still filled */
+	const auto on_device = [&]() -> int {
+		ntsm_hip::Buffers b;
+		ntsm_hip::Events<3> ev;
+		uint8_t *d_geno;
+		uint64_t *d_key_off, *d_site_off;
+		uint32_t *d_ev_ord, *d_ev_ls, *d_site_keys, *d_first;
+		uint16_t *d_cells;
+		double *d_sums;
+		ntsm_vcf_warning *d_warn;
+		unsigned long long *d_n_warn, h_n_warn = 0, d_cap = std::min<uint64_t>(std::max<uint64_t>(warn_cap, 1), kWarnInit);
+		int rc = 0;
+		double t0 = now_ms();
+		HIPCHK(hipSetDevice(device));
+		HIPCHK(ev.create());
+		/* +1 element everywhere: no zero-byte allocations */
+		HIPCHK(b.alloc(&d_geno, n_lines * g_stride + kLane));
+		HIPCHK(b.alloc(&d_key_off, n_keys + 1));
+		HIPCHK(b.alloc(&d_ev_ord, n_events + 1));
+		HIPCHK(b.alloc(&d_ev_ls, n_events + 1));
+		HIPCHK(b.alloc(&d_site_off, 2 * n_sites + 1));
+		HIPCHK(b.alloc(&d_site_keys, n_site_keys + 1));
+		HIPCHK(b.alloc(&d_cells, n_cells + 1));
+		HIPCHK(b.alloc(&d_sums, n_sites));
+		HIPCHK(b.alloc(&d_first, n_sites));
+		HIPCHK(b.alloc(&d_warn, d_cap));
+		HIPCHK(b.alloc(&d_n_warn, 1));
+		if (n_lines) HIPCHK(hipMemcpy(d_geno, geno, n_lines * g_stride, hipMemcpyHostToDevice));
+		HIPCHK(hipMemcpy(d_key_off, key_off, (n_keys + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
+		if (n_events) {
+			HIPCHK(hipMemcpy(d_ev_ord, ev_ord, n_events * sizeof(uint32_t), hipMemcpyHostToDevice));
+			HIPCHK(hipMemcpy(d_ev_ls, ev_ls, n_events * sizeof(uint32_t), hipMemcpyHostToDevice));
 		}
-		VCFCHK(hipEventRecord(e1, 0));
-		hipLaunchKernelGGL(ntsm_vcf_sums, dim3((uint32_t) ((n_sites + 255) / 256)), dim3(256), 0, 0, n_sites, n_samples, d_cells, d_sums, d_first);
-		VCFCHK(hipGetLastError());
-		VCFCHK(hipEventRecord(e2, 0));
-		VCFCHK(hipEventSynchronize(e2));
-		VCFCHK(hipMemcpy(&h_n_warn, d_n_warn, sizeof(h_n_warn), hipMemcpyDeviceToHost));
-		if (h_n_warn <= d_cap) break;
-		VCFCHK(hipFree(d_warn));
-		d_warn = nullptr;
-		d_cap = h_n_warn;
-		VCFCHK(hipMalloc(&d_warn, d_cap * sizeof(ntsm_vcf_warning)));
-	}
-	VCFCHK(hipEventElapsedTime(&ms_state, e0, e1));
-	VCFCHK(hipEventElapsedTime(&ms_sum, e1, e2));
-	*n_warn = h_n_warn;
-	t0 = now_ms();
-	if (n_cells) VCFCHK(hipMemcpy(cells, d_cells, n_cells * sizeof(uint16_t), hipMemcpyDeviceToHost));
-	VCFCHK(hipMemcpy(sums, d_sums, n_sites * sizeof(double), hipMemcpyDeviceToHost));
-	VCFCHK(hipMemcpy(first_undef, d_first, n_sites * sizeof(uint32_t), hipMemcpyDeviceToHost));
-	if (h_n_warn > warn_cap) rc = NTSM_VCF_E_CAPACITY;
-	else if (h_n_warn) VCFCHK(hipMemcpy(warn, d_warn, h_n_warn * sizeof(ntsm_vcf_warning), hipMemcpyDeviceToHost));
-	t_down = now_ms() - t0;
-done:
+		HIPCHK(hipMemcpy(d_site_off, site_off, (2 * n_sites + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
+		if (n_site_keys) HIPCHK(hipMemcpy(d_site_keys, site_keys, n_site_keys * sizeof(uint32_t), hipMemcpyHostToDevice));
+		t_up = now_ms() - t0;
+		for (;;) {                                                 /* a second pass only if the warning buffer overflowed */
+			HIPCHK(hipMemset(d_n_warn, 0, sizeof(unsigned long long)));
+			HIPCHK(hipEventRecord(ev[0], 0));
+			if (n_samples) {
+				const uint32_t n_chunks = (n_samples + kLane - 1) / kLane;
+				const uint32_t block = std::min<uint32_t>(256, (n_chunks + 63) / 64 * 64);
+				hipLaunchKernelGGL(ntsm_vcf_state, dim3((uint32_t) n_sites), dim3(block), 0, 0, n_samples, v1, v2, d_geno, g_stride,
+				    d_key_off, d_ev_ord, d_ev_ls, d_site_off, d_site_keys, d_cells, d_warn, d_cap, d_n_warn);
+				HIPCHK(hipGetLastError());
+				++launches;
+			}
+			HIPCHK(hipEventRecord(ev[1], 0));
+			hipLaunchKernelGGL(ntsm_vcf_sums, dim3((uint32_t) ((n_sites + 255) / 256)), dim3(256), 0, 0, n_sites, n_samples, d_cells, d_sums, d_first);
+			HIPCHK(hipGetLastError());
+			HIPCHK(hipEventRecord(ev[2], 0));
+			HIPCHK(hipEventSynchronize(ev[2]));
+			HIPCHK(hipMemcpy(&h_n_warn, d_n_warn, sizeof(h_n_warn), hipMemcpyDeviceToHost));
+			if (h_n_warn <= d_cap) break;
+			HIPCHK(b.release(&d_warn));                            /* freed first: the two sizes are never held together */
+			d_cap = h_n_warn;
+			HIPCHK(b.alloc(&d_warn, d_cap));
+		}
+		HIPCHK(hipEventElapsedTime(&ms_state, ev[0], ev[1]));
+		HIPCHK(hipEventElapsedTime(&ms_sum, ev[1], ev[2]));
+		*n_warn = h_n_warn;
+		t0 = now_ms();
+		if (n_cells) HIPCHK(hipMemcpy(cells, d_cells, n_cells * sizeof(uint16_t), hipMemcpyDeviceToHost));
+		HIPCHK(hipMemcpy(sums, d_sums, n_sites * sizeof(double), hipMemcpyDeviceToHost));
+		HIPCHK(hipMemcpy(first_undef, d_first, n_sites * sizeof(uint32_t), hipMemcpyDeviceToHost));
+		if (h_n_warn > warn_cap) rc = NTSM_VCF_E_CAPACITY;
+		else if (h_n_warn) HIPCHK(hipMemcpy(warn, d_warn, h_n_warn * sizeof(ntsm_vcf_warning), hipMemcpyDeviceToHost));
+		t_down = now_ms() - t0;
+		return rc;
+	};
+	const int rc = n_sites ? on_device() : 0;
 	if (times) {
 		times->upload_ms = t_up;
 		times->state_kernel_ms = ms_state;
@@ -221,11 +221,5 @@ done:
 		times->kernel_bytes = n_lines * (uint64_t) g_stride + n_events * 8 + (n_keys + 1) * 8 + n_site_keys * 4 + n_cells * 2;
 		times->state_launches = launches;
 	}
-	if (e0) (void) hipEventDestroy(e0);
-	if (e1) (void) hipEventDestroy(e1);
-	if (e2) (void) hipEventDestroy(e2);
-	(void) hipFree(d_geno); (void) hipFree(d_key_off); (void) hipFree(d_ev_ord); (void) hipFree(d_ev_ls);
-	(void) hipFree(d_site_off); (void) hipFree(d_site_keys); (void) hipFree(d_cells); (void) hipFree(d_sums);
-	(void) hipFree(d_first); (void) hipFree(d_warn); (void) hipFree(d_n_warn);
 	return rc;
 }

@@ -18,7 +18,7 @@ import pytest
 from oracle_binding import EvalOracle, ROOT
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_eval import FIELDS, files_for, random_samples, same_bits, write_counts  # noqa: E402
+from test_eval import FIELDS, files_for, py_pair, random_samples, same_bits, write_counts  # noqa: E402
 
 EVAL = os.path.join(ROOT, "build", "ntsmEval")
 DBL_MAX = 1.7976931348623157e308
@@ -302,6 +302,75 @@ def test_score_pairs_equal_all_pairs_records(tmp_path):
                 ne = np.flatnonzero(np.ascontiguousarray(got[f]).view(bits) != want.view(bits))
                 assert ne.size == 0, (n, c, f, [(int(pi[p]), int(pk[p]), got[f][p], want[p]) for p in ne[:5]])
         sess.close()
+
+
+NO_DEVICE = 1 << 20                              # a device ordinal that no machine has: hipSetDevice refuses it (an API error)
+
+
+def zero_records(count):
+    import ntsm_amd.eval as ev
+    return np.zeros(count, dtype=ev.RECORD).tobytes()
+
+
+@pytest.mark.gpu
+def test_eval_entry_points_return_early_on_degenerate_shapes():
+    """Every entry point of include/ntsm_eval_hip.h on the shapes it answers without a kernel: one sample (no pair), no
+    site (all-zero records, a +0.0 cloud), an empty pair list; a listed pair that names a sample twice or a sample that
+    does not exist is refused with -1 and the session goes on scoring, bit-equal to ntsm_eval_pairs."""
+    import ctypes as C
+    import ntsm_amd.eval as ev
+    rec, _ = ev.pairs(np.zeros((1, 5, 2), dtype=np.uint32))
+    assert len(rec) == 0
+    rec, _ = ev.pairs(np.zeros((3, 0, 2), dtype=np.uint32))
+    assert len(rec) == 3 and rec.tobytes() == zero_records(3)
+
+    sess = ev.Session(np.full((1, 5, 2), 7, dtype=np.uint32))
+    pi, pk, dist, _ = sess.candidates(np.zeros((1, 2)), np.array([DBL_MAX]))
+    assert len(pi) == 0 and len(pk) == 0 and len(dist) == 0
+    got, _ = sess.score_pairs([], [])
+    assert len(got) == 0
+    sess.close()
+
+    sess = ev.Session(np.zeros((3, 0, 2), dtype=np.uint32))
+    cloud = np.full((3, 2), np.nan)
+    norm, rot = np.zeros(1, dtype=np.longdouble), np.zeros(2, dtype=np.longdouble)      # no site: neither is read
+    assert ev.lib.ntsm_eval_project(sess.h, ev._ld_ptr(norm), ev._ld_ptr(rot), 2, cloud.ctypes.data, C.byref(C.c_double())) == 0
+    assert cloud.tobytes() == np.zeros((3, 2)).tobytes()                                # +0.0, by the bits
+    got, _ = sess.score_pairs([0, 2], [1, 0])
+    assert len(got) == 2 and got.tobytes() == zero_records(2)
+    sess.close()
+
+    s = cohort(np.random.default_rng(24), 3, 4)
+    want, _ = ev.pairs(s)
+    sess = ev.Session(s)
+    for pi, pk in (([1], [1]), ([0], [3])):
+        with pytest.raises(RuntimeError, match=r"failed: -1$"):
+            sess.score_pairs(pi, pk)
+        got, _ = sess.score_pairs([0], [1])
+        assert got.tobytes() == want[:1].tobytes()
+    sess.close()
+
+
+@pytest.mark.gpu
+def test_eval_reports_a_refused_device_and_works_afterwards():
+    """ntsm_eval_pairs and ntsm_eval_open on a device ordinal that does not exist return -2 (hipSetDevice's error, no
+    device fault), and the next calls on device 0 give the record of py_pair for 2 samples x 3 sites."""
+    import ntsm_amd.eval as ev
+    s = np.array([[[9, 0], [4, 5], [0, 0]], [[0, 8], [6, 3], [7, 7]]], dtype=np.uint32)
+    with pytest.raises(RuntimeError, match=r"ntsm_eval_pairs failed: -2$"):
+        ev.pairs(s, device=NO_DEVICE)
+    with pytest.raises(RuntimeError, match=r"ntsm_eval_open failed: -2$"):
+        ev.Session(s, device=NO_DEVICE)
+    want = py_pair(s[0], s[1], 1)
+    assert want["n_valid"] == 2 and want["ibs0"] == 1 and want["shared_hets"] == 1
+    rec, _ = ev.pairs(s)
+    sess = ev.Session(s)
+    got, _ = sess.score_pairs([0], [1])
+    sess.close()
+    for r in (rec, got):
+        assert len(r) == 1
+        for f in FIELDS:
+            assert same_bits(r[f][0], want[f]) if f.startswith("sum") else int(r[f][0]) == want[f], (f, r[f][0], want[f])
 
 
 @pytest.mark.gpu

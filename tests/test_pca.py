@@ -327,6 +327,20 @@ def test_gram_is_exact_on_integers(built, p, n, split):
 
 
 @pytest.mark.gpu
+def test_gram_reports_a_refused_device_and_works_afterwards(built):
+    """ntsm_pca_gram on a device ordinal that does not exist returns NTSM_PCA_E_HIP (hipSetDevice's error, no device
+    fault), and the next call on device 0 gives the exact Gram matrix of a 2 x 2 matrix."""
+    import ntsm_amd.pca as pca
+    a = np.array([[1.0, 3.0], [6.0, 2.0]])
+    with pytest.raises(RuntimeError, match=r"ntsm_pca_gram failed: %d$" % pca.E_HIP):
+        pca.gram(a, device=1 << 20)
+    g, means, _ = pca.gram(a, centre=False)
+    assert g.tolist() == [[37.0, 15.0], [15.0, 13.0]] and means.tolist() == [2.0, 4.0]
+    g, _, _ = pca.gram(a, centre=True)
+    assert g.tolist() == [[5.0, -5.0], [-5.0, 5.0]]
+
+
+@pytest.mark.gpu
 def test_gram_of_real_cells_is_symmetric_and_repeatable(built):
     """Non-integer cells: G is symmetric bit for bit, two calls agree bit for bit, and it is the float64 product to the
     summation bound of the two products, 2 (p + 1) u |Ac|^T |Ac|."""

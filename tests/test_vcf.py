@@ -420,6 +420,22 @@ def test_device_step_regrows_its_warning_buffer(built):
 
 
 @pytest.mark.gpu
+def test_device_step_reports_a_refused_device_and_works_afterwards(built):
+    """ntsm_vcf_run on a device ordinal that does not exist returns -2 (hipSetDevice's error, no device fault), and the
+    next call on device 0 gives the model's answer for one site with one key."""
+    import ntsm_amd.vcf as V
+    geno = np.array([[V.HOM1, V.HET, V.HOM2]], dtype=np.uint8)
+    key_events, site_ref, site_var = [[(0, 0, 0)]], [[0]], [[]]
+    with pytest.raises(RuntimeError, match=r"ntsm_vcf_run failed: -2$"):
+        V.run(geno, 20, key_events, site_ref, site_var, device=1 << 20)
+    cells, sums, first, warn, times = V.run(geno, 20, key_events, site_ref, site_var)
+    ec, es, ef, ew = numpy_model(geno, 20, key_events, site_ref, site_var)
+    assert ec.tolist() == [[40, 20, 0]] and es.tolist() == [2.0] and ef.tolist() == [2] and ew == []
+    assert np.array_equal(cells, ec) and np.array_equal(sums.view(np.uint64), es.view(np.uint64)) and np.array_equal(first, ef)
+    assert len(warn) == 0 and times.state_launches == 1
+
+
+@pytest.mark.gpu
 def test_chain_centre_file_into_ntsmEval(built, tmp_path):
     """ntsmVCF -p's centre file and a synthetic rotation through ntsmEval -p ROT -n CENTRE give the stdout that the
     restatements (tests/vcf_restatement.cpp for the centres, tests/eval_pca_restatement.cpp for the search) expect."""

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/isa_hash.py [--check FILE | --write FILE] [-D...] -- per-kernel hash of the gfx950 ISA the compiler emits for the
+"""tools/isa_hash.py [--cohort] [--check FILE | --write FILE] [-D...] -- per-kernel hash of the gfx950 ISA the compiler emits for the
 kernel translation units of libntsm_hip.so (ntsm_amd/csrc/kernels_generic.hip, kernels_mz.hip).
 
 A kernel's hash is the SHA-256 (first 16 hex digits) of its instructions with comments, directives and local label numbers
@@ -8,19 +8,26 @@ sources around the kernels (round 5: the split of ntsm_hip.hip into six translat
 ntsm_hooks.h) left the product kernels bit-identical, and by tools/make_traffic.py-style profile gating.
   --write FILE   record the hashes (profiles/r05_isa_hashes.json)
   --check FILE   compare with a recorded file; exit 1 and list the kernels that differ
+  --cohort       the kernels of the five cohort libraries (ntsm_eval, ntsm_eval_pca, ntsm_vcf, ntsm_pca, ntsm_sitegen) instead,
+                 each source with the flags the Makefile gives it (profiles/r12_eval_refactor/isa_*.json)
 Extra -D flags go to the compiler (e.g. -DNTSM_WITH_TAB)."""
 import hashlib, json, os, re, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCES = ["ntsm_amd/csrc/kernels_generic.hip", "ntsm_amd/csrc/kernels_mz.hip", "ntsm_amd/csrc/kernels_run.hip"]
+# source -> the flags its Makefile rule adds to HIPFLAGS
+SOURCES = {"ntsm_amd/csrc/kernels_generic.hip": ["-fvisibility=hidden"], "ntsm_amd/csrc/kernels_mz.hip": ["-fvisibility=hidden"],
+           "ntsm_amd/csrc/kernels_run.hip": ["-fvisibility=hidden"]}
+COHORT = {"ntsm_amd/csrc/ntsm_eval.hip": ["-ffp-contract=off"], "ntsm_amd/csrc/ntsm_eval_pca.hip": ["-ffp-contract=off"],
+          "ntsm_amd/csrc/ntsm_vcf.hip": ["-ffp-contract=off"], "ntsm_amd/csrc/ntsm_pca.hip": ["-fvisibility=hidden", "-ffp-contract=off"],
+          "ntsm_amd/csrc/ntsm_sitegen.hip": ["-fvisibility=hidden"]}
 
 
 def kernel_hashes(defs=(), sources=SOURCES):
     out = {}
     with tempfile.TemporaryDirectory() as td:
-        for src in sources:
+        for src, flags in sources.items():
             asm = os.path.join(td, "k.s")
-            subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fvisibility=hidden", "-S", "--cuda-device-only"] + list(defs) +
+            subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC"] + flags + ["-S", "--cuda-device-only"] + list(defs) +
                                   ["-o", asm, os.path.join(ROOT, src)], stderr=subprocess.DEVNULL, cwd=td)
             text = open(asm).read()
             for m in re.finditer(r"^(_Z\w+):\s*(?:;.*)?$", text, re.M):
@@ -37,7 +44,7 @@ def kernel_hashes(defs=(), sources=SOURCES):
 def main():
     args = sys.argv[1:]
     defs = [a for a in args if a.startswith("-D")]
-    h = kernel_hashes(defs)
+    h = kernel_hashes(defs, COHORT if "--cohort" in args else SOURCES)
     if "--write" in args:
         json.dump({"flags": defs, "kernels": h}, open(args[args.index("--write") + 1], "w"), indent=1, sort_keys=True)
     for k in sorted(h):

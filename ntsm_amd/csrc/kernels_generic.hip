@@ -44,9 +44,9 @@ __global__ __launch_bounds__(kThreads, PER_READ ? 3 : 4) void ntsm_count_kernel(
 			for (int q = 0; q < VPT; ++q) {
 				const int v = t + kThreads * q;
 #if NTSM_STREAM_NT
-				const u32x4 nt = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(p.base + ts + 16ll * v));
+				const ntsm_u32x4 nt = __builtin_nontemporal_load(reinterpret_cast<const ntsm_u32x4 *>(p.base + ts + 16ll * v));
 #else
-				const u32x4 nt = *reinterpret_cast<const u32x4 *>(p.base + ts + 16ll * v);
+				const ntsm_u32x4 nt = *reinterpret_cast<const ntsm_u32x4 *>(p.base + ts + 16ll * v);
 #endif
 				const int row = 1 + (16 * v) / C, col = (16 * v) % C;
 				*reinterpret_cast<uint4 *>(tile + row * ROW + col) = make_uint4(nt.x, nt.y, nt.z, nt.w);
@@ -126,10 +126,8 @@ __global__ __launch_bounds__(kThreads, PER_READ ? 3 : 4) void ntsm_count_kernel(
 						const uint32_t klo = (uint32_t) cn[i], khi = (uint32_t) (cn[i] >> 32);
 						const unsigned long long b1 = 2ull * (ntsm_h1(hh[i]) >> bshift);
 						const unsigned long long b2 = 2ull * (ntsm_h2(hh[i]) >> bshift);
-						if (ba[j].x == klo && ba[j].y == khi) slot = (long long) b1;
-						else if (ba[j].z == klo && ba[j].w == khi) slot = (long long) b1 + 1;
-						else if (bb[j].x == klo && bb[j].y == khi) slot = (long long) b2;
-						else if (bb[j].z == klo && bb[j].w == khi) slot = (long long) b2 + 1;
+						slot = ntsm_slot_in_bucket(ba[j], b1, klo, khi);             /* both buckets are here already: no "bucket 1 full" test */
+						if (slot < 0) slot = ntsm_slot_in_bucket(bb[j], b2, klo, khi);
 						if (slot >= 0) {
 							++nh;
 							if (PER_READ) {
@@ -144,16 +142,7 @@ __global__ __launch_bounds__(kThreads, PER_READ ? 3 : 4) void ntsm_count_kernel(
 		}
 #undef NTSM_ROLL
 	}
-	/* per-wave reduction, one 64-bit atomic per wave and counter */
-#pragma unroll
-	for (int off = 32; off > 0; off >>= 1) {
-		nk += __shfl_down(nk, off, 64);
-		nh += __shfl_down(nh, off, 64);
-	}
-	if ((t & 63) == 0) {
-		if (nk) atomicAdd(p.totals + 0, p.sign * (unsigned long long) nk);
-		if (nh) atomicAdd(p.totals + 1, p.sign * (unsigned long long) nh);
-	}
+	ntsm_add_totals(p, ntsm_wave_sum(nk), ntsm_wave_sum(nh), t);   /* both per lane */
 }
 
 /* dense[i] = count of slot_of[i]; tail = totals */

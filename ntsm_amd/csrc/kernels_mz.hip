@@ -44,17 +44,6 @@ constexpr int kFastC = NTSM_FAST_C;
 [[maybe_unused]] constexpr int kListC = 128;                            /* list mode (tiles handed over by the tabulated kernel, make tab): always 32 KiB tiles */
 constexpr int kQueueCap = 128;                         /* < 64 left over + one position's burst of <= 64 */
 
-/* LDS image of a tile: row r (C bytes) = stream bytes of thread r-1 (row 0 = the 32 bytes in front of the tile, in its
- * last two slots).  The 16-byte slots of a row are permuted per row so that the per-thread ds_read_b64 of "slot s of my
- * row" spreads over the banks without padding: C = 128: slot s sits at s ^ ((r >> 1) & 7) (conflict free); other C:
- * rotated by r >> 3 (two-way). */
-template <int C>
-__device__ __forceinline__ int ntsm_tile_addr(int row, int byte_in_row)
-{
-	if (C == 128) return row * C + ((((byte_in_row >> 4) ^ (row >> 1)) & 7) << 4) + (byte_in_row & 15);
-	return row * C + (int) ((((uint32_t) (byte_in_row >> 4) + ((uint32_t) row >> 3)) % (uint32_t) (C / 16)) << 4) + (byte_in_row & 15);
-}
-
 /* KMODE 0: k = 19 with every constant folded (the reference default and all BASELINE configurations).
  * KMODE 2 .. 9: any other k of ntsm_fast_plan(), KMODE = number of minimizer candidates; k, the minimizer length and
  * the candidate offset are run-time parameters, the rolling words are 64 bits wide (two registers each).
@@ -84,6 +73,7 @@ __global__ __launch_bounds__(kThreads, PER_READ ? 3 : NTSM_FAST_WAVES) void ntsm
 	const NtsmBlockMap blk_map = p.blk_map;
 	/* Buffer resource over the filter blocks, 16-byte stride: the load takes a block INDEX (idxen), the address
 	 * arithmetic and the range check (index >= number of blocks: returns 0, no memory request) are the hardware's. */
+	/* (as in kernels_run.hip: one helper for the descriptors reorders the prologue of 26 of the 36 kernels, forms.txt) */
 	const unsigned long long blk_base = (unsigned long long) p.blocks;
 	const ntsm_i32x4 blk_rsrc = { (int) (uint32_t) blk_base, (int) ((uint32_t) (blk_base >> 32) | (16u << 16)),
 			(int) (p.blk_bytes >> 4), 0x00020000 };
@@ -102,6 +92,7 @@ __global__ __launch_bounds__(kThreads, PER_READ ? 3 : NTSM_FAST_WAVES) void ntsm
 		if (kWithTab && ti >= p.n_tiles) continue;
 		const long long ts = p.t0 + (long long) (ti * (unsigned long long) (kThreads * C));
 		__syncthreads();
+		/* staging: the same lines as in kernels_run.hip -- one shared function reorders some 200 instructions of every kernel (forms.txt) */
 		if (ts >= p.lo && ts + kThreads * C <= p.hi) {
 			/* interior tile: plain coalesced loads (the boundary logic of ntsm_load_vec costs ~100 VALU instructions per
 			 * vector, 6.5 per base position -- a sixth of this kernel's instruction count when it ran for every tile) */
@@ -117,9 +108,9 @@ __global__ __launch_bounds__(kThreads, PER_READ ? 3 : NTSM_FAST_WAVES) void ntsm
 #ifdef NTSM_STREAM_AUX
 				const ntsm_u32x4 nt = __builtin_amdgcn_raw_buffer_load_b128(st_rsrc, 16 * v, 0, NTSM_STREAM_AUX);
 #elif NTSM_STREAM_NT
-				const u32x4 nt = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(p.base + ts + 16ll * v));
+				const ntsm_u32x4 nt = __builtin_nontemporal_load(reinterpret_cast<const ntsm_u32x4 *>(p.base + ts + 16ll * v));
 #else
-				const u32x4 nt = *reinterpret_cast<const u32x4 *>(p.base + ts + 16ll * v);
+				const ntsm_u32x4 nt = *reinterpret_cast<const ntsm_u32x4 *>(p.base + ts + 16ll * v);
 #endif
 				*reinterpret_cast<uint4 *>(tile + ntsm_tile_addr<C>(1 + v / VPT, (v % VPT) * 16)) = make_uint4(nt.x, nt.y, nt.z, nt.w);
 			}
@@ -217,16 +208,7 @@ __global__ __launch_bounds__(kThreads, PER_READ ? 3 : NTSM_FAST_WAVES) void ntsm
 			/* stage 3 */
 			long long slot_of_hit = -1;
 			if (s2_v) {
-				long long slot = -1;
-				if (s2_ba.x == s2_klo && s2_ba.y == s2_khi) slot = (long long) s2_b1;
-				else if (s2_ba.z == s2_klo && s2_ba.w == s2_khi) slot = (long long) s2_b1 + 1;
-				else if ((s2_ba.x & s2_ba.y) != 0xFFFFFFFFu && (s2_ba.z & s2_ba.w) != 0xFFFFFFFFu) {
-					/* bucket 1 full and no match: the key can only be in bucket 2 */
-					const unsigned long long b2 = 2ull * (s2_g2 >> bshift);
-					const uint4 bb = *reinterpret_cast<const uint4 *>(p.keys + 2ull * b2);
-					if (bb.x == s2_klo && bb.y == s2_khi) slot = (long long) b2;
-					else if (bb.z == s2_klo && bb.w == s2_khi) slot = (long long) b2 + 1;
-				}
+				const long long slot = ntsm_find_slot(p.keys, s2_ba, s2_b1, s2_g2, bshift, s2_klo, s2_khi);
 				if (slot >= 0) {
 					++nh;
 					if (PER_READ) atomicAdd(p.read_hits + ntsm_read_of(p, (unsigned long long) (ts + (long long) s2_pos)), 1u);
@@ -275,10 +257,9 @@ __global__ __launch_bounds__(kThreads, PER_READ ? 3 : NTSM_FAST_WAVES) void ntsm
 						 * reverse order (bit reversal + swap inside the pairs reverses the groups) */
 						unsigned long long fw, rv;
 						if (gk >= 16) {
-							auto crev = [](uint32_t x) { const uint32_t y = __builtin_bitreverse32(~x); return ((y >> 1) & 0x55555555u) | ((y & 0x55555555u) << 1); };
 							const uint32_t g2 = 2u * gk - 32u, lowmask = (1u << g2) - 1u;       /* g2 <= 30 */
-							fw = ((unsigned long long) f3 << g2) | (crev(r) & lowmask);
-							rv = ((unsigned long long) r << g2) | (crev(f3) & lowmask);
+							fw = ((unsigned long long) f3 << g2) | (ntsm_rc16(r) & lowmask);
+							rv = ((unsigned long long) r << g2) | (ntsm_rc16(f3) & lowmask);
 						} else {
 							fw = f3 >> (32u - 2u * gk);
 							rv = r >> (32u - 2u * gk);
@@ -395,9 +376,7 @@ __global__ __launch_bounds__(kThreads, PER_READ ? 3 : NTSM_FAST_WAVES) void ntsm
 				for (int j = 4; j < 8; ++j) m2prev[j] = m2[j];
 			}
 		};
-		/* Phase C: four-bit test against the (possibly just fetched) block.  word << field (NTSM_KBITn: bit 31 - field)
-		 * puts the tested bit in the sign position -- the shifter takes the low five bits of the selected byte, so the
-		 * fields need no mask -- and the sign of the AND of the four is the verdict.  Positives go to the wave's queue
+		/* Phase C: four-bit test (ntsm_block_test) against the (possibly just fetched) block.  Positives go to the wave's queue
 		 * as { forward word of the first 16 bases, reverse word of the last 16 }.  (Queueing tile offsets instead and
 		 * rebuilding the window from the tile bytes at drain time was measured: 3 fewer instructions per position in
 		 * this loop, 53.2 instead of 52.2 ms per 3e8 reads.) */
@@ -410,16 +389,11 @@ __global__ __launch_bounds__(kThreads, PER_READ ? 3 : NTSM_FAST_WAVES) void ntsm
 				cur.z = sel ? B.bl[j].z : cur.z;
 				cur.w = sel ? B.bl[j].w : cur.w;
 				const uint32_t u = B.u[j], um = ntsm_kmer_mix(u);
-				uint32_t s0, s1, s2, s3;
-				asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_3 src1_sel:DWORD" : "=v"(s0) : "v"(u), "v"(cur.x));
-				asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_3 src1_sel:DWORD" : "=v"(s1) : "v"(um), "v"(cur.y));
-				asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_2 src1_sel:DWORD" : "=v"(s2) : "v"(um), "v"(cur.z));
-				asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_1 src1_sel:DWORD" : "=v"(s3) : "v"(um), "v"(cur.w));
-				const bool pass = (int32_t) (__builtin_amdgcn_bitop3_b32(s0, s1, s2, 0x80) & s3) < 0;
+				const bool pass = ntsm_block_test(u, um, cur);
 				const unsigned long long m = __builtin_amdgcn_ballot_w64(pass);
 				if (m) {
 					if (pass) {
-						const uint32_t at = qn + __builtin_amdgcn_mbcnt_hi((uint32_t) (m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) m, 0u));
+						const uint32_t at = qn + ntsm_mask_rank(m, 0u);
 						queue[at] = make_uint2(B.f3[j], B.r[j]);
 						if (PER_READ) qpos[at] = (uint16_t) (pos0 + j);
 					}
@@ -460,6 +434,7 @@ __global__ __launch_bounds__(kThreads, PER_READ ? 3 : NTSM_FAST_WAVES) void ntsm
 #undef NTSM_STEP
 #undef NTSM_MMER_G
 	}
+	/* not ntsm_add_totals: with it every one of the 36 kernels is different code (one v_mov_b32 moves, forms.txt) */
 #pragma unroll
 	for (int off = 32; off > 0; off >>= 1) nh += __shfl_down(nh, off, 64);
 	if ((t & 63) == 0) {
@@ -480,28 +455,25 @@ namespace ntsm_rt {
 
 int mz_tile_bytes() { return kThreads * kFastC; }
 
-hipError_t launch_mz(const NtsmCountParams &p, unsigned grid, hipStream_t st, int mode, bool per_read, bool two_level)
+/* one table for both forms: KMODE 0 and 2 .. 9 (a mode without a kernel is an error), with and without -m */
+template <bool TWO>
+hipError_t launch_mz_form(const NtsmCountParams &p, dim3 g, dim3 b, hipStream_t st, int mode, bool per_read)
 {
-	const dim3 g(grid), b(kThreads);
 #define NTSM_MZ_CASE(M_) \
-	case 2 * M_: hipLaunchKernelGGL((ntsm_count_mz_kernel<M_, false, kFastC, false>), g, b, 0, st, p); break; \
-	case 2 * M_ + 1: hipLaunchKernelGGL((ntsm_count_mz_kernel<M_, true, kFastC, false>), g, b, 0, st, p); break;
-#define NTSM_MZ2_CASE(M_) \
-	case 2 * M_: hipLaunchKernelGGL((ntsm_count_mz_kernel<M_, false, kFastC, true>), g, b, 0, st, p); break; \
-	case 2 * M_ + 1: hipLaunchKernelGGL((ntsm_count_mz_kernel<M_, true, kFastC, true>), g, b, 0, st, p); break;
-	if (two_level) {
-		switch (mode * 2 + (per_read ? 1 : 0)) {
-		NTSM_MZ2_CASE(0) NTSM_MZ2_CASE(2) NTSM_MZ2_CASE(3) NTSM_MZ2_CASE(4) NTSM_MZ2_CASE(5) NTSM_MZ2_CASE(6) NTSM_MZ2_CASE(7) NTSM_MZ2_CASE(8) NTSM_MZ2_CASE(9)
-		default: return hipErrorInvalidValue;
-		}
-	} else
+	case 2 * M_: hipLaunchKernelGGL((ntsm_count_mz_kernel<M_, false, kFastC, TWO>), g, b, 0, st, p); break; \
+	case 2 * M_ + 1: hipLaunchKernelGGL((ntsm_count_mz_kernel<M_, true, kFastC, TWO>), g, b, 0, st, p); break;
 	switch (mode * 2 + (per_read ? 1 : 0)) {
 	NTSM_MZ_CASE(0) NTSM_MZ_CASE(2) NTSM_MZ_CASE(3) NTSM_MZ_CASE(4) NTSM_MZ_CASE(5) NTSM_MZ_CASE(6) NTSM_MZ_CASE(7) NTSM_MZ_CASE(8) NTSM_MZ_CASE(9)
 	default: return hipErrorInvalidValue;
 	}
 #undef NTSM_MZ_CASE
-#undef NTSM_MZ2_CASE
 	return hipGetLastError();
+}
+
+hipError_t launch_mz(const NtsmCountParams &p, unsigned grid, hipStream_t st, int mode, bool per_read, bool two_level)
+{
+	const dim3 g(grid), b(kThreads);
+	return two_level ? launch_mz_form<true>(p, g, b, st, mode, per_read) : launch_mz_form<false>(p, g, b, st, mode, per_read);
 }
 
 #ifdef NTSM_WITH_TAB

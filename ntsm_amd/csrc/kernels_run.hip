@@ -58,20 +58,6 @@ constexpr int kCandQueue = (kCandAt - 1 + 64 + 15) / 16 * 16;   /* passing runs 
 constexpr int kKmerAt = NTSM_RUN_KMER_AT;
 constexpr int kKmerQueue = (kKmerAt - 1 + 64 + 15) / 16 * 16;   /* < kKmerAt left over + one expansion step's <= 64 */
 
-template <int C>
-__device__ __forceinline__ int ntsm_run_tile_addr(int row, int byte_in_row)
-{
-	if (C == 128) return row * C + ((((byte_in_row >> 4) ^ (row >> 1)) & 7) << 4) + (byte_in_row & 15);
-	return row * C + (int) ((((uint32_t) (byte_in_row >> 4) + ((uint32_t) row >> 3)) % (uint32_t) (C / 16)) << 4) + (byte_in_row & 15);
-}
-
-/* reverse complement of a 16-base word (oldest base in the top bits): complement, reverse the bits, swap inside the pairs */
-__device__ __forceinline__ uint32_t ntsm_rc16(uint32_t w)
-{
-	const uint32_t y = __builtin_bitreverse32(~w);
-	return ((y >> 1) & 0x55555555u) | ((y & 0x55555555u) << 1);
-}
-
 /* Order key of the 12-mer that ends at the newest base (ntsm_device.h: NTSM_RUN_ORDER): hash << 8 | position mod 16.  F holds the
  * forward code in its low 24 bits, R the reverse-complement code in its top 24. */
 __device__ __forceinline__ uint32_t ntsm_run_key(uint32_t F, uint32_t R, uint32_t pos16, uint32_t kmask)
@@ -109,6 +95,7 @@ __global__ __launch_bounds__(kThreads, NTSM_RUN_WAVES) void ntsm_count_run_kerne
 	uint2 *kq = kq_all[t >> 6];
 	lut64[t] = p.lut64[t];
 	const uint32_t bshift = p.bshift, n_blocks = p.blk_map.n_blocks;
+	/* the descriptor of kernels_mz.hip, written out: a shared helper swaps two instructions of the prologue (forms.txt) */
 	const unsigned long long blk_base = (unsigned long long) p.blocks;
 	const ntsm_i32x4 blk_rsrc = { (int) (uint32_t) blk_base, (int) ((uint32_t) (blk_base >> 32) | (16u << 16)), (int) (p.blk_bytes >> 4), 0x00020000 };
 	unsigned long long nk_s = 0;                             /* wave-uniform, lives across all tiles of the workgroup: 64 bits (a forced small grid over a large stream passes 2^32) */
@@ -116,7 +103,7 @@ __global__ __launch_bounds__(kThreads, NTSM_RUN_WAVES) void ntsm_count_run_kerne
 	uint32_t kmask = 0xFFFFFF00u;
 	asm volatile("" : "+v"(kmask));
 	static_assert(C != 128, "the main loop steps through the additive row rotation");
-	const uint32_t rot0 = (uint32_t) (ntsm_run_tile_addr<C>(t + 1, 0) - (t + 1) * C);
+	const uint32_t rot0 = (uint32_t) (ntsm_tile_addr<C>(t + 1, 0) - (t + 1) * C);
 
 	/* The queues and the two pipelines below live across tiles: records are self-contained (bases, positions mod 16, key), so a
 	 * tile's last partial batches wait for the next tile's records instead of being flushed with half-empty waves; everything
@@ -125,7 +112,7 @@ __global__ __launch_bounds__(kThreads, NTSM_RUN_WAVES) void ntsm_count_run_kerne
 
 	/* ---- look-up of the k-mers of passing runs, 64 at a time, two stages over consecutive calls so that no bucket load is
 	 * consumed by the call that issued it: (A) pop 64 canonical codes, issue the first bucket's load; (B, next call) compare
-	 * (bucket 2 only if bucket 1 is full -- the host inserts with that invariant), one counter update per hit ---- */
+	 * (bucket 2 only if bucket 1 is full: ntsm_find_slot), one counter update per hit ---- */
 	uint32_t l_klo = 0, l_khi = 0, l_g2 = 0;
 	unsigned long long l_b1 = 0;
 	uint4 l_ba = make_uint4(0, 0, 0, 0);
@@ -133,6 +120,7 @@ __global__ __launch_bounds__(kThreads, NTSM_RUN_WAVES) void ntsm_count_run_kerne
 	auto lookup = [&](bool take) {
 		long long slot = -1;
 		if (l_v) {
+			/* ntsm_find_slot written out (the rule and its reason are there): through the function this kernel gains 8 instructions, untimed */
 			if (l_ba.x == l_klo && l_ba.y == l_khi) slot = (long long) l_b1;
 			else if (l_ba.z == l_klo && l_ba.w == l_khi) slot = (long long) l_b1 + 1;
 			else if ((l_ba.x & l_ba.y) != 0xFFFFFFFFu && (l_ba.z & l_ba.w) != 0xFFFFFFFFu) {
@@ -186,7 +174,7 @@ __global__ __launch_bounds__(kThreads, NTSM_RUN_WAVES) void ntsm_count_run_kerne
 				const uint32_t r3 = ((n3 & 3u) << 4) | (n3 & 0xCu) | ((n3 >> 4) & 3u);
 				const uint32_t a_hi = t3, a_lo = lo, b_hi = rl >> 26, b_lo = (rl << 6) | r3;
 				const bool lt = a_hi < b_hi || (a_hi == b_hi && a_lo < b_lo);
-				const uint32_t at = kn + __builtin_amdgcn_mbcnt_hi((uint32_t) (am >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) am, 0u));
+				const uint32_t at = kn + ntsm_mask_rank(am, 0u);
 				kq[at] = make_uint2(lt ? a_lo : b_lo, lt ? a_hi : b_hi);
 			}
 			kn += (uint32_t) __popcll(am);
@@ -217,22 +205,12 @@ __global__ __launch_bounds__(kThreads, NTSM_RUN_WAVES) void ntsm_count_run_kerne
 			const uint32_t wL = __builtin_amdgcn_alignbit(fh, s_rec.x, 2u * o1);
 			const uint32_t uR = wR + ntsm_rc16(wR), uL = wL + ntsm_rc16(wL);
 			const uint32_t mR = ntsm_kmer_mix(uR), mL = ntsm_kmer_mix(uL);
-			/* word << field puts the tested bit (31 - field, NTSM_KBITn) into the sign position; the shifter takes the low five bits
-			 * of the selected byte, and the sign of the AND of the four is the verdict (as in kernels_mz.hip's phase C) */
-			auto passes = [&](uint32_t u, uint32_t um) -> bool {
-				uint32_t s0, s1, s2, s3;
-				asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_3 src1_sel:DWORD" : "=v"(s0) : "v"(u), "v"(s_blk.x));
-				asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_3 src1_sel:DWORD" : "=v"(s1) : "v"(um), "v"(s_blk.y));
-				asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_2 src1_sel:DWORD" : "=v"(s2) : "v"(um), "v"(s_blk.z));
-				asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_1 src1_sel:DWORD" : "=v"(s3) : "v"(um), "v"(s_blk.w));
-				return (int32_t) (__builtin_amdgcn_bitop3_b32(s0, s1, s2, 0x80) & s3) < 0;
-			};
-			cls = (o1 >= 4u && passes(uR, mR) ? 1u : 0u) | (o0 <= 3u && passes(uL, mL) ? 2u : 0u);
+			cls = (o1 >= 4u && ntsm_block_test(uR, mR, s_blk) ? 1u : 0u) | (o0 <= 3u && ntsm_block_test(uL, mL, s_blk) ? 2u : 0u);
 		}
 		const unsigned long long pm = __builtin_amdgcn_ballot_w64(cls != 0u);
 		if (pm && NTSM_RUN_ABL != 2) {
 			if (cls) {
-				const uint32_t at = cn + __builtin_amdgcn_mbcnt_hi((uint32_t) (pm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) pm, 0u));
+				const uint32_t at = cn + ntsm_mask_rank(pm, 0u);
 				uint32_t *q = cq + at;
 				q[0] = s_rec.x; q[kCandQueue] = s_rec.y | (cls << 10); q[2 * kCandQueue] = s_key;
 			}
@@ -260,25 +238,26 @@ __global__ __launch_bounds__(kThreads, NTSM_RUN_WAVES) void ntsm_count_run_kerne
 	for (unsigned long long ti = blockIdx.x; ti < p.n_tiles; ti += gridDim.x) {
 		const long long ts = p.t0 + (long long) (ti * (unsigned long long) (kThreads * C));
 		__syncthreads();
+		/* staging: kernels_mz.hip's, without its #ifdef ladder -- one shared function changes 277 lines of this kernel (forms.txt) */
 		if (ts >= p.lo && ts + kThreads * C <= p.hi) {
 			const __amdgpu_buffer_rsrc_t st_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(p.base + ts), (short) 0, kThreads * C, 0x00020000);
 #pragma unroll
 			for (int q = 0; q < VPT; ++q) {
 				const int v = t + kThreads * q;
 				const ntsm_u32x4 nt = __builtin_amdgcn_raw_buffer_load_b128(st_rsrc, 16 * v, 0, NTSM_STREAM_AUX);
-				*reinterpret_cast<uint4 *>(tile + ntsm_run_tile_addr<C>(1 + v / VPT, (v % VPT) * 16)) = make_uint4(nt.x, nt.y, nt.z, nt.w);
+				*reinterpret_cast<uint4 *>(tile + ntsm_tile_addr<C>(1 + v / VPT, (v % VPT) * 16)) = make_uint4(nt.x, nt.y, nt.z, nt.w);
 			}
 		} else {
 #pragma unroll 1
 			for (int q = 0; q < VPT; ++q) {
 				const int v = t + kThreads * q;
 				const uint4 r = ntsm_load_vec(p, ts + 16ll * v);
-				*reinterpret_cast<uint4 *>(tile + ntsm_run_tile_addr<C>(1 + v / VPT, (v % VPT) * 16)) = r;
+				*reinterpret_cast<uint4 *>(tile + ntsm_tile_addr<C>(1 + v / VPT, (v % VPT) * 16)) = r;
 			}
 		}
 		if (t < 2) {
 			const uint4 r = ntsm_load_vec(p, ts - 32 + 16 * t);
-			*reinterpret_cast<uint4 *>(tile + ntsm_run_tile_addr<C>(0, C - 32 + 16 * t)) = r;
+			*reinterpret_cast<uint4 *>(tile + ntsm_tile_addr<C>(0, C - 32 + 16 * t)) = r;
 		}
 		__syncthreads();
 
@@ -302,8 +281,8 @@ __global__ __launch_bounds__(kThreads, NTSM_RUN_WAVES) void ntsm_count_run_kerne
 		 * without the key -- hence the run -- changing */
 #define NTSM_RKEY(pos16_) ntsm_run_key(F, R, (uint32_t) (pos16_), kmask)
 		{
-			const uint4 v0 = *reinterpret_cast<const uint4 *>(tile + ntsm_run_tile_addr<C>(t, C - 32));
-			const uint4 v1 = *reinterpret_cast<const uint4 *>(tile + ntsm_run_tile_addr<C>(t, C - 16));
+			const uint4 v0 = *reinterpret_cast<const uint4 *>(tile + ntsm_tile_addr<C>(t, C - 32));
+			const uint4 v1 = *reinterpret_cast<const uint4 *>(tile + ntsm_tile_addr<C>(t, C - 16));
 			const uint32_t w[8] = { v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w };
 			uint32_t gw[8];
 			/* Only the last 22 of the 32 bytes in front of the chunk matter: a run of this chunk begins at a position >= 0, its
@@ -349,7 +328,7 @@ __global__ __launch_bounds__(kThreads, NTSM_RUN_WAVES) void ntsm_count_run_kerne
 				nk_s += (unsigned long long) __popcll(~bad);
 				if (endm) {
 					if (__builtin_amdgcn_inverse_ballot_w64(endm)) {
-						const uint32_t at = __builtin_amdgcn_mbcnt_hi((uint32_t) (endm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) endm, qn));
+						const uint32_t at = ntsm_mask_rank(endm, qn);
 						uint32_t *q = rq + at;
 						uint32_t w;                                  /* the last position is the previous one: a scalar */
 						asm("v_lshl_or_b32 %0, %1, 4, %2" : "=v"(w) : "v"(i0), "s"((pcb + (uint32_t) j - 1u) & 15u));
@@ -372,7 +351,7 @@ __global__ __launch_bounds__(kThreads, NTSM_RUN_WAVES) void ntsm_count_run_kerne
 			const unsigned long long endm = ~bad_prev;
 			if (endm) {
 				if (__builtin_amdgcn_inverse_ballot_w64(endm)) {
-					const uint32_t at = __builtin_amdgcn_mbcnt_hi((uint32_t) (endm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) endm, qn));
+					const uint32_t at = ntsm_mask_rank(endm, qn);
 					uint32_t *q = rq + at;
 					q[0] = F; q[kRunQueue] = (Fh << 12) | ((i0 << 4) | (uint32_t) ((C - 1) & 15));
 					q[2 * kRunQueue] = mz_prev;
@@ -389,6 +368,7 @@ __global__ __launch_bounds__(kThreads, NTSM_RUN_WAVES) void ntsm_count_run_kerne
 	while (cn > 0) expand();
 	while (kn > 0) lookup(true);
 	lookup(false);
+	/* not ntsm_add_totals: it swaps the operands of two adds, and this kernel is otherwise byte for byte the parent's */
 	unsigned long long nh_w = nh;                            /* per lane 32 bits are plenty; the sum over the wave is taken in 64 */
 #pragma unroll
 	for (int off = 32; off > 0; off >>= 1) nh_w += __shfl_down(nh_w, off, 64);

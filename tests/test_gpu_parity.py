@@ -2123,7 +2123,12 @@ def test_queues_that_outlive_their_tile(nt, tmp_path):
     ~300 tiles -- one workgroup carries its queues through all of them; 3 leaves the workgroups different numbers of tiles;
     a request larger than the tile count is clamped to one tile per workgroup (the default situation).  Counts and totals against the oracle,
     in one batch and in two (a batch boundary inside the stream: the next launch starts with empty queues); the minimizer-blocked
-    kernel, which drains per tile, through the same grids beside it."""
+    kernel, which drains per tile, in its one-level (2) and two-level (4) forms, and the generic kernel (1) through the same grids
+    beside it: all four walk their tiles with the slot look-up and totals of kernels_common.h (the generic kernel with a staging
+    of its own), and the launch counters and the form of the tables say that each variant ran the kernel it names.
+    The reads hit 90,277 of the set's 104,000 site k-mers (asserted below), 2,054 of them keys that sit in their second bucket
+    (profiles/r13_count_kernels/mutation.txt: a look-up without its bucket-2 branch loses exactly those), so a kernel that misses
+    them cannot pass them off as zeros."""
     sp = str(tmp_path / "s.fa")
     s = nt.SynthShort(sites_seed=20241218, n_sites=4000, read_seed=31, p_embed=0.5, sites_path=sp, min_keep=13)
     sites = nt.Sites(sp)
@@ -2133,7 +2138,8 @@ def test_queues_that_outlive_their_tile(nt, tmp_path):
     fp.process_flat(bases, ends)
     want = fp.kmers()[2]
     assert fp.total_hits > 200_000 and len(bases) > 280 * 20480
-    for variant in (5, 2):
+    assert (len(want), int(np.count_nonzero(want))) == (104_000, 90_277)
+    for variant in (5, 2, 4, 1):
         for grid in (1, 3, 64, 1 << 16):
             ctx = nt.Context(sites.keys)
             ctx.set_kernel(variant)
@@ -2142,6 +2148,9 @@ def test_queues_that_outlive_their_tile(nt, tmp_path):
             t = ctx.sync()
             assert np.array_equal(ctx.counts(), want), (variant, grid)
             assert (t.total_kmers, t.total_hits, t.total_bases) == (fp.total_kmers, fp.total_hits, fp.total_bases), (variant, grid)
+            st = ctx.debug_stats()
+            assert (st["launches_generic"] > 0, st["launches_k19"] > 0, st["launches_tab"]) == (variant == 1, variant != 1, 0), (variant, st)
+            assert variant == 1 or (st["run_form"], st["two_level"]) == (variant == 5, variant == 4), (variant, st)
             cut = n // 3
             cb = int(ends[cut - 1]) + 1
             ctx.submit(bases[:cb], ends[:cut])

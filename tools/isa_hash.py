@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """tools/isa_hash.py [--cohort] [--check FILE | --write FILE] [-D...] -- per-kernel hash of the gfx950 ISA the compiler emits for the
-kernel translation units of libntsm_hip.so (ntsm_amd/csrc/kernels_generic.hip, kernels_mz.hip).
+kernel translation units of libntsm_hip.so (ntsm_amd/csrc/kernels_generic.hip, kernels_mz.hip, kernels_run.hip).
 
 A kernel's hash is the SHA-256 (first 16 hex digits) of its instructions with comments, directives and local label numbers
-stripped, so it changes when -- and only when -- the code the GPU runs changes.  Used to show that a refactoring of the
+stripped, so it changes when -- and only when -- the code the GPU runs changes.  Beside it, shape16 is the hash of the same
+lines with the register numbers erased (v12, s[4:5], a3 -> R): equal shape16 under a different sha16 means registers
+renamed or commutative operands swapped, not different code.  Used to show that a refactoring of the
 sources around the kernels (round 5: the split of ntsm_hip.hip into six translation units, the ablation hooks moved behind
 ntsm_hooks.h) left the product kernels bit-identical, and by tools/make_traffic.py-style profile gating.
   --write FILE   record the hashes (profiles/r05_isa_hashes.json)
@@ -37,7 +39,9 @@ def kernel_hashes(defs=(), sources=SOURCES):
                 lines = [re.sub(r"\.LBB\d+_", ".LBBx_", l) for l in lines if l.strip() and not l.strip().startswith(".")]
                 demangled = subprocess.run(["c++filt", name], stdout=subprocess.PIPE).stdout.decode().strip()
                 demangled = demangled.replace("(anonymous namespace)::", "")
-                out[demangled] = {"instructions": len(lines) - 1, "sha16": hashlib.sha256("\n".join(lines[1:]).encode()).hexdigest()[:16]}
+                shape = [re.sub(r"\b[vsa](?:\d+|\[\d+(?::\d+)?\])", "R", l) for l in lines[1:]]
+                out[demangled] = {"instructions": len(lines) - 1, "sha16": hashlib.sha256("\n".join(lines[1:]).encode()).hexdigest()[:16],
+                                  "shape16": hashlib.sha256("\n".join(shape).encode()).hexdigest()[:16]}
     return out
 
 

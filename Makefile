@@ -8,6 +8,7 @@
 #   ntsm_amd/libntsm_vcf_hip.so, build/ntsmVCF     multi-sample VCF to PCA matrix + centre file (HIP library + CLI mirror)
 #   ntsm_amd/libntsm_pca_hip.so, build/ntsmPCA     exact PCA of the ntsmVCF matrix: rotation for ntsmEval -p (HIP library + CLI)
 #   ntsm_amd/libntsm_sitegen_hip.so, build/ntsmSiteGen   sites files from a genome and a VCF of SNPs (HIP library + CLI)
+#   ntsm_amd/libntsm_sitegen_gap_hip.so                  the device step of `ntsmSiteGen -g`: one-base gapped places as well
 #   oracle/                   CPU checker (+ oracle/_ref when /root/reference is present)
 HIPCC    ?= /opt/rocm/bin/hipcc
 CXX      ?= g++
@@ -21,7 +22,7 @@ HOSTSRC  := $(HOST)/seq_reader.cpp $(HOST)/site_set.cpp $(HOST)/report.cpp $(HOS
             $(HOST)/inflate.cpp $(HOST)/inflate_spec.cpp $(HOST)/gz_stream.cpp $(HOST)/gz_parallel.cpp $(HOST)/crc32_fast.cpp $(HOST)/pack2.cpp
 HOSTHDR  := $(wildcard $(HOST)/*.hpp) include/ntsm_host.h include/ntsm_hip.h
 
-all: oracle_all build/ntsm_synth build/gather_bench build/ntsm_feed_bench build/ubench/inflate_wave ntsm_amd/libntsm_hip.so ntsm_amd/libntsm_synth.so ntsm_amd/libntsm_host.so build/ntsmCount ntsm_amd/libntsm_eval_hip.so build/ntsmEval ntsm_amd/libntsm_vcf_hip.so build/ntsmVCF ntsm_amd/libntsm_pca_hip.so build/ntsmPCA ntsm_amd/libntsm_sitegen_hip.so build/ntsmSiteGen ref_gpu_binding
+all: oracle_all build/ntsm_synth build/gather_bench build/ntsm_feed_bench build/ubench/inflate_wave ntsm_amd/libntsm_hip.so ntsm_amd/libntsm_synth.so ntsm_amd/libntsm_host.so build/ntsmCount ntsm_amd/libntsm_eval_hip.so build/ntsmEval ntsm_amd/libntsm_vcf_hip.so build/ntsmVCF ntsm_amd/libntsm_pca_hip.so build/ntsmPCA ntsm_amd/libntsm_sitegen_hip.so ntsm_amd/libntsm_sitegen_gap_hip.so build/ntsmSiteGen ref_gpu_binding
 
 # host-only pieces (reader, site loader, report formatting): no HIP dependency
 ntsm_amd/libntsm_host.so: $(HOSTSRC) $(HOST)/early_ingest.cpp $(HOST)/host_capi.cpp $(HOSTHDR)
@@ -105,11 +106,16 @@ build/ntsmPCA: $(PCASRC) $(HOST)/ntsm_pca_main.cpp $(HOSTHDR) include/ntsm_pca_h
 ntsm_amd/libntsm_sitegen_hip.so: $(CSRC)/ntsm_sitegen.hip $(CSRC)/ntsm_hip_scope.h include/ntsm_sitegen_hip.h
 	$(HIPCC) $(HIPFLAGS) -fvisibility=hidden -shared -o $@ $(CSRC)/ntsm_sitegen.hip
 
+# the second device library of ntsmSiteGen (-g): substitutions and one-base gaps in one pass (include/ntsm_sitegen_gap_hip.h)
+ntsm_amd/libntsm_sitegen_gap_hip.so: $(CSRC)/ntsm_sitegen_gap.hip $(CSRC)/ntsm_hip_scope.h include/ntsm_sitegen_gap_hip.h
+	$(HIPCC) $(HIPFLAGS) -fvisibility=hidden -shared -o $@ $(CSRC)/ntsm_sitegen_gap.hip
+
 SITEGENSRC := $(HOST)/seq_reader.cpp $(HOST)/inflate.cpp $(HOST)/inflate_spec.cpp $(HOST)/gz_stream.cpp $(HOST)/gz_parallel.cpp \
               $(HOST)/crc32_fast.cpp
-build/ntsmSiteGen: $(SITEGENSRC) $(HOST)/ntsm_sitegen_main.cpp $(HOSTHDR) include/ntsm_sitegen_hip.h ntsm_amd/libntsm_sitegen_hip.so
+build/ntsmSiteGen: $(SITEGENSRC) $(HOST)/ntsm_sitegen_main.cpp $(HOSTHDR) include/ntsm_sitegen_hip.h include/ntsm_sitegen_gap_hip.h \
+                   ntsm_amd/libntsm_sitegen_hip.so ntsm_amd/libntsm_sitegen_gap_hip.so
 	@mkdir -p build
-	$(CXX) $(CXXFLAGS) -o $@ $(SITEGENSRC) $(HOST)/ntsm_sitegen_main.cpp -Lntsm_amd -lntsm_sitegen_hip -lz -pthread \
+	$(CXX) $(CXXFLAGS) -o $@ $(SITEGENSRC) $(HOST)/ntsm_sitegen_main.cpp -Lntsm_amd -lntsm_sitegen_hip -lntsm_sitegen_gap_hip -lz -pthread \
 	    -Wl,-rpath,'$$ORIGIN/../ntsm_amd' -Wl,-rpath,/opt/rocm/lib
 
 # ablation builds (never shipped: wrong counts by construction).  `make ablation`: the default kernels with the switches of

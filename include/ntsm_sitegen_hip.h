@@ -17,6 +17,8 @@
  * forward orientation as the caller wants it reported (the library indexes the reverse complement itself).
  *
  * All functions return 0, -1 for a bad argument, -2 for a HIP error.
+ *
+ * Places that differ by a one-base gap (`ntsmSiteGen -g`) are counted by a second library: include/ntsm_sitegen_gap_hip.h.
  */
 #ifndef NTSM_SITEGEN_HIP_H
 #define NTSM_SITEGEN_HIP_H

@@ -4,6 +4,7 @@
  *
  *   step 1 (host)    candidate sub-k-mers of the SNP windows      contract: ntsm-scripts/extractSNPsfromVCF.py
  *   step 2 (device)  per candidate, the places of the genome within x substitutions (include/ntsm_sitegen_hip.h);
+ *                    with -g, the places with a one-base gap as well (include/ntsm_sitegen_gap_hip.h), in one pass;
  *                    upstream: bwa index / aln -n 1 / samse.  -H reads the counts from a file and leaves the GPU alone
  *   step 3 (host)    keep the candidates with at most one place, write NAME_n{i}.fa    contract: filterRepetiveSNP.pl
  *
@@ -26,6 +27,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "../../../include/ntsm_sitegen_gap_hip.h"
 #include "../../../include/ntsm_sitegen_hip.h"
 #include "seq_reader.hpp"
 
@@ -34,6 +36,8 @@ namespace {
 struct Options {
 	std::string ref, vcf, prefix, hits;
 	long k = 19, w = 31, threads = 4, x = 1, device = 0;
+	long e = -1;                             /* -e / gapskip=: the end margin of -g; -1 = not given (5) */
+	bool gaps = false;                       /* -g / gaps=1 */
 	bool at_cg_only = true;                  /* the script's `ignore`, cleared by -i */
 	int verbose = 0;
 };
@@ -62,14 +66,16 @@ struct Candidate {
 
 void usage()
 {
-	std::cerr << "Usage: ntsmSiteGen -r GENOME.fa[.gz] -v SNPS.vcf -p NAME [-k 19] [-w 31] [-t 4] [-i] [-x 1] [-H HITS.tsv] [-G 0] [-V]\n"
-	             "       ntsmSiteGen generate-sites name=NAME ref=GENOME.fa vcf=SNPS.vcf [k=19] [w=31] [t=4] [hits=HITS.tsv]\n"
+	std::cerr << "Usage: ntsmSiteGen -r GENOME.fa[.gz] -v SNPS.vcf -p NAME [-k 19] [-w 31] [-t 4] [-i] [-x 1] [-g [-e 5]] [-H HITS.tsv] [-G 0] [-V]\n"
+	             "       ntsmSiteGen generate-sites name=NAME ref=GENOME.fa vcf=SNPS.vcf [k=19] [w=31] [t=4] [gaps=1 [gapskip=5]] [hits=HITS.tsv]\n"
 	             "  -r  reference genome, FASTA, plain or gzip\n"
 	             "  -v  VCF of the SNPs (columns CHROM POS ID REF ALT are read)\n"
 	             "  -p  prefix of the output files NAME_subKmers.fa, NAME_subKmerHits.tsv, NAME_n0.fa .. NAME_n{w-k}.fa\n"
 	             "  -k  k-mer size (1 .. 31; the device step needs 11 .. 31)    -w  window size (>= k)\n"
 	             "  -i  keep A/T <-> A/T and C/G <-> C/G SNPs\n"
 	             "  -x  substitutions allowed when places of the genome are counted: 0 or 1\n"
+	             "  -g  count the places that differ by a one-base gap too, as `bwa aln -n 1` does (gaps=1); needs -x 1\n"
+	             "  -e  with -g: no gap within this many bases of either end of the k-mer, 1 .. (k - 1) / 2, default 5 (gapskip=N)\n"
 	             "  -H  take the hit counts from this file (the form of NAME_subKmerHits.tsv); the GPU is not used\n"
 	             "  -t  host threads (never changes the output)    -G  device    -V  timings on stderr\n";
 }
@@ -479,6 +485,42 @@ std::vector<uint32_t> device_hits(const Options &opt, const std::vector<Record> 
 	return std::vector<uint32_t>(h8.begin(), h8.end() - 1);
 }
 
+/* -g: the second library, H and G in one pass; the program's count is min(H + G, 255) */
+std::vector<uint32_t> device_gap_hits(const Options &opt, const std::vector<Record> &genome, const std::vector<Candidate> &cands)
+{
+	if (opt.k < 11)
+		fail("the device step needs k >= 11 (use -H for smaller k)");
+	std::vector<uint64_t> packed(cands.size());
+	for (size_t i = 0; i < cands.size(); i++)
+		packed[i] = cands[i].kmer;
+	ntsm_sitegap *s = nullptr;
+	int rc = ntsm_sitegap_open((int)opt.device, (uint32_t)opt.k, (uint32_t)opt.e, packed.size(), packed.data(), &s);
+	if (rc)
+		fail("ntsm_sitegap_open failed (" + std::to_string(rc) + "): device " + std::to_string(opt.device));
+	for (const Record &r : genome) {
+		const uint64_t end = r.seq.size();
+		if ((rc = ntsm_sitegap_submit(s, r.seq.data(), end, &end, 1)))
+			fail("ntsm_sitegap_submit failed (" + std::to_string(rc) + ")");
+	}
+	std::vector<uint8_t> sub(cands.size() + 1), gap(cands.size() + 1);
+	if ((rc = ntsm_sitegap_hits(s, sub.data(), gap.data())))
+		fail("ntsm_sitegap_hits failed (" + std::to_string(rc) + ")");
+	if (opt.verbose) {
+		struct ntsm_sitegap_stats t;
+		if (!ntsm_sitegap_stats(s, &t))
+			fprintf(stderr, "Device: table build %.1f ms, table upload %.1f ms (%.1f MB), stage %.1f ms, upload %.1f ms, scan kernel %.1f ms in %llu launches "
+			        "(%llu full: %.1f .. %.1f ms each); %llu windows (%llu of k + 1 bases, %llu of k - 1), %llu bitmap tests, %llu probes\n", t.table_build_ms,
+			        t.table_upload_ms, t.table_bytes / 1e6, t.stage_ms, t.upload_ms, t.kernel_ms, (unsigned long long)t.launches, (unsigned long long)t.full_launches,
+			        t.full_kernel_ms_min, t.full_kernel_ms_max, (unsigned long long)t.windows, (unsigned long long)t.windows_long,
+			        (unsigned long long)t.windows_short, (unsigned long long)t.bitmap_tests, (unsigned long long)t.probes);
+	}
+	ntsm_sitegap_close(s);
+	std::vector<uint32_t> hits(cands.size());
+	for (size_t i = 0; i < cands.size(); i++)
+		hits[i] = std::min<uint32_t>((uint32_t)sub[i] + gap[i], 255);
+	return hits;
+}
+
 } // namespace
 
 int main(int argc, char **argv)
@@ -503,6 +545,12 @@ int main(int argc, char **argv)
 			else if (key == "w") ok = ok && parse_long(val.c_str(), opt.w);
 			else if (key == "t") ok = ok && parse_long(val.c_str(), opt.threads);
 			else if (key == "hits") opt.hits = val;      /* -H; not one of upstream's */
+			else if (key == "gaps") {                    /* -g / -e: this program's own as well */
+				long v = -1;
+				ok = ok && parse_long(val.c_str(), v) && (v == 0 || v == 1);
+				opt.gaps = v == 1;
+			}
+			else if (key == "gapskip") ok = ok && parse_long(val.c_str(), opt.e) && opt.e >= 0;
 			else ok = false;
 			if (!ok)
 				fail("cannot read parameter " + a);
@@ -515,8 +563,9 @@ int main(int argc, char **argv)
 			const std::string a = argv[i];
 			if (a == "-i") { opt.at_cg_only = false; continue; }
 			if (a == "-V") { opt.verbose++; continue; }
+			if (a == "-g") { opt.gaps = true; continue; }
 			if (a == "-h" || a == "--help") { usage(); return 0; }
-			if (a.size() != 2 || a[0] != '-' || !strchr("rvpkwtxHG", a[1]) || i + 1 >= argc) {
+			if (a.size() != 2 || a[0] != '-' || !strchr("rvpkwtxeHG", a[1]) || i + 1 >= argc) {
 				std::cerr << "Error - Invalid parameter: " << a << std::endl;
 				die = true;
 				break;
@@ -532,6 +581,7 @@ int main(int argc, char **argv)
 			case 'w': ok = parse_long(val, opt.w); break;
 			case 't': ok = parse_long(val, opt.threads); break;
 			case 'x': ok = parse_long(val, opt.x); break;
+			case 'e': ok = parse_long(val, opt.e) && opt.e >= 0; break;
 			case 'G': ok = parse_long(val, opt.device); break;
 			}
 			if (!ok) {
@@ -552,6 +602,10 @@ int main(int argc, char **argv)
 	if (opt.w < opt.k) fail("w must be at least k");
 	if (opt.w > 65535) fail("w must be below 65536");
 	if (opt.x < 0 || opt.x > 1) fail("x must be 0 or 1");
+	if (opt.e >= 0 && !opt.gaps) fail("-e needs -g (gapskip= needs gaps=1): the end margin is that of the gapped places");
+	if (opt.gaps && opt.x != 1) fail("-g needs -x 1: a one-base gap is counted beside one substitution, as bwa aln -n 1 has it");
+	if (opt.gaps && opt.e < 0) opt.e = 5;
+	if (opt.gaps && (opt.e < 1 || 2 * opt.e > opt.k - 1)) fail("e must be 1 .. (k - 1) / 2, here 1 .. " + std::to_string((opt.k - 1) / 2));
 	if (opt.threads < 1) fail("t must be at least 1");
 	if (opt.device < 0) fail("G must not be negative");
 
@@ -561,7 +615,7 @@ int main(int argc, char **argv)
 	const std::vector<Entry> entries = parse_vcf(opt.vcf);
 	Step1 s1 = step1(opt, genome, entries);
 	double t2 = now_ms();
-	const std::vector<uint32_t> hits = opt.hits.empty() ? device_hits(opt, genome, s1.cands) : read_hits(opt, entries, s1.cands);
+	const std::vector<uint32_t> hits = opt.hits.empty() ? (opt.gaps ? device_gap_hits(opt, genome, s1.cands) : device_hits(opt, genome, s1.cands)) : read_hits(opt, entries, s1.cands);
 	double t3 = now_ms();
 	std::cerr << s1.err;
 	{

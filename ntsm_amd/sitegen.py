@@ -1,5 +1,7 @@
-"""ctypes plumbing for include/ntsm_sitegen_hip.h (the device step of ntsmSiteGen); used by tests and tools.
-Loaded on demand: `import ntsm_amd.sitegen`.  Fails loudly when libntsm_sitegen_hip.so has not been built."""
+"""ctypes plumbing for include/ntsm_sitegen_hip.h (the device step of ntsmSiteGen) and include/ntsm_sitegen_gap_hip.h (the
+device step of `ntsmSiteGen -g`); used by tests and tools.
+Loaded on demand: `import ntsm_amd.sitegen`.  Fails loudly when libntsm_sitegen_hip.so has not been built; the second
+library, libntsm_sitegen_gap_hip.so, is loaded by the first GapSession (or gap_lib()), and fails as loudly then."""
 import ctypes as C
 import os
 
@@ -112,3 +114,83 @@ class Session:
 
     def __exit__(self, *exc):
         self.close()
+
+
+class GapStats(C.Structure):
+    _fields_ = [("table_build_ms", C.c_double), ("table_upload_ms", C.c_double), ("stage_ms", C.c_double), ("upload_ms", C.c_double),
+                ("kernel_ms", C.c_double), ("full_kernel_ms_min", C.c_double), ("full_kernel_ms_max", C.c_double),
+                ("launches", C.c_uint64), ("full_launches", C.c_uint64), ("windows", C.c_uint64), ("windows_long", C.c_uint64),
+                ("windows_short", C.c_uint64), ("bitmap_tests", C.c_uint64), ("probes", C.c_uint64), ("genome_bytes", C.c_uint64),
+                ("table_bytes", C.c_uint64)]
+
+
+_gap = None
+
+
+def gap_lib():
+    """libntsm_sitegen_gap_hip.so, loaded on first use"""
+    global _gap
+    if _gap is None:
+        path = os.path.join(_HERE, "libntsm_sitegen_gap_hip.so")
+        if not os.path.exists(path):
+            raise ImportError("%s is missing: run `make` (there is no CPU fallback)" % path)
+        g = C.CDLL(path)
+        g.ntsm_sitegap_open.restype = C.c_int
+        g.ntsm_sitegap_open.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p)]
+        g.ntsm_sitegap_submit.restype = C.c_int
+        g.ntsm_sitegap_submit.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]
+        g.ntsm_sitegap_hits.restype = C.c_int
+        g.ntsm_sitegap_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        g.ntsm_sitegap_stats.restype = C.c_int
+        g.ntsm_sitegap_stats.argtypes = [C.c_void_p, C.POINTER(GapStats)]
+        g.ntsm_sitegap_close.restype = None
+        g.ntsm_sitegap_close.argtypes = [C.c_void_p]
+        _gap = g
+    return _gap
+
+
+class GapSession(Session):
+    """One candidate set on one device, substitutions and one-base gaps in one pass (end margin e).  submit() and
+    submit_records() as Session has them; hits() returns (min(H, 255), min(G, 255)) per candidate."""
+
+    def __init__(self, kmers, k, e=5, device=0):
+        self._lib = gap_lib()
+        self._h = C.c_void_p()
+        packed = kmers if isinstance(kmers, np.ndarray) and kmers.dtype == np.uint64 else pack(kmers, k)
+        packed = np.ascontiguousarray(packed)
+        self.n = len(packed)
+        rc = self._lib.ntsm_sitegap_open(device, k, e, self.n, packed.ctypes.data if self.n else None, C.byref(self._h))
+        if rc:
+            self._h = None
+            raise RuntimeError("ntsm_sitegap_open failed: %d" % rc)
+
+    def submit(self, bases, ends=()):
+        if isinstance(bases, str):
+            bases = bases.encode()
+        e = np.asarray(ends, dtype=np.uint64)
+        buf = np.frombuffer(bases, dtype=np.uint8)
+        rc = self._lib.ntsm_sitegap_submit(self._h, buf.ctypes.data if len(buf) else None, len(buf), e.ctypes.data if len(e) else None, len(e))
+        if rc:
+            raise RuntimeError("ntsm_sitegap_submit failed: %d" % rc)
+
+    def hits(self):
+        sub, gap = np.zeros(max(self.n, 1), dtype=np.uint8), np.zeros(max(self.n, 1), dtype=np.uint8)
+        rc = self._lib.ntsm_sitegap_hits(self._h, sub.ctypes.data, gap.ctypes.data)
+        if rc:
+            raise RuntimeError("ntsm_sitegap_hits failed: %d" % rc)
+        return sub[:self.n], gap[:self.n]
+
+    def stats(self):
+        st = GapStats()
+        rc = self._lib.ntsm_sitegap_stats(self._h, C.byref(st))
+        if rc:
+            raise RuntimeError("ntsm_sitegap_stats failed: %d" % rc)
+        return st
+
+    def times(self):
+        return self.stats()
+
+    def close(self):
+        if self._h:
+            self._lib.ntsm_sitegap_close(self._h)
+            self._h = None

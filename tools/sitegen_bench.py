@@ -3,7 +3,7 @@
 `build/ntsmSiteGen -V` run, two yardsticks taken in the same session, and two checks of the result.
 
   python3 tools/sitegen_bench.py [--bases 1073741824] [--snps 1000000] [--seed 1] [--dir DIR] [--out OUT.json]
-                                 [--sample 10000] [--no-yardsticks]
+                                 [--sample 10000] [--no-yardsticks] [--gaps]
 
 Genome: 8 records of random bases; 24 repeat families of 300 bases, planted 200 .. 50,000 times each with 3 % of the bases
 substituted per copy (about 5 % of the genome); the first reference 19-mer of one SNP's window planted 1,000 more times
@@ -15,7 +15,10 @@ table build, table upload, staging, genome upload, scan kernel from HIP events, 
 of the scan kernel, the spread of the kernel's full launches, the yardsticks (build/gather_bench's random-gather rate at its largest
 table; the exact-match count kernel's bases/s on the same genome fed as reads against the sites file this run wrote),
 and the checks (--sample candidates against tests/sitegen_restatement.cpp's "halves" brute force on the CPU; the planted
-family's count).  Needs a GPU; there is no fallback."""
+family's count).  --gaps runs the program a second time with -g on the same genome in the same session and adds, under
+"gaps": the same -V figures of that run, its scan kernel over the substitution-only one, the share of candidates whose
+keep / drop verdict (count <= 1) -g changes, and the size and sites of NAME_n10.fa both ways.  Needs a GPU; there is no
+fallback."""
 import argparse
 import json
 import os
@@ -92,10 +95,11 @@ def generate(d, n_bases, n_snps, seed):
 def parse_v(err):
     out = {}
     m = re.search(r"Device: table build ([\d.]+) ms, table upload ([\d.]+) ms \(([\d.]+) MB\), stage ([\d.]+) ms, upload ([\d.]+) ms, "
-                  r"scan kernel ([\d.]+) ms in (\d+) launches \((\d+) full: ([\d.]+) \.\. ([\d.]+) ms each\); (\d+) windows, (\d+) bitmap tests, (\d+) probes", err)
+                  r"scan kernel ([\d.]+) ms in (\d+) launches \((\d+) full: ([\d.]+) \.\. ([\d.]+) ms each\); (\d+) windows"
+                  r"(?: \((\d+) of k \+ 1 bases, (\d+) of k - 1\))?, (\d+) bitmap tests, (\d+) probes", err)
     keys = ["table_build_ms", "table_upload_ms", "table_mb", "stage_ms", "genome_upload_ms", "scan_kernel_ms", "launches", "full_launches",
-            "full_launch_ms_min", "full_launch_ms_max", "windows", "bitmap_tests", "probes"]
-    out.update({k: float(v) for k, v in zip(keys, m.groups())})
+            "full_launch_ms_min", "full_launch_ms_max", "windows", "windows_long", "windows_short", "bitmap_tests", "probes"]
+    out.update({k: float(v) for k, v in zip(keys, m.groups()) if v is not None})
     m = re.search(r"Time: genome ([\d.]+) ms, step 1 ([\d.]+) ms, step 2 ([\d.]+) ms, candidate files ([\d.]+) ms, step 3 ([\d.]+) ms; (\d+) SNPs, (\d+) candidates", err)
     out.update({k: float(v) for k, v in zip(["genome_read_ms", "step1_ms", "step2_ms", "candidate_files_ms", "step3_ms", "snps", "candidates"], m.groups())})
     return out
@@ -176,6 +180,34 @@ def checks(d, res, planted, sample):
     res["sample_above_one"] = sum(1 for w_ in want if int(w_) > 1)
 
 
+def gaps_run(d, res):
+    """the same genome and VCF with -g: the figures of that run beside the first one's"""
+    t0 = time.time()
+    p = subprocess.run([EXE, "-r", os.path.join(d, "genome.fa"), "-v", os.path.join(d, "snps.vcf"), "-p", os.path.join(d, "gap"), "-g", "-V"],
+                       capture_output=True, timeout=3000)
+    if p.returncode:
+        raise SystemExit("ntsmSiteGen -g failed (%d): %s" % (p.returncode, p.stderr.decode()[-500:]))
+    g = parse_v(p.stderr.decode())
+    g["program_wall_s"] = round(time.time() - t0, 1)
+    g["e"] = 5
+    g["scan_kernel_over_substitutions_only"] = g["scan_kernel_ms"] / res["scan_kernel_ms"]
+    g["windows_per_s"] = g["windows"] / g["scan_kernel_ms"] * 1e3
+    g["table_reads_per_s"] = (g["bitmap_tests"] + g["probes"]) / g["scan_kernel_ms"] * 1e3
+    both = subprocess.run("paste %s %s | awk -F'\t' '{a = $2 <= 1; b = $4 <= 1; if (a != b) n++; if (a && !b) lost++; if ($4 < $2) less++} "
+                          "END {print NR, n + 0, lost + 0, less + 0}'" % (os.path.join(d, "run_subKmerHits.tsv"), os.path.join(d, "gap_subKmerHits.tsv")),
+                          shell=True, capture_output=True, check=True).stdout.decode().split()
+    g["candidates"], g["verdict_changed"], g["kept_to_dropped"], g["count_below_substitutions_only"] = (int(x) for x in both)
+    g["verdict_changed_share"] = g["verdict_changed"] / max(g["candidates"], 1)
+    for tag in ("run", "gap"):
+        path = os.path.join(d, "%s_n10.fa" % tag)
+        g["n10_bytes_" + ("with_gaps" if tag == "gap" else "without")] = os.path.getsize(path)
+        g["n10_sites_" + ("with_gaps" if tag == "gap" else "without")] = int(subprocess.run(["grep", "-c", " ref$", path], capture_output=True).stdout or 0)
+    for f in os.listdir(d):
+        if f.startswith("gap_"):
+            os.remove(os.path.join(d, f))
+    res["gaps"] = g
+
+
 def say(what):
     print("[sitegen_bench %s] %s" % (time.strftime("%H:%M:%S"), what), file=sys.stderr, flush=True)
 
@@ -189,6 +221,7 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--sample", type=int, default=10000)
     ap.add_argument("--no-yardsticks", action="store_true")
+    ap.add_argument("--gaps", action="store_true")
     a = ap.parse_args()
     d = a.dir or tempfile.mkdtemp(prefix="sitegen_bench_")
     os.makedirs(d, exist_ok=True)
@@ -214,6 +247,9 @@ def main():
         say("program done in %.1f s; checking" % res["program_wall_s"])
         checks(d, res, planted, a.sample)
         say("checked: %d sampled, %d mismatches; yardsticks" % (res["sample_checked"], res["sample_mismatches"]))
+        if a.gaps:
+            gaps_run(d, res)
+            say("-g run done in %.1f s: scan kernel %.1f ms against %.1f ms" % (res["gaps"]["program_wall_s"], res["gaps"]["scan_kernel_ms"], res["scan_kernel_ms"]))
         for f in os.listdir(d):                               # the large outputs are not needed by the yardsticks
             if f.startswith("run_") and f != "run_n%d.fa" % (W - K):
                 os.remove(os.path.join(d, f))

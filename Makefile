@@ -103,11 +103,14 @@ build/ntsmPCA: $(PCASRC) $(HOST)/ntsm_pca_main.cpp $(HOSTHDR) include/ntsm_pca_h
 	    -Wl,-rpath,'$$ORIGIN/../ntsm_amd' -Wl,-rpath,/opt/rocm/lib
 
 # ntsmSiteGen (genome + VCF of SNPs -> NAME_n{i}.fa sites files): own library, own CLI
-ntsm_amd/libntsm_sitegen_hip.so: $(CSRC)/ntsm_sitegen.hip $(CSRC)/ntsm_hip_scope.h include/ntsm_sitegen_hip.h
+# both device libraries share their host side: the table builder and scan session (ntsm_sitegen_tables.h) and the staging
+# state machine (ntsm_sitegen_stage.h)
+SITEGENHDR := $(CSRC)/ntsm_sitegen_tables.h $(CSRC)/ntsm_sitegen_stage.h $(CSRC)/ntsm_hip_scope.h
+ntsm_amd/libntsm_sitegen_hip.so: $(CSRC)/ntsm_sitegen.hip $(SITEGENHDR) include/ntsm_sitegen_hip.h
 	$(HIPCC) $(HIPFLAGS) -fvisibility=hidden -shared -o $@ $(CSRC)/ntsm_sitegen.hip
 
 # the second device library of ntsmSiteGen (-g): substitutions and one-base gaps in one pass (include/ntsm_sitegen_gap_hip.h)
-ntsm_amd/libntsm_sitegen_gap_hip.so: $(CSRC)/ntsm_sitegen_gap.hip $(CSRC)/ntsm_hip_scope.h include/ntsm_sitegen_gap_hip.h
+ntsm_amd/libntsm_sitegen_gap_hip.so: $(CSRC)/ntsm_sitegen_gap.hip $(SITEGENHDR) include/ntsm_sitegen_gap_hip.h
 	$(HIPCC) $(HIPFLAGS) -fvisibility=hidden -shared -o $@ $(CSRC)/ntsm_sitegen_gap.hip
 
 SITEGENSRC := $(HOST)/seq_reader.cpp $(HOST)/inflate.cpp $(HOST)/inflate_spec.cpp $(HOST)/gz_stream.cpp $(HOST)/gz_parallel.cpp \

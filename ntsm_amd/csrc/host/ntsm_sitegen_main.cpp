@@ -455,22 +455,36 @@ double now_ms()
 	return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-std::vector<uint32_t> device_hits(const Options &opt, const std::vector<Record> &genome, const std::vector<Candidate> &cands)
+/* what either device run begins with: the refusal of a k the libraries do not take, and the candidates as they take them */
+std::vector<uint64_t> device_candidates(const Options &opt, const std::vector<Candidate> &cands)
 {
 	if (opt.k < 11)
 		fail("the device step needs k >= 11 (use -H for smaller k)");
 	std::vector<uint64_t> packed(cands.size());
 	for (size_t i = 0; i < cands.size(); i++)
 		packed[i] = cands[i].kmer;
+	return packed;
+}
+
+/* every record of the genome, one submit each, through the library whose submit function and its name are given */
+template <typename Session>
+void submit_genome(const std::vector<Record> &genome, Session *s, int (*submit)(Session *, const char *, uint64_t, const uint64_t *, uint64_t), const char *name)
+{
+	for (const Record &r : genome) {
+		const uint64_t end = r.seq.size();
+		if (const int rc = submit(s, r.seq.data(), end, &end, 1))
+			fail(std::string(name) + " failed (" + std::to_string(rc) + ")");
+	}
+}
+
+std::vector<uint32_t> device_hits(const Options &opt, const std::vector<Record> &genome, const std::vector<Candidate> &cands)
+{
+	const std::vector<uint64_t> packed = device_candidates(opt, cands);
 	ntsm_sitegen *s = nullptr;
 	int rc = ntsm_sitegen_open((int)opt.device, (uint32_t)opt.k, (uint32_t)opt.x, packed.size(), packed.data(), &s);
 	if (rc)
 		fail("ntsm_sitegen_open failed (" + std::to_string(rc) + "): device " + std::to_string(opt.device));
-	for (const Record &r : genome) {
-		const uint64_t end = r.seq.size();
-		if ((rc = ntsm_sitegen_submit(s, r.seq.data(), end, &end, 1)))
-			fail("ntsm_sitegen_submit failed (" + std::to_string(rc) + ")");
-	}
+	submit_genome(genome, s, ntsm_sitegen_submit, "ntsm_sitegen_submit");
 	std::vector<uint8_t> h8(cands.size() + 1);
 	if ((rc = ntsm_sitegen_hits(s, h8.data())))
 		fail("ntsm_sitegen_hits failed (" + std::to_string(rc) + ")");
@@ -488,20 +502,12 @@ std::vector<uint32_t> device_hits(const Options &opt, const std::vector<Record> 
 /* -g: the second library, H and G in one pass; the program's count is min(H + G, 255) */
 std::vector<uint32_t> device_gap_hits(const Options &opt, const std::vector<Record> &genome, const std::vector<Candidate> &cands)
 {
-	if (opt.k < 11)
-		fail("the device step needs k >= 11 (use -H for smaller k)");
-	std::vector<uint64_t> packed(cands.size());
-	for (size_t i = 0; i < cands.size(); i++)
-		packed[i] = cands[i].kmer;
+	const std::vector<uint64_t> packed = device_candidates(opt, cands);
 	ntsm_sitegap *s = nullptr;
 	int rc = ntsm_sitegap_open((int)opt.device, (uint32_t)opt.k, (uint32_t)opt.e, packed.size(), packed.data(), &s);
 	if (rc)
 		fail("ntsm_sitegap_open failed (" + std::to_string(rc) + "): device " + std::to_string(opt.device));
-	for (const Record &r : genome) {
-		const uint64_t end = r.seq.size();
-		if ((rc = ntsm_sitegap_submit(s, r.seq.data(), end, &end, 1)))
-			fail("ntsm_sitegap_submit failed (" + std::to_string(rc) + ")");
-	}
+	submit_genome(genome, s, ntsm_sitegap_submit, "ntsm_sitegap_submit");
 	std::vector<uint8_t> sub(cands.size() + 1), gap(cands.size() + 1);
 	if ((rc = ntsm_sitegap_hits(s, sub.data(), gap.data())))
 		fail("ntsm_sitegap_hits failed (" + std::to_string(rc) + ")");

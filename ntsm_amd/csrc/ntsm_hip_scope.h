@@ -1,7 +1,7 @@
 /*
  * ntsm_hip_scope.h -- what the host side of every cohort library (ntsm_eval*.hip, ntsm_vcf.hip, ntsm_pca.hip,
- * ntsm_sitegen.hip) needs around its HIP calls: owners that release device buffers and events when their scope ends, on
- * every return path, and one check.  Internal: not part of include/.
+ * ntsm_sitegen.hip, ntsm_sitegen_gap.hip) needs around its HIP calls: owners that release device buffers, events, a stream
+ * and pinned host memory when their scope ends, on every return path, and one check.  Internal: not part of include/.
  *
  * A translation unit names itself before it includes this file:
  *   #define NTSM_HIP_TAG "ntsm_eval"       the prefix of the message
@@ -76,6 +76,30 @@ public:
 		return hipSuccess;
 	}
 	hipEvent_t operator[](int i) const { return ev[i]; }
+};
+
+/* a stream, destroyed when the scope ends */
+class Stream {
+	hipStream_t s = nullptr;
+public:
+	Stream() = default;
+	Stream(const Stream &) = delete;
+	Stream &operator=(const Stream &) = delete;
+	~Stream() { if (s) (void) hipStreamDestroy(s); }
+	hipError_t create() { return hipStreamCreate(&s); }
+	operator hipStream_t() const { return s; }
+};
+
+/* pinned host bytes, freed when the scope ends */
+class Pinned {
+	void *p = nullptr;
+public:
+	Pinned() = default;
+	Pinned(const Pinned &) = delete;
+	Pinned &operator=(const Pinned &) = delete;
+	~Pinned() { if (p) (void) hipHostFree(p); }
+	hipError_t alloc(uint64_t bytes) { return hipHostMalloc(&p, bytes, hipHostMallocDefault); }
+	uint8_t *bytes() const { return (uint8_t *) p; }
 };
 
 }  // namespace ntsm_hip

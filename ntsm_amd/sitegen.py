@@ -11,7 +11,6 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _path = os.path.join(_HERE, "libntsm_sitegen_hip.so")
 if not os.path.exists(_path):
     raise ImportError("%s is missing: run `make` (there is no CPU fallback)" % _path)
-lib = C.CDLL(_path)
 
 
 class Times(C.Structure):
@@ -21,16 +20,30 @@ class Times(C.Structure):
                 ("probes", C.c_uint64), ("genome_bytes", C.c_uint64), ("table_bytes", C.c_uint64)]
 
 
-lib.ntsm_sitegen_open.restype = C.c_int
-lib.ntsm_sitegen_open.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p)]
-lib.ntsm_sitegen_submit.restype = C.c_int
-lib.ntsm_sitegen_submit.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]
-lib.ntsm_sitegen_hits.restype = C.c_int
-lib.ntsm_sitegen_hits.argtypes = [C.c_void_p, C.c_void_p]
-lib.ntsm_sitegen_times_get.restype = C.c_int
-lib.ntsm_sitegen_times_get.argtypes = [C.c_void_p, C.POINTER(Times)]
-lib.ntsm_sitegen_close.restype = None
-lib.ntsm_sitegen_close.argtypes = [C.c_void_p]
+class GapStats(C.Structure):
+    _fields_ = [("table_build_ms", C.c_double), ("table_upload_ms", C.c_double), ("stage_ms", C.c_double), ("upload_ms", C.c_double),
+                ("kernel_ms", C.c_double), ("full_kernel_ms_min", C.c_double), ("full_kernel_ms_max", C.c_double),
+                ("launches", C.c_uint64), ("full_launches", C.c_uint64), ("windows", C.c_uint64), ("windows_long", C.c_uint64),
+                ("windows_short", C.c_uint64), ("bitmap_tests", C.c_uint64), ("probes", C.c_uint64), ("genome_bytes", C.c_uint64),
+                ("table_bytes", C.c_uint64)]
+
+
+def _declare(l, session):
+    """argument and result types of the five functions of the library behind a session class"""
+    def f(name):
+        return getattr(l, session._prefix + "_" + name)
+    f("open").restype = C.c_int
+    f("open").argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p)]
+    f("submit").restype = C.c_int
+    f("submit").argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]
+    f("hits").restype = C.c_int
+    f("hits").argtypes = [C.c_void_p] + [C.c_void_p] * session._n_hits
+    f(session._stats).restype = C.c_int
+    f(session._stats).argtypes = [C.c_void_p, C.POINTER(session._stats_type)]
+    f("close").restype = None
+    f("close").argtypes = [C.c_void_p]
+    return l
+
 
 _CODE = np.full(256, 255, dtype=np.uint8)
 for _i, _c in enumerate(b"ACGT"):
@@ -55,16 +68,29 @@ def pack(kmers, k):
 
 class Session:
     """One candidate set on one device.  submit() takes genome text in pieces; hits() returns min(H, 255) per candidate."""
+    _prefix, _n_hits, _stats, _stats_type = "ntsm_sitegen", 1, "times_get", Times
+
+    @staticmethod
+    def _library():
+        return lib
 
     def __init__(self, kmers, k, x=1, device=0):
+        """x: the substitutions allowed (GapSession: the end margin e, the fourth argument of its open as x is of this one)"""
+        self._lib = self._library()
         self._h = C.c_void_p()
         packed = kmers if isinstance(kmers, np.ndarray) and kmers.dtype == np.uint64 else pack(kmers, k)
         packed = np.ascontiguousarray(packed)
         self.n = len(packed)
-        rc = lib.ntsm_sitegen_open(device, k, x, self.n, packed.ctypes.data if self.n else None, C.byref(self._h))
-        if rc:
+        try:
+            self._call("open", device, k, x, self.n, packed.ctypes.data if self.n else None, C.byref(self._h))
+        except RuntimeError:
             self._h = None
-            raise RuntimeError("ntsm_sitegen_open failed: %d" % rc)
+            raise
+
+    def _call(self, name, *args):
+        rc = getattr(self._lib, self._prefix + "_" + name)(*args)
+        if rc:
+            raise RuntimeError("%s_%s failed: %d" % (self._prefix, name, rc))
 
     def submit(self, bases, ends=()):
         """bases: bytes of record text; ends: the offsets (exclusive) at which a record ends inside `bases`"""
@@ -72,9 +98,7 @@ class Session:
             bases = bases.encode()
         e = np.asarray(ends, dtype=np.uint64)
         buf = np.frombuffer(bases, dtype=np.uint8)
-        rc = lib.ntsm_sitegen_submit(self._h, buf.ctypes.data if len(buf) else None, len(buf), e.ctypes.data if len(e) else None, len(e))
-        if rc:
-            raise RuntimeError("ntsm_sitegen_submit failed: %d" % rc)
+        self._call("submit", self._h, buf.ctypes.data if len(buf) else None, len(buf), e.ctypes.data if len(e) else None, len(e))
 
     def submit_records(self, records, chunk=None):
         """records: sequences (str / bytes), each one whole record; chunk: submit in pieces of this many bytes"""
@@ -90,23 +114,22 @@ class Session:
             if not seq:
                 self.submit(b"", [0])
 
+    def _hit_arrays(self):
+        out = [np.zeros(max(self.n, 1), dtype=np.uint8) for _ in range(self._n_hits)]
+        self._call("hits", self._h, *[o.ctypes.data for o in out])
+        return [o[:self.n] for o in out]
+
     def hits(self):
-        out = np.zeros(max(self.n, 1), dtype=np.uint8)
-        rc = lib.ntsm_sitegen_hits(self._h, out.ctypes.data)
-        if rc:
-            raise RuntimeError("ntsm_sitegen_hits failed: %d" % rc)
-        return out[:self.n]
+        return self._hit_arrays()[0]
 
     def times(self):
-        t = Times()
-        rc = lib.ntsm_sitegen_times_get(self._h, C.byref(t))
-        if rc:
-            raise RuntimeError("ntsm_sitegen_times_get failed: %d" % rc)
+        t = self._stats_type()
+        self._call(self._stats, self._h, C.byref(t))
         return t
 
     def close(self):
         if self._h:
-            lib.ntsm_sitegen_close(self._h)
+            self._call("close", self._h)
             self._h = None
 
     def __enter__(self):
@@ -116,14 +139,7 @@ class Session:
         self.close()
 
 
-class GapStats(C.Structure):
-    _fields_ = [("table_build_ms", C.c_double), ("table_upload_ms", C.c_double), ("stage_ms", C.c_double), ("upload_ms", C.c_double),
-                ("kernel_ms", C.c_double), ("full_kernel_ms_min", C.c_double), ("full_kernel_ms_max", C.c_double),
-                ("launches", C.c_uint64), ("full_launches", C.c_uint64), ("windows", C.c_uint64), ("windows_long", C.c_uint64),
-                ("windows_short", C.c_uint64), ("bitmap_tests", C.c_uint64), ("probes", C.c_uint64), ("genome_bytes", C.c_uint64),
-                ("table_bytes", C.c_uint64)]
-
-
+lib = _declare(C.CDLL(_path), Session)
 _gap = None
 
 
@@ -134,63 +150,21 @@ def gap_lib():
         path = os.path.join(_HERE, "libntsm_sitegen_gap_hip.so")
         if not os.path.exists(path):
             raise ImportError("%s is missing: run `make` (there is no CPU fallback)" % path)
-        g = C.CDLL(path)
-        g.ntsm_sitegap_open.restype = C.c_int
-        g.ntsm_sitegap_open.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p)]
-        g.ntsm_sitegap_submit.restype = C.c_int
-        g.ntsm_sitegap_submit.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]
-        g.ntsm_sitegap_hits.restype = C.c_int
-        g.ntsm_sitegap_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        g.ntsm_sitegap_stats.restype = C.c_int
-        g.ntsm_sitegap_stats.argtypes = [C.c_void_p, C.POINTER(GapStats)]
-        g.ntsm_sitegap_close.restype = None
-        g.ntsm_sitegap_close.argtypes = [C.c_void_p]
-        _gap = g
+        _gap = _declare(C.CDLL(path), GapSession)
     return _gap
 
 
 class GapSession(Session):
     """One candidate set on one device, substitutions and one-base gaps in one pass (end margin e).  submit() and
     submit_records() as Session has them; hits() returns (min(H, 255), min(G, 255)) per candidate."""
+    _prefix, _n_hits, _stats, _stats_type = "ntsm_sitegap", 2, "stats", GapStats
+    _library = staticmethod(gap_lib)
 
     def __init__(self, kmers, k, e=5, device=0):
-        self._lib = gap_lib()
-        self._h = C.c_void_p()
-        packed = kmers if isinstance(kmers, np.ndarray) and kmers.dtype == np.uint64 else pack(kmers, k)
-        packed = np.ascontiguousarray(packed)
-        self.n = len(packed)
-        rc = self._lib.ntsm_sitegap_open(device, k, e, self.n, packed.ctypes.data if self.n else None, C.byref(self._h))
-        if rc:
-            self._h = None
-            raise RuntimeError("ntsm_sitegap_open failed: %d" % rc)
-
-    def submit(self, bases, ends=()):
-        if isinstance(bases, str):
-            bases = bases.encode()
-        e = np.asarray(ends, dtype=np.uint64)
-        buf = np.frombuffer(bases, dtype=np.uint8)
-        rc = self._lib.ntsm_sitegap_submit(self._h, buf.ctypes.data if len(buf) else None, len(buf), e.ctypes.data if len(e) else None, len(e))
-        if rc:
-            raise RuntimeError("ntsm_sitegap_submit failed: %d" % rc)
+        super().__init__(kmers, k, e, device)
 
     def hits(self):
-        sub, gap = np.zeros(max(self.n, 1), dtype=np.uint8), np.zeros(max(self.n, 1), dtype=np.uint8)
-        rc = self._lib.ntsm_sitegap_hits(self._h, sub.ctypes.data, gap.ctypes.data)
-        if rc:
-            raise RuntimeError("ntsm_sitegap_hits failed: %d" % rc)
-        return sub[:self.n], gap[:self.n]
+        return tuple(self._hit_arrays())
 
     def stats(self):
-        st = GapStats()
-        rc = self._lib.ntsm_sitegap_stats(self._h, C.byref(st))
-        if rc:
-            raise RuntimeError("ntsm_sitegap_stats failed: %d" % rc)
-        return st
-
-    def times(self):
-        return self.stats()
-
-    def close(self):
-        if self._h:
-            self._lib.ntsm_sitegap_close(self._h)
-            self._h = None
+        return self.times()

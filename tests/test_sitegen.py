@@ -319,6 +319,17 @@ def test_library_builds_clean_and_its_scalar_memory_instructions_are_loads(built
                                                                      "ntsm_sitegen_times_get", "ntsm_sitegen_close"}
 
 
+def test_staging_state_machine_under_sanitizers(tmp_path):
+    """tests/sitegen_stage_check.cpp, a program of its own under ASan + UBSan: the staging layer that both device libraries
+    share (ntsm_amd/csrc/ntsm_sitegen_stage.h) with buffers of 64 and 256 bytes, k = 11, 19, 31, both seam settings, whole
+    and in chunks around k and around the buffer size: launch shapes, every window counted once, refused ends stage nothing"""
+    exe = str(tmp_path / "sitegen_stage_check")
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe,
+                    os.path.join(ROOT, "tests", "sitegen_stage_check.cpp")], check=True)
+    p = subprocess.run([exe], capture_output=True, timeout=120)
+    assert p.returncode == 0 and p.stdout.startswith(b"stage check ok: 96 cases"), (p.stdout + p.stderr).decode()[-2000:]
+
+
 # ------------------------------------------------------------------------------------------------ GPU: the C ABI
 def fasta_records(path):
     recs = []

@@ -10,8 +10,9 @@ sources around the kernels (round 5: the split of ntsm_hip.hip into six translat
 ntsm_hooks.h) left the product kernels bit-identical, and by tools/make_traffic.py-style profile gating.
   --write FILE   record the hashes (profiles/r05_isa_hashes.json)
   --check FILE   compare with a recorded file; exit 1 and list the kernels that differ
-  --cohort       the kernels of the five cohort libraries (ntsm_eval, ntsm_eval_pca, ntsm_vcf, ntsm_pca, ntsm_sitegen) instead,
-                 each source with the flags the Makefile gives it (profiles/r12_eval_refactor/isa_*.json)
+  --cohort       the kernels of the cohort libraries (ntsm_eval, ntsm_eval_pca, ntsm_vcf, ntsm_pca, ntsm_sitegen,
+                 ntsm_sitegen_gap) instead, each source with the flags the Makefile gives it
+                 (profiles/r12_eval_refactor/isa_*.json, profiles/r15_sitegen_shared/isa_*.json)
 Extra -D flags go to the compiler (e.g. -DNTSM_WITH_TAB)."""
 import hashlib, json, os, re, subprocess, sys, tempfile
 
@@ -21,7 +22,7 @@ SOURCES = {"ntsm_amd/csrc/kernels_generic.hip": ["-fvisibility=hidden"], "ntsm_a
            "ntsm_amd/csrc/kernels_run.hip": ["-fvisibility=hidden"]}
 COHORT = {"ntsm_amd/csrc/ntsm_eval.hip": ["-ffp-contract=off"], "ntsm_amd/csrc/ntsm_eval_pca.hip": ["-ffp-contract=off"],
           "ntsm_amd/csrc/ntsm_vcf.hip": ["-ffp-contract=off"], "ntsm_amd/csrc/ntsm_pca.hip": ["-fvisibility=hidden", "-ffp-contract=off"],
-          "ntsm_amd/csrc/ntsm_sitegen.hip": ["-fvisibility=hidden"]}
+          "ntsm_amd/csrc/ntsm_sitegen.hip": ["-fvisibility=hidden"], "ntsm_amd/csrc/ntsm_sitegen_gap.hip": ["-fvisibility=hidden"]}
 
 
 def kernel_hashes(defs=(), sources=SOURCES):

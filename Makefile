@@ -5,7 +5,8 @@
 #   build/ntsm_synth          generator CLI
 #   build/ntsm_host_test      host-logic test driver (no GPU calls)
 #   ntsm_amd/libntsm_eval_hip.so, build/ntsmEval   all-pairs scoring of ntsmEval (HIP library + CLI mirror)
-#   ntsm_amd/libntsm_vcf_hip.so, build/ntsmVCF     multi-sample VCF to PCA matrix + centre file (HIP library + CLI mirror)
+#   ntsm_amd/libntsm_vcf_hip.so, build/ntsmVCF     multi-sample VCF to PCA matrix + centre file (HIP library + CLI mirror);
+#                                                  with --rotation also the PCA, through libntsm_pca_hip.so
 #   ntsm_amd/libntsm_pca_hip.so, build/ntsmPCA     exact PCA of the ntsmVCF matrix: rotation for ntsmEval -p (HIP library + CLI)
 #   ntsm_amd/libntsm_sitegen_hip.so, build/ntsmSiteGen   sites files from a genome and a VCF of SNPs (HIP library + CLI)
 #   ntsm_amd/libntsm_sitegen_gap_hip.so                  the device step of `ntsmSiteGen -g`: one-base gapped places as well
@@ -86,9 +87,10 @@ ntsm_amd/libntsm_vcf_hip.so: $(CSRC)/ntsm_vcf.hip $(CSRC)/ntsm_hip_scope.h inclu
 
 VCFSRC := $(HOST)/seq_reader.cpp $(HOST)/site_set.cpp $(HOST)/inflate.cpp $(HOST)/inflate_spec.cpp $(HOST)/gz_stream.cpp \
           $(HOST)/gz_parallel.cpp $(HOST)/crc32_fast.cpp
-build/ntsmVCF: $(VCFSRC) $(HOST)/ntsm_vcf_main.cpp $(HOSTHDR) include/ntsm_vcf_hip.h ntsm_amd/libntsm_vcf_hip.so
+build/ntsmVCF: $(VCFSRC) $(HOST)/ntsm_vcf_main.cpp $(HOSTHDR) include/ntsm_vcf_hip.h include/ntsm_pca_hip.h ntsm_amd/libntsm_vcf_hip.so \
+               ntsm_amd/libntsm_pca_hip.so
 	@mkdir -p build
-	$(CXX) $(CXXFLAGS) -ffp-contract=off -o $@ $(VCFSRC) $(HOST)/ntsm_vcf_main.cpp -Lntsm_amd -lntsm_vcf_hip -lz -pthread \
+	$(CXX) $(CXXFLAGS) -ffp-contract=off -o $@ $(VCFSRC) $(HOST)/ntsm_vcf_main.cpp -Lntsm_amd -lntsm_vcf_hip -lntsm_pca_hip -lz -pthread \
 	    -Wl,-rpath,'$$ORIGIN/../ntsm_amd' -Wl,-rpath,/opt/rocm/lib
 
 # ntsmPCA (NAME_matrix.tsv -> NAME_rotationalMatrix.tsv, NAME_components.tsv): own library, own CLI.  rocSOLVER is bound with

@@ -15,6 +15,10 @@
  * workgroups and the partial tiles summed by a second kernel in split order, mirrored into the lower triangle; (3) the
  * eigenpairs of G with rocSOLVER's dsyevd (bound with dlopen on first use); (4) V = Ac U_D / s and T = U_D s.
  * No floating-point atomics anywhere: every result is a pure function of the input and of `split`.
+ *
+ * The matrix may also be given as the 16-bit cells of ntsm_vcf_run (include/ntsm_vcf_hip.h) with the value of every cell
+ * code, the form `ntsmVCF --rotation` hands over: the *_cells entry points below.  The doubles then exist on the device
+ * only: step (0), ntsm_pca_expand, writes the whole padded buffer from the cells, and steps (1) to (4) follow unchanged.
  */
 #ifndef NTSM_PCA_HIP_H
 #define NTSM_PCA_HIP_H
@@ -61,6 +65,39 @@ int ntsm_pca_gram(int device, uint64_t p, uint32_t n, const double *a, int centr
  */
 int ntsm_pca_run(int device, uint64_t p, uint32_t n, const double *a, uint32_t d, uint32_t split,
 		double *eigval, double *rot, double *comp, uint32_t *bad_component, ntsm_pca_times *times);
+
+/*
+ * The matrix as cells.  Cell (s, j) of the p x n matrix is
+ *   code = cells[s * n + j] != 0:  value[0][code] where s * n + j <= first_undef_cell, value[1][code] after it;
+ *   code = 0:                      row_fill[s].
+ * cells:    host [p][n] row-major, as ntsm_vcf_run returns them (maxREF | maxVAR << 8).
+ * value:    host [2][65536] doubles; the caller fills the entries of every code that occurs, entry 0 of both halves is
+ *           not read.  (ntsmVCF fills them with what ntsmPCA would read back from the two texts a code is printed as.)
+ * row_fill: host [p] doubles.
+ * first_undef_cell: a linear index s * n + j, compared in 64 bits; ~0 for none (value[1] is then not read).
+ * expand_ms: out, may be NULL: the expansion kernel's time from HIP events.  times->upload_ms is the upload of cells,
+ *           table and fills.
+ * Argument checks, return codes and `times` are those of the entry points above.
+ *
+ * Contract: ntsm_pca_run_cells(...) returns the same bits as ntsm_pca_run on the matrix ntsm_pca_expand_cells(...)
+ * returns, and ntsm_pca_gram_cells the same bits as ntsm_pca_gram on it -- for the same `split`, in the same process
+ * (the same rocSOLVER build).
+ */
+
+/* The expansion on its own.  a: host out [p][n] row-major (the padding of the device buffer is not returned; that it is
+ * zero shows in G). */
+int ntsm_pca_expand_cells(int device, uint64_t p, uint32_t n, const uint16_t *cells, const double *value,
+		const double *row_fill, uint64_t first_undef_cell, double *a /* host out [p][n] */, double *expand_ms);
+
+/* ntsm_pca_gram on the cells: the test hook for the padding the expansion writes */
+int ntsm_pca_gram_cells(int device, uint64_t p, uint32_t n, const uint16_t *cells, const double *value,
+		const double *row_fill, uint64_t first_undef_cell, int centre, uint32_t split, double *gram, double *means,
+		ntsm_pca_times *times, double *expand_ms);
+
+/* ntsm_pca_run on the cells */
+int ntsm_pca_run_cells(int device, uint64_t p, uint32_t n, const uint16_t *cells, const double *value,
+		const double *row_fill, uint64_t first_undef_cell, uint32_t d, uint32_t split,
+		double *eigval, double *rot, double *comp, uint32_t *bad_component, ntsm_pca_times *times, double *expand_ms);
 
 #ifdef __cplusplus
 }

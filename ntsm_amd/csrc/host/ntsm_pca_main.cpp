@@ -10,6 +10,9 @@
  * bytes on every run and for every -t.  The arithmetic is in libntsm_pca_hip.so
  * (include/ntsm_pca_hip.h); there is no CPU fallback.
  *
+ * The number text, the refusals' words and the writer of the two outputs are in pca_text.hpp, shared with
+ * `ntsmVCF --rotation`, which does this program's work on the cells it has in memory.
+ *
  * The host reads the text (plain or gzip) and converts it on -t threads with std::from_chars, which is correctly
  * rounded; it formats the two outputs on -t threads with std::to_chars' shortest round-trip digits laid out the way
  * Python's repr lays them out, which is how pandas writes a float.
@@ -40,6 +43,7 @@
 
 #include "../../../include/ntsm_pca_hip.h"
 #include "gz_stream.hpp"
+#include "pca_text.hpp"
 
 #define PROGRAM "ntsmPCA"
 
@@ -134,10 +138,10 @@ struct FileBytes {
 	}
 };
 
-struct Name { const char *b; size_t len; };
-
-/* [b, e) without the line's "\r" of a CRLF file */
-const char *line_end(const char *b, const char *e) { return e > b && e[-1] == '\r' ? e - 1 : e; }
+using ntsm::Name;
+using ntsm::format_repr;
+using ntsm::line_end;
+using ntsm::on_threads;
 
 /* one body line into one row of the matrix; an empty string when it is fine, else what is wrong with it */
 std::string parse_row(const char *b, const char *e, uint32_t n, Name &name, double *row)
@@ -150,86 +154,14 @@ std::string parse_row(const char *b, const char *e, uint32_t n, Name &name, doub
 		const char *f = t ? t : e;
 		if (j < n) {
 			double x = 0.0;
-			const auto r = std::from_chars(q, f, x);              /* correctly rounded; no leading '+' or blanks */
-			if (r.ec != std::errc() || r.ptr != f || !std::isfinite(x))
+			if (!ntsm::parse_cell(q, f, x))
 				return "the cell of sample " + std::to_string(j + 1) + " is not a finite number: '" + std::string(q, f) + "'";
 			row[j] = x;
 		}
 		q = f + 1;
 	}
-	if (j != n) return "has " + std::to_string(j + 1) + " fields, the header has " + std::to_string(n + 1);
+	if (j != n) return ntsm::pca_row_fields_error(j + 1, n);
 	return std::string();
-}
-
-/* x as Python's repr writes it (pandas' to_csv): the shortest digits that read back to x; exponent form when the decimal
- * exponent is below -4 or at least 16, the exponent with a sign and at least two digits; "1.0", not "1" */
-size_t format_repr(double x, char *out)
-{
-	char *o = out;
-	if (std::signbit(x)) { *o++ = '-'; x = -x; }
-	if (x == 0.0) { memcpy(o, "0.0", 3); return (size_t) (o + 3 - out); }
-	char buf[40], dig[24];
-	const auto r = std::to_chars(buf, buf + sizeof buf, x, std::chars_format::scientific);   /* d[.ddd]e[+-]XX, shortest */
-	const char *ep = (const char *) memchr(buf, 'e', (size_t) (r.ptr - buf));
-	int nd = 0;
-	for (const char *q = buf; q < ep; ++q) if (*q != '.') dig[nd++] = *q;
-	const int e10 = atoi(std::string(ep + 1, (const char *) r.ptr).c_str());
-	if (e10 >= -4 && e10 < 16) {
-		if (e10 >= 0) {
-			for (int i = 0; i <= e10; ++i) *o++ = i < nd ? dig[i] : '0';
-			*o++ = '.';
-			if (nd > e10 + 1) for (int i = e10 + 1; i < nd; ++i) *o++ = dig[i];
-			else *o++ = '0';
-		} else {
-			*o++ = '0';
-			*o++ = '.';
-			for (int i = 0; i < -e10 - 1; ++i) *o++ = '0';
-			for (int i = 0; i < nd; ++i) *o++ = dig[i];
-		}
-	} else {
-		*o++ = dig[0];
-		if (nd > 1) { *o++ = '.'; for (int i = 1; i < nd; ++i) *o++ = dig[i]; }
-		*o++ = 'e';
-		*o++ = e10 < 0 ? '-' : '+';
-		o += snprintf(o, 8, "%02d", std::abs(e10));
-	}
-	return (size_t) (o - out);
-}
-
-template <class F> void on_threads(unsigned n, F f)
-{
-	std::vector<std::thread> pool;
-	for (unsigned t = 1; t < n; ++t) pool.emplace_back(f, t);
-	f(0u);
-	for (auto &th : pool) th.join();
-}
-
-/* header + one line per name with d values, formatted on T threads in row order */
-bool write_table(const std::string &path, const char *corner, const std::vector<Name> &names, const double *val, uint32_t d, unsigned T)
-{
-	const size_t rows = names.size();
-	std::vector<std::string> part(T);
-	on_threads(T, [&](unsigned t) {
-		const size_t lo = rows * t / T, hi = rows * (t + 1) / T;
-		std::string &s = part[t];
-		char num[48];
-		for (size_t k = lo; k < hi; ++k) {
-			s.append(names[k].b, names[k].len);
-			for (uint32_t i = 0; i < d; ++i) {
-				s.push_back('\t');
-				s.append(num, format_repr(val[k * d + i], num));
-			}
-			s.push_back('\n');
-		}
-	});
-	FILE *f = fopen(path.c_str(), "wb");
-	if (!f) return false;
-	std::string head(corner);
-	for (uint32_t i = 0; i < d; ++i) head += "\t" + std::to_string(i);
-	head += "\n";
-	bool ok = fwrite(head.data(), 1, head.size(), f) == head.size();
-	for (const std::string &s : part) ok = ok && fwrite(s.data(), 1, s.size(), f) == s.size();
-	return (fclose(f) == 0) && ok;
 }
 
 } // namespace
@@ -275,7 +207,7 @@ int main(int argc, char **argv)
 		std::cerr << "Try '--help' for more information.\n";
 		exit(EXIT_FAILURE);
 	}
-	if (opt.numComp < 1) refuse("-n " + std::to_string(opt.numComp) + ": the number of components must be at least 1");
+	if (opt.numComp < 1) refuse(ntsm::pca_dims_low_error(opt.numComp));
 	const unsigned T = opt.threads ? std::min(opt.threads, 256u) : std::max(1u, std::min(64u, std::thread::hardware_concurrency()));
 	auto t_lap = std::chrono::steady_clock::now();
 	const auto t_start = t_lap;
@@ -294,19 +226,8 @@ int main(int argc, char **argv)
 	/* header: alleleID <TAB> sample ... */
 	const char *nl = (const char *) memchr(file.data, '\n', file.size);
 	const char *body = nl ? nl + 1 : end;
-	std::vector<Name> samples;
-	{
-		const char *b = file.data, *e = line_end(b, nl ? nl : end);
-		const char *t = (const char *) memchr(b, '\t', (size_t) (e - b));
-		while (t) {
-			const char *q = t + 1;
-			t = (const char *) memchr(q, '\t', (size_t) (e - q));
-			samples.push_back(Name { q, (size_t) ((t ? t : e) - q) });
-		}
-	}
-	if (samples.size() < 2)
-		refuse("the header of " + opt.matrix + " names " + std::to_string(samples.size()) + " sample(s); a PCA needs at least 2");
-	if (samples.size() >= (1u << 24)) refuse("too many samples: " + std::to_string(samples.size()));
+	const std::vector<Name> samples = ntsm::header_samples(file.data, nl ? nl : end);
+	if (const std::string why = ntsm::pca_shape_error(opt.matrix, samples.size(), 1); !why.empty()) refuse(why);   /* the sites are not counted yet */
 	const uint32_t n = (uint32_t) samples.size();
 
 	/* body lines: cut the bytes into T ranges at line ends, count, then convert every range into its rows */
@@ -330,8 +251,7 @@ int main(int argc, char **argv)
 	});
 	for (unsigned t = 0; t < T; ++t) first[t + 1] += first[t];
 	const uint64_t p = first[T];
-	if (p == 0) refuse("the matrix file " + opt.matrix + " has no sites (only a header)");
-	if (p >= (1ull << 31)) refuse("too many sites: " + std::to_string(p));
+	if (const std::string why = ntsm::pca_shape_error(opt.matrix, n, p); !why.empty()) refuse(why);
 	std::vector<double> a((size_t) p * n);
 	std::vector<Name> sites(p);
 	std::vector<std::string> error(T);
@@ -348,13 +268,10 @@ int main(int argc, char **argv)
 	});
 	for (unsigned t = 0; t < T; ++t)                               /* the first bad line of the file, whatever -t */
 		if (error_row[t] != ~0ull) {
-			const Name &nm = sites[error_row[t]];
-			refuse("line " + std::to_string(error_row[t] + 2) + " of " + opt.matrix + " (" + std::string(nm.b, nm.len) + "): " + error[t]);
+			refuse(ntsm::pca_row_error(opt.matrix, error_row[t], sites[error_row[t]], error[t]));
 		}
 	lap("parse");
-	if ((unsigned long long) opt.numComp > std::min<unsigned long long>(n, p))
-		refuse("-n " + std::to_string(opt.numComp) + " is more than min(samples, sites) = min(" + std::to_string(n) + ", " +
-		    std::to_string(p) + ")");
+	if (const std::string why = ntsm::pca_dims_high_error(opt.numComp, n, p); !why.empty()) refuse(why);
 	const uint32_t d = (uint32_t) opt.numComp;
 	if (opt.verbose) std::cerr << "Matrix: " << p << " sites x " << n << " samples, " << d << " components" << std::endl;
 
@@ -363,23 +280,15 @@ int main(int argc, char **argv)
 	ntsm_pca_times tm;
 	memset(&tm, 0, sizeof tm);
 	const int rc = ntsm_pca_run(opt.device, p, n, a.data(), d, 0, eigval.data(), rot.data(), comp.data(), &bad, &tm);
-	if (rc == NTSM_PCA_E_SOLVER_MISSING) refuse("rocSOLVER cannot be loaded (librocsolver.so.0, librocsolver.so): the eigen step needs it");
-	if (rc == NTSM_PCA_E_RANK)
-		refuse("component " + std::to_string(bad) + " of the " + std::to_string(d) + " requested has no positive eigenvalue beyond rounding "
-		    "(the centred matrix has rank " + std::to_string(bad) + " numerically): ask for fewer components");
-	if (rc == NTSM_PCA_E_SOLVER) refuse("the eigen step failed (rocSOLVER dsyevd)");
-	if (rc != 0) refuse("the device step failed (" + std::to_string(rc) + ") on HIP device " + std::to_string(opt.device));
+	if (rc != 0) refuse(ntsm::pca_run_error(rc, bad, d, opt.device));
 	lap("device");
 	if (opt.verbose) {
-		fprintf(stderr, "[pca] device: upload %.3f ms, centre %.3f ms, gram %.3f ms (%u tiles x %u pieces, %.3f TFLOP/s), eigen %.3f ms, "
-		    "projection %.3f ms, download %.3f ms\n", tm.upload_ms, tm.centre_ms, tm.gram_ms, tm.gram_tiles, tm.gram_split,
-		    tm.gram_ms > 0 ? (double) tm.gram_flops / tm.gram_ms * 1e-9 : 0.0, tm.eigen_ms, tm.project_ms, tm.download_ms);
+		ntsm::pca_print_times(stderr, tm, nullptr);
 		if (opt.verbose > 1) for (uint32_t i = 0; i < d; ++i) fprintf(stderr, "[pca] eigenvalue %u: %.17g\n", i, eigval[i]);
 	}
 
-	const std::string rot_path = opt.prefix + "_rotationalMatrix.tsv", comp_path = opt.prefix + "_components.tsv";
-	if (!write_table(rot_path, "AlleleID", sites, rot.data(), d, T)) refuse("cannot write " + rot_path);
-	if (!write_table(comp_path, "SampleID", samples, comp.data(), d, T)) refuse("cannot write " + comp_path);
+	if (const std::string bad_path = ntsm::write_pca_tables(opt.prefix, sites, samples, rot.data(), comp.data(), d, T); !bad_path.empty())
+		refuse("cannot write " + bad_path);
 	lap("write");
 	if (opt.verbose) fprintf(stderr, "[pca] total: %.4f s\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count());
 	return 0;

@@ -536,7 +536,7 @@ int main(int argc, char **argv)
 	if (argc > 1 && argv[1][0] != '-') {     /* upstream's spelling: a target and name=value pairs */
 		const std::string target = argv[1];
 		if (target == "generate-pca-rot-mat")
-			fail("generate-pca-rot-mat is not one command here: run ntsmVCF on the multi-sample VCF, then ntsmPCA on its matrix");
+			fail("generate-pca-rot-mat is not one command here: run ntsmVCF --rotation on the multi-sample VCF (or ntsmVCF, then ntsmPCA on its matrix)");
 		if (target != "generate-sites")
 			fail("unknown target " + target + " (generate-sites is the one this program has)");
 		for (int i = 2; i < argc; i++) {

@@ -13,6 +13,10 @@
  *                insertCount calls (:151-170) and printNormMatrix's walk of the matrix (MultiCount.hpp:156-187)
  *   matrix       formatted here on -t threads (printNormMatrix, :148-201; iostream's %.*g / %.*Lg, the precision 19
  *                that sticks to the stream after the first undefined cell)
+ *   rotation     -R: the PCA of that matrix in the same run (what ntsmPCA computes from NAME_matrix.tsv): the cells go
+ *                to libntsm_pca_hip.so with the double every cell's text reads back as (include/ntsm_pca_hip.h,
+ *                ntsm_pca_run_cells), and NAME_rotationalMatrix.tsv and NAME_components.tsv are written as ntsmPCA
+ *                writes them (pca_text.hpp); -M leaves NAME_matrix.tsv out
  * Whatever -t is, the result is the one-thread result.  Inputs where the reference throws, asserts or has undefined
  * behaviour are refused with "Error: ..." and exit status 1.  A VCF that starts with the gzip
  * magic is decoded (ntsm::GzStream); the reference reads it as text and finds no samples.
@@ -31,6 +35,7 @@
 #include <cstring>
 #include <fstream>
 #include <iostream>
+#include <limits>
 #include <sstream>
 #include <stdexcept>
 #include <string>
@@ -38,9 +43,11 @@
 #include <unordered_map>
 #include <vector>
 
+#include "../../../include/ntsm_pca_hip.h"
 #include "../../../include/ntsm_vcf_hip.h"
 #include "gz_stream.hpp"
 #include "kmer.hpp"
+#include "pca_text.hpp"
 #include "seq_reader.hpp"
 #include "site_set.hpp"
 
@@ -52,6 +59,8 @@ struct Opt {                                 /* src/Options.h: the members ntsmV
 	int verbose = 0, device = 0;
 	unsigned threads = 1, k = 19, window = 31, multi = 20;
 	bool dupes = false;
+	bool rotation = false, no_matrix = false, dims_given = false;   /* -R, -M, -n (this build only) */
+	long long numComp = 20;                                         /* ntsmPCA's -n and its default */
 	std::string snp, ref, pca;
 };
 
@@ -88,6 +97,11 @@ void printHelpDialog()
 	    "  -w, --window = INT     Window size used. [" << std::to_string(d.window) << "]\n"
 	    "  -r, --ref = STR        Reference fasta. [required]\n"
 	    "  -G, --gpu = INT        HIP device [0] (this build only)\n"
+	    "  -R, --rotation         With -p: also run the PCA of the matrix (as\n"
+	    "                         ntsmPCA does) and write the rotation for\n"
+	    "                         ntsmEval -p and the components. (this build only)\n"
+	    "  -n, --dims = INT       With -R: number of components. [" << std::to_string(d.numComp) << "]\n"
+	    "  -M, --no-matrix        With -R: do not write the matrix file.\n"
 	    "  -h, --help             Display this dialog.\n"
 	    "  -v, --verbose          Display verbose output.\n"
 	    "      --version          Print version information.\n" << std::endl;
@@ -309,12 +323,32 @@ double seconds_since(std::chrono::steady_clock::time_point t)
 	return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
 }
 
-template <class F> void on_threads(unsigned n, F f)
+using ntsm::on_threads;
+
+/* The number text of NAME_matrix.tsv and NAME_center.txt (printNormMatrix, MultiCount.hpp:148-201), stated once: the
+ * matrix writer prints these strings and -R hands the PCA what ntsmPCA would read back from them (text_value). */
+std::string cell_text(unsigned r, unsigned v, int prec)     /* a defined cell: iostream's %.*g of maxREF / (maxREF + maxVAR) */
 {
-	std::vector<std::thread> pool;
-	for (unsigned t = 1; t < n; ++t) pool.emplace_back(f, t);
-	f(0u);
-	for (auto &th : pool) th.join();
+	char b[64];
+	snprintf(b, sizeof b, "%.*g", prec, double(r) / double(r + v));
+	return std::string(b);
+}
+
+std::string centre_text(double sum, uint32_t n_samples)     /* a row's centre, also the text of its undefined cells */
+{
+	char b[128];
+	const long double sizeFloat = n_samples;
+	const long double center = sum / sizeFloat;
+	snprintf(b, sizeof b, "%.19Lg", center);
+	return std::string(b);
+}
+
+constexpr int kShortDigits = 6, kLongDigits = 19;           /* the stream's precision up to / after the first undefined cell */
+
+double text_value(const std::string &text)                  /* the cell ntsmPCA reads from this text; NaN if it would refuse it */
+{
+	double x = 0.0;
+	return ntsm::parse_cell(text.data(), text.data() + text.size(), x) ? x : std::numeric_limits<double>::quiet_NaN();
 }
 
 } // namespace
@@ -330,9 +364,11 @@ int main(int argc, char **argv)
 		{ "kmer", required_argument, nullptr, 'k' }, { "multi", required_argument, nullptr, 'm' },
 		{ "window", required_argument, nullptr, 'w' }, { "ref", required_argument, nullptr, 'r' },
 		{ "help", no_argument, nullptr, 'h' }, { "version", no_argument, &OPT_VERSION, 1 },
-		{ "verbose", no_argument, nullptr, 'v' }, { "gpu", required_argument, nullptr, 'G' }, { nullptr, 0, nullptr, 0 } };
+		{ "verbose", no_argument, nullptr, 'v' }, { "gpu", required_argument, nullptr, 'G' },
+		{ "rotation", no_argument, nullptr, 'R' }, { "dims", required_argument, nullptr, 'n' },
+		{ "no-matrix", no_argument, nullptr, 'M' }, { nullptr, 0, nullptr, 0 } };
 	int ch;
-	while ((ch = getopt_long(argc, argv, "s:t:vhk:dr:w:m:p:G:", long_options, nullptr)) != -1) {
+	while ((ch = getopt_long(argc, argv, "s:t:vhk:dr:w:m:p:G:Rn:M", long_options, nullptr)) != -1) {
 		switch (ch) {                            /* src/ntSeqMatchVCF.cpp:82-156 */
 		case 'h': printHelpDialog(); break;
 		case 'd': opt.dupes = true; break;
@@ -344,6 +380,14 @@ int main(int argc, char **argv)
 		case 't': if (!parse(optarg, opt.threads)) { std::cerr << "Error - Invalid parameter t: " << optarg << std::endl; return 0; } break;
 		case 'r': if (!parse(optarg, opt.ref)) { std::cerr << "Error - Invalid parameter r: " << optarg << std::endl; return 0; } break;
 		case 'G': if (!parse(optarg, opt.device)) { std::cerr << "Error - Invalid parameter G: " << optarg << std::endl; return 0; } break;
+		case 'R': opt.rotation = true; break;
+		case 'M': opt.no_matrix = true; break;
+		case 'n': {                                  /* the whole value, as ntsmPCA reads its -n; a bad one is an error */
+			std::stringstream c(optarg);
+			opt.dims_given = true;
+			if (!(c >> opt.numComp) || !c.eof()) { std::cerr << "Error - Invalid parameter n: " << optarg << std::endl; die = true; }
+			break;
+		}
 		case 'v': opt.verbose++; break;
 		case '?': die = true; break;
 		default: break;
@@ -367,10 +411,19 @@ int main(int argc, char **argv)
 		std::cerr << "Error: Unable to load reference file" << std::endl;
 		die = true;
 	}
+	if (opt.rotation && opt.pca.empty()) {
+		std::cerr << "Error: -R needs -p" << std::endl;
+		die = true;
+	}
+	if (!opt.rotation && (opt.dims_given || opt.no_matrix)) {
+		std::cerr << "Error: " << (opt.dims_given ? "-n" : "-M") << " needs -R" << std::endl;
+		die = true;
+	}
 	if (die) {
 		std::cerr << "Try '--help' for more information.\n";
 		exit(EXIT_FAILURE);
 	}
+	if (opt.rotation && opt.numComp < 1) refuse(ntsm::pca_dims_low_error(opt.numComp));
 	if (inputs.size() > 1) refuse("ntsmVCF takes one VCF file, " + std::to_string(inputs.size()) + " were given");   /* :199 asserts */
 	if (opt.k == 0 || opt.k == 32) refuse("-k " + std::to_string(opt.k) + " is not supported (k must be 1 to 31)");
 	if (opt.window >= kMaxWindow) refuse("-w " + std::to_string(opt.window) + " is too large (at most " + std::to_string(kMaxWindow - 1) + ")");
@@ -511,6 +564,23 @@ int main(int argc, char **argv)
 		}
 	lap("events");
 
+	/* -R: what ntsmPCA refuses from the shape of the matrix alone is refused here, in its words, after every refusal of
+	 * the VCF and before the device is touched.  The names are read back from the header line as ntsmPCA reads them (a
+	 * CRLF header's "\r" goes); site ids hold no white space (ntsm::SeqReader), so every row has the header's fields */
+	std::string head = "alleleID";
+	for (const std::string &sm : samples) { head += "\t"; head += sm; }
+	head += "\n";
+	std::vector<ntsm::Name> pca_samples, pca_sites;
+	if (opt.rotation) {
+		const std::string matrix_name = opt.pca + "_matrix.tsv";
+		pca_samples = ntsm::header_samples(head.data(), head.data() + head.size() - 1);
+		std::string why = ntsm::pca_shape_error(matrix_name, pca_samples.size(), n_sites);
+		if (why.empty() && pca_samples.size() != n_samples) why = "the header of " + matrix_name + " does not read back as its samples";
+		if (why.empty()) why = ntsm::pca_dims_high_error(opt.numComp, n_samples, n_sites);
+		if (!why.empty()) refuse(why);
+		for (const std::string &id : sites.ids) pca_sites.push_back(ntsm::Name { id.data(), id.size() });
+	}
+
 	/* the device step: inserts, maxima, sums (include/ntsm_vcf_hip.h) */
 	std::vector<uint16_t> cells((size_t) n_sites * n_samples);
 	std::vector<double> sums(n_sites);
@@ -565,20 +635,14 @@ int main(int argc, char **argv)
 			std::cerr << "Outputting matrix and normalization values for PCA" << std::endl;
 		}
 		/* printNormMatrix (:148-201) */
-		FILE *out = fopen((opt.pca + "_matrix.tsv").c_str(), "wb");
-		FILE *cf = fopen((opt.pca + "_center.txt").c_str(), "wb");
-		if (!out || !cf) refuse("cannot write " + opt.pca + "_matrix.tsv / _center.txt");
+		const std::string matrix_path = opt.pca + "_matrix.tsv", centre_path = opt.pca + "_center.txt";
 		uint64_t first_undef_cell = ~0ull;                       /* row-major: precision 19 from here on */
 		for (size_t s = 0; s < n_sites && first_undef_cell == ~0ull; ++s)
 			if (first_undef[s] < n_samples) first_undef_cell = (uint64_t) s * n_samples + first_undef[s];
 		std::vector<std::string> centre(n_sites);
 		std::string ctext;
-		char buf[128];
 		for (size_t s = 0; s < n_sites; ++s) {
-			const long double sizeFloat = n_samples;
-			const long double center = sums[s] / sizeFloat;
-			snprintf(buf, sizeof buf, "%.19Lg", center);
-			centre[s] = buf;
+			centre[s] = centre_text(sums[s], n_samples);
 			ctext += centre[s];
 			ctext += "\n";
 		}
@@ -587,21 +651,44 @@ int main(int argc, char **argv)
 		tab[0].resize(65536);
 		tab[1].resize(65536);
 		const unsigned bv[3] = { 0u, opt.multi & 255u, (opt.multi * 2u) & 255u };
-		auto cell_text = [](unsigned r, unsigned v, int prec) {
-			char b[64];
-			snprintf(b, sizeof b, "%.*g", prec, double(r) / double(r + v));
-			return std::string(b);
-		};
 		for (unsigned r : bv)
 			for (unsigned v : bv)
-				if (r + v) { tab[0][r | v << 8] = cell_text(r, v, 6); tab[1][r | v << 8] = cell_text(r, v, 19); }
-		std::string head = "alleleID";
-		for (const std::string &sm : samples) { head += "\t"; head += sm; }
-		head += "\n";
-		fwrite(head.data(), 1, head.size(), out);
+				if (r + v) { tab[0][r | v << 8] = cell_text(r, v, kShortDigits); tab[1][r | v << 8] = cell_text(r, v, kLongDigits); }
+
+		/* -R: the PCA, before anything is written (a refusal writes nothing).  The matrix it sees is the text's: a code's
+		 * value is what ntsmPCA reads back from the code's text, an undefined cell's from the row's centre text.  A code
+		 * outside the table cannot occur (the device step writes only those bytes); its value is NaN, which the eigen
+		 * step's rank test refuses */
+		std::vector<double> rot, comp;
+		const uint32_t dims = (uint32_t) opt.numComp;
+		if (opt.rotation) {
+			lap("cell and centre text");
+			std::vector<double> value(2 * 65536, std::numeric_limits<double>::quiet_NaN()), row_fill(n_sites), eigval(dims);
+			for (int form = 0; form < 2; ++form)
+				for (unsigned c = 1; c < 65536; ++c)
+					if (!tab[form][c].empty()) value[(size_t) form * 65536 + c] = text_value(tab[form][c]);
+			for (size_t s = 0; s < n_sites; ++s) row_fill[s] = text_value(centre[s]);
+			rot.resize((size_t) n_sites * dims);
+			comp.resize((size_t) n_samples * dims);
+			if (opt.verbose) std::cerr << "Matrix: " << n_sites << " sites x " << n_samples << " samples, " << dims << " components" << std::endl;
+			uint32_t bad = 0;
+			double expand_ms = 0.0;
+			ntsm_pca_times ptm;
+			memset(&ptm, 0, sizeof ptm);
+			const int rc = ntsm_pca_run_cells(opt.device, n_sites, n_samples, cells.data(), value.data(), row_fill.data(), first_undef_cell, dims,
+			    0, eigval.data(), rot.data(), comp.data(), &bad, &ptm, &expand_ms);
+			if (rc != 0) refuse(ntsm::pca_run_error(rc, bad, dims, opt.device));
+			if (opt.verbose || prof) ntsm::pca_print_times(stderr, ptm, &expand_ms);
+			lap("pca (total)");
+		}
+
+		FILE *out = opt.no_matrix ? nullptr : fopen(matrix_path.c_str(), "wb");
+		FILE *cf = fopen(centre_path.c_str(), "wb");
+		if ((!out && !opt.no_matrix) || !cf) refuse("cannot write " + opt.pca + "_matrix.tsv / _center.txt");
+		if (out) fwrite(head.data(), 1, head.size(), out);
 		const size_t batch = std::max<size_t>(1, (size_t) (64u << 20) / ((size_t) n_samples * 8 + 64));   /* ~64 MB of text per thread */
 		std::vector<std::string> text(T);
-		for (size_t s0 = 0; s0 < n_sites; s0 += batch * T) {
+		for (size_t s0 = 0; out && s0 < n_sites; s0 += batch * T) {
 			on_threads(T, [&](unsigned t) {
 				std::string &o = text[t];
 				o.clear();
@@ -616,7 +703,7 @@ int main(int argc, char **argv)
 						const int hi19 = (uint64_t) s * n_samples + j > first_undef_cell;
 						const std::string &x = tab[hi19][c];
 						if (!x.empty()) o += x;
-						else o += cell_text(c & 255u, c >> 8, hi19 ? 19 : 6);
+						else o += cell_text(c & 255u, c >> 8, hi19 ? kLongDigits : kShortDigits);
 					}
 					o += '\n';
 				}
@@ -624,9 +711,14 @@ int main(int argc, char **argv)
 			for (unsigned t = 0; t < T; ++t) fwrite(text[t].data(), 1, text[t].size(), out);
 		}
 		fwrite(ctext.data(), 1, ctext.size(), cf);
-		const bool ok = fclose(out) == 0;
+		const bool ok = !out || fclose(out) == 0;
 		if (fclose(cf) != 0 || !ok) refuse("writing " + opt.pca + "_matrix.tsv / _center.txt failed");
 		lap("format + write");
+		if (opt.rotation) {
+			const std::string bad_path = ntsm::write_pca_tables(opt.pca, pca_sites, pca_samples, rot.data(), comp.data(), dims, T);
+			if (!bad_path.empty()) refuse("cannot write " + bad_path);
+			lap("rotation + components write");
+		}
 	}
 	std::cerr << "Time: " << seconds_since(t_start) << " s Memory: " << rss_kbytes() << " kbytes" << std::endl;
 	return 0;

@@ -4,6 +4,9 @@
  *
  * The uploaded matrix lives in a zero-padded buffer [p_pad][ld] (ld = n rounded up to the 128-sample tile, p_pad = p
  * rounded up to the 16-site chunk), so no kernel has a ragged inner loop: the padding contributes exact zeros.
+ *   ntsm_pca_expand        the cells of ntsm_vcf_run into that buffer, padding included: a wave per row, one 16-byte store per
+ *                          lane (two samples), the lanes side by side along the sample dimension; a cell's value from a table
+ *                          by its code
  *   ntsm_pca_centre        one workgroup per site: the row sum in a fixed order (per-thread strided partial sums, then a
  *                          binary tree in LDS), mean = sum / n, and the row rewritten as Ac (padding stays 0)
  *   ntsm_pca_gram_tiles    the hot path: one workgroup per (upper 128 x 128 tile, piece of the site dimension); 4 waves,
@@ -39,6 +42,42 @@ constexpr int kLds = kTile + 16;             /* LDS row stride in doubles: rows 
 constexpr int kProjRows = 4, kProjComp = 8;  /* per wave of the projection kernel */
 
 typedef double v4d __attribute__((ext_vector_type(4)));
+
+/* The whole padded buffer [p_pad][ld] from the 16-bit cells: a wave owns a row at a time (grid-stride over the rows), lane l
+ * the samples 2 l and 2 l + 1 of every 128-sample piece, so each store instruction writes 1 KiB of the row, 16 bytes per lane
+ * (ld is a multiple of 128), and nothing but the row's base is computed in 64 bits.  A live cell is
+ * value[lin > first_undef][code] with lin = row * n + sample, row_fill[row] for code 0; padding is zero.  Rows of cells are
+ * 2 n bytes apart, so the two codes are loaded as two 16-bit values. */
+__global__ __launch_bounds__(256) void ntsm_pca_expand(const uint16_t *__restrict__ cells, const double *__restrict__ value,
+		const double *__restrict__ row_fill, uint64_t first_undef, uint64_t p, uint32_t n, uint64_t p_pad, uint32_t ld,
+		double *__restrict__ a)
+{
+	const uint32_t lane = threadIdx.x & 63;
+	const uint64_t waves = (uint64_t) gridDim.x * 4;
+	for (uint64_t row = (uint64_t) blockIdx.x * 4 + (threadIdx.x >> 6); row < p_pad; row += waves) {
+		double *out_row = a + row * ld;
+		if (row >= p) {                                          /* a padding row (the branch is uniform in the wave) */
+			for (uint32_t col = lane * 2; col < ld; col += 128) *reinterpret_cast<double2 *>(out_row + col) = double2 { 0.0, 0.0 };
+			continue;
+		}
+		const uint64_t base = row * n;
+		const uint16_t *in_row = cells + base;
+		const double fill = row_fill[row];
+#pragma unroll 2
+		for (uint32_t col = lane * 2; col < ld; col += 128) {
+			double2 out = { 0.0, 0.0 };
+			if (col < n) {
+				const uint32_t c0 = in_row[col];
+				out.x = c0 ? value[(base + col > first_undef ? 65536u : 0u) + c0] : fill;
+				if (col + 1 < n) {
+					const uint32_t c1 = in_row[col + 1];
+					out.y = c1 ? value[(base + col + 1 > first_undef ? 65536u : 0u) + c1] : fill;
+				}
+			}
+			*reinterpret_cast<double2 *>(out_row + col) = out;
+		}
+	}
+}
 
 __global__ __launch_bounds__(256) void ntsm_pca_centre(double *a, size_t ld, uint32_t n, double *means, int subtract)
 {
@@ -234,7 +273,10 @@ double ms_since(std::chrono::steady_clock::time_point t)
 /* everything both entry points share: the padded matrix on the device, the row means, G; released with the scope */
 struct Device {
 	ntsm_hip::Buffers buf;
-	ntsm_hip::Events<3> ev;
+	ntsm_hip::Events<5> ev;
+	uint16_t *cells = nullptr;
+	double *value = nullptr, *row_fill = nullptr;
+	double expand_ms = 0.0;
 	double *a = nullptr, *means = nullptr, *partial = nullptr, *g = nullptr;
 	double *w = nullptr, *e = nullptr, *s = nullptr, *ud = nullptr, *t = nullptr, *v = nullptr;
 	rocblas_int *info = nullptr;
@@ -251,23 +293,83 @@ struct Handle {
 	~Handle() { if (h) (void) sv.destroy_handle(h); }
 };
 
+/* where the matrix comes from: host doubles [p][n], or the cells of ntsm_vcf_run with the values of their codes */
+struct Source {
+	const double *a = nullptr;
+	const uint16_t *cells = nullptr;
+	const double *value = nullptr, *row_fill = nullptr;
+	uint64_t first_undef_cell = ~0ull;
+};
+
+bool shape_ok(uint64_t p, uint32_t n)
+{
+	return p >= 1 && n >= 1 && p < (1ull << 31) && n < (1u << 24);
+}
 bool args_ok(uint64_t p, uint32_t n, const double *a)
 {
-	return a && p >= 1 && n >= 1 && p < (1ull << 31) && n < (1u << 24);
+	return a && shape_ok(p, n);
+}
+bool args_ok(uint64_t p, uint32_t n, const Source &src)
+{
+	return src.cells && src.value && src.row_fill && shape_ok(p, n);
+}
+bool run_args_ok(uint64_t p, uint32_t n, uint32_t d, const double *eigval, const double *rot, const double *comp)
+{
+	return n >= 2 && d >= 1 && d <= n && d <= p && eigval && rot && comp;
 }
 
-/* upload, centre, Gram: leaves Ac (or A) in dev.a, the means in dev.means and G in dev.g */
-int gram_on_device(Device &dev, int device, uint64_t p, uint32_t n, const double *a, int centre, uint32_t split, ntsm_pca_times &tm)
+/* the matrix into the padded buffer dev.a: host doubles are copied into a zeroed buffer; cells are uploaded as they are
+ * and expanded by ntsm_pca_expand, which writes the padding too (dev.expand_ms, HIP events) */
+int matrix_on_device(Device &dev, int device, uint64_t p, uint32_t n, const Source &src, ntsm_pca_times &tm)
+{
+	const uint32_t edge = (n + kTile - 1) / kTile;
+	dev.ld = (size_t) edge * kTile;
+	dev.p_pad = (p + kChunk - 1) / kChunk * kChunk;
+	auto t0 = std::chrono::steady_clock::now();
+	HIPCHK(hipSetDevice(device));
+	HIPCHK(dev.ev.create());
+	HIPCHK(dev.buf.alloc(&dev.a, dev.p_pad * dev.ld));
+	if (src.a) {
+		HIPCHK(hipMemset(dev.a, 0, dev.p_pad * dev.ld * sizeof(double)));
+		HIPCHK(hipMemcpy2D(dev.a, dev.ld * sizeof(double), src.a, (size_t) n * sizeof(double), (size_t) n * sizeof(double), p, hipMemcpyHostToDevice));
+		HIPCHK(hipDeviceSynchronize());
+		tm.upload_ms = ms_since(t0);
+		return 0;
+	}
+	float ms = 0;
+	hipDeviceProp_t prop;
+	HIPCHK(hipGetDeviceProperties(&prop, device));
+	HIPCHK(dev.buf.alloc(&dev.cells, p * n));
+	HIPCHK(dev.buf.alloc(&dev.value, 2 * 65536));
+	HIPCHK(dev.buf.alloc(&dev.row_fill, p));
+	HIPCHK(hipMemcpy(dev.cells, src.cells, p * n * sizeof(uint16_t), hipMemcpyHostToDevice));
+	HIPCHK(hipMemcpy(dev.value, src.value, 2 * 65536 * sizeof(double), hipMemcpyHostToDevice));
+	HIPCHK(hipMemcpy(dev.row_fill, src.row_fill, p * sizeof(double), hipMemcpyHostToDevice));
+	HIPCHK(hipDeviceSynchronize());
+	tm.upload_ms = ms_since(t0);
+	/* a grid-stride walk over the rows, four per workgroup: 32 workgroups per compute unit keep every unit's store queue
+	 * fed, and a short buffer gets no more workgroups than it has rows */
+	const unsigned blocks = (unsigned) std::min<uint64_t>(dev.p_pad / 4, 32ull * (uint64_t) prop.multiProcessorCount);
+	HIPCHK(hipEventRecord(dev.ev[3], 0));
+	ntsm_pca_expand<<<dim3(blocks), dim3(256)>>>(dev.cells, dev.value, dev.row_fill, src.first_undef_cell, p, n, dev.p_pad,
+	    (uint32_t) dev.ld, dev.a);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(dev.ev[4], 0));
+	HIPCHK(hipEventSynchronize(dev.ev[4]));
+	HIPCHK(hipEventElapsedTime(&ms, dev.ev[3], dev.ev[4]));
+	dev.expand_ms = ms;
+	return 0;
+}
+
+/* matrix, centre, Gram: leaves Ac (or A) in dev.a, the means in dev.means and G in dev.g */
+int gram_on_device(Device &dev, int device, uint64_t p, uint32_t n, const Source &src, int centre, uint32_t split, ntsm_pca_times &tm)
 {
 	float ms = 0;
 	const uint32_t edge = (n + kTile - 1) / kTile, n_tiles = edge * (edge + 1) / 2;
 	const uint32_t chunks = (uint32_t) ((p + kChunk - 1) / kChunk);
-	dev.ld = (size_t) edge * kTile;
-	dev.p_pad = (uint64_t) chunks * kChunk;
 	uint32_t pieces = split, cpp = 0;
 	hipDeviceProp_t prop;
-	auto t0 = std::chrono::steady_clock::now();
-	HIPCHK(hipSetDevice(device));
+	if (const int rc = matrix_on_device(dev, device, p, n, src, tm)) return rc;
 	HIPCHK(hipGetDeviceProperties(&prop, device));
 	if (!pieces) {
 		/* about 32 workgroups per compute unit: two are resident at a time (128 accumulator registers per lane), so the
@@ -278,15 +380,9 @@ int gram_on_device(Device &dev, int device, uint64_t p, uint32_t n, const double
 	pieces = std::max(1u, std::min(pieces, chunks));
 	cpp = (chunks + pieces - 1) / pieces;
 	pieces = (chunks + cpp - 1) / cpp;                          /* no empty piece; the last one may be short */
-	HIPCHK(dev.ev.create());
-	HIPCHK(dev.buf.alloc(&dev.a, dev.p_pad * dev.ld));
 	HIPCHK(dev.buf.alloc(&dev.means, dev.p_pad));
 	HIPCHK(dev.buf.alloc(&dev.partial, (size_t) pieces * n_tiles * kTile * kTile));
 	HIPCHK(dev.buf.alloc(&dev.g, (size_t) n * n));
-	HIPCHK(hipMemset(dev.a, 0, dev.p_pad * dev.ld * sizeof(double)));
-	HIPCHK(hipMemcpy2D(dev.a, dev.ld * sizeof(double), a, (size_t) n * sizeof(double), (size_t) n * sizeof(double), p, hipMemcpyHostToDevice));
-	HIPCHK(hipDeviceSynchronize());
-	tm.upload_ms = ms_since(t0);
 
 	HIPCHK(hipEventRecord(dev.ev[0], 0));
 	ntsm_pca_centre<<<dim3((unsigned) p), dim3(256)>>>(dev.a, dev.ld, n, dev.means, centre ? 1 : 0);
@@ -310,27 +406,26 @@ int gram_on_device(Device &dev, int device, uint64_t p, uint32_t n, const double
 	return 0;
 }
 
-} // namespace
-
-extern "C" __attribute__((visibility("default"))) int ntsm_pca_gram(int device, uint64_t p, uint32_t n, const double *a,
-		int centre, uint32_t split, double *gram, double *means, ntsm_pca_times *times)
+/* the Gram step of either source */
+int gram_of(int device, uint64_t p, uint32_t n, const Source &src, int centre, uint32_t split, double *gram, double *means,
+		ntsm_pca_times *times, double *expand_ms)
 {
-	if (!args_ok(p, n, a) || !gram) return NTSM_PCA_E_ARG;
 	ntsm_pca_times tm = {};
 	Device dev;
-	if (const int rc = gram_on_device(dev, device, p, n, a, centre, split, tm)) return rc;
+	if (const int rc = gram_on_device(dev, device, p, n, src, centre, split, tm)) return rc;
 	auto t0 = std::chrono::steady_clock::now();
 	HIPCHK(hipMemcpy(gram, dev.g, (size_t) n * n * sizeof(double), hipMemcpyDeviceToHost));
 	if (means) HIPCHK(hipMemcpy(means, dev.means, p * sizeof(double), hipMemcpyDeviceToHost));
 	tm.download_ms = ms_since(t0);
 	if (times) *times = tm;
+	if (expand_ms) *expand_ms = dev.expand_ms;
 	return 0;
 }
 
-extern "C" __attribute__((visibility("default"))) int ntsm_pca_run(int device, uint64_t p, uint32_t n, const double *a,
-		uint32_t d, uint32_t split, double *eigval, double *rot, double *comp, uint32_t *bad_component, ntsm_pca_times *times)
+/* the whole PCA of either source */
+int run_of(int device, uint64_t p, uint32_t n, const Source &src, uint32_t d, uint32_t split, double *eigval, double *rot,
+		double *comp, uint32_t *bad_component, ntsm_pca_times *times, double *expand_ms)
 {
-	if (!args_ok(p, n, a) || n < 2 || d < 1 || d > n || d > p || !eigval || !rot || !comp) return NTSM_PCA_E_ARG;
 	const Solver &sv = solver_bind();
 	if (!sv.ok) return NTSM_PCA_E_SOLVER_MISSING;
 	float ms = 0;
@@ -340,7 +435,7 @@ extern "C" __attribute__((visibility("default"))) int ntsm_pca_run(int device, u
 	rocblas_int info = 0;
 	const uint32_t d_pad = (d + kProjComp - 1) / kProjComp * kProjComp;
 	std::vector<double> w(n), s(d_pad, 1.0);
-	if (const int rc = gram_on_device(dev, device, p, n, a, 1, split, tm)) return rc;
+	if (const int rc = gram_on_device(dev, device, p, n, src, 1, split, tm)) return rc;
 
 	/* eigenpairs of G: dsyevd overwrites G with the eigenvectors (column-major), eigenvalues ascending in w */
 	HIPCHK(dev.buf.alloc(&dev.w, n));
@@ -409,5 +504,71 @@ extern "C" __attribute__((visibility("default"))) int ntsm_pca_run(int device, u
 		for (uint32_t j = 0; j < n; ++j) comp[(size_t) j * d + i] = -comp[(size_t) j * d + i];
 	}
 	if (times) *times = tm;
+	if (expand_ms) *expand_ms = dev.expand_ms;
 	return 0;
+}
+
+Source host_matrix(const double *a)
+{
+	Source src;
+	src.a = a;
+	return src;
+}
+Source cell_matrix(const uint16_t *cells, const double *value, const double *row_fill, uint64_t first_undef_cell)
+{
+	Source src;
+	src.cells = cells;
+	src.value = value;
+	src.row_fill = row_fill;
+	src.first_undef_cell = first_undef_cell;
+	return src;
+}
+
+} // namespace
+
+#define NTSM_PCA_EXPORT extern "C" __attribute__((visibility("default")))
+
+NTSM_PCA_EXPORT int ntsm_pca_gram(int device, uint64_t p, uint32_t n, const double *a, int centre, uint32_t split, double *gram,
+		double *means, ntsm_pca_times *times)
+{
+	if (!args_ok(p, n, a) || !gram) return NTSM_PCA_E_ARG;
+	return gram_of(device, p, n, host_matrix(a), centre, split, gram, means, times, nullptr);
+}
+
+NTSM_PCA_EXPORT int ntsm_pca_run(int device, uint64_t p, uint32_t n, const double *a, uint32_t d, uint32_t split, double *eigval,
+		double *rot, double *comp, uint32_t *bad_component, ntsm_pca_times *times)
+{
+	if (!args_ok(p, n, a) || !run_args_ok(p, n, d, eigval, rot, comp)) return NTSM_PCA_E_ARG;
+	return run_of(device, p, n, host_matrix(a), d, split, eigval, rot, comp, bad_component, times, nullptr);
+}
+
+NTSM_PCA_EXPORT int ntsm_pca_expand_cells(int device, uint64_t p, uint32_t n, const uint16_t *cells, const double *value,
+		const double *row_fill, uint64_t first_undef_cell, double *a, double *expand_ms)
+{
+	const Source src = cell_matrix(cells, value, row_fill, first_undef_cell);
+	if (!args_ok(p, n, src) || !a) return NTSM_PCA_E_ARG;
+	ntsm_pca_times tm = {};
+	Device dev;
+	if (const int rc = matrix_on_device(dev, device, p, n, src, tm)) return rc;
+	HIPCHK(hipMemcpy2D(a, (size_t) n * sizeof(double), dev.a, dev.ld * sizeof(double), (size_t) n * sizeof(double), p, hipMemcpyDeviceToHost));
+	if (expand_ms) *expand_ms = dev.expand_ms;
+	return 0;
+}
+
+NTSM_PCA_EXPORT int ntsm_pca_gram_cells(int device, uint64_t p, uint32_t n, const uint16_t *cells, const double *value,
+		const double *row_fill, uint64_t first_undef_cell, int centre, uint32_t split, double *gram, double *means,
+		ntsm_pca_times *times, double *expand_ms)
+{
+	const Source src = cell_matrix(cells, value, row_fill, first_undef_cell);
+	if (!args_ok(p, n, src) || !gram) return NTSM_PCA_E_ARG;
+	return gram_of(device, p, n, src, centre, split, gram, means, times, expand_ms);
+}
+
+NTSM_PCA_EXPORT int ntsm_pca_run_cells(int device, uint64_t p, uint32_t n, const uint16_t *cells, const double *value,
+		const double *row_fill, uint64_t first_undef_cell, uint32_t d, uint32_t split, double *eigval, double *rot, double *comp,
+		uint32_t *bad_component, ntsm_pca_times *times, double *expand_ms)
+{
+	const Source src = cell_matrix(cells, value, row_fill, first_undef_cell);
+	if (!args_ok(p, n, src) || !run_args_ok(p, n, d, eigval, rot, comp)) return NTSM_PCA_E_ARG;
+	return run_of(device, p, n, src, d, split, eigval, rot, comp, bad_component, times, expand_ms);
 }

@@ -34,6 +34,15 @@ lib.ntsm_pca_gram.argtypes = [C.c_int, C.c_uint64, C.c_uint32, C.c_void_p, C.c_i
 lib.ntsm_pca_run.restype = C.c_int
 lib.ntsm_pca_run.argtypes = [C.c_int, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                              C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(Times)]
+_CELLS = [C.c_int, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+lib.ntsm_pca_expand_cells.restype = C.c_int
+lib.ntsm_pca_expand_cells.argtypes = _CELLS + [C.c_void_p, C.POINTER(C.c_double)]
+lib.ntsm_pca_gram_cells.restype = C.c_int
+lib.ntsm_pca_gram_cells.argtypes = _CELLS + [C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Times), C.POINTER(C.c_double)]
+lib.ntsm_pca_run_cells.restype = C.c_int
+lib.ntsm_pca_run_cells.argtypes = _CELLS + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32),
+                                            C.POINTER(Times), C.POINTER(C.c_double)]
+NO_UNDEF = (1 << 64) - 1
 
 
 def _matrix(a):
@@ -77,3 +86,77 @@ def run(a, d, split=0, device=0):
     if rc:
         raise RuntimeError("ntsm_pca_run failed: %d" % rc)
     return eigval, rot, comp, times
+
+
+def _cells(cells, value, row_fill, first_undef_cell):
+    """The cell form of the matrix as the ABI takes it: (p, n, cells, value, row_fill, first_undef_cell).  None stays
+    None (a NULL pointer, which the library refuses)."""
+    if cells is not None:
+        cells = np.ascontiguousarray(cells, dtype=np.uint16)
+        if cells.ndim != 2 or cells.shape[0] < 1 or cells.shape[1] < 1:
+            raise ValueError("the cells must be 2-D [sites][samples] and not empty")
+    if value is not None:
+        value = np.ascontiguousarray(value, dtype=np.float64)
+        if value.shape != (2, 65536):
+            raise ValueError("value must be [2][65536]: [long form][cell code]")
+    if row_fill is not None:
+        row_fill = np.ascontiguousarray(row_fill, dtype=np.float64)
+        if cells is not None and row_fill.shape != (cells.shape[0],):
+            raise ValueError("row_fill must hold one value per site")
+    first = NO_UNDEF if first_undef_cell is None else int(first_undef_cell)
+    return cells, value, row_fill, first
+
+
+def _ptr(x):
+    return None if x is None else x.ctypes.data
+
+
+def expand_cells(cells, value, row_fill, first_undef_cell=None, device=0, shape=None):
+    """The expansion step on its own.  cells: uint16 [p sites][n samples] of ntsm_amd.vcf.run; value: float64 [2][65536],
+    [long form][code]; row_fill: float64 [p], the value of a cell of code 0; first_undef_cell: the linear index after
+    which the long form holds, None for none.  Returns (the matrix float64 [p][n], the kernel's milliseconds).
+    shape: (p, n) where cells is None (the argument checks)."""
+    cells, value, row_fill, first = _cells(cells, value, row_fill, first_undef_cell)
+    p, n = cells.shape if cells is not None else shape
+    a = np.empty((p, n), dtype=np.float64)
+    ms = C.c_double()
+    rc = lib.ntsm_pca_expand_cells(device, p, n, _ptr(cells), _ptr(value), _ptr(row_fill), first, a.ctypes.data, C.byref(ms))
+    if rc:
+        raise RuntimeError("ntsm_pca_expand_cells failed: %d" % rc)
+    return a, ms.value
+
+
+def gram_cells(cells, value, row_fill, first_undef_cell=None, centre=True, split=0, device=0):
+    """gram() on the cell form of the matrix: (G, the row means, Times)."""
+    cells, value, row_fill, first = _cells(cells, value, row_fill, first_undef_cell)
+    p, n = cells.shape
+    g = np.empty((n, n), dtype=np.float64)
+    means = np.empty(p, dtype=np.float64)
+    times = Times()
+    rc = lib.ntsm_pca_gram_cells(device, p, n, _ptr(cells), _ptr(value), _ptr(row_fill), first, 1 if centre else 0, split,
+                                 g.ctypes.data, means.ctypes.data, C.byref(times), None)
+    if rc:
+        raise RuntimeError("ntsm_pca_gram_cells failed: %d" % rc)
+    return g, means, times
+
+
+def run_cells(cells, value, row_fill, d, first_undef_cell=None, split=0, device=0, shape=None):
+    """run() on the cell form of the matrix: (eigenvalues, rotation, components, Times, the expansion's milliseconds) --
+    the same bits as run(expand_cells(...)[0], d, split) in the same process."""
+    cells, value, row_fill, first = _cells(cells, value, row_fill, first_undef_cell)
+    p, n = cells.shape if cells is not None else shape
+    eigval = np.empty(max(d, 1), dtype=np.float64)
+    rot = np.empty((p, max(d, 1)), dtype=np.float64)
+    comp = np.empty((n, max(d, 1)), dtype=np.float64)
+    bad = C.c_uint32()
+    times = Times()
+    ms = C.c_double()
+    rc = lib.ntsm_pca_run_cells(device, p, n, _ptr(cells), _ptr(value), _ptr(row_fill), first, d, split, eigval.ctypes.data,
+                                rot.ctypes.data, comp.ctypes.data, C.byref(bad), C.byref(times), C.byref(ms))
+    if rc == E_RANK:
+        raise RankError(bad.value)
+    if rc == E_SOLVER_MISSING:
+        raise RuntimeError("rocSOLVER cannot be loaded (librocsolver.so.0, librocsolver.so)")
+    if rc:
+        raise RuntimeError("ntsm_pca_run_cells failed: %d" % rc)
+    return eigval, rot, comp, times, ms.value

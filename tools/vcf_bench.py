@@ -7,9 +7,12 @@ events), download, format + write, wall time, and the state kernel's bytes over 
 VCF text) and the matrix (1-7 GB of text, depending on where the first undefined cell falls) live in a temporary
 directory that is removed afterwards, unless --dir names one to keep the inputs in (the matrix is removed anyway).
 --rocprof runs the same command under `rocprofv3 --kernel-trace --stats` instead, with its output in --rocprof-out.
+--rotation measures the three routes from the VCF to the rotation on the same inputs instead and prints one JSON line
+per leg: `ntsmVCF -p`, then `ntsmPCA` on its matrix; `ntsmVCF -R`; `ntsmVCF -R -M` -- wall time of every program and its
+lap lines (--raw-out DIR keeps every program's stderr laps as text).
 
   python3 tools/vcf_bench.py [--sites 96287] [--samples 3202] [--threads 16] [--seed 1] [--dir DIR]
-                             [--rocprof --rocprof-out DIR]
+                             [--rocprof --rocprof-out DIR] [--rotation [--dims 20] [--raw-out DIR]]
 """
 import argparse
 import json
@@ -25,6 +28,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 VCF = os.path.join(ROOT, "build", "ntsmVCF")
+PCA = os.path.join(ROOT, "build", "ntsmPCA")
 ALT = {65: 71, 67: 84, 71: 65, 84: 67}
 
 
@@ -76,6 +80,51 @@ def generate(d, n_sites, n_samples, seed, k=19):
         f.close()
 
 
+def laps(err):
+    """The lap lines of a program's stderr: {"[vcf] parse": seconds, ...} and the device lines as text"""
+    phases = {m.group(1) + " " + m.group(2): float(m.group(3)) for m in re.finditer(r"^(\[(?:vcf|pca)\]) ([^:\n]+): ([0-9.]+) s$", err, re.M)}
+    device = [l for l in err.splitlines() if l.startswith(("[vcf] device:", "[pca] device:"))]
+    return phases, device
+
+
+def rotation_legs(a, d, tmp):
+    """Three routes to NAME_center.txt + NAME_rotationalMatrix.tsv + NAME_components.tsv, in one session"""
+    env = dict(os.environ, NTSM_VCF_PROF="1")
+    common = [VCF, "-d", "-t", str(a.threads), "-s", os.path.join(d, "sites.fa"), "-r", os.path.join(d, "genome.fa")]
+    vcf = os.path.join(d, "cohort.vcf")
+    two, fused, nomat = os.path.join(tmp, "two"), os.path.join(tmp, "fused"), os.path.join(tmp, "nomat")
+    legs = [("two_programs", [common + ["-p", two, vcf],
+                              [PCA, "-v", "-t", str(a.threads), "-n", str(a.dims), "-m", two + "_matrix.tsv", "-p", two]]),
+            ("rotation", [common + ["-R", "-n", str(a.dims), "-p", fused, vcf]]),
+            ("rotation_no_matrix", [common + ["-R", "-M", "-n", str(a.dims), "-p", nomat, vcf]])]
+    raw = []
+    for name, cmds in legs:
+        res = dict(leg=name, sites=a.sites, samples=a.samples, threads=a.threads, dims=a.dims, programs=[])
+        total = 0.0
+        for cmd in cmds:
+            t0 = time.time()
+            p = subprocess.run(cmd, env=env, capture_output=True)
+            wall = time.time() - t0
+            err = p.stderr.decode(errors="replace")
+            if p.returncode != 0:
+                sys.stderr.write(err[-3000:])
+                sys.exit(p.returncode)
+            phases, device = laps(err)
+            total += wall
+            res["programs"].append(dict(program=os.path.basename(cmd[0]), wall_s=round(wall, 3), laps_s=phases, device=device))
+            raw.append("== %s: %s\n" % (name, " ".join(os.path.basename(c) if os.sep in c else c for c in cmd)) +
+                       "".join(l + "\n" for l in err.splitlines() if l.startswith(("[vcf]", "[pca]", "Time:", "Matrix:"))))
+        res["wall_s"] = round(total, 3)
+        print(json.dumps(res), flush=True)
+    same = all(open(two + s, "rb").read() == open(fused + s, "rb").read() for s in ("_center.txt", "_rotationalMatrix.tsv", "_components.tsv"))
+    same = same and all(open(fused + s, "rb").read() == open(nomat + s, "rb").read() for s in ("_center.txt", "_rotationalMatrix.tsv", "_components.tsv"))
+    print(json.dumps(dict(leg="check", same_bytes_on_every_route=same, matrix_bytes=os.path.getsize(fused + "_matrix.tsv"))), flush=True)
+    if a.raw_out:
+        os.makedirs(a.raw_out, exist_ok=True)
+        with open(os.path.join(a.raw_out, "laps.txt"), "w") as f:
+            f.write("".join(raw))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--sites", type=int, default=96287)
@@ -85,6 +134,9 @@ def main():
     ap.add_argument("--dir", default=None, help="keep the generated inputs here (reused when present)")
     ap.add_argument("--rocprof", action="store_true")
     ap.add_argument("--rocprof-out", default=None)
+    ap.add_argument("--rotation", action="store_true", help="measure the routes to the rotation instead (three legs)")
+    ap.add_argument("--dims", type=int, default=20)
+    ap.add_argument("--raw-out", default=None)
     a = ap.parse_args()
     tmp = tempfile.mkdtemp(prefix="vcf_bench_")
     d = a.dir or tmp
@@ -94,6 +146,9 @@ def main():
         if not os.path.exists(os.path.join(d, "cohort.vcf")):
             generate(d, a.sites, a.samples, a.seed)
         gen_s = time.time() - t0
+        if a.rotation:
+            rotation_legs(a, d, tmp)
+            return
         prefix = os.path.join(tmp, "out")
         cmd = [VCF, "-d", "-t", str(a.threads), "-s", os.path.join(d, "sites.fa"), "-r", os.path.join(d, "genome.fa"), "-p", prefix,
                os.path.join(d, "cohort.vcf")]

@@ -89,7 +89,9 @@ int ntsm_set_submit_threads(ntsm_ctx *ctx, int n_threads);
  * ntsm_host_pin below; anything else is refused with NTSM_ERR_ARG): the H2D copy reads the caller's buffer directly, no
  * staging copy.  Asynchronous with two batches in flight: `bases` must stay untouched until the SECOND next
  * ntsm_submit_pinned call on this context has returned, or until ntsm_sync (an armed context, max_hits != 0, is
- * synchronous: free on return).  read_end is ordinary memory and free on return.  This is the form of the per-read call
+ * synchronous: free on return).  read_end is ordinary memory and free on return.  A batch whose copy or launch fails is lost and
+ * marks the context failed (NTSM_ERR_STATE from then on, see ntsm_debug_fail_after): ntsm_destroy, which waits for the device,
+ * is then what frees `bases`.  This is the form of the per-read call
  * src/FingerPrint.hpp:66-69 that needs no host-side copy at all when the parser writes into pinned memory it owns. */
 int ntsm_submit_pinned(ntsm_ctx *ctx, const uint8_t *bases, uint64_t n_bytes, const uint64_t *read_end,
 		uint32_t n_reads);
@@ -235,10 +237,12 @@ int ntsm_debug_stats(ntsm_ctx *ctx, uint64_t out[8]);
  * hipErrorOutOfMemory (allocations) / hipErrorUnknown (copies); only that one call fails.  nth = 0 disarms.  Returns the
  * number of calls of that kind seen since the previous arming (so a test can first count the calls an operation makes and
  * then fail each in turn), -1 for an unknown kind.  What a failure must look like to the caller: ntsm_create returns an
- * error and leaves nothing allocated; a failed table rebuild (ntsm_set_kernel / ntsm_set_tuning) or a lost lane batch marks
- * the context failed -- every later counting / merging / reporting call answers NTSM_ERR_STATE, ntsm_lane_close repeats the
- * lane's first error -- so an incomplete count can never be printed (the reference: exit(1) with a message,
- * src/FingerPrint.hpp:51-57, :493-499). */
+ * error and leaves nothing allocated; a staging slot or a lane that cannot be allocated whole is not allocated at all (the call
+ * may be repeated); a failed table rebuild (ntsm_set_kernel / ntsm_set_tuning) or a LOST batch of any submit form -- its copy or
+ * its launch failed: ntsm_submit, ntsm_submit_staged, ntsm_submit_pinned, ntsm_lane_submit, ntsm_lane_submit_packed -- marks the
+ * context failed: every later counting / merging / reporting call answers NTSM_ERR_STATE, ntsm_lane_close repeats the lane's
+ * first error, so an incomplete count can never be printed and no slot is reused under a copy still in flight (the reference:
+ * exit(1) with a message, src/FingerPrint.hpp:51-57, :493-499). */
 long long ntsm_debug_fail_after(int kind, long long nth);
 /* Test hook, host code only (no device needed): the run-anchored kernel's filter (ntsm_set_kernel 5, k = 19) for `keys` (canonical
  * codes) as ntsm_create would build it, kib = its size in KiB (0 = automatic).  *n_blocks receives the number of 128-bit blocks;

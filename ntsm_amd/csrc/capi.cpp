@@ -149,12 +149,7 @@ void ntsm_destroy(ntsm_ctx *c)
 	if (!c) return;
 	(void) hipSetDevice(c->device);
 	(void) hipDeviceSynchronize();
-	for (auto &s : c->slot) {
-		free_slot(s);
-		stream_put(c->device, s.stream);
-		if (s.done) (void) hipEventDestroy(s.done);
-		if (s.copied) (void) hipEventDestroy(s.copied);
-	}
+	for (auto &s : c->slot) slot_release(s);
 	stream_put(c->device, c->rstream);
 	stream_put(c->device, c->cstream);
 	for (hipStream_t st : c->lane_stream) stream_put(c->device, st);
@@ -179,7 +174,7 @@ int ntsm_set_batch_capacity(ntsm_ctx *c, uint64_t cap_bytes, uint64_t cap_reads)
 	for (auto &s : c->slot) {
 		int rc = wait_slot(s);
 		if (rc) return rc;
-		free_slot(s);
+		slot_release(s);
 	}
 	c->cap_bytes = cap_bytes;
 	c->cap_reads = cap_reads;
@@ -193,7 +188,7 @@ int ntsm_staging_acquire(ntsm_ctx *c, uint8_t **bases, uint64_t *cap_bytes, uint
 	HIPCHK(hipSetDevice(c->device));
 	Slot &s = c->slot[c->next_slot];
 	if (!s.d_bases) {
-		int rc = alloc_slot(s, c->device, c->cap_bytes, c->cap_reads, true);
+		int rc = slot_acquire(s, { c->device, c->cap_bytes, c->cap_reads, true, SlotDesc::kByteStaging, nullptr, nullptr });
 		if (rc) return rc;
 	} else if (!s.h_bases) {                               /* the slot was made by ntsm_submit_pinned, without staging for the bases */
 		int rc = slot_add_host_bases(s);
@@ -222,7 +217,7 @@ int ntsm_submit_staged(ntsm_ctx *c, uint64_t n_bytes, uint32_t n_reads)
 	if (c->early_stop) return NTSM_OK;                    /* threshold already tripped: nothing more is counted */
 	c->reduced = false;
 	HIPCHK(hipSetDevice(c->device));
-	rc = submit_slot(c, s, n_bytes, n_reads);
+	rc = submit_slot(c, s, s.h_bases, n_bytes, n_reads);
 	c->next_slot ^= 1;
 	return rc;
 }
@@ -280,15 +275,10 @@ static int lane_open(ntsm_ctx *c, uint64_t cap_bytes, uint64_t cap_reads, bool p
 		st = slot_stream;
 	}
 	if (!st) { delete l; return NTSM_ERR_HIP; }
-	for (int i = 0; i < 2; ++i) {
-		Slot &s = l->slot[i];
-		s.stream = st;
-		int rc = alloc_slot(s, c->device, cap_bytes, cap_reads, false, packed_only, c);
+	for (auto &s : l->slot) {
+		int rc = slot_acquire(s, { c->device, cap_bytes, cap_reads, false, packed_only ? SlotDesc::kPackedStaging : SlotDesc::kByteStaging, c, st });
 		if (rc) {
-			for (auto &q : l->slot) {
-				free_slot(q, c);
-				if (q.done) (void) hipEventDestroy(q.done);
-			}
+			for (auto &q : l->slot) slot_release(q);            /* the one acquired before, if any */
 			delete l;
 			return rc;
 		}
@@ -330,15 +320,11 @@ static int lane_lost_batch(ntsm_lane *l, int rc)
 	return rc;
 }
 
-#define LANECHK(call)                                                                     \
-	do {                                                                                  \
-		hipError_t e_ = (call);                                                           \
-		if (e_ != hipSuccess) {                                                           \
-			set_last_hip((int) e_);                                                       \
-			fprintf(stderr, "ntsm_hip: %s failed: %s (%s:%d)\n", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-			return lane_lost_batch(l, NTSM_ERR_HIP);                                      \
-		}                                                                                 \
-	} while (0)
+static int lane_set_device(ntsm_lane *l)        /* a lane's thread makes the device current per batch; failing that, the batch is lost too */
+{
+	HIPCHK(hipSetDevice(l->c->device));
+	return NTSM_OK;
+}
 
 int ntsm_lane_submit(ntsm_lane *l, uint64_t n_bytes, uint32_t n_reads)
 {
@@ -351,18 +337,9 @@ int ntsm_lane_submit(ntsm_lane *l, uint64_t n_bytes, uint32_t n_reads)
 	int rc = check_layout(s.h_read_end, n_reads, n_bytes);
 	if (rc) return rc;
 	if (n_reads == 0) return NTSM_OK;
-	ntsm_ctx *c = l->c;
-	LANECHK(hipSetDevice(c->device));
-	{
-		void *const dst[1] = { s.d_bases };
-		const void *const src[1] = { s.h_bases };
-		const size_t bytes[1] = { (size_t) n_bytes };
-		LANECHK(slot_copy(c, s, dst, src, bytes, 1));
-	}
-	rc = launch_count(c, s.stream, s.d_bases, 0, n_bytes, nullptr, 0, false, +1);
+	rc = lane_set_device(l);
+	if (!rc) rc = enqueue_batch(l->c, s, s.d_bases, s.h_bases, n_bytes, nullptr, nullptr, 0, 0, n_bytes);
 	if (rc) return lane_lost_batch(l, rc);
-	LANECHK(hipEventRecord(s.done, s.stream));
-	s.busy = true;
 	l->total_bases += n_bytes - n_reads;
 	l->reads_consumed += n_reads;
 	l->next_slot ^= 1;
@@ -399,37 +376,22 @@ int ntsm_lane_submit_packed(ntsm_lane *l, uint64_t n_positions, uint32_t n_reads
 	const uint64_t cap_pos = l->cap_bytes & ~31ull;
 	if ((n_positions & 7) || n_positions > cap_pos || n_bases + n_reads > n_positions) return NTSM_ERR_ARG;
 	if (n_reads == 0 || n_positions == 0) return NTSM_OK;
-	ntsm_ctx *c = l->c;
-	LANECHK(hipSetDevice(c->device));
 	/* whole groups of 32 positions cross the link and are unpacked: what lies between the end of the batch and the next
 	 * multiple of 32 is marked invalid here (the caller may have left anything there) */
 	const uint64_t n_out = (n_positions + 31) & ~31ull;
 	uint8_t *h_valid = s.h_bases + cap_pos / 4;
 	for (uint64_t p = n_positions; p < n_out; p += 8) h_valid[p >> 3] = 0;
-	{
-		/* The two planes lie at the same offsets in the pinned slot and in its device image, so a (nearly) full batch crosses
-		 * as ONE copy -- the codes plane to its end, then the used part of the validity plane.  Every copy on the copy stream is
-		 * followed by ~50 us before the next one starts (profiles/r06_feed/lanes_packed_16.summary.txt), which is about what
-		 * a 3 MiB batch itself takes: the unused tail of the codes plane (at most 1 MiB here) is cheaper than a second copy. */
-		const uint64_t unused_codes = cap_pos / 4 - n_out / 4;
-		if (unused_codes <= (1ull << 20)) {
-			void *const dst[1] = { s.d_packed };
-			const void *const src[1] = { s.h_bases };
-			const size_t bytes[1] = { (size_t) (cap_pos / 4 + n_out / 8) };
-			LANECHK(slot_copy(c, s, dst, src, bytes, 1));
-		} else {
-			void *const dst[2] = { s.d_packed, s.d_packed + cap_pos / 4 };
-			const void *const src[2] = { s.h_bases, h_valid };
-			const size_t bytes[2] = { (size_t) (n_out / 4), (size_t) (n_out / 8) };
-			LANECHK(slot_copy(c, s, dst, src, bytes, 2));
-		}
-	}
-	const uint64_t n16 = n_out / 16;
-	LANECHK(launch_unpack((const uint32_t *) s.d_packed, (const uint16_t *) (s.d_packed + cap_pos / 4), s.d_bases, (unsigned long long) n16, s.stream));
-	int rc = launch_count(c, s.stream, s.d_bases, 0, n_out, nullptr, 0, false, +1);
+	/* The two planes lie at the same offsets in the pinned slot and in its device image, so a (nearly) full batch crosses
+	 * as ONE copy -- the codes plane to its end, then the used part of the validity plane.  Every copy on the copy stream is
+	 * followed by ~50 us before the next one starts (profiles/r06_feed/lanes_packed_16.summary.txt), which is about what
+	 * a 3 MiB batch itself takes: the unused tail of the codes plane (at most 1 MiB here) is cheaper than a second copy. */
+	const uint64_t unused_codes = cap_pos / 4 - n_out / 4;
+	int rc = lane_set_device(l);
+	if (!rc && unused_codes <= (1ull << 20))
+		rc = enqueue_batch(l->c, s, s.d_packed, s.h_bases, cap_pos / 4 + n_out / 8, nullptr, nullptr, 0, cap_pos / 4, n_out);
+	else if (!rc)
+		rc = enqueue_batch(l->c, s, s.d_packed, s.h_bases, n_out / 4, s.d_packed + cap_pos / 4, h_valid, n_out / 8, cap_pos / 4, n_out);
 	if (rc) return lane_lost_batch(l, rc);
-	LANECHK(hipEventRecord(s.done, s.stream));
-	s.busy = true;
 	l->total_bases += n_bases;
 	l->reads_consumed += n_reads;
 	l->next_slot ^= 1;
@@ -444,10 +406,7 @@ int ntsm_lane_close(ntsm_lane *l)
 	if (hipSetDevice(c->device) != hipSuccess && !rc) rc = NTSM_ERR_HIP;
 	for (auto &s : l->slot) {                            /* the stream is shared: wait for this lane's own batches only */
 		if (s.busy && hipEventSynchronize(s.done) != hipSuccess && !rc) rc = NTSM_ERR_HIP;
-		s.busy = false;
-		free_slot(s, c);                                  /* device buffers go to the context's cache (nothing of this lane is in flight any more) */
-		if (s.done) (void) hipEventDestroy(s.done);
-		if (s.copied) (void) hipEventDestroy(s.copied);
+		slot_release(s);                                  /* device buffers go to the context's cache (nothing of this lane is in flight any more) */
 	}
 	{
 		std::lock_guard<std::mutex> lk(c->mu);
@@ -533,33 +492,17 @@ int ntsm_submit_pinned(ntsm_ctx *c, const uint8_t *bases, uint64_t n_bytes, cons
 	if (c->early_stop) return NTSM_OK;                    /* threshold already tripped: nothing more is counted */
 	Slot &s = c->slot[c->next_slot];
 	if (s.acquired) return NTSM_ERR_STATE;                /* a staged batch is being filled on this slot */
-	if (!s.d_bases) {
-		rc = alloc_slot(s, c->device, c->cap_bytes, c->cap_reads, true, false, nullptr, false);
+	if (!s.d_bases) {                                      /* no pinned staging for the bases: the copy reads the caller's memory */
+		rc = slot_acquire(s, { c->device, c->cap_bytes, c->cap_reads, true, SlotDesc::kNoStaging, nullptr, nullptr });
 		if (rc) return rc;
 	}
 	rc = wait_slot(s);
 	if (rc) return rc;
 	c->reduced = false;
+	if (c->armed) memcpy(s.h_read_end, read_end, (size_t) n_reads * sizeof(uint64_t));
+	rc = submit_slot(c, s, bases, n_bytes, n_reads);
 	c->next_slot ^= 1;
-	if (c->armed) {
-		HIPCHK(h2d_async(s.d_bases, bases, n_bytes, s.stream));
-		memcpy(s.h_read_end, read_end, (size_t) n_reads * sizeof(uint64_t));
-		HIPCHK(h2d_async(s.d_read_end, s.h_read_end, n_reads * sizeof(uint64_t), s.stream));
-		return armed_batch(c, s.stream, s.d_bases, n_bytes, s.d_read_end, s.h_read_end, n_reads);   /* synchronous: the buffer is free on return */
-	}
-	{
-		void *const dst[1] = { s.d_bases };
-		const void *const src[1] = { bases };
-		const size_t nb[1] = { (size_t) n_bytes };
-		HIPCHK(slot_copy(c, s, dst, src, nb, 1));
-	}
-	rc = launch_count(c, s.stream, s.d_bases, 0, n_bytes, nullptr, 0, false, +1);
-	if (rc) return rc;
-	HIPCHK(hipEventRecord(s.done, s.stream));
-	s.busy = true;
-	c->total_bases += n_bytes - n_reads;
-	c->reads_consumed += n_reads;
-	return NTSM_OK;
+	return rc;
 }
 
 int ntsm_count_resident(ntsm_ctx *c, const void *d_bases, uint64_t n_bytes, const void *d_read_end, uint64_t n_reads, int sign)
@@ -713,6 +656,19 @@ int ntsm_get_timing(ntsm_ctx *c, uint64_t *n_launches, double *total_ms)
 	return NTSM_OK;
 }
 
+/* New tables for a synchronised context (ntsm_set_tuning, ntsm_set_kernel): counts and totals start from zero again. */
+static int rebuild_tables(ntsm_ctx *c, int filter_log2_req)
+{
+	HIPCHK(hipSetDevice(c->device));
+	const int rc = build_tables(c, filter_log2_req);
+	if (rc) { c->failed = true; return rc; }              /* old tables freed, new ones incomplete: the context is unusable */
+	HIPCHK(hipMemset(c->d_totals, 0, 4 * sizeof(uint64_t)));
+	HIPCHK(hipDeviceSynchronize());
+	c->total_bases = c->reads_consumed = 0;
+	c->early_stop = c->reduced = false;
+	return NTSM_OK;
+}
+
 int ntsm_set_tuning(ntsm_ctx *c, int filter_log2_bits, int grid_blocks)
 {
 	if (!c) return NTSM_ERR_ARG;
@@ -747,24 +703,11 @@ int ntsm_set_tuning(ntsm_ctx *c, int filter_log2_bits, int grid_blocks)
 			if (v < 10 || v > 28) return NTSM_ERR_ARG;
 			c->bloom_words_req = (filter_log2_bits >= 250 ? 3u : 1u) << (v - 5);
 		}
-		filter_log2_bits = c->filter_log2_req;
-		HIPCHK(hipSetDevice(c->device));
-		rc = build_tables(c, filter_log2_bits);
-		if (rc) { c->failed = true; return rc; }          /* old tables freed, new ones incomplete: the context is unusable */
-		HIPCHK(hipMemset(c->d_totals, 0, 4 * sizeof(uint64_t)));
-		HIPCHK(hipDeviceSynchronize());
-		c->total_bases = c->reads_consumed = 0;
-		c->early_stop = c->reduced = false;
-		return NTSM_OK;
+		return rebuild_tables(c, c->filter_log2_req);
 	}
 	if (filter_log2_bits > 0) {
 		c->filter_log2_req = filter_log2_bits;
-		rc = build_tables(c, filter_log2_bits);              /* rebuilds filters and table: counts start from zero again */
-		if (rc) { c->failed = true; return rc; }
-		HIPCHK(hipMemset(c->d_totals, 0, 4 * sizeof(uint64_t)));
-		HIPCHK(hipDeviceSynchronize());
-		c->total_bases = c->reads_consumed = 0;
-		c->early_stop = c->reduced = false;
+		return rebuild_tables(c, filter_log2_bits);
 	}
 	return NTSM_OK;
 }
@@ -788,7 +731,6 @@ int ntsm_set_kernel(ntsm_ctx *c, int variant)
 	if (variant == 4 && ntsm_fast_plan((uint32_t) c->k, true).m != NTSM_TWO_M) return NTSM_ERR_ARG;   /* 15 <= k <= 31 */
 	int rc = ntsm_sync(c, nullptr);
 	if (rc) return rc;
-	const int before = c->kernel_variant;
 	c->kernel_variant = variant;
 	/* one-level and two-level filters are different tables (12-mer / 14-mer minimizers): a change of level rebuilds them */
 	/* (the tabulated kernel hands its exotic tiles to the ONE-level k = 19 kernel: variant 3 on a context that had chosen two
@@ -796,34 +738,35 @@ int ntsm_set_kernel(ntsm_ctx *c, int variant)
 	const bool want_run = choose_run_form(c, variant, c->filter_log2_req);
 	const bool want_two = ntsm_fast_plan((uint32_t) c->k, true).m == NTSM_TWO_M && variant != 1 && variant != 3 && !want_run &&
 		(variant == 4 || (variant == 0 && c->filter_log2_req == 0 && wants_two_level(c->n_kmers)));
-	(void) before;
-	if (variant != 1 && (want_two != c->two_level || want_run != c->run_form)) {   /* the run form has a filter of its own */
-		HIPCHK(hipSetDevice(c->device));
-		rc = build_tables(c, c->filter_log2_req);
-		if (rc) { c->failed = true; return rc; }            /* old tables freed, new ones incomplete: the context is unusable */
-		HIPCHK(hipMemset(c->d_totals, 0, 4 * sizeof(uint64_t)));
-		HIPCHK(hipDeviceSynchronize());
-		c->total_bases = c->reads_consumed = 0;
-		c->early_stop = c->reduced = false;
-	}
+	if (variant != 1 && (want_two != c->two_level || want_run != c->run_form))   /* the run form has a filter of its own */
+		return rebuild_tables(c, c->filter_log2_req);
 	return NTSM_OK;
 }
 
 long long ntsm_debug_fail_after(int kind, long long nth) { return fault_arm(kind, nth); }
+
+/* What the two hooks below hand to tables.cpp: a context that never sees a device -- k, the mask and the canonical keys. */
+static ntsm_ctx *host_only_ctx(const uint64_t *keys, uint32_t n_kmers, int k, int key_kind)
+{
+	ntsm_ctx *c = new (std::nothrow) ntsm_ctx();
+	if (!c) return nullptr;
+	c->k = k;
+	c->n_kmers = n_kmers;
+	c->mask = mask_for_k(k);
+	c->canon.resize(n_kmers);
+	for (uint32_t i = 0; i < n_kmers; ++i) c->canon[i] = key_kind == NTSM_KEYS_HASH64 ? ntsm_hash64_inv(keys[i], k) : keys[i];
+	return c;
+}
 
 /* The run-anchored kernel's filter as tables.cpp builds it, WITHOUT a device (host code only): for the CPU test that walks every
  * site k-mer through the device's derivation (tests/test_host_cpu.py::test_run_form_filter_has_no_false_negatives). */
 int ntsm_debug_run_filter(const uint64_t *keys, uint32_t n_kmers, uint32_t kib, uint32_t *blocks_out, uint64_t *n_blocks)
 {
 	if (!keys || !n_kmers || !n_blocks) return NTSM_ERR_ARG;
-	ntsm_ctx *c = new (std::nothrow) ntsm_ctx();
+	ntsm_ctx *c = host_only_ctx(keys, n_kmers, NTSM_FAST_K, NTSM_KEYS_CANONICAL);
 	if (!c) return NTSM_ERR_NOMEM;
-	c->k = NTSM_FAST_K;
-	c->n_kmers = n_kmers;
-	c->mask = mask_for_k(c->k);
 	c->kernel_variant = 5;
 	c->blocks_kib_req = kib;
-	c->canon.assign(keys, keys + n_kmers);
 	TableImages img;
 	const int rc = build_tables_host(c, 0, img);
 	if (rc == NTSM_OK) {
@@ -839,13 +782,8 @@ int ntsm_debug_form_choice(const uint64_t *keys, uint32_t n_kmers, int k, int ke
 {
 	if ((!keys && n_kmers) || !form || k < 1 || k > 32) return NTSM_ERR_ARG;
 	if (key_kind != NTSM_KEYS_CANONICAL && key_kind != NTSM_KEYS_HASH64) return NTSM_ERR_ARG;
-	ntsm_ctx *c = new (std::nothrow) ntsm_ctx();
+	ntsm_ctx *c = host_only_ctx(keys, n_kmers, k, key_kind);
 	if (!c) return NTSM_ERR_NOMEM;
-	c->k = k;
-	c->n_kmers = n_kmers;
-	c->mask = mask_for_k(k);
-	c->canon.resize(n_kmers);
-	for (uint32_t i = 0; i < n_kmers; ++i) c->canon[i] = key_kind == NTSM_KEYS_HASH64 ? ntsm_hash64_inv(keys[i], k) : keys[i];
 	const bool run = choose_run_form(c, 0, 0);
 	const bool two = !run && ntsm_fast_plan((uint32_t) k, true).m == NTSM_TWO_M && wants_two_level(n_kmers);
 	*form = ntsm_fast_plan((uint32_t) k, two).mode < 0 ? 3 : run ? 2 : two ? 1 : 0;

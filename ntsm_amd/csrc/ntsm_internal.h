@@ -7,9 +7,10 @@
  *   kernels_mz.hip       minimizer-blocked count kernels, launch_mz (+ the tabulated kernel in `make tab` builds)
  *   kernels_run.hip      run-anchored count kernel (k = 19, one filter test per minimizer run), launch_run
  *   tables.cpp           host-side construction of the cuckoo key table and the filters (no HIP call, no device code)
- *   runtime.cpp          pools, staging slots, table upload, launch_count, the exact -m early stop (armed_batch)
+ *   runtime.cpp          pools, the staging slot's lifecycle (slot_acquire / slot_release), table upload, launch_count, the one enqueue
+ *                        step of a batch (enqueue_batch) and a context's use of it (submit_slot), the exact -m early stop (armed_batch)
  *   rccl_bind.cpp        RCCL bound with dlopen on first use; the group all-reduce of ntsm_allreduce
- *   capi.cpp             the C ABI (include/ntsm_hip.h): argument checks and state, nothing else
+ *   capi.cpp             the C ABI (include/ntsm_hip.h): argument checks and state (rebuild_tables, lane_lost_batch), nothing else
  */
 #ifndef NTSM_INTERNAL_H
 #define NTSM_INTERNAL_H
@@ -65,13 +66,24 @@ long long fault_arm(int kind, long long nth);   /* ntsm_debug_fail_after */
 
 namespace ntsm_rt {
 
+/* What slot_acquire is asked for: everything a staging slot of a context or of a lane differs in. */
+struct SlotDesc {
+	int device = 0;
+	uint64_t cap_bytes = 0, cap_reads = 0;
+	bool ends_on_device = true;                /* false (lanes): read_end never leaves the host, plain malloc */
+	enum { kNoStaging, kByteStaging, kPackedStaging } staging = kByteStaging;   /* pinned host buffer for the bases: none yet (ntsm_submit_pinned
+	                                            * reads the caller's own pinned memory; slot_add_host_bases adds one), 1 byte or 3/8 byte per position */
+	ntsm_ctx *cache = nullptr;                 /* lanes: device buffers come from and go back to this context's device_cache */
+	hipStream_t shared_stream = nullptr;       /* lanes: the context's lane stream; nullptr: the slot owns a stream of the pool */
+};
+
 struct Slot {
 	uint8_t *h_bases = nullptr, *d_bases = nullptr;
 	uint8_t *d_packed = nullptr;               /* packed lanes: device copy of codes + validity bits (3/8 byte per position) */
 	uint64_t *h_read_end = nullptr, *d_read_end = nullptr;
 	uint64_t h_bases_bytes = 0, h_ends_bytes = 0;
 	uint64_t d_bases_bytes = 0, d_packed_bytes = 0;   /* sizes of the device buffers (device_cache of the context) */
-	bool ends_on_device = true;                /* false (lanes): read_end never leaves the host, plain malloc */
+	SlotDesc desc;                             /* as acquired: slot_release reads it */
 	hipStream_t stream = nullptr;
 	hipEvent_t done = nullptr;                 /* last use of the host buffer finished */
 	hipEvent_t copied = nullptr;               /* the batch's H2D copies (on the context's copy stream) finished: what the slot's kernels wait for */
@@ -176,8 +188,8 @@ struct ntsm_ctx {
 	uint64_t total_bases = 0, reads_consumed = 0;
 	bool early_stop = false, reduced = false;
 	/* A table rebuild failed half way (ntsm_set_kernel / ntsm_set_tuning: the tables no longer describe one consistent filter
-	 * organisation), or a batch of a producer lane was lost (its copy or launch failed: the counts no longer cover what the
-	 * caller submitted).  Every later call that would count, merge or report answers NTSM_ERR_STATE; only ntsm_destroy helps. */
+	 * organisation), or a batch was lost, a lane's or the context's own (enqueue_batch or the armed form failed: the counts no
+	 * longer cover what the caller submitted, and a copy may still be in flight with no event to wait for).  Every later call that would count, merge or report answers NTSM_ERR_STATE; only ntsm_destroy helps. */
 	bool failed = false;
 	uint64_t red_totals[4] = { 0, 0, 0, 0 };
 	/* tuning / timing */
@@ -251,21 +263,30 @@ void stream_put(int device, hipStream_t s);
 int build_tables(ntsm_ctx *c, int filter_log2_req, int (*before_upload)(ntsm_ctx *) = nullptr);
 hipError_t device_take(ntsm_ctx *c, void **p, uint64_t bytes);
 void device_give(ntsm_ctx *c, void *p, uint64_t bytes);
-int alloc_slot(Slot &s, int device, uint64_t cap_bytes, uint64_t cap_reads, bool ends_on_device, bool packed_only = false, ntsm_ctx *cache = nullptr,
-		bool host_bases = true);
-int slot_add_host_bases(Slot &s);            /* pin the bases staging of a slot created without one (ntsm_submit_pinned came first) */
+/* A slot's whole lifecycle.  slot_acquire fills an EMPTY slot (d_bases == nullptr) or, on any failure, leaves it empty: buffers, stream
+ * and both events, all or nothing.  slot_release waits for nothing (callers do: wait_slot, a device synchronise) and empties the slot:
+ * host buffers to the pinned pool, device buffers to desc.cache, both events destroyed, an owned stream back to the stream pool. */
+int slot_acquire(Slot &s, const SlotDesc &d);
+void slot_release(Slot &s);
+int slot_add_host_bases(Slot &s);            /* the one lazy step: pin the bases staging of a slot acquired with kNoStaging (ntsm_submit_pinned came first) */
 void staged_copy(ntsm_ctx *c, uint8_t *dst, const uint8_t *src, uint64_t n);   /* ntsm_submit: the batch into the pinned slot, on submit_threads threads */
 void copy_pool_release(ntsm_ctx *c);
-/* enqueue `n_copies` host-to-device copies of one batch on the context's copy stream and make the slot's stream wait for them */
-hipError_t slot_copy(ntsm_ctx *c, Slot &s, void *const *dst, const void *const *src, const size_t *bytes, int n_copies);
-void free_slot(Slot &s, ntsm_ctx *cache = nullptr);
 int launch_count(ntsm_ctx *c, hipStream_t st, const uint8_t *d_bases, uint64_t lo, uint64_t hi,
 		const uint64_t *d_read_end, uint64_t n_reads, bool per_read, int sign);
 int read_device_totals(ntsm_ctx *c, uint64_t out[2]);
 int armed_batch(ntsm_ctx *c, hipStream_t st, const uint8_t *d_bases, uint64_t n_bytes,
 		const uint64_t *d_read_end, const uint64_t *h_read_end_or_null, uint64_t n_reads);
 int check_layout(const uint64_t *read_end, uint32_t n_reads, uint64_t n_bytes);
-int submit_slot(ntsm_ctx *c, Slot &s, uint64_t n_bytes, uint32_t n_reads);
+/* The one enqueue step of an unarmed batch on a slot, whatever submit form it came in by: copy 0 (and copy 1 when bytes1 != 0) on the
+ * context's copy stream, the slot's stream waits for them, the packed planes are unpacked into d_bases when packed_valid_at != 0 (the
+ * offset of the validity plane in d_packed), stream bytes [0, n) of d_bases are counted, `done` is recorded and the slot is busy.
+ * ANY error it returns means the batch is LOST -- possibly half copied, not or half counted: a lane calls lane_lost_batch, a context
+ * marks itself failed (submit_slot). */
+int enqueue_batch(ntsm_ctx *c, Slot &s, void *dst0, const void *src0, size_t bytes0, void *dst1, const void *src1, size_t bytes1,
+		uint64_t packed_valid_at, uint64_t n);
+/* a context's own batch from pinned h_bases (ntsm_submit_staged: the slot's, ntsm_submit_pinned: the caller's): two copies on the slot's
+ * stream + armed_batch, or enqueue_batch + the host totals; the context is marked failed when the batch is lost */
+int submit_slot(ntsm_ctx *c, Slot &s, const uint8_t *h_bases, uint64_t n_bytes, uint32_t n_reads);
 int wait_slot(Slot &s);
 void tab_release(ntsm_ctx *c);               /* no-op unless NTSM_WITH_TAB */
 uint64_t tab_exotic_seen(ntsm_ctx *c, int *rc);

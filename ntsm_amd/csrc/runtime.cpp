@@ -286,16 +286,17 @@ int slot_add_host_bases(Slot &s)
 	return NTSM_OK;
 }
 
-int alloc_slot(Slot &s, int device, uint64_t cap_bytes, uint64_t cap_reads, bool ends_on_device, bool packed_only, ntsm_ctx *cache, bool host_bases)
+static int slot_take(Slot &s)                 /* everything s.desc asks for, in this order; slot_acquire cleans up after a failure */
 {
-	s.ends_on_device = ends_on_device;
-	s.h_bases_bytes = (packed_only ? (cap_bytes & ~31ull) / 4 + (cap_bytes & ~31ull) / 8 : cap_bytes) + 64;   /* packed: 3/8 byte per position */
-	s.h_ends_bytes = cap_reads * sizeof(uint64_t);
-	if (host_bases) {                                       /* ntsm_submit_pinned reads the caller's own pinned memory: no staging for the bases */
+	const SlotDesc &d = s.desc;
+	const uint64_t cap_pos = d.cap_bytes & ~31ull;
+	s.h_bases_bytes = (d.staging == SlotDesc::kPackedStaging ? cap_pos / 4 + cap_pos / 8 : d.cap_bytes) + 64;   /* packed: 3/8 byte per position */
+	s.h_ends_bytes = d.cap_reads * sizeof(uint64_t);
+	if (d.staging != SlotDesc::kNoStaging) {
 		const int rcb = slot_add_host_bases(s);
 		if (rcb) return rcb;
 	}
-	if (ends_on_device) {
+	if (d.ends_on_device) {
 		s.h_read_end = (uint64_t *) pool_alloc(s.h_ends_bytes);
 		if (!s.h_read_end) HIPCHK(pinned_malloc((void **) &s.h_read_end, s.h_ends_bytes));
 		HIPCHK(dev_malloc(&s.d_read_end, s.h_ends_bytes));
@@ -303,33 +304,39 @@ int alloc_slot(Slot &s, int device, uint64_t cap_bytes, uint64_t cap_reads, bool
 		s.h_read_end = (uint64_t *) malloc(s.h_ends_bytes);
 		if (!s.h_read_end) return NTSM_ERR_NOMEM;
 	}
-	s.d_bases_bytes = cap_bytes + 64;
-	HIPCHK(device_take(cache, (void **) &s.d_bases, s.d_bases_bytes));
-	if (!s.stream) {
-		s.stream = stream_get(device);
-		if (!s.stream) return NTSM_ERR_HIP;
-	}
+	s.d_bases_bytes = d.cap_bytes + 64;
+	HIPCHK(device_take(d.cache, (void **) &s.d_bases, s.d_bases_bytes));
+	s.stream = d.shared_stream ? d.shared_stream : stream_get(d.device);
+	if (!s.stream) return NTSM_ERR_HIP;
 	/* (events with hipEventBlockingSync -- waiting threads sleep instead of spinning -- were measured on the 16-CPU pod: no gain for
 	 * 16 packed lanes, 68.5 vs 67.3 Gbases/s, and ntsm_submit 25 % slower, 39.9 vs 53.4 GB/s: NOTEBOOK.md round 6) */
-	if (!s.done) HIPCHK(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
-	if (!s.copied) HIPCHK(hipEventCreateWithFlags(&s.copied, hipEventDisableTiming));
-	s.busy = false;
-	s.acquired = false;
+	HIPCHK(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+	HIPCHK(hipEventCreateWithFlags(&s.copied, hipEventDisableTiming));
 	return NTSM_OK;
 }
 
-void free_slot(Slot &s, ntsm_ctx *cache)
+int slot_acquire(Slot &s, const SlotDesc &d)
+{
+	s.desc = d;
+	const int rc = slot_take(s);
+	if (rc) slot_release(s);                               /* all or nothing: a retry finds an empty slot, not pieces to overwrite */
+	return rc;
+}
+
+void slot_release(Slot &s)
 {
 	if (s.h_bases && !pool_free(s.h_bases, s.h_bases_bytes)) (void) hipHostFree(s.h_bases);
 	if (s.h_read_end) {
-		if (!s.ends_on_device) free(s.h_read_end);
+		if (!s.desc.ends_on_device) free(s.h_read_end);
 		else if (!pool_free(s.h_read_end, s.h_ends_bytes)) (void) hipHostFree(s.h_read_end);
 	}
-	device_give(cache, s.d_bases, s.d_bases_bytes);
-	device_give(cache, s.d_packed, s.d_packed_bytes);
+	device_give(s.desc.cache, s.d_bases, s.d_bases_bytes);
+	device_give(s.desc.cache, s.d_packed, s.d_packed_bytes);
 	if (s.d_read_end) (void) hipFree(s.d_read_end);
-	s.h_bases = s.d_bases = s.d_packed = nullptr;
-	s.h_read_end = s.d_read_end = nullptr;
+	if (s.done) (void) hipEventDestroy(s.done);
+	if (s.copied) (void) hipEventDestroy(s.copied);
+	if (!s.desc.shared_stream) stream_put(s.desc.device, s.stream);   /* idle: the caller has waited for the slot's last batch */
+	s = Slot();
 }
 
 /* launch one count pass over stream bytes [lo, hi) of d_bases */
@@ -613,38 +620,41 @@ int check_layout(const uint64_t *read_end, uint32_t n_reads, uint64_t n_bytes)
 	return NTSM_OK;
 }
 
-hipError_t slot_copy(ntsm_ctx *c, Slot &s, void *const *dst, const void *const *src, const size_t *bytes, int n_copies)
+int enqueue_batch(ntsm_ctx *c, Slot &s, void *dst0, const void *src0, size_t bytes0, void *dst1, const void *src1, size_t bytes1,
+		uint64_t packed_valid_at, uint64_t n)
 {
-	for (int i = 0; i < n_copies; ++i) {
-		const hipError_t e = h2d_async(dst[i], src[i], bytes[i], c->cstream);
-		if (e != hipSuccess) return e;
-	}
-	hipError_t e = hipEventRecord(s.copied, c->cstream);     /* lanes enqueue concurrently: the event may also cover a neighbour's copy, never less than ours */
-	if (e != hipSuccess) return e;
-	return hipStreamWaitEvent(s.stream, s.copied, 0);
-}
-
-int submit_slot(ntsm_ctx *c, Slot &s, uint64_t n_bytes, uint32_t n_reads)
-{
-	if (n_reads == 0) return NTSM_OK;
-	if (c->armed) {                                          /* synchronous anyway: everything on the slot's stream */
-		HIPCHK(h2d_async(s.d_bases, s.h_bases, n_bytes, s.stream));
-		HIPCHK(h2d_async(s.d_read_end, s.h_read_end, n_reads * sizeof(uint64_t), s.stream));
-		return armed_batch(c, s.stream, s.d_bases, n_bytes, s.d_read_end, s.h_read_end, n_reads);
-	}
-	{
-		void *const dst[1] = { s.d_bases };
-		const void *const src[1] = { s.h_bases };
-		const size_t bytes[1] = { (size_t) n_bytes };
-		HIPCHK(slot_copy(c, s, dst, src, bytes, 1));
-	}
-	int rc = launch_count(c, s.stream, s.d_bases, 0, n_bytes, nullptr, 0, false, +1);
+	HIPCHK(h2d_async(dst0, src0, bytes0, c->cstream));
+	if (bytes1) HIPCHK(h2d_async(dst1, src1, bytes1, c->cstream));
+	HIPCHK(hipEventRecord(s.copied, c->cstream));            /* lanes enqueue concurrently: the event may also cover a neighbour's copy, never less than ours */
+	HIPCHK(hipStreamWaitEvent(s.stream, s.copied, 0));
+	if (packed_valid_at)
+		HIPCHK(launch_unpack((const uint32_t *) s.d_packed, (const uint16_t *) (s.d_packed + packed_valid_at), s.d_bases, (unsigned long long) (n / 16), s.stream));
+	const int rc = launch_count(c, s.stream, s.d_bases, 0, n, nullptr, 0, false, +1);
 	if (rc) return rc;
 	HIPCHK(hipEventRecord(s.done, s.stream));
 	s.busy = true;
-	c->total_bases += n_bytes - n_reads;
-	c->reads_consumed += n_reads;
 	return NTSM_OK;
+}
+
+int submit_slot(ntsm_ctx *c, Slot &s, const uint8_t *h_bases, uint64_t n_bytes, uint32_t n_reads)
+{
+	if (n_reads == 0) return NTSM_OK;
+	auto armed = [&]() -> int {                              /* synchronous anyway: everything on the slot's stream (the buffers are free on return) */
+		HIPCHK(h2d_async(s.d_bases, h_bases, n_bytes, s.stream));
+		HIPCHK(h2d_async(s.d_read_end, s.h_read_end, n_reads * sizeof(uint64_t), s.stream));
+		return armed_batch(c, s.stream, s.d_bases, n_bytes, s.d_read_end, s.h_read_end, n_reads);   /* adds to the host totals itself */
+	};
+	const int rc = c->armed ? armed() : enqueue_batch(c, s, s.d_bases, h_bases, n_bytes, nullptr, nullptr, 0, 0, n_bytes);
+	if (rc) {
+		/* lost: a copy from h_bases may still be in flight with no `done` event to wait for, and the counts no longer cover what the
+		 * caller submitted -- no later call may reuse the slot or fetch the counts */
+		std::lock_guard<std::mutex> lk(c->mu);
+		c->failed = true;
+	} else if (!c->armed) {
+		c->total_bases += n_bytes - n_reads;
+		c->reads_consumed += n_reads;
+	}
+	return rc;
 }
 
 int wait_slot(Slot &s)

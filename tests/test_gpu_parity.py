@@ -1,8 +1,10 @@
 """GPU parity tests (run with -m gpu on an MI355X): the HIP path, called through the C ABI, must give
 the oracle's per-k-mer counts and totals bit for bit, and the CLI must print the reference's bytes."""
+import contextlib
 import gzip
 import hashlib
 import json
+import mmap
 import os
 import subprocess
 import sys
@@ -1815,6 +1817,166 @@ def test_fault_injection_lost_lane_batch_surfaces_from_lane_close(nt, tmp_path):
             ctx.close()
     finally:
         debug_fail_after(FAULT_H2D, 0)
+
+
+@pytest.fixture(scope="module")
+def small_batch(nt, tmp_path_factory):
+    """One batch of 2,000 reads against 200 sites with the oracle's counts, for the slot tests below: with set_batch_capacity /
+    open_lane (1 MiB, 4096 reads) every slot is about 1 MiB."""
+    path = str(tmp_path_factory.mktemp("slots") / "s.fa")
+    synth = nt.SynthShort(sites_seed=11, n_sites=200, read_seed=5, p_embed=0.5, sites_path=path)
+    sites = nt.Sites(path)
+    bases, ends = synth.host_bytes(0, 2000), synth.read_end(2000)
+    fp = OracleFP(path)
+    fp.process_flat(bases, ends)
+    return sites.keys, bases, ends, fp.kmers()[2]
+
+
+@contextlib.contextmanager
+def _pinned_copy(arr):
+    """arr's bytes in an anonymous mapping of their own, pinned with host_pin and un-pinned on the way out (hipHostRegister locks
+    whole pages: of a small array on the malloc heap those are its neighbours' pages too)."""
+    from ntsm_amd.capi import host_pin, host_unpin
+    out = np.frombuffer(mmap.mmap(-1, arr.nbytes), dtype=np.uint8, count=arr.nbytes)
+    out[:] = arr
+    host_pin(out)
+    try:
+        yield out
+    finally:
+        host_unpin(out)
+
+
+SLOT_CAP = (1 << 20, 1 << 12)
+
+
+def _gated_calls(kinds, op):
+    """How many gated calls of each kind `op` makes (armed far away: nothing fails)."""
+    from ntsm_amd.capi import debug_fail_after
+    for kind in kinds:
+        debug_fail_after(kind, 1 << 40)
+    op()
+    return {kind: debug_fail_after(kind, 0) for kind in kinds}
+
+
+@pytest.mark.parametrize("how", ("submit", "submit_pinned"))
+def test_fault_injection_slot_allocation_is_all_or_nothing(nt, small_batch, how):
+    """A staging slot whose allocation fails half way -- every device allocation and every pinned allocation of a context's first
+    ntsm_submit / ntsm_submit_pinned, failed in turn -- is given back whole: the call reports the error, the SAME call repeated on
+    the same context finds an empty slot (not pieces to overwrite), counts what the oracle counts, and ntsm_destroy returns the
+    device to where it was before the context existed (hipMemGetInfo)."""
+    from ntsm_amd.capi import FAULT_DEVICE_ALLOC, FAULT_PINNED_ALLOC, NtsmError, debug_fail_after
+    keys, bases, ends, want = small_batch
+    kinds = (FAULT_DEVICE_ALLOC, FAULT_PINNED_ALLOC)
+    pin = contextlib.ExitStack()
+    pinned = pin.enter_context(_pinned_copy(bases))
+
+    def fresh():
+        ctx = nt.Context(keys)
+        ctx.set_batch_capacity(*SLOT_CAP)
+        return ctx
+
+    send = (lambda ctx: ctx.submit(bases, ends)) if how == "submit" else (lambda ctx: ctx.submit_pinned(pinned, ends))
+    try:
+        ctx = fresh()                                               # runtime, stream pool and allocator warmed up; and the count
+        n_calls = _gated_calls(kinds, lambda: send(ctx))
+        assert np.array_equal(ctx.counts(), want)
+        ctx.close()
+        assert n_calls[FAULT_DEVICE_ALLOC] == 2, n_calls            # d_read_end, d_bases
+        for kind in kinds:
+            for nth in range(1, n_calls[kind] + 1):
+                before = _free_hbm()
+                ctx = fresh()
+                debug_fail_after(kind, nth)
+                with pytest.raises(NtsmError, match="ntsm_" + how):
+                    send(ctx)
+                debug_fail_after(kind, 0)
+                send(ctx)
+                assert np.array_equal(ctx.counts(), want), (kind, nth)
+                ctx.close()
+                assert _free_hbm() == before, (kind, nth, before, _free_hbm())
+    finally:
+        for kind in kinds:
+            debug_fail_after(kind, 0)
+        pin.close()
+
+
+@pytest.mark.parametrize("packed", (False, True), ids=("bytes", "packed"))
+def test_fault_injection_lane_open_is_all_or_nothing(nt, small_batch, packed):
+    """ntsm_lane_open / ntsm_lane_open_packed with each of its device and pinned allocations failed in turn: the call reports the
+    error and keeps nothing (buffers, events); the next lane of the context opens, counts what the oracle counts, and ntsm_destroy
+    returns the device to where it was before the context existed."""
+    from ntsm_amd.capi import FAULT_DEVICE_ALLOC, FAULT_PINNED_ALLOC, NtsmError, debug_fail_after
+    keys, bases, ends, want = small_batch
+    reads = [bytes(bases[i * 151:i * 151 + 150]) for i in range(2000)]
+    kinds = (FAULT_DEVICE_ALLOC, FAULT_PINNED_ALLOC)
+
+    def good_lane(ctx):
+        lane = ctx.open_lane(*SLOT_CAP, packed_only=packed)
+        lane.submit_packed(reads) if packed else lane.submit(bases, ends)
+        lane.close()
+        assert np.array_equal(ctx.counts(), want)
+
+    try:
+        ctx = nt.Context(keys)
+        ctx.open_lane(*SLOT_CAP, packed_only=packed).close()        # two lanes: both lane streams of a context exist in the pool from here on
+        good_lane(ctx)
+        ctx.close()
+        ctx = nt.Context(keys)
+        n_calls = _gated_calls(kinds, lambda: ctx.open_lane(*SLOT_CAP, packed_only=packed).close())
+        ctx.close()
+        assert n_calls[FAULT_DEVICE_ALLOC] == 2, n_calls            # d_bases of both slots
+        for kind in kinds:
+            for nth in range(1, n_calls[kind] + 1):
+                before = _free_hbm()
+                ctx = nt.Context(keys)
+                debug_fail_after(kind, nth)
+                with pytest.raises(NtsmError, match="ntsm_lane_open"):
+                    ctx.open_lane(*SLOT_CAP, packed_only=packed)
+                debug_fail_after(kind, 0)
+                good_lane(ctx)
+                ctx.close()
+                assert _free_hbm() == before, (kind, nth, before, _free_hbm())
+    finally:
+        for kind in kinds:
+            debug_fail_after(kind, 0)
+
+
+@pytest.mark.parametrize("how", ("submit", "submit_pinned"))
+def test_fault_injection_lost_context_batch_marks_the_context_failed(nt, small_batch, how):
+    """include/ntsm_hip.h: a batch of the context's own submit forms whose host-to-device copy fails is LOST like a lane's -- the
+    call reports it and the context is marked failed, so that no later call reuses the slot under a copy that may still be in
+    flight or fetches the incomplete counts: ntsm_sync, ntsm_counts, ntsm_submit and ntsm_submit_pinned answer NTSM_ERR_STATE;
+    ntsm_destroy still releases everything."""
+    from ntsm_amd.capi import FAULT_H2D, NtsmError, debug_fail_after
+    keys, bases, ends, _ = small_batch
+    pin = contextlib.ExitStack()
+    pinned = pin.enter_context(_pinned_copy(bases))
+
+    def fresh():
+        ctx = nt.Context(keys)
+        ctx.set_batch_capacity(*SLOT_CAP)
+        return ctx
+
+    send = (lambda ctx: ctx.submit(bases, ends)) if how == "submit" else (lambda ctx: ctx.submit_pinned(pinned, ends))
+    try:
+        ctx = fresh()
+        nth = _gated_calls((FAULT_H2D,), lambda: send(ctx))[FAULT_H2D]   # an unarmed submit's last (and only) upload is the batch itself
+        ctx.close()
+        assert nth == 1, nth
+        before = _free_hbm()
+        ctx = fresh()
+        debug_fail_after(FAULT_H2D, nth)
+        with pytest.raises(NtsmError, match="ntsm_" + how):
+            send(ctx)
+        debug_fail_after(FAULT_H2D, 0)
+        for call in (ctx.sync, ctx.counts, lambda: ctx.submit(bases, ends), lambda: ctx.submit_pinned(pinned, ends)):
+            with pytest.raises(NtsmError, match="invalid state"):
+                call()
+        ctx.close()
+        assert _free_hbm() == before, (before, _free_hbm())
+    finally:
+        debug_fail_after(FAULT_H2D, 0)
+        pin.close()
 
 
 def test_cli_turns_device_failures_into_exit_1_one_message_no_counts(nt, tmp_path):

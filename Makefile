@@ -29,9 +29,9 @@ all: oracle_all build/ntsm_synth build/gather_bench build/ntsm_feed_bench build/
 ntsm_amd/libntsm_host.so: $(HOSTSRC) $(HOST)/early_ingest.cpp $(HOST)/host_capi.cpp $(HOSTHDR)
 	$(CXX) $(CXXFLAGS) -shared -o $@ $(HOSTSRC) $(HOST)/early_ingest.cpp $(HOST)/host_capi.cpp -lz -pthread
 
-build/ntsmCount: $(HOSTSRC) $(HOST)/fingerprint.cpp $(HOST)/early_ingest.cpp $(HOST)/ntsm_count_main.cpp $(HOSTHDR) ntsm_amd/libntsm_hip.so
+build/ntsmCount: $(HOSTSRC) $(HOST)/feeder.cpp $(HOST)/fingerprint.cpp $(HOST)/early_ingest.cpp $(HOST)/ntsm_count_main.cpp $(HOSTHDR) ntsm_amd/libntsm_hip.so
 	@mkdir -p build
-	$(CXX) $(CXXFLAGS) -o $@ $(HOSTSRC) $(HOST)/fingerprint.cpp $(HOST)/early_ingest.cpp $(HOST)/ntsm_count_main.cpp \
+	$(CXX) $(CXXFLAGS) -o $@ $(HOSTSRC) $(HOST)/feeder.cpp $(HOST)/fingerprint.cpp $(HOST)/early_ingest.cpp $(HOST)/ntsm_count_main.cpp \
 	    -Lntsm_amd -lntsm_hip -lz -pthread -Wl,-rpath,'$$ORIGIN/../ntsm_amd' -Wl,-rpath,/opt/rocm/lib
 
 # libntsm_hip.so = three device translation units (the kernels + their launchers) and four host-only ones

@@ -21,7 +21,7 @@
  * gzip input, FASTA, or small files are not eligible (open() returns false): the caller uses the sequential
  * reader for the whole file.
  *
- * Sink concept (one per thread; ntsm::Feeder and the test collector in host_capi.cpp):
+ * Sink concept (one per thread; ntsm::Feeder of feeder.hpp, EarlyIngest::Sink and the test collector in host_capi.cpp):
  *     bool has_room(uint64_t len)   feed(seq, len) would not have to submit first
  *     void feed(const char *seq, uint64_t len)
  *     void flush()                  submit what is staged (only called for validated content)

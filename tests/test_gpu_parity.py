@@ -1354,11 +1354,12 @@ def test_cli_block_parallel_single_file(nt, tmp_path):
     files = [wrapped, contig, fq]
     base = subprocess.run([exe, "-s", sites_fa] + files, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
     assert base.returncode == 0, base.stderr[-400:]
-    for t, blk, batch in (("4", "65536", "262144"), ("2", "300000", "1048576")):
-        env = dict(os.environ, NTSM_BLOCK_BYTES=blk, NTSM_BATCH_BYTES=batch)
-        p = subprocess.run([exe, "-s", sites_fa, "-t", t] + files, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
-        assert p.returncode == 0, p.stderr[-400:]
-        assert p.stdout == base.stdout and _summary(p.stderr) == _summary(base.stderr)
+    for no_pack in ({}, {"NTSM_NO_PACK": "1"}):                         # packed lanes, and lanes of raw bytes
+        for t, blk, batch in (("4", "65536", "262144"), ("2", "300000", "1048576")):
+            env = dict(os.environ, NTSM_BLOCK_BYTES=blk, NTSM_BATCH_BYTES=batch, **no_pack)
+            p = subprocess.run([exe, "-s", sites_fa, "-t", t] + files, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
+            assert p.returncode == 0, p.stderr[-400:]
+            assert p.stdout == base.stdout and _summary(p.stderr) == _summary(base.stderr)
 
 
 def test_fuzz_arbitrary_bytes(nt, tmp_path):
@@ -2323,4 +2324,29 @@ def test_queues_that_outlive_their_tile(nt, tmp_path):
             ctx.close()
 
 
-
+@pytest.mark.gpu
+def test_cli_big_gzip_inputs_side_by_side_or_one_by_one(nt, tmp_path):
+    """Where the big .gz inputs are many (from max(3, threads / 4) on) they are read side by side, one reader per file, and the
+    first one is not taken early; fewer are read one after the other with the decoder pool, the first one beside the start-up.
+    The constructor and computeCounts make that decision each on its own and have to agree.  -t 4: four files go side by side
+    (neither `early ingest (` nor `parallel gzip:` on stderr), the first two of them as `early ingest (gzip` and
+    `parallel gzip:`; counts.txt and the summary are the single-thread bytes both times."""
+    exe = os.path.join(ROOT, "build", "ntsmCount")
+    sp = str(tmp_path / "s.fa")
+    s = nt.SynthShort(sites_seed=11, n_sites=200, read_seed=5, p_embed=0.4, sites_path=sp)
+    paths = []
+    for i in range(4):
+        fq = str(tmp_path / ("r%d.fq" % i))
+        s.write_fastq(fq, 20000 * i, 20000)
+        paths.append(fq + ".gz")
+        with open(fq, "rb") as fi, gzip.open(paths[-1], "wb", compresslevel=1) as fo:
+            fo.write(fi.read())
+    env = dict(os.environ, NTSM_GZ_PARALLEL_MIN="1000")
+    for files, one_by_one in ((paths, False), (paths[:2], True)):
+        base = subprocess.run([exe, "-s", sp] + files, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+        assert base.returncode == 0, base.stderr[-400:]
+        p = subprocess.run([exe, "-s", sp, "-t", "4", "-v"] + files, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
+        assert p.returncode == 0, p.stderr[-400:]
+        assert p.stdout == base.stdout and _summary(p.stderr) == _summary(base.stderr), len(files)
+        assert (b"early ingest (" in p.stderr, b"parallel gzip:" in p.stderr) == (one_by_one, one_by_one), p.stderr[-600:]
+        assert not one_by_one or b"early ingest (gzip" in p.stderr

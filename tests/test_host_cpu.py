@@ -1332,3 +1332,17 @@ def test_pack2_packer_under_sanitizers(tmp_path):
                     os.path.join(ROOT, "tools", "pack_sanitize.cpp"), os.path.join(host, "pack2.cpp")], check=True)
     p = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE)
     assert p.returncode == 0 and b"pack2 sanitize ok" in p.stdout, p.stderr.decode()[-2000:]
+
+
+def test_feeder_slot_lifecycle_under_sanitizers(tmp_path):
+    """tests/feeder_check.cpp, a program of its own under ASan + UBSan: Feeder (ntsm_amd/csrc/host/feeder.cpp) against a fake of
+    the libntsm_hip calls it makes, whose slots are malloc'ed at exactly the capacity they report and which aborts on a protocol
+    error -- the context's own slots, a lane of bytes and a packed lane at the 4096-byte minimum: reads come back in order,
+    the read-count limit, the sink contract, growth at today's sizes, discard(), the held but empty slot, submitChunk,
+    an armed context that stops, finish() and the destructor"""
+    exe = str(tmp_path / "feeder_check")
+    host = os.path.join(ROOT, "ntsm_amd", "csrc", "host")
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe,
+                    os.path.join(ROOT, "tests", "feeder_check.cpp"), os.path.join(host, "feeder.cpp"), os.path.join(host, "pack2.cpp")], check=True)
+    p = subprocess.run([exe], capture_output=True, timeout=120)
+    assert p.returncode == 0 and p.stdout.startswith(b"feeder check ok: 31 cases"), (p.stdout + p.stderr).decode()[-2000:]

@@ -76,7 +76,7 @@ xlib:
 ntsm_amd/libntsm_eval_hip.so: $(CSRC)/ntsm_eval.hip $(CSRC)/ntsm_eval_pca.hip $(CSRC)/ntsm_eval_score.h $(CSRC)/ntsm_hip_scope.h $(CSRC)/xprec.h include/ntsm_eval_hip.h
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -shared -o $@ $(CSRC)/ntsm_eval.hip $(CSRC)/ntsm_eval_pca.hip
 
-build/ntsmEval: $(HOST)/ntsm_eval_main.cpp $(CSRC)/xprec.h include/ntsm_eval_hip.h ntsm_amd/libntsm_eval_hip.so
+build/ntsmEval: $(HOST)/ntsm_eval_main.cpp $(HOST)/cli.hpp $(HOST)/gz_stream.hpp $(CSRC)/xprec.h include/ntsm_eval_hip.h ntsm_amd/libntsm_eval_hip.so
 	@mkdir -p build
 	$(CXX) $(CXXFLAGS) -ffp-contract=off -o $@ $(HOST)/ntsm_eval_main.cpp -Lntsm_amd -lntsm_eval_hip \
 	    -Wl,-rpath,'$$ORIGIN/../ntsm_amd' -Wl,-rpath,/opt/rocm/lib

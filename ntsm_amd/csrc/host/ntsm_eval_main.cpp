@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../../include/ntsm_eval_hip.h"
+#include "cli.hpp"
 
 #define PROGRAM "ntsmEval"
 
@@ -174,8 +175,6 @@ void printHelpDialog()
 	exit(EXIT_SUCCESS);
 }
 
-template <typename T> bool parse(const char *s, T &out) { std::stringstream c(s); return bool(c >> out); }
-
 /* skew (:1081-1083) and computeLogLikelihood (:1093-1099) over a pair's record: sample i is sample 1 */
 double pairScore(const ntsm_eval_record &r, const Genotype &gi, const Genotype &gj, const Opt &opt)
 {
@@ -188,10 +187,13 @@ double pairScore(const ntsm_eval_record &r, const Genotype &gi, const Genotype &
 	return score;
 }
 
-/* resultsStr (:843-905) + "\n" for pair (i, j), sample i as sample 1 */
-void appendRow(std::string &temp, const Counts &c, const std::vector<Genotype> &g, const Opt &opt, const ntsm_eval_record &r,
-		double score, const std::string &dist, uint32_t i, uint32_t j)
+/* one scored pair (i, j), sample i as sample 1: kept under -a or below the threshold, then resultsStr (:843-905) + "\n"
+ * on stdout; temp is the caller's line buffer */
+void printRow(std::string &temp, const Counts &c, const std::vector<Genotype> &g, const Opt &opt, const ntsm_eval_record &r,
+		uint32_t i, uint32_t j, const std::string &dist)
 {
+	const double score = pairScore(r, g[i], g[j], opt);
+	if (!(opt.all || score < opt.scoreThresh)) return;
 	const double homConcord = (double(r.shared_homs) - 2.0 * double(r.ibs0)) / double(r.homs1 < r.homs2 ? r.homs1 : r.homs2);
 	const double relate = (double(r.shared_hets) - 2.0 * double(r.ibs0)) / double(r.hets1 < r.hets2 ? r.hets1 : r.hets2);
 	temp.clear();
@@ -209,6 +211,7 @@ void appendRow(std::string &temp, const Counts &c, const std::vector<Genotype> &
 	temp += "\t"; temp += std::to_string(g[i].homs); temp += "\t"; temp += std::to_string(g[j].homs);
 	temp += "\t"; temp += std::to_string(g[i].hets); temp += "\t"; temp += std::to_string(g[j].hets);
 	temp += "\n";
+	std::cout << temp;
 }
 
 const char *kHeader = "sample1\tsample2\tscore\tsame\tdist\trelate\tibs0\tibs2\thomConcord\thet1\thet2\tsharedHet\thom1\thom2\tsharedHom\tn"
@@ -276,6 +279,11 @@ int gpuFail(const char *what, int rc)
 	return 3;
 }
 
+struct Session {                             /* closes the library session it holds when its scope ends */
+	ntsm_eval_session *h = nullptr;
+	~Session() { if (h) ntsm_eval_close(h); }
+};
+
 /* projectPCs (:166-211) on the device: cloud [n][dim] */
 int project(const Counts &c, const Opt &opt, ntsm_eval_session *h, const std::vector<long double> &norm, const std::vector<long double> &rot,
 		std::vector<double> &cloud)
@@ -320,12 +328,7 @@ int scorePCA(const Counts &c, std::vector<Genotype> &g, const Opt &opt, ntsm_eva
 	if (opt.verbose > 1) std::cerr << "search kernels: " << msSearch << " ms, scoring kernel: " << msScore << " ms for " << np << " pairs" << std::endl;
 	std::cout << kHeader << "\n";
 	std::string temp;
-	for (uint64_t p = 0; p < np; ++p) {
-		const double score = pairScore(rec[p], g[pi[p]], g[pk[p]], opt);
-		if (!(opt.all || score < opt.scoreThresh)) continue;
-		appendRow(temp, c, g, opt, rec[p], score, std::to_string(dist[p]), pi[p], pk[p]);
-		std::cout << temp;
-	}
+	for (uint64_t p = 0; p < np; ++p) printRow(temp, c, g, opt, rec[p], pi[p], pk[p], std::to_string(dist[p]));
 	return 0;
 }
 
@@ -350,23 +353,23 @@ int main(int argc, char **argv)
 		switch (ch) {
 		case 'h': printHelpDialog(); break;
 		case 'a': opt.all = true; break;
-		case 's': if (!parse(optarg, opt.scoreThresh)) { std::cerr << "Error - Invalid parameter s: " << optarg << std::endl; return 0; } break;
-		case 'w': if (!parse(optarg, opt.covSkew)) { std::cerr << "Error - Invalid parameter w: " << optarg << std::endl; return 0; } break;
-		case 'c': if (!parse(optarg, opt.minCov)) { std::cerr << "Error - Invalid parameter c: " << optarg << std::endl; return 0; } break;
-		case 'g': if (!parse(optarg, opt.genomeSize)) { std::cerr << "Error - Invalid parameter g: " << optarg << std::endl; return 0; } break;
-		case 't': if (!parse(optarg, opt.threads)) { std::cerr << "Error - Invalid parameter t: " << optarg << std::endl; return 0; } break;
-		case 'G': if (!parse(optarg, opt.device)) { std::cerr << "Error - Invalid parameter G: " << optarg << std::endl; return 0; } break;
+		case 's': ntsm::reference_flag('s', optarg, opt.scoreThresh); break;
+		case 'w': ntsm::reference_flag('w', optarg, opt.covSkew); break;
+		case 'c': ntsm::reference_flag('c', optarg, opt.minCov); break;
+		case 'g': ntsm::reference_flag('g', optarg, opt.genomeSize); break;
+		case 't': ntsm::reference_flag('t', optarg, opt.threads); break;
+		case 'G': ntsm::reference_flag('G', optarg, opt.device); break;
 		case 'e': opt.merge = optarg; break;
 		case 'o': opt.onlyMerge = true; break;
-		case 'p': if (!parse(optarg, opt.pca)) { std::cerr << "Error - Invalid parameter p: " << optarg << std::endl; return 0; } break;
-		case 'n': if (!parse(optarg, opt.norm)) { std::cerr << "Error - Invalid parameter n: " << optarg << std::endl; return 0; } break;
-		case 'd': if (!parse(optarg, opt.dim)) { std::cerr << "Error - Invalid parameter d: " << optarg << std::endl; return 0; } break;
-		case 'r': if (!parse(optarg, opt.pcErrorThresh)) { std::cerr << "Error - Invalid parameter r: " << optarg << std::endl; return 0; } break;
-		case '1': if (!parse(optarg, opt.pcMissSite1)) { std::cerr << "Error - Invalid parameter 1: " << optarg << std::endl; return 0; } break;
-		case '2': if (!parse(optarg, opt.pcMissSite2)) { std::cerr << "Error - Invalid parameter 2: " << optarg << std::endl; return 0; } break;
-		case 'S': if (!parse(optarg, opt.pcSearchRadius1)) { std::cerr << "Error - Invalid parameter S: " << optarg << std::endl; return 0; } break;
-		case 'l': if (!parse(optarg, opt.pcSearchRadius2)) { std::cerr << "Error - Invalid parameter l: " << optarg << std::endl; return 0; } break;
-		case 'b': if (!parse(optarg, opt.debug)) { std::cerr << "Error - Invalid parameter b: " << optarg << std::endl; return 0; } break;
+		case 'p': ntsm::reference_flag('p', optarg, opt.pca); break;
+		case 'n': ntsm::reference_flag('n', optarg, opt.norm); break;
+		case 'd': ntsm::reference_flag('d', optarg, opt.dim); break;
+		case 'r': ntsm::reference_flag('r', optarg, opt.pcErrorThresh); break;
+		case '1': ntsm::reference_flag('1', optarg, opt.pcMissSite1); break;
+		case '2': ntsm::reference_flag('2', optarg, opt.pcMissSite2); break;
+		case 'S': ntsm::reference_flag('S', optarg, opt.pcSearchRadius1); break;
+		case 'l': ntsm::reference_flag('l', optarg, opt.pcSearchRadius2); break;
+		case 'b': ntsm::reference_flag('b', optarg, opt.debug); break;
 		case 'v': opt.verbose++; break;
 		case '?': die = true; break;
 		default: break;                              /* m: read by the reference, without effect */
@@ -395,24 +398,23 @@ int main(int argc, char **argv)
 			die = true;
 		}
 	}
-	if (die) { std::cerr << "Try '--help' for more information.\n"; exit(EXIT_FAILURE); }
+	ntsm::try_help_if(die);
 	const auto t0 = std::chrono::steady_clock::now();
 	if (opt.verbose > 0) std::cerr << "Reading count files" << std::endl;
 	load(c);
 	std::vector<Genotype> g = summaries(c, opt);
 	std::vector<long double> norm, rot;
 	if (pcaRuns) loadPCA(opt, c.nSites(), norm, rot);     /* every refusal and abort of the PCA inputs comes before the GPU */
+	if (c.files.size() > 1 && opt.verbose > 1) std::cerr << "Finished loading files. Now comparing all samples." << std::endl;
 	if (c.files.size() == 1) {                           /* computeScoreSingle, :541-585 */
 		if (opt.verbose > 1) std::cerr << "Detected only 1 file, providing only QC information." << std::endl;
 		std::string head = "sample\tcov\terrorRate\tmiss\thom\thet";
 		std::vector<double> cloud;
 		if (pcaRuns) {                                   /* projectPCs + the PC columns */
-			ntsm_eval_session *h = nullptr;
-			int rc = ntsm_eval_open(opt.device, c.counts.data(), 1, (uint32_t) c.nSites(), opt.minCov, &h);
+			Session session;
+			int rc = ntsm_eval_open(opt.device, c.counts.data(), 1, (uint32_t) c.nSites(), opt.minCov, &session.h);
 			if (rc) return gpuFail("session", rc);
-			rc = project(c, opt, h, norm, rot, cloud);
-			ntsm_eval_close(h);
-			if (rc) return rc;
+			if ((rc = project(c, opt, session.h, norm, rot, cloud)) != 0) return rc;
 			for (unsigned d = 1; d <= opt.dim; ++d) { head += "\tPC"; head += std::to_string(d); }
 		}
 		std::cout << head << std::endl;
@@ -420,21 +422,17 @@ int main(int argc, char **argv)
 		          << "\t" << std::to_string(g[0].homs) << "\t" << std::to_string(g[0].hets);
 		for (double v : cloud) std::cout << "\t" << std::to_string(v);
 	} else if (opt.onlyMerge) {                          /* src/ntSeqMatchEval.cpp:314-322 */
-		if (opt.verbose > 1) std::cerr << "Finished loading files. Now comparing all samples." << std::endl;
 		if (opt.merge.empty()) { std::cerr << "(-l) cannot be used without --merge (-e) option." << std::endl; exit(EXIT_FAILURE); }
 		std::cerr << " (-l) option detected. Not performing analysis, only merging." << std::endl;
 	} else if (pcaRuns) {                                /* projectPCs + computeScorePCA, src/ntSeqMatchEval.cpp:333-341 */
-		if (opt.verbose > 1) std::cerr << "Finished loading files. Now comparing all samples." << std::endl;
-		ntsm_eval_session *h = nullptr;
-		int rc = ntsm_eval_open(opt.device, c.counts.data(), (uint32_t) c.files.size(), (uint32_t) c.nSites(), opt.minCov, &h);
+		Session session;
+		int rc = ntsm_eval_open(opt.device, c.counts.data(), (uint32_t) c.files.size(), (uint32_t) c.nSites(), opt.minCov, &session.h);
 		if (rc) return gpuFail("session", rc);
 		std::vector<double> cloud;
-		rc = project(c, opt, h, norm, rot, cloud);
-		if (!rc) rc = scorePCA(c, g, opt, h, cloud);
-		ntsm_eval_close(h);
+		rc = project(c, opt, session.h, norm, rot, cloud);
+		if (!rc) rc = scorePCA(c, g, opt, session.h, cloud);
 		if (rc) return rc;
 	} else {                                             /* computeScore, :591-624 */
-		if (opt.verbose > 1) std::cerr << "Finished loading files. Now comparing all samples." << std::endl;
 		std::cerr << "Performing all-to-all score computation.\nSpecify -p (--pca) to enable faster comparisons." << std::endl;
 		const uint32_t n = (uint32_t) c.files.size();
 		std::vector<ntsm_eval_record> rec((size_t) n * (n - 1) / 2);
@@ -446,13 +444,7 @@ int main(int argc, char **argv)
 		std::cout << "\n";
 		std::string temp;
 		for (uint32_t i = 0; i < n; ++i)
-			for (uint32_t j = i + 1; j < n; ++j) {
-				const ntsm_eval_record &r = rec[ntsm_eval_pair_index(i, j, n)];
-				const double score = pairScore(r, g[i], g[j], opt);
-				if (!(opt.all || score < opt.scoreThresh)) continue;
-				appendRow(temp, c, g, opt, r, score, "-1", i, j);
-				std::cout << temp;
-			}
+			for (uint32_t j = i + 1; j < n; ++j) printRow(temp, c, g, opt, rec[ntsm_eval_pair_index(i, j, n)], i, j, "-1");
 	}
 	std::cout.flush();
 	if (c.files.size() > 1 && !opt.merge.empty()) {      /* mergeCounts, :626-674 */

@@ -11,7 +11,7 @@
  * (include/ntsm_pca_hip.h); there is no CPU fallback.
  *
  * The number text, the refusals' words and the writer of the two outputs are in pca_text.hpp, shared with
- * `ntsmVCF --rotation`, which does this program's work on the cells it has in memory.
+ * `ntsmVCF --rotation`, which does this program's work on the cells it has in memory (loader, cutter, flags: cli.hpp).
  *
  * The host reads the text (plain or gzip) and converts it on -t threads with std::from_chars, which is correctly
  * rounded; it formats the two outputs on -t threads with std::to_chars' shortest round-trip digits laid out the way
@@ -22,27 +22,17 @@
  * cell that is not a finite number, D < 1 or D > min(samples, sites).  After the eigen step: a requested component
  * whose eigenvalue is not positive beyond rounding.
  */
-#include <fcntl.h>
 #include <getopt.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
 
-#include <algorithm>
-#include <charconv>
-#include <chrono>
-#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
-#include <sstream>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../../include/ntsm_pca_hip.h"
-#include "gz_stream.hpp"
+#include "cli.hpp"
 #include "pca_text.hpp"
 
 #define PROGRAM "ntsmPCA"
@@ -55,19 +45,6 @@ struct Opt {
 	long long numComp = 20;
 	std::string matrix, prefix;
 };
-
-[[noreturn]] void refuse(const std::string &msg)
-{
-	std::cerr << "Error: " << msg << std::endl;
-	exit(EXIT_FAILURE);
-}
-
-void printVersion()
-{
-	std::cerr << PROGRAM " (ntsm-mi355x)\n"
-	          << "Exact PCA rotation matrix of an ntsmVCF matrix on the MI355X\n" << std::endl;
-	exit(EXIT_SUCCESS);
-}
 
 void printHelpDialog()
 {
@@ -87,60 +64,10 @@ void printHelpDialog()
 	exit(EXIT_SUCCESS);
 }
 
-template <typename T> bool parse(const char *s, T &out)
-{
-	std::stringstream c(s);
-	return bool(c >> out) && c.eof();
-}
-
-/* The matrix file as bytes (plain: mapped; gzip: decoded) */
-struct FileBytes {
-	const char *data = nullptr;
-	size_t size = 0;
-	std::vector<char> owned;
-	void *map = nullptr;
-	~FileBytes() { if (map) munmap(map, size); }
-	bool load(const std::string &path, unsigned threads)
-	{
-		if (ntsm::GzStream::is_gzip(path)) {
-			ntsm::GzStream::set_decoder_threads(threads);
-			ntsm::GzStream gz;
-			if (!gz.open(path)) return false;
-			std::vector<char> buf(1 << 22);
-			for (;;) {
-				const int n = gz.read(buf.data(), (unsigned) buf.size());
-				if (n < 0) return false;
-				if (n == 0) break;
-				owned.insert(owned.end(), buf.data(), buf.data() + n);
-			}
-			data = owned.data();
-			size = owned.size();
-			return true;
-		}
-		const int fd = open(path.c_str(), O_RDONLY);
-		if (fd < 0) return false;
-		struct stat st;
-		if (fstat(fd, &st) != 0 || S_ISDIR(st.st_mode)) { close(fd); return false; }
-		if (S_ISREG(st.st_mode) && st.st_size > 0) {
-			size = (size_t) st.st_size;
-			map = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
-			close(fd);
-			if (map == MAP_FAILED) { map = nullptr; return false; }
-			data = (const char *) map;
-			return true;
-		}
-		std::vector<char> buf(1 << 20);                         /* empty, or not a regular file: read it through */
-		for (ssize_t n; (n = read(fd, buf.data(), buf.size())) > 0;) owned.insert(owned.end(), buf.data(), buf.data() + n);
-		close(fd);
-		data = owned.data();
-		size = owned.size();
-		return true;
-	}
-};
-
 using ntsm::Name;
-using ntsm::format_repr;
+using ntsm::format_repr;                     /* tests/pca_text_check.cpp calls it from this file's scope */
 using ntsm::line_end;
+using ntsm::refuse;
 using ntsm::on_threads;
 
 /* one body line into one row of the matrix; an empty string when it is fine, else what is wrong with it */
@@ -164,6 +91,43 @@ std::string parse_row(const char *b, const char *e, uint32_t n, Name &name, doub
 	return std::string();
 }
 
+struct Matrix {
+	std::vector<Name> samples, sites;        /* views into the file's bytes */
+	std::vector<double> a;                   /* [sites][samples] */
+};
+
+/* the text into the matrix: the header, then the body cut into T ranges at line ends, counted, and every range converted
+ * into its rows.  Refused in this order: the header's shape, no sites, the first bad line of the file (whatever -t) */
+Matrix read_matrix(const std::string &name, const ntsm::FileBytes &file, unsigned T)
+{
+	Matrix m;
+	const char *const end = file.data + file.size;
+	const char *nl = (const char *) memchr(file.data, '\n', file.size);   /* header: alleleID <TAB> sample ... */
+	m.samples = ntsm::header_samples(file.data, nl ? nl : end);
+	if (const std::string why = ntsm::pca_shape_error(name, m.samples.size(), 1); !why.empty()) refuse(why);   /* the sites are not counted yet */
+	const uint32_t n = (uint32_t) m.samples.size();
+	const ntsm::LineCuts cut = ntsm::cut_lines(nl ? nl + 1 : end, end, T);
+	const uint64_t p = cut.lines_before[T];
+	if (const std::string why = ntsm::pca_shape_error(name, n, p); !why.empty()) refuse(why);
+	m.a.resize((size_t) p * n);
+	m.sites.resize(p);
+	std::vector<std::string> error(T);
+	std::vector<uint64_t> error_row(T, ~0ull);
+	on_threads(T, [&](unsigned t) {
+		uint64_t k = cut.lines_before[t];
+		for (const char *q = cut.at[t]; q < cut.at[t + 1]; ++k) {
+			const char *x = (const char *) memchr(q, '\n', (size_t) (cut.at[t + 1] - q));
+			const char *e = x ? x : cut.at[t + 1];
+			error[t] = parse_row(q, line_end(q, e), n, m.sites[k], m.a.data() + (size_t) k * n);
+			if (!error[t].empty()) { error_row[t] = k; return; }
+			q = x ? x + 1 : cut.at[t + 1];
+		}
+	});
+	for (unsigned t = 0; t < T; ++t)
+		if (error_row[t] != ~0ull) refuse(ntsm::pca_row_error(name, error_row[t], m.sites[error_row[t]], error[t]));
+	return m;
+}
+
 } // namespace
 
 int main(int argc, char **argv)
@@ -176,120 +140,51 @@ int main(int argc, char **argv)
 		{ "prefix", required_argument, nullptr, 'p' }, { "threads", required_argument, nullptr, 't' },
 		{ "gpu", required_argument, nullptr, 'G' }, { "help", no_argument, nullptr, 'h' },
 		{ "version", no_argument, &OPT_VERSION, 1 }, { "verbose", no_argument, nullptr, 'v' }, { nullptr, 0, nullptr, 0 } };
-	auto invalid = [&](char flag) {
-		std::cerr << "Error - Invalid parameter " << flag << ": " << optarg << std::endl;
-		die = true;
-	};
 	int ch;
 	while ((ch = getopt_long(argc, argv, "m:n:p:t:G:vh", long_options, nullptr)) != -1) {
 		switch (ch) {
 		case 'h': printHelpDialog(); break;
 		case 'm': opt.matrix = optarg; break;
 		case 'p': opt.prefix = optarg; break;
-		case 'n': if (!parse(optarg, opt.numComp)) invalid('n'); break;
-		case 't': if (!parse(optarg, opt.threads)) invalid('t'); break;
-		case 'G': if (!parse(optarg, opt.device)) invalid('G'); break;
+		case 'n': ntsm::whole_flag('n', optarg, opt.numComp, die); break;
+		case 't': ntsm::whole_flag('t', optarg, opt.threads, die); break;
+		case 'G': ntsm::whole_flag('G', optarg, opt.device, die); break;
 		case 'v': opt.verbose++; break;
 		case '?': die = true; break;
 		default: break;
 		}
 	}
-	if (OPT_VERSION) printVersion();
-	if (optind < argc) {
-		std::cerr << "Error: Unexpected argument " << argv[optind] << " (the matrix is given with -m)" << std::endl;
-		die = true;
-	}
-	if (opt.matrix.empty()) {
-		std::cerr << "Error: Need Input File (-m)" << std::endl;
-		die = true;
-	}
-	if (die) {
-		std::cerr << "Try '--help' for more information.\n";
-		exit(EXIT_FAILURE);
-	}
+	if (OPT_VERSION) ntsm::print_version(PROGRAM, "Exact PCA rotation matrix of an ntsmVCF matrix on the MI355X");
+	auto usage = [&](const std::string &msg) { std::cerr << msg << std::endl; die = true; };
+	if (optind < argc) usage(std::string("Error: Unexpected argument ") + argv[optind] + " (the matrix is given with -m)");
+	if (opt.matrix.empty()) usage("Error: Need Input File (-m)");
+	ntsm::try_help_if(die);
 	if (opt.numComp < 1) refuse(ntsm::pca_dims_low_error(opt.numComp));
-	const unsigned T = opt.threads ? std::min(opt.threads, 256u) : std::max(1u, std::min(64u, std::thread::hardware_concurrency()));
-	auto t_lap = std::chrono::steady_clock::now();
-	const auto t_start = t_lap;
-	auto lap = [&](const char *what) {
-		const auto t = std::chrono::steady_clock::now();
-		if (opt.verbose) fprintf(stderr, "[pca] %s: %.4f s\n", what, std::chrono::duration<double>(t - t_lap).count());
-		t_lap = t;
-	};
-
-	FileBytes file;
-	if (!file.load(opt.matrix, T)) refuse("cannot read the matrix file " + opt.matrix);
+	const unsigned T = ntsm::thread_count(opt.threads);
+	ntsm::LapTimer timer { "[pca]", opt.verbose > 0 };
+	ntsm::FileBytes file;                        /* a directory is not a matrix file */
+	if (!file.load(opt.matrix, T, ntsm::FileBytes::kDirectoryIsUnreadable)) refuse("cannot read the matrix file " + opt.matrix);
 	if (file.size == 0) refuse("the matrix file " + opt.matrix + " is empty");
-	lap("read");
-	const char *const end = file.data + file.size;
-
-	/* header: alleleID <TAB> sample ... */
-	const char *nl = (const char *) memchr(file.data, '\n', file.size);
-	const char *body = nl ? nl + 1 : end;
-	const std::vector<Name> samples = ntsm::header_samples(file.data, nl ? nl : end);
-	if (const std::string why = ntsm::pca_shape_error(opt.matrix, samples.size(), 1); !why.empty()) refuse(why);   /* the sites are not counted yet */
-	const uint32_t n = (uint32_t) samples.size();
-
-	/* body lines: cut the bytes into T ranges at line ends, count, then convert every range into its rows */
-	std::vector<const char *> cut(T + 1, end);
-	cut[0] = body;
-	for (unsigned t = 1; t < T; ++t) {
-		const char *q = body + (size_t) (end - body) * t / T;
-		q = std::max(q, cut[t - 1]);
-		const char *x = q < end ? (const char *) memchr(q, '\n', (size_t) (end - q)) : nullptr;
-		cut[t] = x ? x + 1 : end;
-	}
-	std::vector<uint64_t> first(T + 1, 0);
-	on_threads(T, [&](unsigned t) {
-		uint64_t c = 0;
-		for (const char *q = cut[t]; q < cut[t + 1];) {
-			const char *x = (const char *) memchr(q, '\n', (size_t) (cut[t + 1] - q));
-			++c;
-			q = x ? x + 1 : cut[t + 1];
-		}
-		first[t + 1] = c;
-	});
-	for (unsigned t = 0; t < T; ++t) first[t + 1] += first[t];
-	const uint64_t p = first[T];
-	if (const std::string why = ntsm::pca_shape_error(opt.matrix, n, p); !why.empty()) refuse(why);
-	std::vector<double> a((size_t) p * n);
-	std::vector<Name> sites(p);
-	std::vector<std::string> error(T);
-	std::vector<uint64_t> error_row(T, ~0ull);
-	on_threads(T, [&](unsigned t) {
-		uint64_t k = first[t];
-		for (const char *q = cut[t]; q < cut[t + 1]; ++k) {
-			const char *x = (const char *) memchr(q, '\n', (size_t) (cut[t + 1] - q));
-			const char *e = x ? x : cut[t + 1];
-			error[t] = parse_row(q, line_end(q, e), n, sites[k], a.data() + (size_t) k * n);
-			if (!error[t].empty()) { error_row[t] = k; return; }
-			q = x ? x + 1 : cut[t + 1];
-		}
-	});
-	for (unsigned t = 0; t < T; ++t)                               /* the first bad line of the file, whatever -t */
-		if (error_row[t] != ~0ull) {
-			refuse(ntsm::pca_row_error(opt.matrix, error_row[t], sites[error_row[t]], error[t]));
-		}
-	lap("parse");
+	timer.lap("read");
+	const Matrix m = read_matrix(opt.matrix, file, T);
+	timer.lap("parse");
+	const uint64_t p = m.sites.size();
+	const uint32_t n = (uint32_t) m.samples.size(), d = (uint32_t) opt.numComp;
 	if (const std::string why = ntsm::pca_dims_high_error(opt.numComp, n, p); !why.empty()) refuse(why);
-	const uint32_t d = (uint32_t) opt.numComp;
 	if (opt.verbose) std::cerr << "Matrix: " << p << " sites x " << n << " samples, " << d << " components" << std::endl;
-
 	std::vector<double> eigval(d), rot((size_t) p * d), comp((size_t) n * d);
 	uint32_t bad = 0;
-	ntsm_pca_times tm;
-	memset(&tm, 0, sizeof tm);
-	const int rc = ntsm_pca_run(opt.device, p, n, a.data(), d, 0, eigval.data(), rot.data(), comp.data(), &bad, &tm);
+	ntsm_pca_times tm {};
+	const int rc = ntsm_pca_run(opt.device, p, n, m.a.data(), d, 0, eigval.data(), rot.data(), comp.data(), &bad, &tm);
 	if (rc != 0) refuse(ntsm::pca_run_error(rc, bad, d, opt.device));
-	lap("device");
+	timer.lap("device");
 	if (opt.verbose) {
 		ntsm::pca_print_times(stderr, tm, nullptr);
 		if (opt.verbose > 1) for (uint32_t i = 0; i < d; ++i) fprintf(stderr, "[pca] eigenvalue %u: %.17g\n", i, eigval[i]);
 	}
-
-	if (const std::string bad_path = ntsm::write_pca_tables(opt.prefix, sites, samples, rot.data(), comp.data(), d, T); !bad_path.empty())
+	if (const std::string bad_path = ntsm::write_pca_tables(opt.prefix, m.sites, m.samples, rot.data(), comp.data(), d, T); !bad_path.empty())
 		refuse("cannot write " + bad_path);
-	lap("write");
-	if (opt.verbose) fprintf(stderr, "[pca] total: %.4f s\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count());
+	timer.lap("write");
+	if (opt.verbose) fprintf(stderr, "[pca] total: %.4f s\n", timer.total());
 	return 0;
 }

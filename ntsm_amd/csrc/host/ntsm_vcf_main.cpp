@@ -21,31 +21,24 @@
  * behaviour are refused with "Error: ..." and exit status 1.  A VCF that starts with the gzip
  * magic is decoded (ntsm::GzStream); the reference reads it as text and finds no samples.
  */
-#include <fcntl.h>
 #include <getopt.h>
-#include <sys/mman.h>
 #include <sys/resource.h>
-#include <sys/stat.h>
-#include <unistd.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <iostream>
 #include <limits>
-#include <sstream>
 #include <stdexcept>
 #include <string>
-#include <thread>
 #include <unordered_map>
 #include <vector>
 
 #include "../../../include/ntsm_pca_hip.h"
 #include "../../../include/ntsm_vcf_hip.h"
-#include "gz_stream.hpp"
+#include "cli.hpp"
 #include "kmer.hpp"
 #include "pca_text.hpp"
 #include "seq_reader.hpp"
@@ -62,22 +55,11 @@ struct Opt {                                 /* src/Options.h: the members ntsmV
 	bool rotation = false, no_matrix = false, dims_given = false;   /* -R, -M, -n (this build only) */
 	long long numComp = 20;                                         /* ntsmPCA's -n and its default */
 	std::string snp, ref, pca;
+	std::vector<std::string> inputs;                                /* the arguments after the flags */
+	unsigned T = 1;                                                 /* ntsm::thread_count(threads) */
 };
 
 constexpr unsigned kMaxWindow = 1u << 20;    /* getSeqFromSite keeps two window + 1 byte arrays on the stack */
-
-[[noreturn]] void refuse(const std::string &msg)
-{
-	std::cerr << "Error: " << msg << std::endl;
-	exit(EXIT_FAILURE);
-}
-
-void printVersion()
-{
-	std::cerr << PROGRAM " (ntsm-mi355x)\n"
-	          << "MI355X-native implementation of ntsmVCF (multi-sample VCF to PCA matrix)\n" << std::endl;
-	exit(EXIT_SUCCESS);
-}
 
 void printHelpDialog()
 {
@@ -107,8 +89,6 @@ void printHelpDialog()
 	    "      --version          Print version information.\n" << std::endl;
 	exit(EXIT_SUCCESS);
 }
-
-template <typename T> bool parse(const char *s, T &out) { std::stringstream c(s); return bool(c >> out); }
 
 bool fexists(const std::string &f) { return std::ifstream(f).good(); }       /* src/Util.h:22-27 */
 
@@ -147,51 +127,6 @@ private:
 struct Genome {                              /* VCFConvert::m_ref / m_chrIDs */
 	std::vector<std::string> seq;
 	std::unordered_map<std::string, uint32_t> id;
-};
-
-/* The VCF as bytes (plain: mapped; gzip / BGZF: decoded) */
-struct VcfBytes {
-	const char *data = nullptr;
-	size_t size = 0;
-	std::vector<char> owned;
-	void *map = nullptr;
-	~VcfBytes() { if (map) munmap(map, size); }
-	bool load(const std::string &path, unsigned threads)
-	{
-		if (ntsm::GzStream::is_gzip(path)) {
-			ntsm::GzStream::set_decoder_threads(threads);
-			ntsm::GzStream gz;
-			if (!gz.open(path)) return false;
-			std::vector<char> buf(1 << 22);
-			for (;;) {
-				const int n = gz.read(buf.data(), (unsigned) buf.size());
-				if (n < 0) return false;
-				if (n == 0) break;
-				owned.insert(owned.end(), buf.data(), buf.data() + n);
-			}
-			data = owned.data();
-			size = owned.size();
-			return true;
-		}
-		const int fd = open(path.c_str(), O_RDONLY);
-		if (fd < 0) return false;
-		struct stat st;
-		if (fstat(fd, &st) != 0) { close(fd); return false; }
-		if (S_ISREG(st.st_mode) && st.st_size > 0) {
-			size = (size_t) st.st_size;
-			map = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
-			close(fd);
-			if (map == MAP_FAILED) { map = nullptr; return false; }
-			data = (const char *) map;
-			return true;
-		}
-		std::vector<char> buf(1 << 20);                         /* not a regular file: read it through */
-		for (ssize_t n; (n = read(fd, buf.data(), buf.size())) > 0;) owned.insert(owned.end(), buf.data(), buf.data() + n);
-		close(fd);
-		data = owned.data();
-		size = owned.size();
-		return true;
-	}
 };
 
 /* What one body line of the VCF contributes (VCFConvert::count, :102-171) */
@@ -318,12 +253,7 @@ long rss_kbytes()                            /* Util::getRSS: only in the Time l
 	return ru.ru_maxrss;
 }
 
-double seconds_since(std::chrono::steady_clock::time_point t)
-{
-	return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
-}
-
-using ntsm::on_threads;
+using ntsm::on_threads, ntsm::refuse;
 
 /* The number text of NAME_matrix.tsv and NAME_center.txt (printNormMatrix, MultiCount.hpp:148-201), stated once: the
  * matrix writer prints these strings and -R hands the PCA what ntsmPCA would read back from them (text_value). */
@@ -351,9 +281,8 @@ double text_value(const std::string &text)                  /* the cell ntsmPCA 
 	return ntsm::parse_cell(text.data(), text.data() + text.size(), x) ? x : std::numeric_limits<double>::quiet_NaN();
 }
 
-} // namespace
-
-int main(int argc, char **argv)
+/* the flags and what is refused from them alone, in the reference's order (src/ntSeqMatchVCF.cpp:82-199), then this build's */
+Opt read_options(int argc, char **argv)
 {
 	Opt opt;
 	bool die = false;
@@ -372,85 +301,49 @@ int main(int argc, char **argv)
 		switch (ch) {                            /* src/ntSeqMatchVCF.cpp:82-156 */
 		case 'h': printHelpDialog(); break;
 		case 'd': opt.dupes = true; break;
-		case 's': if (!parse(optarg, opt.snp)) { std::cerr << "Error - Invalid parameter s: " << optarg << std::endl; return 0; } break;
-		case 'p': if (!parse(optarg, opt.pca)) { std::cerr << "Error - Invalid parameter p: " << optarg << std::endl; return 0; } break;
-		case 'k': if (!parse(optarg, opt.k)) { std::cerr << "Error - Invalid parameter k: " << optarg << std::endl; return 0; } break;
-		case 'w': if (!parse(optarg, opt.window)) { std::cerr << "Error - Invalid parameter w: " << optarg << std::endl; return 0; } break;
-		case 'm': if (!parse(optarg, opt.multi)) { std::cerr << "Error - Invalid parameter m: " << optarg << std::endl; return 0; } break;
-		case 't': if (!parse(optarg, opt.threads)) { std::cerr << "Error - Invalid parameter t: " << optarg << std::endl; return 0; } break;
-		case 'r': if (!parse(optarg, opt.ref)) { std::cerr << "Error - Invalid parameter r: " << optarg << std::endl; return 0; } break;
-		case 'G': if (!parse(optarg, opt.device)) { std::cerr << "Error - Invalid parameter G: " << optarg << std::endl; return 0; } break;
+		case 's': ntsm::reference_flag('s', optarg, opt.snp); break;
+		case 'p': ntsm::reference_flag('p', optarg, opt.pca); break;
+		case 'k': ntsm::reference_flag('k', optarg, opt.k); break;
+		case 'w': ntsm::reference_flag('w', optarg, opt.window); break;
+		case 'm': ntsm::reference_flag('m', optarg, opt.multi); break;
+		case 't': ntsm::reference_flag('t', optarg, opt.threads); break;
+		case 'r': ntsm::reference_flag('r', optarg, opt.ref); break;
+		case 'G': ntsm::reference_flag('G', optarg, opt.device); break;
 		case 'R': opt.rotation = true; break;
 		case 'M': opt.no_matrix = true; break;
-		case 'n': {                                  /* the whole value, as ntsmPCA reads its -n; a bad one is an error */
-			std::stringstream c(optarg);
-			opt.dims_given = true;
-			if (!(c >> opt.numComp) || !c.eof()) { std::cerr << "Error - Invalid parameter n: " << optarg << std::endl; die = true; }
-			break;
-		}
+		case 'n': opt.dims_given = true; ntsm::whole_flag('n', optarg, opt.numComp, die); break;   /* as ntsmPCA reads its -n */
 		case 'v': opt.verbose++; break;
 		case '?': die = true; break;
 		default: break;
 		}
 	}
-	if (OPT_VERSION) printVersion();
-	if (opt.k > 32) {                                                /* :168-171 */
-		die = true;
-		std::cerr << "k cannot be greater than 32" << std::endl;
-	}
-	std::vector<std::string> inputs;
+	if (OPT_VERSION) ntsm::print_version(PROGRAM, "MI355X-native implementation of ntsmVCF (multi-sample VCF to PCA matrix)");
+	auto usage = [&](const char *msg) { std::cerr << msg << std::endl; die = true; };
+	if (opt.k > 32) usage("k cannot be greater than 32");            /* :168-171 */
 	while (optind < argc) {
-		inputs.emplace_back(argv[optind++]);
-		if (!fexists(inputs.back())) refuse("input file " + inputs.back() + " does not exist");   /* :176 asserts */
+		opt.inputs.emplace_back(argv[optind++]);
+		if (!fexists(opt.inputs.back())) refuse("input file " + opt.inputs.back() + " does not exist");   /* :176 asserts */
 	}
-	if (inputs.empty()) {
-		std::cerr << "Error: Need Input File" << std::endl;
-		die = true;
-	}
-	if (!fexists(opt.ref)) {
-		std::cerr << "Error: Unable to load reference file" << std::endl;
-		die = true;
-	}
-	if (opt.rotation && opt.pca.empty()) {
-		std::cerr << "Error: -R needs -p" << std::endl;
-		die = true;
-	}
-	if (!opt.rotation && (opt.dims_given || opt.no_matrix)) {
-		std::cerr << "Error: " << (opt.dims_given ? "-n" : "-M") << " needs -R" << std::endl;
-		die = true;
-	}
-	if (die) {
-		std::cerr << "Try '--help' for more information.\n";
-		exit(EXIT_FAILURE);
-	}
+	if (opt.inputs.empty()) usage("Error: Need Input File");
+	if (!fexists(opt.ref)) usage("Error: Unable to load reference file");
+	if (opt.rotation && opt.pca.empty()) usage("Error: -R needs -p");
+	if (!opt.rotation && (opt.dims_given || opt.no_matrix)) usage(opt.dims_given ? "Error: -n needs -R" : "Error: -M needs -R");
+	ntsm::try_help_if(die);
 	if (opt.rotation && opt.numComp < 1) refuse(ntsm::pca_dims_low_error(opt.numComp));
-	if (inputs.size() > 1) refuse("ntsmVCF takes one VCF file, " + std::to_string(inputs.size()) + " were given");   /* :199 asserts */
+	if (opt.inputs.size() > 1) refuse("ntsmVCF takes one VCF file, " + std::to_string(opt.inputs.size()) + " were given");   /* :199 asserts */
 	if (opt.k == 0 || opt.k == 32) refuse("-k " + std::to_string(opt.k) + " is not supported (k must be 1 to 31)");
 	if (opt.window >= kMaxWindow) refuse("-w " + std::to_string(opt.window) + " is too large (at most " + std::to_string(kMaxWindow - 1) + ")");
-	const unsigned T = opt.threads ? std::min(opt.threads, 256u) : std::max(1u, std::min(64u, std::thread::hardware_concurrency()));
-	const auto t_start = std::chrono::steady_clock::now();
-	const bool prof = getenv("NTSM_VCF_PROF") != nullptr;      /* phase times on stderr (tools/vcf_bench.py) */
-	auto t_lap = t_start;
-	auto lap = [&](const char *what) {
-		if (!prof) return;
-		const auto t = std::chrono::steady_clock::now();
-		fprintf(stderr, "[vcf] %s: %.4f s\n", what, std::chrono::duration<double>(t - t_lap).count());
-		t_lap = t;
-	};
+	opt.T = ntsm::thread_count(opt.threads);
+	return opt;
+}
 
-	/* VCFConvert's constructor: the sites (MultiCount's, initialised first), then the genome */
+ntsm::SiteSet load_sites(const Opt &opt)         /* VCFConvert's constructor, first half: the sites (MultiCount's) */
+{
 	ntsm::SiteSet sites;
-	{
-		if (!fexists(opt.snp)) {                                    /* MultiCount.hpp:218-221 */
-			std::cerr << "file " << opt.snp << " cannot be opened" << std::endl;
-			exit(1);
-		}
-		if (opt.verbose) std::cerr << "Opening " << opt.snp << std::endl;
-		if (!sites.load(opt.snp, opt.k, opt.dupes, std::cerr)) {
-			std::cerr << "file " << opt.snp << " cannot be opened" << std::endl;
-			exit(1);
-		}
-	}
+	auto cannot_open = [&]() { std::cerr << "file " << opt.snp << " cannot be opened" << std::endl; exit(1); };
+	if (!fexists(opt.snp)) cannot_open();                           /* MultiCount.hpp:218-221 */
+	if (opt.verbose) std::cerr << "Opening " << opt.snp << std::endl;
+	if (!sites.load(opt.snp, opt.k, opt.dupes, std::cerr)) cannot_open();
 	const size_t n_sites = sites.ids.size();
 	if (sites.ref.size() != sites.var.size())
 		refuse("the sites file has an odd number of records (" + std::to_string(sites.ref.size() + sites.var.size()) + "): site " +
@@ -464,26 +357,34 @@ int main(int argc, char **argv)
 		refuse("the sites file has k-mers shared between sites (first at site " + sites.ids[std::min(s, n_sites - 1)] +
 		    "); -p needs -d for such a file");
 	}
-	lap("sites");
+	return sites;
+}
+
+Genome load_genome(const Opt &opt)               /* the constructor's second half (VCFConvert.hpp:43-58) */
+{
 	if (opt.verbose > 1) std::cerr << "Loading Reference " << opt.ref << std::endl;
 	Genome genome;
-	{
-		ntsm::SeqReader rd;
-		if (!rd.open(opt.ref)) refuse("cannot read the reference file " + opt.ref);
-		for (int64_t l = rd.next(); l >= 0; l = rd.next()) {
-			genome.id[rd.name()] = (uint32_t) genome.seq.size();
-			genome.seq.emplace_back(rd.seq_data(), (size_t) l);
-		}
+	ntsm::SeqReader rd;
+	if (!rd.open(opt.ref)) refuse("cannot read the reference file " + opt.ref);
+	for (int64_t l = rd.next(); l >= 0; l = rd.next()) {
+		genome.id[rd.name()] = (uint32_t) genome.seq.size();
+		genome.seq.emplace_back(rd.seq_data(), (size_t) l);
 	}
-	lap("genome");
+	return genome;
+}
 
-	/* VCFConvert::count (:63-172) */
-	if (opt.verbose > 1) std::cerr << "Reading VCF file: " << inputs[0] << std::endl;
-	VcfBytes vcf;
-	if (!vcf.load(inputs[0], T)) refuse("cannot read the VCF file " + inputs[0]);
-	const char *p = vcf.data, *const end = vcf.data + vcf.size;
+struct Header {
 	std::vector<std::string> samples;
-	for (uint64_t line_no = 1; p < end; ++line_no) {            /* the header (:70-93) */
+	std::string matrix_head = "alleleID";              /* the header line of NAME_matrix.tsv: alleleID <TAB> sample ... */
+	const char *body = nullptr, *body_end = nullptr;   /* the complete lines after the #CHROM line */
+	uint64_t lines = 0;                                /* the lines before them */
+};
+
+Header read_header(const ntsm::FileBytes &vcf)   /* VCFConvert::count, :70-93 */
+{
+	Header h;
+	const char *p = vcf.data, *const end = vcf.data + vcf.size;
+	for (uint64_t line_no = 1; p < end; ++line_no) {
 		const char *nl = (const char *) memchr(p, '\n', (size_t) (end - p));
 		const char *b = p, *e = nl ? nl : end;
 		p = nl ? nl + 1 : end;
@@ -493,233 +394,292 @@ int main(int argc, char **argv)
 		if (std::string(b, t ? t : e) != "#CHROM") continue;
 		Fields fl;
 		fl.split(b, e);
-		for (size_t i = 9; i < fl.n_read(); ++i) samples.emplace_back(fl.f[i].first, fl.f[i].second);
+		for (size_t i = 9; i < fl.n_read(); ++i) h.samples.emplace_back(fl.f[i].first, fl.f[i].second);
 		break;
 	}
-	const uint64_t header_lines = (uint64_t) std::count(vcf.data, p, '\n');
-	const uint32_t n_samples = (uint32_t) samples.size();
-	if (opt.verbose > 1) std::cerr << "Starting multicount of each rsID for " << n_samples << " samples." << std::endl;
+	for (const std::string &sm : h.samples) { h.matrix_head += "\t"; h.matrix_head += sm; }
+	h.matrix_head += "\n";
+	h.lines = (uint64_t) std::count(vcf.data, p, '\n');
 	/* body: complete lines only (a last line without '\n' fails fh.good(), :108) */
-	const char *body_end = p;
+	h.body = h.body_end = p;
 	for (const char *q = end; q > p; --q)
-		if (q[-1] == '\n') { body_end = q; break; }
-	const uint32_t stride = (n_samples + 15) / 16 * 16;
-	KeyTable table(sites.keys);
-	const Ctx ctx { opt, genome, table, n_samples, stride };
+		if (q[-1] == '\n') { h.body_end = q; break; }
+	return h;
+}
+
+/* the body on T threads (:102-171); the first failure in file order is the refusal, whatever -t */
+std::vector<Part> parse_body(const Ctx &ctx, const Header &h, unsigned T)
+{
 	std::vector<Part> parts(T);
-	std::vector<const char *> cut(T + 1, body_end);
-	cut[0] = p;
-	for (unsigned t = 1; t < T; ++t) {
-		const char *q = std::max(cut[t - 1], p + (size_t) (body_end - p) / T * t);
-		while (q < body_end && q > p && q[-1] != '\n') ++q;
-		cut[t] = q;
-	}
-	std::vector<uint64_t> first_line(T + 1, header_lines + 1);
-	on_threads(T, [&](unsigned t) {                              /* line numbers of the cuts (for messages) */
-		first_line[t + 1] = (uint64_t) std::count(cut[t], cut[t + 1], '\n');
-	});
-	for (unsigned t = 0; t < T; ++t) first_line[t + 1] += first_line[t];
-	on_threads(T, [&](unsigned t) { parse_lines(ctx, cut[t], cut[t + 1], first_line[t], parts[t]); });
+	const ntsm::LineCuts cut = ntsm::cut_lines(h.body, h.body_end, T);
+	on_threads(T, [&](unsigned t) { parse_lines(ctx, cut.at[t], cut.at[t + 1], h.lines + 1 + cut.lines_before[t], parts[t]); });
 	for (const Part &pt : parts)
 		if (pt.failed) refuse(pt.error);
-	lap("parse");
-	/* events in one-thread order -> per-key lists (CSR), ascending ordinals */
-	uint64_t n_events = 0, n_used = 0;
-	for (const Part &pt : parts) { n_events += pt.ev_key.size(); n_used += pt.used; }
-	if (n_events > 0xFFFFFFFFull || n_used > 0x7FFFFFFFull) refuse("too many window k-mers in the VCF");
-	const uint64_t n_keys = sites.keys.size();
-	std::vector<uint64_t> key_off(n_keys + 1, 0);
+	return parts;
+}
+
+struct Events {                              /* the inputs of ntsm_vcf_run (include/ntsm_vcf_hip.h), under its names */
+	uint64_t n_lines = 0, n_keys = 0, n_events = 0, n_sites = 0;
+	uint32_t g_stride = 0;
+	std::vector<uint8_t> geno;
+	std::vector<uint64_t> key_off, site_off;
+	std::vector<uint32_t> ev_ord, ev_ls, site_keys;
+};
+
+/* events in one-thread order -> per-key lists (CSR), ascending ordinals; the parts' genotype rows move into one array */
+Events build_events(std::vector<Part> &parts, const ntsm::SiteSet &sites, uint32_t stride)
+{
+	const unsigned T = (unsigned) parts.size();
+	Events ev;
+	ev.g_stride = stride;
+	for (const Part &pt : parts) { ev.n_events += pt.ev_key.size(); ev.n_lines += pt.used; }
+	if (ev.n_events > 0xFFFFFFFFull || ev.n_lines > 0x7FFFFFFFull) refuse("too many window k-mers in the VCF");
+	ev.n_keys = sites.keys.size();
+	ev.key_off.assign(ev.n_keys + 1, 0);
 	for (const Part &pt : parts)
-		for (uint32_t q : pt.ev_key) key_off[q + 1]++;
-	for (uint64_t q = 0; q < n_keys; ++q) key_off[q + 1] += key_off[q];
-	std::vector<uint32_t> ev_ord(n_events), ev_ls(n_events);
-	std::vector<uint8_t> geno((size_t) n_used * stride);
-	{
-		std::vector<uint64_t> fill(key_off.begin(), key_off.end() - 1);
-		uint64_t ord = 0, line_base = 0;
-		std::vector<uint64_t> geno_at(T + 1, 0);
-		for (unsigned t = 0; t < T; ++t) {
-			const Part &pt = parts[t];
-			for (size_t i = 0; i < pt.ev_key.size(); ++i, ++ord) {
-				const uint64_t at = fill[pt.ev_key[i]]++;
-				ev_ord[at] = (uint32_t) ord;
-				ev_ls[at] = (uint32_t) ((line_base + pt.ev_line[i]) * 2 + pt.ev_side[i]);
-			}
-			line_base += pt.used;
-			geno_at[t + 1] = geno_at[t] + pt.geno.size();
+		for (uint32_t q : pt.ev_key) ev.key_off[q + 1]++;
+	for (uint64_t q = 0; q < ev.n_keys; ++q) ev.key_off[q + 1] += ev.key_off[q];
+	ev.ev_ord.resize(ev.n_events);
+	ev.ev_ls.resize(ev.n_events);
+	ev.geno.resize((size_t) ev.n_lines * stride);
+	std::vector<uint64_t> fill(ev.key_off.begin(), ev.key_off.end() - 1);
+	uint64_t ord = 0, line_base = 0;
+	std::vector<uint64_t> geno_at(T + 1, 0);
+	for (unsigned t = 0; t < T; ++t) {
+		const Part &pt = parts[t];
+		for (size_t i = 0; i < pt.ev_key.size(); ++i, ++ord) {
+			const uint64_t at = fill[pt.ev_key[i]]++;
+			ev.ev_ord[at] = (uint32_t) ord;
+			ev.ev_ls[at] = (uint32_t) ((line_base + pt.ev_line[i]) * 2 + pt.ev_side[i]);
 		}
-		on_threads(T, [&](unsigned t) {
-			if (!parts[t].geno.empty()) memcpy(geno.data() + geno_at[t], parts[t].geno.data(), parts[t].geno.size());
-			std::vector<uint8_t>().swap(parts[t].geno);
-		});
+		line_base += pt.used;
+		geno_at[t + 1] = geno_at[t] + pt.geno.size();
 	}
+	on_threads(T, [&](unsigned t) {
+		if (!parts[t].geno.empty()) memcpy(ev.geno.data() + geno_at[t], parts[t].geno.data(), parts[t].geno.size());
+		std::vector<uint8_t>().swap(parts[t].geno);
+	});
 	/* per-site key lists (erased k-mers -- only without -d, and then without -p -- have no events: left out) */
-	std::vector<uint64_t> site_off(2 * n_sites + 1, 0);
-	std::vector<uint32_t> site_keys;
-	for (size_t s = 0; s < n_sites; ++s)
+	ev.n_sites = sites.ids.size();
+	ev.site_off.assign(2 * ev.n_sites + 1, 0);
+	for (size_t s = 0; s < ev.n_sites; ++s)
 		for (int side = 0; side < 2; ++side) {
 			for (int64_t q : side ? sites.var[s] : sites.ref[s])
-				if (q >= 0) site_keys.push_back((uint32_t) q);
-			site_off[2 * s + side + 1] = site_keys.size();
+				if (q >= 0) ev.site_keys.push_back((uint32_t) q);
+			ev.site_off[2 * s + side + 1] = ev.site_keys.size();
 		}
-	lap("events");
+	return ev;
+}
 
-	/* -R: what ntsmPCA refuses from the shape of the matrix alone is refused here, in its words, after every refusal of
-	 * the VCF and before the device is touched.  The names are read back from the header line as ntsmPCA reads them (a
-	 * CRLF header's "\r" goes); site ids hold no white space (ntsm::SeqReader), so every row has the header's fields */
-	std::string head = "alleleID";
-	for (const std::string &sm : samples) { head += "\t"; head += sm; }
-	head += "\n";
-	std::vector<ntsm::Name> pca_samples, pca_sites;
-	if (opt.rotation) {
-		const std::string matrix_name = opt.pca + "_matrix.tsv";
-		pca_samples = ntsm::header_samples(head.data(), head.data() + head.size() - 1);
-		std::string why = ntsm::pca_shape_error(matrix_name, pca_samples.size(), n_sites);
-		if (why.empty() && pca_samples.size() != n_samples) why = "the header of " + matrix_name + " does not read back as its samples";
-		if (why.empty()) why = ntsm::pca_dims_high_error(opt.numComp, n_samples, n_sites);
-		if (!why.empty()) refuse(why);
-		for (const std::string &id : sites.ids) pca_sites.push_back(ntsm::Name { id.data(), id.size() });
-	}
+struct PcaNames { std::vector<ntsm::Name> samples, sites; };   /* views into the matrix header and the site ids */
 
-	/* the device step: inserts, maxima, sums (include/ntsm_vcf_hip.h) */
-	std::vector<uint16_t> cells((size_t) n_sites * n_samples);
-	std::vector<double> sums(n_sites);
-	std::vector<uint32_t> first_undef(n_sites);
-	std::vector<ntsm_vcf_warning> warn(1 << 20);                  /* 16 MB: more warnings cost a second call */
+/* -R: what ntsmPCA refuses from the shape of the matrix alone is refused here, in its words, after every refusal of
+ * the VCF and before the device is touched.  The names are read back from the header line as ntsmPCA reads them (a
+ * CRLF header's "\r" goes); site ids hold no white space (ntsm::SeqReader), so every row has the header's fields */
+PcaNames rotation_shape_check(const Opt &opt, const std::string &head, const ntsm::SiteSet &sites, uint32_t n_samples)
+{
+	const std::string matrix_name = opt.pca + "_matrix.tsv";
+	const size_t n_sites = sites.ids.size();
+	PcaNames names { ntsm::header_samples(head.data(), head.data() + head.size() - 1), {} };
+	std::string why = ntsm::pca_shape_error(matrix_name, names.samples.size(), n_sites);
+	if (why.empty() && names.samples.size() != n_samples) why = "the header of " + matrix_name + " does not read back as its samples";
+	if (why.empty()) why = ntsm::pca_dims_high_error(opt.numComp, n_samples, n_sites);
+	if (!why.empty()) refuse(why);
+	for (const std::string &id : sites.ids) names.sites.push_back(ntsm::Name { id.data(), id.size() });
+	return names;
+}
+
+struct Step {                                /* the outputs of ntsm_vcf_run; warn in the library's order */
+	std::vector<uint16_t> cells;
+	std::vector<double> sums;
+	std::vector<uint32_t> first_undef;
+	std::vector<ntsm_vcf_warning> warn;
+};
+
+/* the device step: inserts, maxima, sums (include/ntsm_vcf_hip.h); called again when the warnings need more room */
+Step device_step(const Opt &opt, const Events &ev, uint32_t n_samples, bool prof)
+{
+	Step st { std::vector<uint16_t>((size_t) ev.n_sites * n_samples), std::vector<double>(ev.n_sites), std::vector<uint32_t>(ev.n_sites),
+	    std::vector<ntsm_vcf_warning>(1 << 20) };               /* 16 MB: more warnings cost a second call */
 	uint64_t n_warn = 0;
 	ntsm_vcf_times tm {};
 	for (;;) {
-		const int rc = ntsm_vcf_run(opt.device, n_samples, opt.multi, n_used, geno.data(), stride, n_keys, key_off.data(), n_events,
-		    ev_ord.data(), ev_ls.data(), n_sites, site_off.data(), site_keys.data(), cells.data(), sums.data(), first_undef.data(),
-		    warn.data(), warn.size(), &n_warn, &tm);
-		if (rc == NTSM_VCF_E_CAPACITY) { warn.resize(n_warn); continue; }
+		const int rc = ntsm_vcf_run(opt.device, n_samples, opt.multi, ev.n_lines, ev.geno.data(), ev.g_stride, ev.n_keys, ev.key_off.data(),
+		    ev.n_events, ev.ev_ord.data(), ev.ev_ls.data(), ev.n_sites, ev.site_off.data(), ev.site_keys.data(), st.cells.data(),
+		    st.sums.data(), st.first_undef.data(), st.warn.data(), st.warn.size(), &n_warn, &tm);
+		if (rc == NTSM_VCF_E_CAPACITY) { st.warn.resize(n_warn); continue; }
 		if (rc) refuse("the HIP device step failed (" + std::to_string(rc) + ")");
 		break;
 	}
 	if (prof) fprintf(stderr, "[vcf] device: upload %.4f s, state kernel %.4f s, sum kernel %.4f s, download %.4f s, kernel bytes %llu, "
 	    "state launches %llu\n", tm.upload_ms / 1e3, tm.state_kernel_ms / 1e3, tm.sum_kernel_ms / 1e3, tm.download_ms / 1e3,
 	    (unsigned long long) tm.kernel_bytes, (unsigned long long) tm.state_launches);
-	lap("device step (total)");
-	warn.resize(n_warn);
+	st.warn.resize(n_warn);
+	return st;
+}
+
+/* the insert warnings in the one-thread order; under -v -v -v "Processing site" per line, its warnings after it */
+void print_warnings(const Opt &opt, const std::vector<Part> &parts, std::vector<ntsm_vcf_warning> &warn)
+{
 	std::sort(warn.begin(), warn.end(), [](const ntsm_vcf_warning &a, const ntsm_vcf_warning &b) {
 		return a.event != b.event ? a.event < b.event : a.sample < b.sample;
 	});
-	{
-		std::string text;
-		auto put = [&](const ntsm_vcf_warning &w) {             /* MultiCount.hpp:59-60 */
-			text += "Warning: Inconsistent k-mer counts, check for overlapping sites: ";
-			text += (char) (uint8_t) w.old;
-			text += " vs ";
-			text += std::to_string(w.value);
-			text += "\n";
-		};
-		if (opt.verbose > 2) {                                   /* "Processing site" per line, its warnings after it */
-			size_t wi = 0;
-			uint64_t ev_end = 0;
-			for (const Part &pt : parts)
-				for (size_t i = 0; i < pt.rs_id.size(); ++i) {
-					text += "Processing site: " + pt.rs_id[i] + "\n";
-					ev_end += pt.line_events[i];
-					for (; wi < warn.size() && warn[wi].event < ev_end; ++wi) put(warn[wi]);
-				}
-		} else {
-			for (const ntsm_vcf_warning &w : warn) put(w);
-		}
-		std::cerr << text << std::flush;
-	}
-	if (opt.pca.empty()) {
-		if (opt.verbose > 1) std::cerr << "Outputting counts" << std::endl;
+	std::string text;
+	auto put = [&](const ntsm_vcf_warning &w) {                 /* MultiCount.hpp:59-60 */
+		text += "Warning: Inconsistent k-mer counts, check for overlapping sites: ";
+		text += (char) (uint8_t) w.old;
+		text += " vs " + std::to_string(w.value) + "\n";
+	};
+	if (opt.verbose > 2) {
+		size_t wi = 0;
+		uint64_t ev_end = 0;
+		for (const Part &pt : parts)
+			for (size_t i = 0; i < pt.rs_id.size(); ++i) {
+				text += "Processing site: " + pt.rs_id[i] + "\n";
+				ev_end += pt.line_events[i];
+				for (; wi < warn.size() && warn[wi].event < ev_end; ++wi) put(warn[wi]);
+			}
 	} else {
-		if (opt.verbose > 1) {
-			std::cerr << "Outputting matrix and normalization values for PCA" << std::endl;
-			std::cerr << "Outputting matrix and normalization values for PCA" << std::endl;
-		}
-		/* printNormMatrix (:148-201) */
-		const std::string matrix_path = opt.pca + "_matrix.tsv", centre_path = opt.pca + "_center.txt";
-		uint64_t first_undef_cell = ~0ull;                       /* row-major: precision 19 from here on */
+		for (const ntsm_vcf_warning &w : warn) put(w);
+	}
+	std::cerr << text << std::flush;
+}
+
+/* printNormMatrix's text (MultiCount.hpp:148-201) from the device step's cells: the matrix writer and -R both read it here */
+struct MatrixText {
+	const uint32_t n_samples;
+	const uint16_t *const cells;
+	uint64_t first_undef_cell = ~0ull;               /* row-major; ~0: none */
+	std::vector<std::string> centre, tab[2];         /* per site; per form (6 / 19 digits) the text of every code that can occur */
+	MatrixText(const Opt &opt, const Step &st, uint32_t n) : n_samples(n), cells(st.cells.data()), centre(st.sums.size())
+	{
+		const size_t n_sites = st.sums.size();
 		for (size_t s = 0; s < n_sites && first_undef_cell == ~0ull; ++s)
-			if (first_undef[s] < n_samples) first_undef_cell = (uint64_t) s * n_samples + first_undef[s];
-		std::vector<std::string> centre(n_sites);
-		std::string ctext;
-		for (size_t s = 0; s < n_sites; ++s) {
-			centre[s] = centre_text(sums[s], n_samples);
-			ctext += centre[s];
-			ctext += "\n";
-		}
-		/* the cell text of every (maxREF, maxVAR) pair that can occur: bytes 0, (uint8_t) m, (uint8_t) 2m */
-		std::vector<std::string> tab[2];
+			if (st.first_undef[s] < n_samples) first_undef_cell = (uint64_t) s * n_samples + st.first_undef[s];
+		for (size_t s = 0; s < n_sites; ++s) centre[s] = centre_text(st.sums[s], n_samples);
 		tab[0].resize(65536);
 		tab[1].resize(65536);
-		const unsigned bv[3] = { 0u, opt.multi & 255u, (opt.multi * 2u) & 255u };
+		const unsigned bv[3] = { 0u, opt.multi & 255u, (opt.multi * 2u) & 255u };   /* the bytes 0, (uint8_t) m, (uint8_t) 2m */
 		for (unsigned r : bv)
 			for (unsigned v : bv)
 				if (r + v) { tab[0][r | v << 8] = cell_text(r, v, kShortDigits); tab[1][r | v << 8] = cell_text(r, v, kLongDigits); }
+	}
+	/* the text of cell (s, j): an undefined cell is its row's centre; the stream's precision is 19 after the first
+	 * undefined cell, 6 up to and including it */
+	void append_cell(std::string &o, size_t s, uint32_t j) const
+	{
+		const unsigned c = cells[s * n_samples + j];
+		if ((c & 255u) + (c >> 8) == 0) { o += centre[s]; return; }
+		const int long_form = (uint64_t) s * n_samples + j > first_undef_cell;
+		const std::string &x = tab[long_form][c];
+		if (!x.empty()) o += x;
+		else o += cell_text(c & 255u, c >> 8, long_form ? kLongDigits : kShortDigits);
+	}
+};
 
-		/* -R: the PCA, before anything is written (a refusal writes nothing).  The matrix it sees is the text's: a code's
-		 * value is what ntsmPCA reads back from the code's text, an undefined cell's from the row's centre text.  A code
-		 * outside the table cannot occur (the device step writes only those bytes); its value is NaN, which the eigen
-		 * step's rank test refuses */
-		std::vector<double> rot, comp;
-		const uint32_t dims = (uint32_t) opt.numComp;
-		if (opt.rotation) {
-			lap("cell and centre text");
-			std::vector<double> value(2 * 65536, std::numeric_limits<double>::quiet_NaN()), row_fill(n_sites), eigval(dims);
-			for (int form = 0; form < 2; ++form)
-				for (unsigned c = 1; c < 65536; ++c)
-					if (!tab[form][c].empty()) value[(size_t) form * 65536 + c] = text_value(tab[form][c]);
-			for (size_t s = 0; s < n_sites; ++s) row_fill[s] = text_value(centre[s]);
-			rot.resize((size_t) n_sites * dims);
-			comp.resize((size_t) n_samples * dims);
-			if (opt.verbose) std::cerr << "Matrix: " << n_sites << " sites x " << n_samples << " samples, " << dims << " components" << std::endl;
-			uint32_t bad = 0;
-			double expand_ms = 0.0;
-			ntsm_pca_times ptm;
-			memset(&ptm, 0, sizeof ptm);
-			const int rc = ntsm_pca_run_cells(opt.device, n_sites, n_samples, cells.data(), value.data(), row_fill.data(), first_undef_cell, dims,
-			    0, eigval.data(), rot.data(), comp.data(), &bad, &ptm, &expand_ms);
-			if (rc != 0) refuse(ntsm::pca_run_error(rc, bad, dims, opt.device));
-			if (opt.verbose || prof) ntsm::pca_print_times(stderr, ptm, &expand_ms);
-			lap("pca (total)");
-		}
+struct Rotation { std::vector<double> rot, comp; uint32_t dims; };
 
-		FILE *out = opt.no_matrix ? nullptr : fopen(matrix_path.c_str(), "wb");
-		FILE *cf = fopen(centre_path.c_str(), "wb");
-		if ((!out && !opt.no_matrix) || !cf) refuse("cannot write " + opt.pca + "_matrix.tsv / _center.txt");
-		if (out) fwrite(head.data(), 1, head.size(), out);
-		const size_t batch = std::max<size_t>(1, (size_t) (64u << 20) / ((size_t) n_samples * 8 + 64));   /* ~64 MB of text per thread */
-		std::vector<std::string> text(T);
-		for (size_t s0 = 0; out && s0 < n_sites; s0 += batch * T) {
-			on_threads(T, [&](unsigned t) {
-				std::string &o = text[t];
-				o.clear();
-				const size_t lo = std::min(n_sites, s0 + batch * t), hi = std::min(n_sites, s0 + batch * (t + 1));
-				for (size_t s = lo; s < hi; ++s) {
-					o += sites.ids[s];
-					const uint16_t *row = cells.data() + s * n_samples;
-					for (uint32_t j = 0; j < n_samples; ++j) {
-						o += '\t';
-						const unsigned c = row[j];
-						if ((c & 255u) + (c >> 8) == 0) { o += centre[s]; continue; }
-						const int hi19 = (uint64_t) s * n_samples + j > first_undef_cell;
-						const std::string &x = tab[hi19][c];
-						if (!x.empty()) o += x;
-						else o += cell_text(c & 255u, c >> 8, hi19 ? kLongDigits : kShortDigits);
-					}
-					o += '\n';
-				}
-			});
-			for (unsigned t = 0; t < T; ++t) fwrite(text[t].data(), 1, text[t].size(), out);
-		}
-		fwrite(ctext.data(), 1, ctext.size(), cf);
-		const bool ok = !out || fclose(out) == 0;
-		if (fclose(cf) != 0 || !ok) refuse("writing " + opt.pca + "_matrix.tsv / _center.txt failed");
-		lap("format + write");
+/* -R: the PCA, before anything is written (a refusal writes nothing) */
+Rotation run_rotation(const Opt &opt, const Step &st, const MatrixText &text, size_t n_sites, uint32_t n_samples, bool prof)
+{
+	const uint32_t dims = (uint32_t) opt.numComp;
+	Rotation r { std::vector<double>((size_t) n_sites * dims), std::vector<double>((size_t) n_samples * dims), dims };
+	/* the matrix the PCA sees is the text's: a code's value is what ntsmPCA reads back from the code's text, an undefined
+	 * cell's from the row's centre text.  A code outside the table cannot occur (the device step writes only those bytes);
+	 * its value is NaN, which the eigen step's rank test refuses */
+	std::vector<double> value(2 * 65536, std::numeric_limits<double>::quiet_NaN()), row_fill(n_sites), eigval(dims);
+	for (int form = 0; form < 2; ++form)
+		for (unsigned c = 1; c < 65536; ++c)
+			if (!text.tab[form][c].empty()) value[(size_t) form * 65536 + c] = text_value(text.tab[form][c]);
+	for (size_t s = 0; s < n_sites; ++s) row_fill[s] = text_value(text.centre[s]);
+	if (opt.verbose) std::cerr << "Matrix: " << n_sites << " sites x " << n_samples << " samples, " << dims << " components" << std::endl;
+	uint32_t bad = 0;
+	double expand_ms = 0.0;
+	ntsm_pca_times ptm {};
+	const int rc = ntsm_pca_run_cells(opt.device, n_sites, n_samples, st.cells.data(), value.data(), row_fill.data(), text.first_undef_cell,
+	    dims, 0, eigval.data(), r.rot.data(), r.comp.data(), &bad, &ptm, &expand_ms);
+	if (rc != 0) refuse(ntsm::pca_run_error(rc, bad, dims, opt.device));
+	if (opt.verbose || prof) ntsm::pca_print_times(stderr, ptm, &expand_ms);
+	return r;
+}
+
+/* printNormMatrix's two files (:148-201), both opened before either is written; the rows are formatted on T threads */
+void write_outputs(const Opt &opt, const std::string &head, const std::vector<std::string> &ids, const MatrixText &text, uint32_t n_samples)
+{
+	FILE *out = opt.no_matrix ? nullptr : fopen((opt.pca + "_matrix.tsv").c_str(), "wb");
+	FILE *cf = fopen((opt.pca + "_center.txt").c_str(), "wb");
+	if ((!out && !opt.no_matrix) || !cf) refuse("cannot write " + opt.pca + "_matrix.tsv / _center.txt");
+	if (out) fwrite(head.data(), 1, head.size(), out);
+	const unsigned T = opt.T;
+	const size_t n_sites = ids.size();
+	const size_t batch = std::max<size_t>(1, (size_t) (64u << 20) / ((size_t) n_samples * 8 + 64));   /* ~64 MB of text per thread */
+	std::vector<std::string> part(T);
+	for (size_t s0 = 0; out && s0 < n_sites; s0 += batch * T) {
+		on_threads(T, [&](unsigned t) {
+			std::string &o = part[t];
+			o.clear();
+			const size_t lo = std::min(n_sites, s0 + batch * t), hi = std::min(n_sites, s0 + batch * (t + 1));
+			for (size_t s = lo; s < hi; ++s) {
+				o += ids[s];
+				for (uint32_t j = 0; j < n_samples; ++j) { o += '\t'; text.append_cell(o, s, j); }
+				o += '\n';
+			}
+		});
+		for (unsigned t = 0; t < T; ++t) fwrite(part[t].data(), 1, part[t].size(), out);
+	}
+	std::string ctext;
+	for (const std::string &c : text.centre) { ctext += c; ctext += "\n"; }
+	fwrite(ctext.data(), 1, ctext.size(), cf);
+	const bool ok = !out || fclose(out) == 0;
+	if (fclose(cf) != 0 || !ok) refuse("writing " + opt.pca + "_matrix.tsv / _center.txt failed");
+}
+
+} // namespace
+
+/* The order is the contract: every refusal of the inputs before the device, nothing written before -R's PCA has succeeded */
+int main(int argc, char **argv)
+{
+	const Opt opt = read_options(argc, argv);
+	ntsm::LapTimer timer { "[vcf]", getenv("NTSM_VCF_PROF") != nullptr };   /* phase times on stderr (tools/vcf_bench.py) */
+	const ntsm::SiteSet sites = load_sites(opt);
+	timer.lap("sites");
+	const Genome genome = load_genome(opt);
+	timer.lap("genome");
+	if (opt.verbose > 1) std::cerr << "Reading VCF file: " << opt.inputs[0] << std::endl;
+	ntsm::FileBytes vcf;                         /* a directory reads as an empty VCF */
+	if (!vcf.load(opt.inputs[0], opt.T, ntsm::FileBytes::kDirectoryIsEmpty)) refuse("cannot read the VCF file " + opt.inputs[0]);
+	const Header header = read_header(vcf);
+	const uint32_t n_samples = (uint32_t) header.samples.size(), stride = (n_samples + 15) / 16 * 16;
+	if (opt.verbose > 1) std::cerr << "Starting multicount of each rsID for " << n_samples << " samples." << std::endl;
+	const KeyTable table(sites.keys);
+	std::vector<Part> parts = parse_body(Ctx { opt, genome, table, n_samples, stride }, header, opt.T);
+	timer.lap("parse");
+	const Events events = build_events(parts, sites, stride);
+	timer.lap("events");
+	const PcaNames names = opt.rotation ? rotation_shape_check(opt, header.matrix_head, sites, n_samples) : PcaNames();
+	Step step = device_step(opt, events, n_samples, timer.on);
+	timer.lap("device step (total)");
+	print_warnings(opt, parts, step.warn);
+	if (opt.pca.empty()) {
+		if (opt.verbose > 1) std::cerr << "Outputting counts" << std::endl;
+	} else {
+		for (int i = 0; i < 2 && opt.verbose > 1; ++i) std::cerr << "Outputting matrix and normalization values for PCA" << std::endl;
+		const MatrixText text(opt, step, n_samples);
+		Rotation rotation {};
 		if (opt.rotation) {
-			const std::string bad_path = ntsm::write_pca_tables(opt.pca, pca_sites, pca_samples, rot.data(), comp.data(), dims, T);
+			timer.lap("cell and centre text");
+			rotation = run_rotation(opt, step, text, sites.ids.size(), n_samples, timer.on);
+			timer.lap("pca (total)");
+		}
+		write_outputs(opt, header.matrix_head, sites.ids, text, n_samples);
+		timer.lap("format + write");
+		if (opt.rotation) {
+			const std::string bad_path = ntsm::write_pca_tables(opt.pca, names.sites, names.samples, rotation.rot.data(), rotation.comp.data(),
+			    rotation.dims, opt.T);
 			if (!bad_path.empty()) refuse("cannot write " + bad_path);
-			lap("rotation + components write");
+			timer.lap("rotation + components write");
 		}
 	}
-	std::cerr << "Time: " << seconds_since(t_start) << " s Memory: " << rss_kbytes() << " kbytes" << std::endl;
+	std::cerr << "Time: " << timer.total() << " s Memory: " << rss_kbytes() << " kbytes" << std::endl;
 	return 0;
 }

@@ -2,7 +2,7 @@
  * pca_text.hpp -- the text side of the PCA that ntsmPCA (ntsm_pca_main.cpp) and `ntsmVCF --rotation` (ntsm_vcf_main.cpp)
  * share, so that the two routes cannot drift apart: how a matrix cell's text becomes a double, how the header line
  * becomes the sample names, what is refused and in which words, and how the rotation and the components are written.
- * Header only; the arithmetic is in libntsm_pca_hip.so (include/ntsm_pca_hip.h).
+ * Header only; the arithmetic is in libntsm_pca_hip.so (include/ntsm_pca_hip.h); on_threads comes from cli.hpp.
  */
 #ifndef NTSM_PCA_TEXT_HPP
 #define NTSM_PCA_TEXT_HPP
@@ -15,10 +15,10 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../../include/ntsm_pca_hip.h"
+#include "cli.hpp"
 
 namespace ntsm {
 
@@ -135,14 +135,6 @@ inline size_t format_repr(double x, char *out)
 		o += snprintf(o, 8, "%02d", std::abs(e10));
 	}
 	return (size_t) (o - out);
-}
-
-template <class F> void on_threads(unsigned n, F f)
-{
-	std::vector<std::thread> pool;
-	for (unsigned t = 1; t < n; ++t) pool.emplace_back(f, t);
-	f(0u);
-	for (auto &th : pool) th.join();
 }
 
 /* header + one line per name with d values, formatted on T threads in row order */

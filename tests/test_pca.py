@@ -193,6 +193,20 @@ def test_refusals(built, tmp_path, name, args, msg):
     assert p.stdout == b"" and sorted(os.listdir(str(tmp_path))) == before
 
 
+def test_bad_cell_in_a_last_line_without_newline_names_its_line_for_every_t(built, tmp_path):
+    """6 sites x 4 samples, no '\\n' after the last line, a bad cell in it: line 7, whether one thread reads the whole body or
+    16 threads are cut more ranges than there are lines (the refusal comes before the device: every device is hidden)."""
+    rows = ["rs%d\t0\t0.5\t1\t0.25" % k for k in range(5)] + ["rs5\t0\t0.5\tbad\t0.25"]
+    with open(str(tmp_path / "m.tsv"), "w", newline="") as f:
+        f.write("alleleID\tA\tB\tC\tD\n" + "\n".join(rows))
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1")
+    for t in ("1", "16"):
+        p = subprocess.run([PCA, "-m", "m.tsv", "-n", "2", "-t", t, "-p", "out"], cwd=str(tmp_path), capture_output=True, env=env, timeout=120)
+        assert p.returncode == 1 and p.stdout == b"", t
+        assert p.stderr == b"Error: line 7 of m.tsv (rs5): the cell of sample 3 is not a finite number: 'bad'\n", (t, p.stderr)
+    assert sorted(os.listdir(str(tmp_path))) == ["m.tsv"]
+
+
 def test_flag_errors(built, tmp_path):
     """Flag errors in ntsmVCF's style: the message, then "Try '--help' for more information.", exit status 1; --help and
     --version exit with 0; the long names are the upstream script's."""
@@ -443,6 +457,26 @@ def test_same_bytes_every_run_every_t_and_from_gzip(cohort_run):
         p = run_pca(args + ["-p", prefix], tmp)
         assert p.returncode == 0, p.stderr[-500:]
         assert [open(f, "rb").read() for f in outputs(tmp, prefix)] == want, prefix
+
+
+@pytest.mark.gpu
+def test_crlf_matrix_without_final_newline_gives_the_same_files_for_every_t(built, tmp_path):
+    """6 sites x 4 samples, CRLF line ends, no line end after the last row: -n 2 writes the same two files under -t 1,
+    -t 4 and -t 16 (more ranges than lines), and they hold 6 and 4 rows of 2 finite values"""
+    a = structured_cohort(5, 4, 6, 2, thirds=0.3)
+    data = open(write_matrix(str(tmp_path / "lf.tsv"), a), "rb").read()
+    with open(str(tmp_path / "m.tsv"), "wb") as f:
+        f.write(data[:-1].replace(b"\n", b"\r\n"))
+    outs = []
+    for t in ("1", "4", "16"):
+        p = run_pca(["-m", "m.tsv", "-n", "2", "-t", t, "-p", "t" + t], tmp_path)
+        assert p.returncode == 0, p.stderr[-500:]
+        outs.append([open(f, "rb").read() for f in outputs(tmp_path, "t" + t)])
+    assert outs[0] == outs[1] == outs[2]
+    names, v, _ = read_table(outputs(tmp_path, "t1")[0])
+    assert names == ["rs%d" % k for k in range(6)] and v.shape == (6, 2) and np.isfinite(v).all()
+    names, c, _ = read_table(outputs(tmp_path, "t1")[1])
+    assert len(names) == 4 and c.shape == (4, 2) and np.isfinite(c).all() and b"\r" not in outs[0][0] + outs[0][1]
 
 
 @pytest.mark.gpu

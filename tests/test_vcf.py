@@ -4,13 +4,15 @@ ntsm_amd/csrc/ntsm_vcf.hip, ntsm_amd/vcf.py).
 The contract is one thread of the reference with the sample x k-mer matrix sized for the header's samples.  The
 fixtures under tests/golden/vcf/ were recorded from the reference classes with only that change (README there);
 tests/vcf_restatement.cpp is an independent restatement written from the reference text.  CPU: the restatement
-reproduces every fixture, and the CLI's refusals and flag errors.  GPU: the CLI against the fixtures and against the
+reproduces every fixture, the CLI's refusals and flag errors, and the whole program -- ntsm_vcf_main.cpp built against
+tests/vcf_step_standin.cpp, a plain C++ ntsm_vcf_run, under ASan + UBSan -- against the fixtures and the restatement.  GPU: the CLI against the fixtures and against the
 restatement on seeded cohorts, -t 1 against -t 16, gzip / BGZF input, the device step against a numpy model (also on
 cohorts past 1,024 and 4,096 samples, where the state kernel widens its workgroup and then loops a lane over chunks),
 and the chain into ntsmEval -p / -n."""
 import gzip
 import json
 import os
+import re
 import struct
 import subprocess
 import sys
@@ -217,6 +219,123 @@ def test_flag_errors(built, tmp_path):
     assert p.returncode == 1 and p.stderr == ("file %s cannot be opened\n" % (tmp_path / "none.fa")).encode()
     p = subprocess.run([VCF, "-h"], capture_output=True)
     assert p.returncode == 0 and p.stderr.startswith(b"Usage: ntsmVCF -s [FASTA] -r [FASTA] [VCF]\n")
+
+
+# ------------------------------------------------------------------------------ the whole program on the CPU
+@pytest.fixture(scope="module")
+def cpu_program(tmp_path_factory):
+    """ntsm_vcf_main.cpp + the Makefile's $(VCFSRC) + tests/vcf_step_standin.cpp (ntsm_vcf_run in plain C++, written from
+    include/ntsm_vcf_hip.h) as a program of its own under ASan + UBSan: it is run directly, nothing is preloaded."""
+    mk = open(os.path.join(ROOT, "Makefile")).read()
+    vcfsrc = re.search(r"^VCFSRC := ((?:.*\\\n)*.*)$", mk, re.M).group(1).replace("\\\n", " ").split()
+    host = os.path.join(ROOT, "ntsm_amd", "csrc", "host")
+    src = [os.path.join(host, "ntsm_vcf_main.cpp")] + [f.replace("$(HOST)", host) for f in vcfsrc]
+    assert len(src) > 5 and all(os.path.exists(f) for f in src), src
+    exe = str(tmp_path_factory.mktemp("vcpu") / "ntsmVCF_cpu")
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-ffp-contract=off",
+                    "-o", exe] + src + [os.path.join(ROOT, "tests", "vcf_step_standin.cpp"), "-lz", "-pthread"], check=True)
+    return exe
+
+
+def run_cpu(exe, args, cwd, prefix):
+    """run(), and no sanitizer report on stderr"""
+    out = run(exe, args, cwd, prefix)
+    assert b"Sanitizer" not in out[3] and b"runtime error" not in out[3], out[3][-3000:].decode(errors="replace")
+    return out
+
+
+def test_cpu_program_gives_the_fixtures(cpu_program, tmp_path):
+    for case in CASES:
+        d = os.path.join(GOLD, case["name"])
+        prefix = str(tmp_path / case["name"])
+        rc, mat, cen, err = run_cpu(cpu_program, ["-s", "sites.fa", "-r", "genome.fa"] + case["args"] + ["-p", prefix, "in.vcf"], d, prefix)
+        assert rc == 0, (case, err)
+        assert mat == open(os.path.join(d, "expected_matrix.tsv"), "rb").read(), case
+        assert cen == open(os.path.join(d, "expected_center.txt"), "rb").read(), case
+        assert err == open(os.path.join(d, "expected_stderr.txt"), "rb").read(), case
+
+
+@pytest.mark.parametrize("n_samples,n_snps,seed", [(7, 60, 46), (33, 120, 32)], ids=["7x60", "33x120"])
+def test_cpu_program_matches_restatement_for_every_t(cpu_program, restatement, tmp_path, n_samples, n_snps, seed):
+    """Dense seeded cohorts (33 samples cross the 16- and 32-byte genotype stride) under -t 1, -t 5 and -t 64 -- more
+    threads than the first cohort has body lines: matrix, centre file and stderr byte for byte against the restatement."""
+    g, s, v = cohort(tmp_path, np.random.default_rng(seed), n_samples, n_snps)
+    b = str(tmp_path / "rs")
+    p = subprocess.run([restatement, "-s", s, "-r", g, "-d", "-p", b, v], capture_output=True, check=True)
+    want = (0, open(b + "_matrix.tsv", "rb").read(), open(b + "_center.txt", "rb").read(), p.stderr)
+    assert b"Inconsistent k-mer counts" in p.stderr and want[1].count(b"\n") == n_snps + 1
+    if n_snps == 60:
+        assert open(v, "rb").read().count(b"\n") - 2 < 64                         # this seed: 58 body lines
+    for t in ("1", "5", "64"):
+        a = str(tmp_path / ("t" + t))
+        assert run_cpu(cpu_program, ["-s", s, "-r", g, "-d", "-t", t, "-p", a, v], str(tmp_path), a) == want, t
+
+
+def test_cpu_program_threads_give_identical_verbose_stderr(cpu_program, tmp_path):
+    """-v -v -v interleaves "Processing site" with the warnings of its line: the same stderr for -t 1 and -t 5"""
+    g, s, v = cohort(tmp_path, np.random.default_rng(33), 7, 60)
+    outs = []
+    for t in ("1", "5"):
+        prefix = str(tmp_path / ("t" + t))
+        outs.append(run_cpu(cpu_program, ["-s", s, "-r", g, "-d", "-t", t, "-p", prefix, "-v", "-v", "-v", v], str(tmp_path), prefix))
+    assert outs[0][0] == 0 and outs[0] == outs[1]
+    assert b"Processing site: " in outs[0][3] and b"Inconsistent k-mer counts" in outs[0][3]
+
+
+def test_cpu_program_calls_again_when_the_warnings_need_more_room(cpu_program, monkeypatch, tmp_path):
+    """The stand-in's first call has room for 3 warnings (NTSM_STANDIN_FIRST_CAP): the program takes NTSM_VCF_E_CAPACITY,
+    makes the room the call asked for and calls again; files and stderr are those of the run with room from the start."""
+    g, s, v = cohort(tmp_path, np.random.default_rng(33), 7, 60)
+    a, b = str(tmp_path / "plain"), str(tmp_path / "again")
+    want = run_cpu(cpu_program, ["-s", s, "-r", g, "-d", "-t", "5", "-p", a, v], str(tmp_path), a)
+    assert want[0] == 0 and want[3].count(b"Inconsistent k-mer counts") > 3
+    monkeypatch.setenv("NTSM_STANDIN_FIRST_CAP", "3")
+    assert run_cpu(cpu_program, ["-s", s, "-r", g, "-d", "-t", "5", "-p", b, v], str(tmp_path), b) == want
+
+
+def test_cpu_program_names_the_line_of_a_refusal_for_every_t(cpu_program, tmp_path):
+    """A bad POS in the last body line: the message names that line of the file, under -t 1 and -t 5"""
+    g, s, v = cohort(tmp_path, np.random.default_rng(34), 7, 60)
+    with open(v, "a") as f:
+        f.write("c0\tabc\trsX\tA\tC\t.\tPASS\t.\tGT" + "\t0|1" * 7 + "\n")
+    n_lines = open(v, "rb").read().count(b"\n")
+    for t in ("1", "5"):
+        prefix = str(tmp_path / ("t" + t))
+        rc, mat, cen, err = run_cpu(cpu_program, ["-s", s, "-r", g, "-d", "-t", t, "-p", prefix, v], str(tmp_path), prefix)
+        assert rc == 1 and mat is None and cen is None
+        assert err.splitlines()[-1] == ("Error: line %d of the VCF: POS 'abc' is not an int" % n_lines).encode(), (t, err)
+
+
+def test_cpu_program_prints_19_digits_only_after_the_first_undefined_cell(cpu_program, restatement, tmp_path):
+    """Three sites, two samples; the site in the middle has no VCF line, so its row is undefined.  Sample 2 of the sites
+    around it is hom2 in one line and het in a second one (REF m, VAR 2m: 1/3).  The cell right before the first
+    undefined cell is printed with the stream's 6 digits, the same value after it with 19 -- for -t 1 and -t 5."""
+    chrom = "".join(np.random.default_rng(36).choice(list("ACGT"), size=400))
+    sites = [site_of(chrom, pos, rs="rs%d" % pos) for pos in (100, 200, 300)]
+    lines = [["chr1", str(pos), "rs%d" % pos, chrom[pos - 1], ALT[chrom[pos - 1]], ".", "PASS", ".", "GT", "0|0", gt]
+             for pos in (100, 300) for gt in ("1|1", "0|1")]
+    g, s, v = write_case(tmp_path, [("chr1", chrom)], sites, ["S0", "S1"], lines)
+    b = str(tmp_path / "rs")
+    p = subprocess.run([restatement, "-s", s, "-r", g, "-p", b, v], capture_output=True, check=True)
+    want = (0, open(b + "_matrix.tsv", "rb").read(), open(b + "_center.txt", "rb").read(), p.stderr)
+    rows = want[1].split(b"\n")
+    assert rows[1] == b"rs100\t1\t0.333333" and rows[3] == b"rs300\t1\t0.3333333333333333148" and rows[2].startswith(b"rs200\t")
+    for t in ("1", "5"):
+        a = str(tmp_path / ("t" + t))
+        assert run_cpu(cpu_program, ["-s", s, "-r", g, "-t", t, "-p", a, v], str(tmp_path), a) == want, t
+
+
+def test_cpu_program_reads_a_directory_as_an_empty_vcf(cpu_program, tmp_path):
+    """A directory given as the VCF: the exit status and the bytes of the same command on an empty file"""
+    g, s, _ = cohort(tmp_path, np.random.default_rng(35), 7, 60)
+    empty, folder = str(tmp_path / "empty.vcf"), str(tmp_path / "folder.vcf")
+    open(empty, "wb").close()
+    os.mkdir(folder)
+    outs = []
+    for name, v in (("e", empty), ("f", folder)):
+        prefix = str(tmp_path / name)
+        outs.append(run_cpu(cpu_program, ["-s", s, "-r", g, "-d", "-t", "5", "-p", prefix, v], str(tmp_path), prefix))
+    assert outs[0] == outs[1] and outs[0][0] == 0 and outs[0][1].startswith(b"alleleID\n")
 
 
 # ---------------------------------------------------------------------------------------------------- GPU

@@ -11,7 +11,9 @@
  * score = skew(-2 * (joint - (single1 + single2)), cov1, cov2) / n_valid  (:611-615, :1081-1083), relatedness and
  * homConcord (:1190-1194) and prints (resultsStr, :843-905) -- ntsm_amd/csrc/host/ntsm_eval_main.cpp does.
  * The sums are accumulated in site order with IEEE double operations and no contraction, i.e. bit for bit what one
- * thread of the reference computes.  Parity with the reference itself is UNPINNED.
+ * thread of the reference computes.  Pinned to the reference itself: the CLI's stdout equals, byte for byte, that of
+ * oracle/_ref/ref_ntsmEval -- the unmodified src/CompareCounts.hpp behind oracle/ref_eval_driver.cpp -- and its recordings
+ * under tests/golden/eval/ (tests/test_eval_reference.py).
  */
 #ifndef NTSM_EVAL_HIP_H
 #define NTSM_EVAL_HIP_H

@@ -5,8 +5,9 @@
  * GPU unless -p asks for its PC columns; -e FILE writes the merged counts (mergeCounts, :626-674), -o skips the analysis.
  * -p ROT -n NORM is the PCA-guided search (projectPCs, :116-211, computeScorePCA, :285-398): projection, candidate pairs
  * and their scoring in the library's session calls, printed in the one-thread order.  Not built: -b (the debug
- * ground-truth mode) and -p without a normalization file (the reference dies in an assert); both are refused.  Parity with
- * the reference is unpinned: the reference's scoring class cannot be compiled in this image.
+ * ground-truth mode) and -p without a normalization file (the reference dies in an assert); both are refused.  Pinned to
+ * the reference: stdout equals, byte for byte, that of the unmodified scoring class (oracle/ref_eval_driver.cpp ->
+ * oracle/_ref/ref_ntsmEval -t 1) and its recordings, tests/test_eval_reference.py.
  */
 #include <getopt.h>
 
@@ -104,7 +105,7 @@ void load(Counts &c)
 			const auto cnt = loadPair(ss, item);
 			c.counts[(i * m + s) * 2] = cnt.first;
 			c.counts[(i * m + s) * 2 + 1] = cnt.second;
-			c.total[i] += (uint64_t) cnt.first + cnt.second;
+			c.total[i] += cnt.first + cnt.second;                  /* :104-106 unsigned + unsigned: wraps at 2^32, then widens */
 			const auto sm = loadPair(ss, item);
 			c.sums[(i * m + s) * 2] = sm.first;
 			c.sums[(i * m + s) * 2 + 1] = sm.second;

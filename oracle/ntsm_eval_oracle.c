@@ -5,14 +5,12 @@
  * reading counts files, the per-sample genotype summary and error rate, and for every pair of samples
  * the log-likelihood score, the relatedness tallies and the result line.
  *
- * PARITY UNPINNED.  The reference class (src/CompareCounts.hpp) cannot be compiled in this image:
- * its line 19 includes vendor/kfunc.c, whose line 28 includes the autoconf-generated config.h, and the
- * reference ships neither that file, nor tests, nor recorded outputs for this path.  What is here follows
- * the reference text function by function (file:line cited at each), in the same order of floating-point
- * operations (sequential double sums over the sites in file order, no contraction), but it has never been
- * compared with the reference's own output -- except for the genotype tallies and the two ratios derived from them,
- * which tests/test_eval.py checks against the six example rows of the reference's README (README.md:143-150); the
- * log-likelihood score has no such anchor.
+ * PARITY PIN: the unmodified reference class (src/CompareCounts.hpp) compiled in place behind oracle/ref_eval_driver.cpp
+ * (oracle/_ref/ref_ntsmEval) and its recordings under tests/golden/eval/: tests/test_eval_reference.py requires the printer
+ * here to reproduce its stdout and its merge file byte for byte.  What is here follows the reference text function by
+ * function (file:line cited at each), in the same order of floating-point operations (sequential double sums over the
+ * sites in file order, no contraction).  tests/test_eval.py also checks the genotype tallies and the two ratios derived from
+ * them against the six example rows of the reference's README (README.md:143-150).
  *
  * Covered: CompareCounts::CompareCounts (:30-114), computeScoreSingle (:541-585, without PCA columns),
  * computeScore (:591-624, one thread: pairs in i < j order), calcHomHetMiss (:742-767), loadPair (:934-940),
@@ -199,7 +197,7 @@ ntsm_eval_oracle *ntsm_eval_oracle_load(const char *const *files, unsigned n_fil
 					const char *nf; size_t nn;
 					next_field(&q, end, &f, &n);
 					if (load_pair(&q, end, f, n, &c[0], &c[1], &nf, &nn)) { free(buf); ntsm_eval_oracle_free(e); return NULL; }
-					e->total[i] += (uint64_t) c[0] + c[1];
+					e->total[i] += c[0] + c[1];                         /* :104-106 unsigned + unsigned wraps, then widens */
 					if (load_pair(&q, end, nf, nn, &m[0], &m[1], &nf, &nn)) { free(buf); ntsm_eval_oracle_free(e); return NULL; }
 				}
 			}

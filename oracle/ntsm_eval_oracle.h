@@ -1,6 +1,6 @@
 /*
  * oracle/ntsm_eval_oracle.h -- TEST INFRASTRUCTURE ONLY: CPU restatement of ntsmEval's all-pairs scoring
- * (src/CompareCounts.hpp).  PARITY UNPINNED: see ntsm_eval_oracle.c.  Only tests/ may use it.
+ * (src/CompareCounts.hpp).  Pinned to the unmodified class (oracle/_ref/ref_ntsmEval): see ntsm_eval_oracle.c.  Only tests/ may use it.
  */
 #ifndef NTSM_EVAL_ORACLE_H
 #define NTSM_EVAL_ORACLE_H

@@ -1,8 +1,8 @@
 // tests/eval_pca_restatement.cpp -- TEST INFRASTRUCTURE: an independent CPU restatement of ntsmEval's PCA-guided search,
 // written from the reference text (src/CompareCounts.hpp:116-211 projectPCs, :285-398 computeScorePCA, :926-932
-// calcDistance; vendor/nanoflann.hpp:452-486 L2_Adaptor::evalMetric, :305-307 RadiusResultSet::addPoint).  PARITY WITH THE
-// REFERENCE IS UNPINNED: what it pins is the HIP path (include/ntsm_eval_hip.h) against the same
-// statement of the arithmetic.  Built by tests/test_eval_pca.py with g++ -O2 -std=c++11 -ffp-contract=off on x86-64, so
+// calcDistance; vendor/nanoflann.hpp:452-486 L2_Adaptor::evalMetric, :305-307 RadiusResultSet::addPoint).  It pins the HIP path
+// (include/ntsm_eval_hip.h) against the same statement of the arithmetic, and is itself held to the unmodified reference
+// class (oracle/_ref/ref_ntsmEval -p -n, tests/test_eval_reference.py).  Built by tests/test_eval_pca.py with g++ -O2 -std=c++11 -ffp-contract=off on x86-64, so
 // long double is the x87 format, as in the reference's build.
 //
 //   project COUNTS.bin N M MIN_COV NORM.txt ROT.tsv DIM CLOUD.out NORM.out ROT.out

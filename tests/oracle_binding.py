@@ -145,7 +145,7 @@ class OracleFP:
             pass
 
 
-# ---- ntsmEval all-pairs scoring (oracle/ntsm_eval_oracle.c; parity with the reference unpinned) ---------------
+# ---- ntsmEval all-pairs scoring (oracle/ntsm_eval_oracle.c; pinned in tests/test_eval_reference.py) ---------------
 _elib = None
 
 

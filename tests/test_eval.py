@@ -1,10 +1,11 @@
 """ntsmEval all-pairs scoring: oracle/ntsm_eval_oracle.c, include/ntsm_eval_hip.h,
 build/ntsmEval.
 
-PARITY WITH THE REFERENCE IS UNPINNED: src/CompareCounts.hpp cannot be compiled in this image (it includes
-vendor/kfunc.c, which needs autoconf's config.h) and the reference holds no fixtures for this path.  What these tests
-pin is (CPU) the oracle against an independent statement of the formulas written here from the reference text and
-against hand-checkable cases, and (GPU) the HIP library and the CLI against the oracle, bit for bit: every record of
+PARITY WITH THE REFERENCE is pinned in tests/test_eval_reference.py: the oracle's printer and build/ntsmEval against
+oracle/_ref/ref_ntsmEval (the unmodified src/CompareCounts.hpp behind oracle/ref_eval_driver.cpp) and its recordings
+under tests/golden/eval/, stdout byte for byte.  The oracle stays the per-record, per-field checker.  What the tests of
+this file pin is (CPU) the oracle against an independent statement of the formulas written here from the reference text
+and against hand-checkable cases, and (GPU) the HIP library and the CLI against the oracle, bit for bit: every record of
 all pairs (not samples of them) against vec_pairs, a numpy model of all pairs that a CPU test pins to that statement
 and to the oracle, also on cohorts past 1,024 samples, where the pair kernel runs 256-thread workgroups."""
 import math
@@ -239,7 +240,8 @@ def test_eval_library_exports_and_cli_without_gpu(tmp_path):
     lib = ctypes.CDLL(os.path.join(ROOT, "ntsm_amd", "libntsm_eval_hip.so"))
     assert hasattr(lib, "ntsm_eval_pairs")
     hdr = open(os.path.join(ROOT, "include", "ntsm_eval_hip.h")).read()
-    assert "int ntsm_eval_pairs(" in hdr and "PARITY" not in hdr or "UNPINNED" in hdr
+    assert "int ntsm_eval_pairs(" in hdr and "UNPINNED" not in hdr
+    assert "oracle/_ref/ref_ntsmEval" in hdr and "tests/test_eval_reference.py" in hdr      # what the library is pinned to, and where
 
     def run(*args):
         return subprocess.run([EVAL] + list(args), capture_output=True)

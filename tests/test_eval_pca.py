@@ -1,8 +1,9 @@
 """ntsmEval's PCA-guided pair search (-p / -n): ntsm_amd/csrc/xprec.h, the session calls of include/ntsm_eval_hip.h
 (ntsm_eval_project, ntsm_eval_candidates, ntsm_eval_score_pairs) and build/ntsmEval -p.
 
-PARITY WITH THE REFERENCE IS UNPINNED, as for the all-pairs path (tests/test_eval.py): the reference's CompareCounts.hpp
-cannot be compiled in this image.  What these tests pin is (CPU) the integer x87 add against the x87 itself, and the
+PARITY WITH THE REFERENCE is pinned in tests/test_eval_reference.py, as for the all-pairs path: expected_text below and
+build/ntsmEval -p against projectPCs + computeScorePCA of the unmodified CompareCounts.hpp (oracle/_ref/ref_ntsmEval) and
+its recordings, byte for byte.  What the tests of this file pin is (CPU) the integer x87 add against the x87 itself, and the
 CLI's refusals and flag errors; (GPU) the projection and the candidate list against tests/eval_pca_restatement.cpp, an
 independent restatement written from the reference text and compiled here with real long double, the listed-pair scoring
 against ntsm_eval_pairs, and the CLI's stdout against text assembled from the restatement and the all-pairs oracle

@@ -88,6 +88,33 @@ int ntsm_eval_candidates(ntsm_eval_session *h, const double *cloud, uint32_t dim
 int ntsm_eval_score_pairs(ntsm_eval_session *h, const uint32_t *pi, const uint32_t *pk, uint64_t n_pairs, ntsm_eval_record *out,
 		double *kernel_ms);
 
+/* ---- Queries against a cohort (ntsmEval --against STORE; ntsm_amd/csrc/ntsm_eval_cross.hip): the n_q x n_db rectangle of
+ * pairs (query, database sample), tiled like the all-pairs kernel -- database samples across the lanes, a group of queries
+ * wave-uniform -- with the database walked in chunks, so a cohort store mapped from disk (ntsm_amd/csrc/host/eval_store.hpp)
+ * is passed as it lies and never has to fit on the device at once.  The arithmetic is ntsm_eval_score.h's. */
+typedef struct ntsm_eval_cross_times {   /* milliseconds */
+	double upload_ms, prepare_kernel_ms, cross_kernel_ms, download_ms;   /* summed over the chunks; prepare includes the tallies */
+	uint32_t chunks;
+} ntsm_eval_cross_times;
+
+/* q_counts: host [n_q][n_sites][2].
+ * db_counts: host; sample d at (const char *) db_counts + d * db_stride_bytes, [n_sites][2] each.
+ *   db_stride_bytes >= 8 * n_sites and a multiple of 4, so a mapped store is passed as it lies.
+ * db_chunk: database samples per pass; 0 = the library's choice (as many as fit in half of the device's free memory).
+ *   Device memory is O((n_q + chunk) * n_sites + n_q * chunk), never O(n_db * n_sites).
+ * out: [n_q][n_db].  out[q * n_db + d] is, bit for bit, the record ntsm_eval_pairs gives for pair (q, n_q + d)
+ *   of the concatenation [queries; database] -- the query is sample 1.
+ * db_geno (may be NULL): [n_db][3] = hets, homs, miss of each database sample at min_cov (calcHomHetMiss, :742-767).
+ * times (may be NULL).
+ * Returns 0, -1 bad argument, -2 HIP error.  n_q == 0, n_db == 0 or n_sites == 0: zeroed outputs, no device work. */
+int ntsm_eval_cross(int device, const uint32_t *q_counts, uint32_t n_q, const void *db_counts, uint64_t db_stride_bytes,
+		uint32_t n_db, uint32_t n_sites, uint32_t min_cov, uint32_t db_chunk,
+		ntsm_eval_record *out, uint32_t *db_geno, ntsm_eval_cross_times *times);
+
+/* For measurements only (tools/eval_store_bench.py): force the cross kernel's workgroup width (64 or 256) and query group
+ * size (1, 2 or 4) of later calls in this process; 0 = the library's rule.  Returns 0, -1 for another value. */
+int ntsm_eval_cross_tune(uint32_t width, uint32_t query_group);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,9 @@
  * (include/ntsm_eval_hip.h).  A single input file prints the QC table (computeScoreSingle, :541-585) without touching the
  * GPU unless -p asks for its PC columns; -e FILE writes the merged counts (mergeCounts, :626-674), -o skips the analysis.
  * -p ROT -n NORM is the PCA-guided search (projectPCs, :116-211, computeScorePCA, :285-398): projection, candidate pairs
- * and their scoring in the library's session calls, printed in the one-thread order.  Not built: -b (the debug
+ * and their scoring in the library's session calls, printed in the one-thread order.  This build only: --pack STORE FILES...
+ * writes or extends a cohort store (eval_store.hpp, no GPU), --against STORE FILES... scores the files against the store's
+ * samples (ntsm_eval_cross) and against each other and prints computeScore's rows for them.  Not built: -b (the debug
  * ground-truth mode) and -p without a normalization file (the reference dies in an assert); both are refused.  Pinned to
  * the reference: stdout equals, byte for byte, that of the unmodified scoring class (oracle/ref_eval_driver.cpp ->
  * oracle/_ref/ref_ntsmEval -t 1) and its recordings, tests/test_eval_reference.py.
@@ -25,6 +27,7 @@
 
 #include "../../../include/ntsm_eval_hip.h"
 #include "cli.hpp"
+#include "eval_store.hpp"
 
 #define PROGRAM "ntsmEval"
 
@@ -37,6 +40,7 @@ struct Opt {                                 /* src/Options.h:44-55 */
 	uint64_t genomeSize = 6200000000ull;
 	int verbose = 0, device = 0;
 	std::string pca, merge, norm, debug;
+	std::string pack, against;               /* --pack STORE, --against STORE (this build only) */
 	bool onlyMerge = false;
 	unsigned dim = 20;                       /* src/Options.h:22, 35-39: the PCA search */
 	double pcSearchRadius1 = 2, pcSearchRadius2 = 15, pcErrorThresh = 0.01, pcMissSite1 = 0.01, pcMissSite2 = 0.3;
@@ -51,36 +55,12 @@ struct Counts {                              /* the members of CompareCounts the
 	size_t nSites() const { return locus.size(); }
 };
 
-/* src/CompareCounts.hpp:934-940 */
-std::pair<unsigned, unsigned> loadPair(std::stringstream &ss, std::string &item)
+/* src/CompareCounts.hpp:30-114: the first file fixes loci and distinct counts, then every file fills its row.  Under
+ * --against the store has fixed them (c.locus, c.distinct and `index` come filled) and a locus it lacks is a refusal.  The
+ * reading of one file is eval_store.hpp's, shared with --pack. */
+void load(Counts &c, ntsm::eval_store::LocusIndex index = {}, bool fromStore = false)
 {
-	const unsigned a = (unsigned) std::stoul(item);
-	std::getline(ss, item, '\t');
-	const unsigned b = (unsigned) std::stoul(item);
-	std::getline(ss, item, '\t');
-	return std::make_pair(a, b);
-}
-
-/* src/CompareCounts.hpp:30-114: the first file fixes loci and distinct counts, then every file fills its row */
-void load(Counts &c)
-{
-	std::unordered_map<std::string, unsigned> index;
-	{
-		std::ifstream fh(c.files.at(0));
-		std::string line;
-		while (fh.is_open() && std::getline(fh, line)) {
-			if (line.empty() || line[0] == '#') continue;
-			std::stringstream ss(line);
-			std::string item;
-			std::getline(ss, item, '\t');
-			index[item] = (unsigned) c.locus.size();
-			c.locus.push_back(item);
-			for (int s = 0; s < 5; ++s) std::getline(ss, item, '\t');
-			const auto d = loadPair(ss, item);
-			c.distinct.push_back(d.first);
-			c.distinct.push_back(d.second);
-		}
-	}
+	if (!fromStore) ntsm::eval_store::read_locus_table(c.files.at(0), index, c.locus, c.distinct);
 	const size_t n = c.files.size(), m = c.nSites();
 	c.counts.assign(n * m * 2, 0u);
 	c.sums.assign(n * m * 2, 0u);
@@ -88,28 +68,11 @@ void load(Counts &c)
 	c.total.assign(n, 0);
 	c.kmerSize.assign(n, 0);
 	for (size_t i = 0; i < n; ++i) {
-		std::ifstream fh(c.files[i]);
-		std::string line;
-		while (fh.is_open() && std::getline(fh, line)) {
-			if (line.empty()) continue;
-			std::stringstream ss(line);
-			std::string item;
-			std::getline(ss, item, '\t');
-			if (line[0] == '#') {
-				if (item == "#@TK") { std::getline(ss, item, '\t'); c.rawTotal[i] = std::stoull(item); }
-				else if (item == "#@KS") { std::getline(ss, item, '\t'); c.kmerSize[i] = (unsigned) std::stoull(item); }
-				continue;
-			}
-			const unsigned s = index.at(item);                     /* unknown locus: std::out_of_range, as in the reference */
-			std::getline(ss, item, '\t');
-			const auto cnt = loadPair(ss, item);
-			c.counts[(i * m + s) * 2] = cnt.first;
-			c.counts[(i * m + s) * 2 + 1] = cnt.second;
-			c.total[i] += cnt.first + cnt.second;                  /* :104-106 unsigned + unsigned: wraps at 2^32, then widens */
-			const auto sm = loadPair(ss, item);
-			c.sums[(i * m + s) * 2] = sm.first;
-			c.sums[(i * m + s) * 2 + 1] = sm.second;
-		}
+		ntsm::eval_store::Scalars sc;
+		ntsm::eval_store::parse_counts_file(c.files[i], index, c.counts.data() + i * m * 2, c.sums.data() + i * m * 2, sc, fromStore);
+		c.rawTotal[i] = sc.raw_total;
+		c.total[i] = sc.total;
+		c.kmerSize[i] = sc.kmer_size;
 	}
 }
 
@@ -120,6 +83,7 @@ std::vector<Genotype> summaries(const Counts &c, const Opt &opt)
 {
 	const size_t m = c.nSites();
 	std::vector<Genotype> g(c.files.size());
+	const uint64_t distinctSum = ntsm::eval_store::sum_of_pairs(c.distinct.data(), m);
 	for (size_t i = 0; i < g.size(); ++i) {
 		const uint32_t *cnt = &c.counts[i * m * 2];
 		for (size_t s = 0; s < m; ++s) {
@@ -127,15 +91,8 @@ std::vector<Genotype> summaries(const Counts &c, const Opt &opt)
 			else if (cnt[2 * s + 1] > opt.minCov) ++g[i].homs;
 			else ++g[i].miss;
 		}
-		if (c.rawTotal[i] > 0 && c.kmerSize[i] > 0) {
-			uint64_t sum = 0, distinct = 0;
-			for (size_t s = 0; s < m; ++s) {
-				sum += c.sums[(i * m + s) * 2] + c.sums[(i * m + s) * 2 + 1];
-				distinct += c.distinct[2 * s] + c.distinct[2 * s + 1];
-			}
-			const double expected = double(c.rawTotal[i]) * double(distinct) / double(opt.genomeSize);
-			g[i].errorRate = 1.0 - std::pow(double(sum) / expected, 1.0 / double(c.kmerSize[i]));
-		} else g[i].errorRate = -1.0;
+		g[i].errorRate = ntsm::eval_store::error_rate(c.rawTotal[i], c.kmerSize[i], ntsm::eval_store::sum_of_pairs(c.sums.data() + i * m * 2, m),
+				distinctSum, opt.genomeSize);
 		g[i].cov = double(c.total[i]) / double(m);
 	}
 	return g;
@@ -169,10 +126,18 @@ void printHelpDialog()
 	    "  -2, --miss_large = FLOAT   Missing site threshold large PCA based search [" << std::to_string(d.pcMissSite2) << "]\n"
 	    "  -S, --small = FLOAT        Search radius for small PCA based search [" << std::to_string(d.pcSearchRadius1) << "]\n"
 	    "  -l, --large = FLOAT        Search radius for large PCA based search [" << std::to_string(d.pcSearchRadius2) << "]\n"
-	    "  -G, --gpu = INT            HIP device [0] (this build only)\n"
 	    "  -h, --help                 Display this dialog.\n"
 	    "  -v, --verbose              Display verbose output.\n"
-	    "Not in this build: -b (debug mode of the PCA search).\n" << std::endl;
+	    "This build only:\n"
+	    "  -G, --gpu = INT            HIP device [0]\n"
+	    "      --pack = STORE         Write the counts of FILES to the binary cohort store\n"
+	    "                             STORE, or append them if it exists. Needs no GPU.\n"
+	    "      --against = STORE      Score FILES against every sample of STORE and against\n"
+	    "                             each other: the rows of the all-to-all run over FILES\n"
+	    "                             followed by the store's samples whose sample1 is one of\n"
+	    "                             FILES. Not with -p, -b, -e or -o.\n"
+	    "Not in this build: -b (debug mode of the PCA search); the PCA-guided search (-p)\n"
+	    "against a store; merging (-e) from a store.\n" << std::endl;
 	exit(EXIT_SUCCESS);
 }
 
@@ -333,12 +298,86 @@ int scorePCA(const Counts &c, std::vector<Genotype> &g, const Opt &opt, ntsm_eva
 	return 0;
 }
 
+constexpr int kOptPack = 1000, kOptAgainst = 1001;   /* long-only: no letter of the reference's option string is taken */
+
+/* --pack STORE FILES...: no GPU */
+int packStore(const Counts &c, const Opt &opt)
+{
+	try {
+		const uint64_t n = ntsm::eval_store::pack(opt.pack, c.files);
+		if (opt.verbose > 0) std::cerr << "Packed " << c.files.size() << " files; " << opt.pack << " holds " << n << " samples" << std::endl;
+	} catch (const std::exception &e) {                   /* a refusal, or a number that does not parse: the store is as it was */
+		ntsm::refuse(e.what());
+	}
+	return 0;
+}
+
+double msSince(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); }
+
+/* --against STORE FILES...: the rows of computeScore (:591-624) over [FILES..., the store's samples] whose sample 1 is one
+ * of FILES -- a prefix of that run's output.  The store's locus table and distinct columns play the part of the first file. */
+int scoreAgainst(Counts &c, const Opt &opt, std::chrono::steady_clock::time_point t0)
+{
+	namespace st = ntsm::eval_store;
+	st::View store;
+	const auto tMap = std::chrono::steady_clock::now();
+	try {
+		store.open(opt.against);
+		if (store.h.n_samples == 0) throw st::Error(opt.against + " holds no samples");
+		if (store.h.n_samples + c.files.size() > UINT32_MAX) throw st::Error(opt.against + " holds more samples than one run scores");
+		if (opt.verbose > 0) std::cerr << "Reading count files" << std::endl;
+		c.locus = store.locus;
+		c.distinct.assign(store.distinct, store.distinct + 2 * (size_t) store.h.n_sites);
+		load(c, store.index(), true);
+	} catch (const std::exception &e) {
+		ntsm::refuse(e.what());
+	}
+	const double mapMs = msSince(tMap);                  /* mapping the store and reading the query files */
+	std::vector<Genotype> g = summaries(c, opt);
+	const uint32_t nq = (uint32_t) c.files.size(), nd = (uint32_t) store.h.n_samples, m = store.h.n_sites;
+	if (opt.verbose > 1) std::cerr << "Finished loading files. Now comparing " << nq << " samples against the " << nd << " of " << opt.against << "." << std::endl;
+	std::cerr << "Performing all-to-all score computation.\nSpecify -p (--pca) to enable faster comparisons." << std::endl;
+	std::vector<ntsm_eval_record> qq((size_t) nq * (nq - 1) / 2), cross((size_t) nq * nd);
+	std::vector<uint32_t> geno((size_t) nd * 3);
+	double ms = 0;
+	int rc = nq >= 2 ? ntsm_eval_pairs(opt.device, c.counts.data(), nq, m, opt.minCov, qq.data(), &ms) : 0;
+	if (rc) return gpuFail("scoring", rc);
+	ntsm_eval_cross_times times {};
+	rc = ntsm_eval_cross(opt.device, c.counts.data(), nq, store.counts(0), store.h.stride, nd, m, opt.minCov, 0, cross.data(), geno.data(), &times);
+	if (rc) return gpuFail("scoring against the store", rc);
+	const uint64_t distinctSum = st::sum_of_pairs(c.distinct.data(), m);
+	g.resize((size_t) nq + nd);
+	c.files.reserve((size_t) nq + nd);
+	for (uint32_t d = 0; d < nd; ++d) {                   /* the store's samples as samples nq ... of the run */
+		const st::RecordHead &h = store.head(d);
+		Genotype &s = g[nq + d];
+		s.hets = geno[3 * d]; s.homs = geno[3 * d + 1]; s.miss = geno[3 * d + 2];
+		s.errorRate = st::error_rate(h.raw_total, h.kmer_size, h.sum_of_sums, distinctSum, opt.genomeSize);
+		s.cov = double(h.total) / double(m);
+		c.files.push_back(store.name(d));
+	}
+	const auto tPrint = std::chrono::steady_clock::now();
+	std::cout << kHeader << "\n";
+	std::string temp;
+	for (uint32_t q = 0; q < nq; ++q) {
+		for (uint32_t j = q + 1; j < nq; ++j) printRow(temp, c, g, opt, qq[ntsm_eval_pair_index(q, j, nq)], q, j, "-1");
+		for (uint32_t d = 0; d < nd; ++d) printRow(temp, c, g, opt, cross[(size_t) q * nd + d], q, nq + d, "-1");
+	}
+	std::cout.flush();
+	if (opt.verbose > 1)
+		std::cerr << "store query: " << times.chunks << " chunks, map+load " << mapMs << " ms, query pairs " << ms << " ms, upload " << times.upload_ms
+		          << " ms, prepare " << times.prepare_kernel_ms << " ms, cross kernel " << times.cross_kernel_ms << " ms, download " << times.download_ms
+		          << " ms, print " << msSince(tPrint) << " ms" << std::endl;
+	std::cerr << "Time: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << " s" << std::endl;
+	return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv)
 {
 	Opt opt;
-	bool die = false;
+	bool die = false, storeMode = false;
 	static struct option long_options[] = {
 		{ "score_thresh", required_argument, nullptr, 's' }, { "all", no_argument, nullptr, 'a' },
 		{ "min_cov", required_argument, nullptr, 'c' }, { "skew", required_argument, nullptr, 'w' },
@@ -348,7 +387,8 @@ int main(int argc, char **argv)
 		{ "error_rate", required_argument, nullptr, 'r' }, { "miss_small", required_argument, nullptr, '1' },
 		{ "miss_large", required_argument, nullptr, '2' }, { "small", required_argument, nullptr, 'k' },   /* 'k': as in the reference's table, no effect */
 		{ "large", required_argument, nullptr, 'l' }, { "debug", required_argument, nullptr, 'b' },
-		{ "gpu", required_argument, nullptr, 'G' }, { "verbose", no_argument, nullptr, 'v' }, { nullptr, 0, nullptr, 0 } };
+		{ "gpu", required_argument, nullptr, 'G' }, { "verbose", no_argument, nullptr, 'v' },
+		{ "pack", required_argument, nullptr, kOptPack }, { "against", required_argument, nullptr, kOptAgainst }, { nullptr, 0, nullptr, 0 } };
 	int ch;
 	while ((ch = getopt_long(argc, argv, "t:vhs:c:m:aw:g:p:n:d:r:e:o1:2:S:l:b:G:", long_options, nullptr)) != -1) {
 		switch (ch) {
@@ -372,12 +412,22 @@ int main(int argc, char **argv)
 		case 'l': ntsm::reference_flag('l', optarg, opt.pcSearchRadius2); break;
 		case 'b': ntsm::reference_flag('b', optarg, opt.debug); break;
 		case 'v': opt.verbose++; break;
+		case kOptPack: opt.pack = optarg; storeMode = true; break;
+		case kOptAgainst: opt.against = optarg; storeMode = true; break;
 		case '?': die = true; break;
 		default: break;                              /* m: read by the reference, without effect */
 		}
 	}
 	Counts c;
 	while (optind < argc) c.files.emplace_back(argv[optind++]);
+	if (storeMode) {                                     /* what --pack and --against do not go with: refused before any file is read */
+		const char *mode = opt.pack.empty() ? "--against" : "--pack";
+		if (!opt.pack.empty() && !opt.against.empty()) ntsm::refuse("--pack and --against are two runs: give one of them");
+		if (!opt.pca.empty()) ntsm::refuse(std::string("the PCA-guided search (-p) ") + (opt.pack.empty() ? "against a store" : "with --pack") + " is not part of this build");
+		if (!opt.debug.empty()) ntsm::refuse(std::string("-b with ") + mode + " is not part of this build");
+		if (!opt.merge.empty() || opt.onlyMerge) ntsm::refuse(std::string("merging (-e, -o) with ") + mode + " is not part of this build: the store does not hold the per-site sums");
+		if (c.files.empty()) ntsm::refuse(std::string(mode) + " needs input files");
+	}
 	for (const std::string &f : c.files)
 		if (!std::ifstream(f).good()) {                  /* the reference asserts (src/ntSeqMatchEval.cpp:286) */
 			std::cerr << PROGRAM ": input file " << f << " does not exist" << std::endl;
@@ -401,6 +451,8 @@ int main(int argc, char **argv)
 	}
 	ntsm::try_help_if(die);
 	const auto t0 = std::chrono::steady_clock::now();
+	if (!opt.pack.empty()) return packStore(c, opt);
+	if (!opt.against.empty()) return scoreAgainst(c, opt, t0);
 	if (opt.verbose > 0) std::cerr << "Reading count files" << std::endl;
 	load(c);
 	std::vector<Genotype> g = summaries(c, opt);

@@ -1,0 +1,231 @@
+/*
+ * ntsm_eval_cross.hip -- queries against a cohort on one MI355X (include/ntsm_eval_hip.h: ntsm_eval_cross): the n_q x n_db
+ * rectangle of pairs (query q, database sample d), each record bit for bit what ntsm_eval_pairs gives for pair (q, n_q + d)
+ * of the concatenation [queries; database].
+ *
+ * Layout.  As in ntsm_eval.hip one thread owns one pair and walks the sites in order with one ntsm_eval_acc
+ * (ntsm_eval_score.h), so the sums are the reference's sequential sums.  The database samples go across the lanes: the
+ * counts of a chunk of them are transposed to at / cg / term [site][chunk sample], one coalesced 4 + 4 + 8-byte load per lane
+ * and site.  A workgroup holds a group of TQ queries on the wave-uniform side (their arrays are [site][query]: scalar loads,
+ * one ntsm_eval_side per query and site reused by every lane).  A rectangle has no diagonal: no tile is skipped and no
+ * record is mirrored; the query is sample 1 of every record.
+ *
+ * Chunks.  The database is a host array with a fixed pitch between samples (a cohort store mapped from disk).  Per chunk:
+ * one 2-D copy of the chunk's counts to a dense [chunk sample][site][2] buffer, the transpose (through LDS, so that both its
+ * reads and its writes are coalesced), the genotype tallies of the chunk's samples (one workgroup per sample over the dense
+ * buffer), the cross kernel, and one 2-D copy of the chunk's columns of `out` back.  One stream, no overlap.  Device memory is
+ * O((n_q + chunk) * n_sites + n_q * chunk).
+ */
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstdint>
+#include <cstring>
+
+#include "../../include/ntsm_eval_hip.h"
+#include "ntsm_eval_score.h"
+#define NTSM_HIP_TAG "ntsm_eval_cross"
+#include "ntsm_hip_scope.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kTile = 64;                    /* the transpose moves 64 samples x 64 sites per workgroup */
+constexpr uint64_t kFillWaves = 1024;        /* one wave on every SIMD of the 256 CUs */
+
+uint32_t g_width = 0, g_query_group = 0;     /* ntsm_eval_cross_tune */
+
+/* counts [sample][site][2] (dense) -> at / cg / term [site][sample] */
+__global__ __launch_bounds__(kThreads) void ntsm_eval_cross_prepare(const uint2 *__restrict__ counts, uint32_t n_samples, uint32_t n_sites,
+		uint32_t min_cov, uint32_t *__restrict__ at, uint32_t *__restrict__ cg, double *__restrict__ term)
+{
+	__shared__ uint2 tile[kTile][kTile + 1];
+	const uint32_t m0 = blockIdx.x * kTile, s0 = blockIdx.y * kTile;
+	const uint32_t lo = threadIdx.x % kTile, hi = threadIdx.x / kTile;              /* hi: 0 ... 3 */
+	for (uint32_t r = hi; r < (uint32_t) kTile; r += kThreads / kTile) {             /* lanes along the sites of one sample */
+		const uint32_t s = s0 + r, site = m0 + lo;
+		if (s < n_samples && site < n_sites) tile[r][lo] = counts[(uint64_t) s * n_sites + site];
+	}
+	__syncthreads();
+	for (uint32_t r = hi; r < (uint32_t) kTile; r += kThreads / kTile) {             /* lanes along the samples of one site */
+		const uint32_t s = s0 + lo, site = m0 + r;
+		if (s >= n_samples || site >= n_sites) continue;
+		const uint2 c = tile[lo][r];
+		const uint64_t cell = (uint64_t) site * n_samples + s;
+		at[cell] = c.x;
+		cg[cell] = c.y;
+		term[cell] = ntsm_eval_term(c.x, c.y, min_cov);
+	}
+}
+
+/* hets, homs, miss of every sample of the chunk (calcHomHetMiss, :742-767): one workgroup per sample; integer sums */
+__global__ __launch_bounds__(kThreads) void ntsm_eval_cross_tally(const uint2 *__restrict__ counts, uint32_t n_sites, uint32_t min_cov,
+		uint32_t *__restrict__ geno)
+{
+	__shared__ uint32_t sum[3];
+	if (threadIdx.x < 3) sum[threadIdx.x] = 0;
+	__syncthreads();
+	const uint2 *row = counts + (uint64_t) blockIdx.x * n_sites;
+	uint32_t hets = 0, homs = 0, miss = 0;
+	for (uint32_t site = threadIdx.x; site < n_sites; site += kThreads) {
+		const uint2 c = row[site];
+		const bool a = c.x > min_cov, b = c.y > min_cov;
+		hets += a && b;
+		homs += a != b;
+		miss += !a && !b;
+	}
+	atomicAdd(&sum[0], hets);
+	atomicAdd(&sum[1], homs);
+	atomicAdd(&sum[2], miss);
+	__syncthreads();
+	if (threadIdx.x < 3) geno[(uint64_t) blockIdx.x * 3 + threadIdx.x] = sum[threadIdx.x];
+}
+
+/* grid (chunk samples / blockDim.x, queries / TQ); out [n_q][out_pitch], the chunk's sample d at column d */
+template <int TQ> __global__ __launch_bounds__(kThreads) void ntsm_eval_cross_kernel(const uint32_t *__restrict__ qat, const uint32_t *__restrict__ qcg,
+		const double *__restrict__ qterm, uint32_t n_q, const uint32_t *__restrict__ at, const uint32_t *__restrict__ cg,
+		const double *__restrict__ term, uint32_t n_d, uint32_t n_sites, uint32_t min_cov, ntsm_eval_record *__restrict__ out, uint32_t out_pitch)
+{
+	const uint32_t d = blockIdx.x * blockDim.x + threadIdx.x;
+	const uint32_t q0 = blockIdx.y * TQ;
+	const uint32_t dc = d < n_d ? d : n_d - 1;                                   /* lanes past the end compute a copy of the last sample, not stored */
+	uint32_t q[TQ];
+#pragma unroll
+	for (int k = 0; k < TQ; ++k) q[k] = q0 + k < n_q ? q0 + k : n_q - 1;         /* wave-uniform: scalar loads */
+	ntsm_eval_acc acc[TQ];
+	for (uint32_t site = 0; site < n_sites; ++site) {
+		const uint64_t rd = (uint64_t) site * n_d + dc, rq = (uint64_t) site * n_q;
+		const ntsm_eval_side sd = ntsm_eval_side_of(at[rd], cg[rd], term[rd], min_cov);
+#pragma unroll
+		for (int k = 0; k < TQ; ++k) acc[k].add(ntsm_eval_side_of(qat[rq + q[k]], qcg[rq + q[k]], qterm[rq + q[k]], min_cov), sd, min_cov);
+	}
+	if (d >= n_d) return;
+#pragma unroll
+	for (int k = 0; k < TQ; ++k)
+		if (q0 + k < n_q) out[(uint64_t) (q0 + k) * out_pitch + d] = acc[k].record();
+}
+
+int launch_prepare(const uint32_t *counts, uint32_t n_samples, uint32_t n_sites, uint32_t min_cov, uint32_t *at, uint32_t *cg, double *term)
+{
+	hipLaunchKernelGGL(ntsm_eval_cross_prepare, dim3((n_sites + kTile - 1) / kTile, (n_samples + kTile - 1) / kTile), dim3(kThreads), 0, 0,
+			(const uint2 *) counts, n_samples, n_sites, min_cov, at, cg, term);
+	HIPCHK(hipGetLastError());
+	return 0;
+}
+
+/* Workgroup width and query group of one launch.  A lane's walk over the sites is sequential, so the only parallelism is
+ * across pairs: the widest query group whose launch still puts a wave on every SIMD wins (each database value loaded is used
+ * TQ times); a rectangle too small for that takes single queries, which at least spreads what there is.  One-wave workgroups
+ * at every size: measured 4 to 5 % faster than 256 threads on 1 and 8 queries against 4,096 samples,
+ * so unlike ntsm_eval.hip there is no width switch; 256 is reachable through ntsm_eval_cross_tune only. */
+void launch_shape(uint32_t n_q, uint32_t n_d, uint32_t &width, uint32_t &tq)
+{
+	width = g_width ? g_width : 64;
+	const uint64_t waves = (n_d + 63) / 64;
+	tq = 1;
+	for (uint32_t t = 4; t > 1; t /= 2)
+		if (t / 2 < n_q && waves * ((n_q + t - 1) / t) >= kFillWaves) { tq = t; break; }
+	if (g_query_group) tq = g_query_group;
+}
+
+}  // namespace
+
+extern "C" int ntsm_eval_cross_tune(uint32_t width, uint32_t query_group)
+{
+	if ((width != 0 && width != 64 && width != 256) || (query_group != 0 && query_group != 1 && query_group != 2 && query_group != 4)) return -1;
+	g_width = width;
+	g_query_group = query_group;
+	return 0;
+}
+
+extern "C" int ntsm_eval_cross(int device, const uint32_t *q_counts, uint32_t n_q, const void *db_counts, uint64_t db_stride_bytes,
+		uint32_t n_db, uint32_t n_sites, uint32_t min_cov, uint32_t db_chunk,
+		ntsm_eval_record *out, uint32_t *db_geno, ntsm_eval_cross_times *times)
+{
+	if (times) *times = ntsm_eval_cross_times {};
+	if ((!q_counts && n_q && n_sites) || (!db_counts && n_db && n_sites) || (!out && n_q && n_db)) return -1;
+	if (db_stride_bytes < 8ull * n_sites || db_stride_bytes % 4) return -1;
+	if (n_q && n_db) memset(out, 0, (size_t) n_q * n_db * sizeof(ntsm_eval_record));
+	if (db_geno && n_db) memset(db_geno, 0, (size_t) n_db * 3 * sizeof(uint32_t));
+	if (n_q == 0 || n_db == 0 || n_sites == 0) return 0;
+
+	const uint64_t row_bytes = 8ull * n_sites;
+	HIPCHK(hipSetDevice(device));
+	uint32_t chunk = db_chunk;
+	if (chunk == 0) {                                   /* as many samples as fit in half of what is free: fewer passes, fuller launches */
+		size_t free_b = 0, total_b = 0;
+		HIPCHK(hipMemGetInfo(&free_b, &total_b));
+		const uint64_t per_sample = 3 * row_bytes + (uint64_t) n_q * sizeof(ntsm_eval_record) + 12, fixed = 3ull * n_q * row_bytes;
+		const uint64_t budget = free_b / 2 > fixed ? free_b / 2 - fixed : 0;
+		chunk = (uint32_t) std::min<uint64_t>(n_db, std::max<uint64_t>(64, budget / per_sample));
+	}
+	chunk = std::min(chunk, n_db);
+
+	ntsm_hip::Buffers b;
+	ntsm_hip::Events<3> ev;
+	uint32_t *d_q, *d_qat, *d_qcg, *d_raw, *d_at, *d_cg, *d_geno;
+	double *d_qterm, *d_term;
+	ntsm_eval_record *d_out;
+	const uint64_t qcells = (uint64_t) n_q * n_sites, cells = (uint64_t) chunk * n_sites;
+	HIPCHK(b.alloc(&d_q, qcells * 2));
+	HIPCHK(b.alloc(&d_qat, qcells));
+	HIPCHK(b.alloc(&d_qcg, qcells));
+	HIPCHK(b.alloc(&d_qterm, qcells));
+	HIPCHK(b.alloc(&d_raw, cells * 2));
+	HIPCHK(b.alloc(&d_at, cells));
+	HIPCHK(b.alloc(&d_cg, cells));
+	HIPCHK(b.alloc(&d_term, cells));
+	HIPCHK(b.alloc(&d_geno, (uint64_t) chunk * 3));
+	HIPCHK(b.alloc(&d_out, (uint64_t) n_q * chunk));
+	HIPCHK(ev.create());
+
+	typedef std::chrono::steady_clock clock;
+	const auto ms_since = [](clock::time_point t) { return std::chrono::duration<double, std::milli>(clock::now() - t).count(); };
+	ntsm_eval_cross_times tm {};
+	auto t = clock::now();
+	HIPCHK(hipMemcpy(d_q, q_counts, qcells * 2 * sizeof(uint32_t), hipMemcpyHostToDevice));
+	tm.upload_ms += ms_since(t);
+	HIPCHK(hipEventRecord(ev[0], 0));
+	if (launch_prepare(d_q, n_q, n_sites, min_cov, d_qat, d_qcg, d_qterm)) return NTSM_HIP_FAIL;
+	HIPCHK(hipEventRecord(ev[1], 0));
+	HIPCHK(hipEventSynchronize(ev[1]));
+	float ms = 0;
+	HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+	tm.prepare_kernel_ms += ms;
+
+	for (uint32_t c0 = 0; c0 < n_db; c0 += chunk) {
+		const uint32_t cn = std::min(chunk, n_db - c0);
+		t = clock::now();
+		HIPCHK(hipMemcpy2D(d_raw, row_bytes, (const char *) db_counts + (uint64_t) c0 * db_stride_bytes, db_stride_bytes, row_bytes, cn,
+				hipMemcpyHostToDevice));
+		tm.upload_ms += ms_since(t);
+		HIPCHK(hipEventRecord(ev[0], 0));
+		if (launch_prepare(d_raw, cn, n_sites, min_cov, d_at, d_cg, d_term)) return NTSM_HIP_FAIL;
+		if (db_geno) {
+			hipLaunchKernelGGL(ntsm_eval_cross_tally, dim3(cn), dim3(kThreads), 0, 0, (const uint2 *) d_raw, n_sites, min_cov, d_geno);
+			HIPCHK(hipGetLastError());
+		}
+		HIPCHK(hipEventRecord(ev[1], 0));
+		uint32_t width, tq;
+		launch_shape(n_q, cn, width, tq);
+		const dim3 grid((cn + width - 1) / width, (n_q + tq - 1) / tq);
+		auto kernel = tq == 4 ? ntsm_eval_cross_kernel<4> : tq == 2 ? ntsm_eval_cross_kernel<2> : ntsm_eval_cross_kernel<1>;
+		hipLaunchKernelGGL(kernel, grid, dim3(width), 0, 0, d_qat, d_qcg, d_qterm, n_q, d_at, d_cg, d_term, cn, n_sites, min_cov, d_out, chunk);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipEventRecord(ev[2], 0));
+		HIPCHK(hipEventSynchronize(ev[2]));
+		t = clock::now();
+		HIPCHK(hipMemcpy2D(out + c0, (size_t) n_db * sizeof(ntsm_eval_record), d_out, (size_t) chunk * sizeof(ntsm_eval_record),
+				(size_t) cn * sizeof(ntsm_eval_record), n_q, hipMemcpyDeviceToHost));
+		if (db_geno) HIPCHK(hipMemcpy(db_geno + (uint64_t) c0 * 3, d_geno, (size_t) cn * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+		tm.download_ms += ms_since(t);
+		HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+		tm.prepare_kernel_ms += ms;
+		HIPCHK(hipEventElapsedTime(&ms, ev[1], ev[2]));
+		tm.cross_kernel_ms += ms;
+		tm.chunks++;
+	}
+	if (times) *times = tm;
+	return 0;
+}

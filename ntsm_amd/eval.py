@@ -151,3 +151,35 @@ def score_pairs(counts, pi, pk, min_cov=1, device=0):
         return s.score_pairs(pi, pk)
     finally:
         s.close()
+
+
+# ---- queries against a cohort (ntsmEval --against; include/ntsm_eval_hip.h: ntsm_eval_cross)
+class CrossTimes(C.Structure):
+    _fields_ = [("upload_ms", C.c_double), ("prepare_kernel_ms", C.c_double), ("cross_kernel_ms", C.c_double), ("download_ms", C.c_double),
+                ("chunks", C.c_uint32)]
+
+
+lib.ntsm_eval_cross.restype = C.c_int
+lib.ntsm_eval_cross.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                C.c_void_p, C.c_void_p, C.POINTER(CrossTimes)]
+lib.ntsm_eval_cross_tune.restype = C.c_int
+lib.ntsm_eval_cross_tune.argtypes = [C.c_uint32, C.c_uint32]
+
+
+def cross(q, db, min_cov=1, db_chunk=0, device=0):
+    """q: uint32 [n_q][n_sites][2], db: uint32 [n_db][n_sites][2].  Returns (records [n_q, n_db], the record of (q, d) being
+    that of pair (q, n_q + d) of pairs(concatenate([q, db])); geno [n_db, 3] = hets, homs, miss of each database sample;
+    times, a CrossTimes).  db_chunk: database samples per pass, 0 = the library's choice."""
+    q = np.ascontiguousarray(q, dtype=np.uint32)
+    db = np.ascontiguousarray(db, dtype=np.uint32)
+    n_q, n_db, m = q.shape[0], db.shape[0], q.shape[1]
+    if q.ndim != 3 or db.ndim != 3 or db.shape[1] != m or q.shape[2] != 2 or db.shape[2] != 2:
+        raise ValueError("cross: q and db are [samples][sites][2] over the same sites")
+    out = np.zeros((n_q, n_db), dtype=RECORD)
+    geno = np.zeros((n_db, 3), dtype=np.uint32)
+    times = CrossTimes()
+    rc = lib.ntsm_eval_cross(device, q.ctypes.data, n_q, db.ctypes.data, 8 * m, n_db, m, min_cov, db_chunk, out.ctypes.data,
+                             geno.ctypes.data, C.byref(times))
+    if rc:
+        raise RuntimeError("ntsm_eval_cross failed: %d" % rc)
+    return out, geno, times

@@ -5,7 +5,8 @@
 #   build/ntsm_synth          generator CLI
 #   build/ntsm_host_test      host-logic test driver (no GPU calls)
 #   ntsm_amd/libntsm_eval_hip.so, build/ntsmEval   all-pairs scoring of ntsmEval (HIP library + CLI mirror), its PCA-guided
-#                                                  search, and queries against a cohort store (--pack / --against)
+#                                                  search, queries against a cohort store (--pack / --against) and the
+#                                                  PCA-guided search against one (--index / --near)
 #   ntsm_amd/libntsm_vcf_hip.so, build/ntsmVCF     multi-sample VCF to PCA matrix + centre file (HIP library + CLI mirror);
 #                                                  with --rotation also the PCA, through libntsm_pca_hip.so
 #   ntsm_amd/libntsm_pca_hip.so, build/ntsmPCA     exact PCA of the ntsmVCF matrix: rotation for ntsmEval -p (HIP library + CLI)
@@ -75,12 +76,16 @@ xlib:
 # ntsmEval all-pairs scoring: own library, own CLI
 # + the PCA-guided pair search (-p / -n): ntsm_eval_pca.hip with the x87 add of xprec.h
 # + queries against a cohort store (--against): ntsm_eval_cross.hip; the store itself is host code (host/eval_store.hpp)
-ntsm_amd/libntsm_eval_hip.so: $(CSRC)/ntsm_eval.hip $(CSRC)/ntsm_eval_pca.hip $(CSRC)/ntsm_eval_cross.hip $(CSRC)/ntsm_eval_score.h $(CSRC)/ntsm_hip_scope.h $(CSRC)/xprec.h include/ntsm_eval_hip.h
-	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -shared -o $@ $(CSRC)/ntsm_eval.hip $(CSRC)/ntsm_eval_pca.hip $(CSRC)/ntsm_eval_cross.hip
+# + the PCA-guided search against a store (--index / --near): ntsm_eval_near.hip; it shares a chunk's preparation with the cross
+#   path (ntsm_eval_chunk.h) and the search's steps with the session search (ntsm_eval_pca.h); the index is host code (host/eval_index.hpp)
+EVALSRC := $(CSRC)/ntsm_eval.hip $(CSRC)/ntsm_eval_pca.hip $(CSRC)/ntsm_eval_cross.hip $(CSRC)/ntsm_eval_near.hip
+ntsm_amd/libntsm_eval_hip.so: $(EVALSRC) $(CSRC)/ntsm_eval_score.h $(CSRC)/ntsm_eval_chunk.h $(CSRC)/ntsm_eval_pca.h $(CSRC)/ntsm_hip_scope.h $(CSRC)/xprec.h include/ntsm_eval_hip.h
+	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -shared -o $@ $(EVALSRC)
 
-build/ntsmEval: $(HOST)/ntsm_eval_main.cpp $(HOST)/cli.hpp $(HOST)/eval_store.hpp $(HOST)/gz_stream.hpp $(CSRC)/xprec.h include/ntsm_eval_hip.h ntsm_amd/libntsm_eval_hip.so
+build/ntsmEval: $(HOST)/ntsm_eval_main.cpp $(HOST)/cli.hpp $(HOST)/eval_store.hpp $(HOST)/eval_index.hpp $(HOST)/crc32_fast.cpp $(HOST)/crc32_fast.hpp \
+                $(HOST)/gz_stream.hpp $(CSRC)/xprec.h include/ntsm_eval_hip.h ntsm_amd/libntsm_eval_hip.so
 	@mkdir -p build
-	$(CXX) $(CXXFLAGS) -ffp-contract=off -o $@ $(HOST)/ntsm_eval_main.cpp -Lntsm_amd -lntsm_eval_hip \
+	$(CXX) $(CXXFLAGS) -ffp-contract=off -o $@ $(HOST)/ntsm_eval_main.cpp $(HOST)/crc32_fast.cpp -Lntsm_amd -lntsm_eval_hip -lz \
 	    -Wl,-rpath,'$$ORIGIN/../ntsm_amd' -Wl,-rpath,/opt/rocm/lib
 
 # the store's writer and reader on their own under the host sanitizers (tools/eval_store_check.cpp; not part of `all`)
@@ -88,6 +93,12 @@ store_check: build/eval_store_check
 build/eval_store_check: tools/eval_store_check.cpp $(HOST)/eval_store.hpp
 	@mkdir -p build
 	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ tools/eval_store_check.cpp
+
+# the index's writer, reader, append and validity failures likewise (tools/eval_index_check.cpp; not part of `all`)
+index_check: build/eval_index_check
+build/eval_index_check: tools/eval_index_check.cpp $(HOST)/eval_index.hpp $(HOST)/eval_store.hpp $(HOST)/crc32_fast.cpp $(HOST)/crc32_fast.hpp
+	@mkdir -p build
+	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ tools/eval_index_check.cpp $(HOST)/crc32_fast.cpp -lz
 
 # ntsmVCF (multi-sample VCF -> PCA matrix and centre file): own library, own CLI
 ntsm_amd/libntsm_vcf_hip.so: $(CSRC)/ntsm_vcf.hip $(CSRC)/ntsm_hip_scope.h include/ntsm_vcf_hip.h
@@ -172,4 +183,4 @@ build/gather_bench: tools/gather_bench.hip
 clean:
 	rm -rf build ntsm_amd/*.so
 	$(MAKE) -C oracle clean
-.PHONY: all oracle_all ref_gpu_binding clean ablation abl_tab tab m12 xlib store_check
+.PHONY: all oracle_all ref_gpu_binding clean ablation abl_tab tab m12 xlib store_check index_check

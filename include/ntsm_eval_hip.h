@@ -115,6 +115,40 @@ int ntsm_eval_cross(int device, const uint32_t *q_counts, uint32_t n_q, const vo
  * size (1, 2 or 4) of later calls in this process; 0 = the library's rule.  Returns 0, -1 for another value. */
 int ntsm_eval_cross_tune(uint32_t width, uint32_t query_group);
 
+/* ---- The PCA-guided search of new samples against a cohort store (ntsmEval --index / --near; ntsm_amd/csrc/ntsm_eval_near.hip;
+ * DESIGN.md section 9.2): projectPCs (src/CompareCounts.hpp:116-211) over a mapped store, computeScorePCA's pairs (:285-398)
+ * that have a query in them, and their records.  Indices follow the concatenation [queries; database] throughout: query q is
+ * sample q, database sample d is sample n_q + d.  ntsm_eval_cross_times is reused: cross_kernel_ms is the projection or
+ * scoring kernel, prepare_kernel_ms the tallies or the terms, upload_ms includes the row copies.
+ *
+ * ntsm_eval_project_store: db_counts / db_stride_bytes / db_chunk as for ntsm_eval_cross (one 2-D copy per chunk, no
+ *   host-side gather); norm [n_sites], rot [dim][n_sites] as for ntsm_eval_project.
+ *   cloud: out [n_db][dim], bit for bit what ntsm_eval_project gives on a dense copy of the same samples (:166-211).
+ *   db_geno (may be NULL): [n_db][3] as ntsm_eval_cross's (calcHomHetMiss, :742-767).
+ *   Returns 0, -1 bad argument, -2 HIP error.  n_db == 0 or n_sites == 0: zeroed outputs, no device work. */
+int ntsm_eval_project_store(int device, const void *db_counts, uint64_t db_stride_bytes, uint32_t n_db, uint32_t n_sites, uint32_t min_cov,
+		const long double *norm, const long double *rot, uint32_t dim, uint32_t db_chunk, double *cloud, uint32_t *db_geno,
+		ntsm_eval_cross_times *times);
+
+/* ntsm_eval_cross_candidates: exactly the sublist of ntsm_eval_candidates' output on the concatenated clouds and radii in
+ *   which pi < n_q or pk < n_q -- order, indices and dist (calcDistance, :926-932) the same, query-query pairs included.  A
+ *   pair (q, d) stands in the row of d when radius[d] > radius[q], else in the row of q (:318-334); rows ascending, queries
+ *   first; a radius row by ascending evalMetric (vendor/nanoflann.hpp:452-486), ties by ascending k; a search-all row by k.
+ *   q_cloud [n_q][dim], db_cloud [n_db][dim], radii squared, DBL_MAX = search all.  One pass over the rectangle, database
+ *   samples across the lanes.  Capacity protocol and return codes as ntsm_eval_candidates. */
+int ntsm_eval_cross_candidates(int device, const double *q_cloud, const double *q_radius, uint32_t n_q, const double *db_cloud,
+		const double *db_radius, uint32_t n_db, uint32_t dim, uint32_t *pi, uint32_t *pk, double *dist, uint64_t capacity, uint64_t *n_pairs,
+		double *kernel_ms);
+
+/* ntsm_eval_cross_score_pairs: out[p] is, bit for bit, the record ntsm_eval_score_pairs gives for (pi[p], pk[p]) on the
+ *   concatenation (sample pi[p] as sample 1; either orientation).  Only the distinct database samples the list names leave
+ *   the host: copied row by row from db_counts in passes of at most db_chunk distinct samples (0 = the library's choice from
+ *   free memory); device memory is O((n_q + chunk) * n_sites + n_pairs).
+ *   Returns 0, -1 (a bad argument, an index out of range, pi[p] == pk[p], or a pair with no query in it), -2. */
+int ntsm_eval_cross_score_pairs(int device, const uint32_t *q_counts, uint32_t n_q, const void *db_counts, uint64_t db_stride_bytes,
+		uint32_t n_db, uint32_t n_sites, uint32_t min_cov, const uint32_t *pi, const uint32_t *pk, uint64_t n_pairs, uint32_t db_chunk,
+		ntsm_eval_record *out, ntsm_eval_cross_times *times);
+
 #ifdef __cplusplus
 }
 #endif

@@ -202,6 +202,7 @@ public:
 			throw Error(path + ": " + std::to_string(size_) + " bytes, but its header describes " + std::to_string(h.n_samples) + " samples");
 		distinct = (const uint32_t *) (base + at);
 	}
+	const char *base() const { return (const char *) map_; }                         /* the locus section is bytes 64 ... h.first */
 	const RecordHead &head(uint64_t r) const { return *(const RecordHead *) ((const char *) map_ + h.first + r * h.stride); }
 	const uint32_t *counts(uint64_t r) const { return (const uint32_t *) ((const char *) map_ + h.first + r * h.stride + kRecordHead); }
 	std::string name(uint64_t r) const { const char *n = head(r).name; return std::string(n, strnlen(n, kNameBytes)); }

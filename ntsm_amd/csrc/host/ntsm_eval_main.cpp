@@ -6,7 +6,11 @@
  * -p ROT -n NORM is the PCA-guided search (projectPCs, :116-211, computeScorePCA, :285-398): projection, candidate pairs
  * and their scoring in the library's session calls, printed in the one-thread order.  This build only: --pack STORE FILES...
  * writes or extends a cohort store (eval_store.hpp, no GPU), --against STORE FILES... scores the files against the store's
- * samples (ntsm_eval_cross) and against each other and prints computeScore's rows for them.  Not built: -b (the debug
+ * samples (ntsm_eval_cross) and against each other and prints computeScore's rows for them; --index STORE -p ROT -n NORM
+ * projects the store's samples into STORE.pcaidx (eval_index.hpp, ntsm_eval_project_store) and --near STORE FILES... runs the
+ * PCA-guided search of the files against the store through that index (ntsm_eval_cross_candidates, then ntsm_eval_cross for
+ * the search-all queries and ntsm_eval_cross_score_pairs for the rest) and prints the rows of the -p run over [FILES...,
+ * the store's samples] that name one of FILES.  Not built: -b (the debug
  * ground-truth mode) and -p without a normalization file (the reference dies in an assert); both are refused.  Pinned to
  * the reference: stdout equals, byte for byte, that of the unmodified scoring class (oracle/ref_eval_driver.cpp ->
  * oracle/_ref/ref_ntsmEval -t 1) and its recordings, tests/test_eval_reference.py.
@@ -19,6 +23,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
+#include <functional>
 #include <iostream>
 #include <sstream>
 #include <string>
@@ -27,6 +32,7 @@
 
 #include "../../../include/ntsm_eval_hip.h"
 #include "cli.hpp"
+#include "eval_index.hpp"
 #include "eval_store.hpp"
 
 #define PROGRAM "ntsmEval"
@@ -41,6 +47,8 @@ struct Opt {                                 /* src/Options.h:44-55 */
 	int verbose = 0, device = 0;
 	std::string pca, merge, norm, debug;
 	std::string pack, against;               /* --pack STORE, --against STORE (this build only) */
+	std::string index, near;                 /* --index STORE, --near STORE: the PCA-guided search against a store */
+	bool minCovGiven = false, dimGiven = false;
 	bool onlyMerge = false;
 	unsigned dim = 20;                       /* src/Options.h:22, 35-39: the PCA search */
 	double pcSearchRadius1 = 2, pcSearchRadius2 = 15, pcErrorThresh = 0.01, pcMissSite1 = 0.01, pcMissSite2 = 0.3;
@@ -136,8 +144,16 @@ void printHelpDialog()
 	    "                             each other: the rows of the all-to-all run over FILES\n"
 	    "                             followed by the store's samples whose sample1 is one of\n"
 	    "                             FILES. Not with -p, -b, -e or -o.\n"
+	    "      --index = STORE        Project every sample of STORE with -p ROT -n NORM [-d -c]\n"
+	    "                             and write STORE.pcaidx, or extend it after an append.\n"
+	    "                             Takes no FILES.\n"
+	    "      --near = STORE         PCA-guided search of FILES against STORE through\n"
+	    "                             STORE.pcaidx: the rows of the -p run over FILES followed\n"
+	    "                             by the store's samples that name one of FILES. Rotation,\n"
+	    "                             centre, -d and -c come from the index. Not with -p, -n,\n"
+	    "                             -b, -e or -o.\n"
 	    "Not in this build: -b (debug mode of the PCA search); the PCA-guided search (-p)\n"
-	    "against a store; merging (-e) from a store.\n" << std::endl;
+	    "against a store (--index and --near are that search); merging (-e) from a store.\n" << std::endl;
 	exit(EXIT_SUCCESS);
 }
 
@@ -264,19 +280,25 @@ int project(const Counts &c, const Opt &opt, ntsm_eval_session *h, const std::ve
 	return 0;
 }
 
-/* computeScorePCA (:285-398), the one-thread order of its rows */
-int scorePCA(const Counts &c, std::vector<Genotype> &g, const Opt &opt, ntsm_eval_session *h, const std::vector<double> &cloud)
+/* the squared search radius of every sample (:297-305; pow(x, 2) = x * x); DBL_MAX = search all */
+std::vector<double> searchRadii(std::vector<Genotype> &g, size_t m, const Opt &opt)
 {
-	if (opt.verbose > 1) std::cerr << "Generating kd-tree" << std::endl;
-	const size_t n = c.files.size(), m = c.nSites();
-	std::vector<double> radius(n);
-	for (size_t i = 0; i < n; ++i) {                    /* :297-305; pow(x, 2) = x * x */
+	std::vector<double> radius(g.size());
+	for (size_t i = 0; i < g.size(); ++i) {
 		const double propMissing = double(g[i].miss) / double(m);
 		g[i].radius = DBL_MAX;
 		if (g[i].errorRate < opt.pcErrorThresh && propMissing < opt.pcMissSite1) g[i].radius = opt.pcSearchRadius1 * opt.pcSearchRadius1;
 		else if (propMissing < opt.pcMissSite2) g[i].radius = opt.pcSearchRadius2 * opt.pcSearchRadius2;
 		radius[i] = g[i].radius;
 	}
+	return radius;
+}
+
+/* computeScorePCA (:285-398), the one-thread order of its rows */
+int scorePCA(const Counts &c, std::vector<Genotype> &g, const Opt &opt, ntsm_eval_session *h, const std::vector<double> &cloud)
+{
+	if (opt.verbose > 1) std::cerr << "Generating kd-tree" << std::endl;
+	const std::vector<double> radius = searchRadii(g, c.nSites(), opt);
 	if (opt.verbose > 1) std::cerr << "Starting Score Computation with PCA" << std::endl;
 	uint64_t np = 0;
 	double msSearch = 0, msScore = 0;
@@ -298,7 +320,7 @@ int scorePCA(const Counts &c, std::vector<Genotype> &g, const Opt &opt, ntsm_eva
 	return 0;
 }
 
-constexpr int kOptPack = 1000, kOptAgainst = 1001;   /* long-only: no letter of the reference's option string is taken */
+constexpr int kOptPack = 1000, kOptAgainst = 1001, kOptIndex = 1002, kOptNear = 1003;   /* long-only: no letter of the reference's option string is taken */
 
 /* --pack STORE FILES...: no GPU */
 int packStore(const Counts &c, const Opt &opt)
@@ -313,6 +335,25 @@ int packStore(const Counts &c, const Opt &opt)
 }
 
 double msSince(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); }
+
+/* the store's samples as samples nq ... of a run: names, summaries from the record scalars and the given tallies */
+void appendStoreSamples(Counts &c, std::vector<Genotype> &g, const ntsm::eval_store::View &store, const Opt &opt,
+		const std::function<void(uint32_t, Genotype &)> &tallies)
+{
+	namespace st = ntsm::eval_store;
+	const uint32_t nq = (uint32_t) c.files.size(), nd = (uint32_t) store.h.n_samples, m = store.h.n_sites;
+	const uint64_t distinctSum = st::sum_of_pairs(c.distinct.data(), m);
+	g.resize((size_t) nq + nd);
+	c.files.reserve((size_t) nq + nd);
+	for (uint32_t d = 0; d < nd; ++d) {
+		const st::RecordHead &h = store.head(d);
+		Genotype &s = g[nq + d];
+		tallies(d, s);
+		s.errorRate = st::error_rate(h.raw_total, h.kmer_size, h.sum_of_sums, distinctSum, opt.genomeSize);
+		s.cov = double(h.total) / double(m);
+		c.files.push_back(store.name(d));
+	}
+}
 
 /* --against STORE FILES...: the rows of computeScore (:591-624) over [FILES..., the store's samples] whose sample 1 is one
  * of FILES -- a prefix of that run's output.  The store's locus table and distinct columns play the part of the first file. */
@@ -345,17 +386,7 @@ int scoreAgainst(Counts &c, const Opt &opt, std::chrono::steady_clock::time_poin
 	ntsm_eval_cross_times times {};
 	rc = ntsm_eval_cross(opt.device, c.counts.data(), nq, store.counts(0), store.h.stride, nd, m, opt.minCov, 0, cross.data(), geno.data(), &times);
 	if (rc) return gpuFail("scoring against the store", rc);
-	const uint64_t distinctSum = st::sum_of_pairs(c.distinct.data(), m);
-	g.resize((size_t) nq + nd);
-	c.files.reserve((size_t) nq + nd);
-	for (uint32_t d = 0; d < nd; ++d) {                   /* the store's samples as samples nq ... of the run */
-		const st::RecordHead &h = store.head(d);
-		Genotype &s = g[nq + d];
-		s.hets = geno[3 * d]; s.homs = geno[3 * d + 1]; s.miss = geno[3 * d + 2];
-		s.errorRate = st::error_rate(h.raw_total, h.kmer_size, h.sum_of_sums, distinctSum, opt.genomeSize);
-		s.cov = double(h.total) / double(m);
-		c.files.push_back(store.name(d));
-	}
+	appendStoreSamples(c, g, store, opt, [&](uint32_t d, Genotype &s) { s.hets = geno[3 * d]; s.homs = geno[3 * d + 1]; s.miss = geno[3 * d + 2]; });
 	const auto tPrint = std::chrono::steady_clock::now();
 	std::cout << kHeader << "\n";
 	std::string temp;
@@ -372,12 +403,183 @@ int scoreAgainst(Counts &c, const Opt &opt, std::chrono::steady_clock::time_poin
 	return 0;
 }
 
+/* --index STORE -p ROT -n NORM [-d -c]: project the store's samples, or the tail an append added, into STORE.pcaidx */
+int buildIndex(const Opt &opt, std::chrono::steady_clock::time_point t0)
+{
+	namespace st = ntsm::eval_store;
+	namespace ix = ntsm::eval_index;
+	const std::string path = ix::path_of(opt.index);
+	st::View store;
+	ix::View old;
+	bool extend = false;
+	std::vector<char> matrices;
+	std::vector<long double> norm, rot;
+	try {
+		store.open(opt.index);
+		if (store.h.n_samples == 0) throw st::Error(opt.index + " holds no samples");
+		if (store.h.n_samples > UINT32_MAX) throw st::Error(opt.index + " holds more samples than one run projects");
+		loadPCA(opt, store.h.n_sites, norm, rot);
+		matrices = ix::matrix_bytes(norm, rot);
+		struct stat sb;
+		if (stat(path.c_str(), &sb) == 0) {                   /* an index is there: extend it, or refuse */
+			try {
+				old.open(path);
+				old.check_store(path, store, true);
+			} catch (const st::Error &e) {
+				throw st::Error(std::string(e.what()) + "; delete " + path + " to index the store anew");
+			}
+			if (old.h.dim != opt.dim || old.h.min_cov != opt.minCov || old.matrix_size() != matrices.size()
+			    || memcmp(old.matrices(), matrices.data(), matrices.size()) != 0)
+				throw st::Error(path + " was written with another -d, -c, rotation or centre; delete " + path + " to index the store anew");
+			extend = true;
+		}
+	} catch (const std::exception &e) {
+		ntsm::refuse(e.what());
+	}
+	const uint64_t kept = extend ? old.h.n_samples : 0, added = store.h.n_samples - kept;
+	if (added == 0) {
+		std::cerr << path << " is up to date: " << kept << " samples" << std::endl;
+		return 0;
+	}
+	std::vector<double> cloud((size_t) added * opt.dim);
+	std::vector<uint32_t> geno((size_t) added * 3);
+	ntsm_eval_cross_times times {};
+	const int rc = ntsm_eval_project_store(opt.device, store.counts(kept), store.h.stride, (uint32_t) added, store.h.n_sites, opt.minCov, norm.data(),
+			rot.data(), opt.dim, 0, cloud.data(), geno.data(), &times);
+	if (rc) return gpuFail("projecting the store", rc);
+	try {
+		ix::write(path, store, opt.dim, opt.minCov, matrices, extend ? old.records() : nullptr, kept, cloud.data(), geno.data(), added);
+	} catch (const std::exception &e) {
+		ntsm::refuse(e.what());
+	}
+	if (opt.verbose > 0) std::cerr << "Projected " << added << " samples; " << path << " holds " << kept + added << std::endl;
+	if (opt.verbose > 1)
+		std::cerr << "store index: " << times.chunks << " chunks, upload " << times.upload_ms << " ms, prepare " << times.prepare_kernel_ms
+		          << " ms, projection kernel " << times.cross_kernel_ms << " ms, download " << times.download_ms << " ms" << std::endl;
+	std::cerr << "Time: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << " s" << std::endl;
+	return 0;
+}
+
+/* --near STORE FILES...: the rows of computeScorePCA (:285-398) over [FILES..., the store's samples] in which sample 1 or
+ * sample 2 is one of FILES, in that run's one-thread order.  The store's projections and tallies come from STORE.pcaidx, the
+ * radii are formed here (scorePCA's), and only the counts of the candidates' samples leave the store -- except for a query
+ * whose radius is DBL_MAX: it owns a whole row of the store, which ntsm_eval_cross scores as the dense rectangle it is. */
+int searchNear(Counts &c, Opt &opt, std::chrono::steady_clock::time_point t0)
+{
+	namespace st = ntsm::eval_store;
+	namespace ix = ntsm::eval_index;
+	const std::string path = ix::path_of(opt.near);
+	st::View store;
+	ix::View index;
+	const auto tMap = std::chrono::steady_clock::now();
+	try {
+		store.open(opt.near);
+		if (store.h.n_samples == 0) throw st::Error(opt.near + " holds no samples");
+		if (store.h.n_samples + c.files.size() > UINT32_MAX) throw st::Error(opt.near + " holds more samples than one run scores");
+		struct stat sb;
+		if (stat(path.c_str(), &sb) != 0) throw st::Error("there is no index " + path + ": run --index on the store first");
+		index.open(path);
+		index.check_store(path, store, false);
+		if (opt.minCovGiven && opt.minCov != index.h.min_cov)
+			throw st::Error("-c " + std::to_string(opt.minCov) + ", but " + path + " was written with -c " + std::to_string(index.h.min_cov));
+		if (opt.dimGiven && opt.dim != index.h.dim)
+			throw st::Error("-d " + std::to_string(opt.dim) + ", but " + path + " was written with -d " + std::to_string(index.h.dim));
+		opt.minCov = index.h.min_cov;
+		opt.dim = index.h.dim;
+		if (opt.verbose > 0) std::cerr << "Reading count files" << std::endl;
+		c.locus = store.locus;
+		c.distinct.assign(store.distinct, store.distinct + 2 * (size_t) store.h.n_sites);
+		load(c, store.index(), true);
+	} catch (const std::exception &e) {
+		ntsm::refuse(e.what());
+	}
+	const double mapMs = msSince(tMap);
+	std::vector<Genotype> g = summaries(c, opt);
+	const uint32_t nq = (uint32_t) c.files.size(), nd = (uint32_t) store.h.n_samples, m = store.h.n_sites, dim = opt.dim;
+	if (opt.verbose > 1) std::cerr << "Finished loading files. Now searching " << nq << " samples against the " << nd << " of " << opt.near << "." << std::endl;
+
+	auto t = std::chrono::steady_clock::now();
+	std::vector<double> qCloud;
+	{
+		std::vector<long double> norm, rot;
+		index.matrices(norm, rot);
+		Session session;
+		int rc = ntsm_eval_open(opt.device, c.counts.data(), nq, m, opt.minCov, &session.h);
+		if (rc) return gpuFail("session", rc);
+		if ((rc = project(c, opt, session.h, norm, rot, qCloud)) != 0) return rc;
+	}
+	const double projectMs = msSince(t);
+
+	t = std::chrono::steady_clock::now();
+	std::vector<double> dbCloud((size_t) nd * dim);
+	appendStoreSamples(c, g, store, opt, [&](uint32_t d, Genotype &s) {
+		const ix::Entry e = index.entry(d);
+		s.hets = e.hets; s.homs = e.homs; s.miss = e.miss;
+		memcpy(&dbCloud[(size_t) d * dim], e.cloud, sizeof(double) * dim);
+	});
+	const std::vector<double> radius = searchRadii(g, m, opt);
+	if (opt.verbose > 1) std::cerr << "Starting Score Computation with PCA" << std::endl;
+	uint64_t np = 0;
+	double msSearch = 0;
+	int rc = ntsm_eval_cross_candidates(opt.device, qCloud.data(), radius.data(), nq, dbCloud.data(), radius.data() + nq, nd, dim, nullptr, nullptr, nullptr,
+			0, &np, &msSearch);
+	if (rc && rc != NTSM_EVAL_E_CAPACITY) return gpuFail("candidate search", rc);
+	std::vector<uint32_t> pi(np), pk(np);
+	std::vector<double> dist(np);
+	if (np) {
+		rc = ntsm_eval_cross_candidates(opt.device, qCloud.data(), radius.data(), nq, dbCloud.data(), radius.data() + nq, nd, dim, pi.data(), pk.data(),
+				dist.data(), np, &np, &msSearch);
+		if (rc) return gpuFail("candidate search", rc);
+	}
+	const double searchMs = msSince(t);
+
+	/* routing: the search-all queries' rows of the store through the dense rectangle, every other pair through the list */
+	t = std::chrono::steady_clock::now();
+	std::vector<uint32_t> dense, denseRow(nq, UINT32_MAX);
+	for (uint32_t q = 0; q < nq; ++q)
+		if (!(radius[q] < DBL_MAX)) { denseRow[q] = (uint32_t) dense.size(); dense.push_back(q); }
+	std::vector<ntsm_eval_record> rect((size_t) dense.size() * nd), rec(np);
+	ntsm_eval_cross_times crossTimes {}, listTimes {};
+	if (!dense.empty()) {
+		std::vector<uint32_t> sub(dense.size() * (size_t) m * 2);
+		for (size_t r = 0; r < dense.size(); ++r) memcpy(&sub[r * m * 2], &c.counts[(size_t) dense[r] * m * 2], sizeof(uint32_t) * m * 2);
+		rc = ntsm_eval_cross(opt.device, sub.data(), (uint32_t) dense.size(), store.counts(0), store.h.stride, nd, m, opt.minCov, 0, rect.data(), nullptr,
+				&crossTimes);
+		if (rc) return gpuFail("scoring against the store", rc);
+	}
+	std::vector<uint32_t> li, lk;
+	std::vector<uint64_t> where;
+	for (uint64_t p = 0; p < np; ++p) {
+		if (pi[p] < nq && pk[p] >= nq && denseRow[pi[p]] != UINT32_MAX) rec[p] = rect[(size_t) denseRow[pi[p]] * nd + (pk[p] - nq)];
+		else { li.push_back(pi[p]); lk.push_back(pk[p]); where.push_back(p); }
+	}
+	std::vector<ntsm_eval_record> listed(li.size());
+	rc = ntsm_eval_cross_score_pairs(opt.device, c.counts.data(), nq, store.counts(0), store.h.stride, nd, m, opt.minCov, li.data(), lk.data(), li.size(), 0,
+			listed.data(), &listTimes);
+	if (rc) return gpuFail("scoring the candidate pairs", rc);
+	for (size_t x = 0; x < where.size(); ++x) rec[where[x]] = listed[x];
+	const double scoreMs = msSince(t);
+
+	const auto tPrint = std::chrono::steady_clock::now();
+	std::cout << kHeader << "\n";
+	std::string temp;
+	for (uint64_t p = 0; p < np; ++p) printRow(temp, c, g, opt, rec[p], pi[p], pk[p], std::to_string(dist[p]));
+	std::cout.flush();
+	if (opt.verbose > 1)
+		std::cerr << "store search: " << np << " pairs (" << li.size() << " listed, " << dense.size() << " dense rows), map+load " << mapMs << " ms, project "
+		          << projectMs << " ms, search " << searchMs << " ms (kernels " << msSearch << " ms), score " << scoreMs << " ms (gather "
+		          << listTimes.upload_ms << " ms, list kernel " << listTimes.cross_kernel_ms << " ms in " << listTimes.chunks << " passes, dense upload "
+		          << crossTimes.upload_ms << " ms, dense kernel " << crossTimes.cross_kernel_ms << " ms), print " << msSince(tPrint) << " ms" << std::endl;
+	std::cerr << "Time: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << " s" << std::endl;
+	return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv)
 {
 	Opt opt;
-	bool die = false, storeMode = false;
+	bool die = false, storeMode = false, nearMode = false;
 	static struct option long_options[] = {
 		{ "score_thresh", required_argument, nullptr, 's' }, { "all", no_argument, nullptr, 'a' },
 		{ "min_cov", required_argument, nullptr, 'c' }, { "skew", required_argument, nullptr, 'w' },
@@ -388,7 +590,8 @@ int main(int argc, char **argv)
 		{ "miss_large", required_argument, nullptr, '2' }, { "small", required_argument, nullptr, 'k' },   /* 'k': as in the reference's table, no effect */
 		{ "large", required_argument, nullptr, 'l' }, { "debug", required_argument, nullptr, 'b' },
 		{ "gpu", required_argument, nullptr, 'G' }, { "verbose", no_argument, nullptr, 'v' },
-		{ "pack", required_argument, nullptr, kOptPack }, { "against", required_argument, nullptr, kOptAgainst }, { nullptr, 0, nullptr, 0 } };
+		{ "pack", required_argument, nullptr, kOptPack }, { "against", required_argument, nullptr, kOptAgainst },
+		{ "index", required_argument, nullptr, kOptIndex }, { "near", required_argument, nullptr, kOptNear }, { nullptr, 0, nullptr, 0 } };
 	int ch;
 	while ((ch = getopt_long(argc, argv, "t:vhs:c:m:aw:g:p:n:d:r:e:o1:2:S:l:b:G:", long_options, nullptr)) != -1) {
 		switch (ch) {
@@ -396,7 +599,7 @@ int main(int argc, char **argv)
 		case 'a': opt.all = true; break;
 		case 's': ntsm::reference_flag('s', optarg, opt.scoreThresh); break;
 		case 'w': ntsm::reference_flag('w', optarg, opt.covSkew); break;
-		case 'c': ntsm::reference_flag('c', optarg, opt.minCov); break;
+		case 'c': ntsm::reference_flag('c', optarg, opt.minCov); opt.minCovGiven = true; break;
 		case 'g': ntsm::reference_flag('g', optarg, opt.genomeSize); break;
 		case 't': ntsm::reference_flag('t', optarg, opt.threads); break;
 		case 'G': ntsm::reference_flag('G', optarg, opt.device); break;
@@ -404,7 +607,7 @@ int main(int argc, char **argv)
 		case 'o': opt.onlyMerge = true; break;
 		case 'p': ntsm::reference_flag('p', optarg, opt.pca); break;
 		case 'n': ntsm::reference_flag('n', optarg, opt.norm); break;
-		case 'd': ntsm::reference_flag('d', optarg, opt.dim); break;
+		case 'd': ntsm::reference_flag('d', optarg, opt.dim); opt.dimGiven = true; break;
 		case 'r': ntsm::reference_flag('r', optarg, opt.pcErrorThresh); break;
 		case '1': ntsm::reference_flag('1', optarg, opt.pcMissSite1); break;
 		case '2': ntsm::reference_flag('2', optarg, opt.pcMissSite2); break;
@@ -414,13 +617,30 @@ int main(int argc, char **argv)
 		case 'v': opt.verbose++; break;
 		case kOptPack: opt.pack = optarg; storeMode = true; break;
 		case kOptAgainst: opt.against = optarg; storeMode = true; break;
+		case kOptIndex: opt.index = optarg; nearMode = true; break;
+		case kOptNear: opt.near = optarg; nearMode = true; break;
 		case '?': die = true; break;
 		default: break;                              /* m: read by the reference, without effect */
 		}
 	}
 	Counts c;
 	while (optind < argc) c.files.emplace_back(argv[optind++]);
-	if (storeMode) {                                     /* what --pack and --against do not go with: refused before any file is read */
+	if (nearMode) {                                      /* --index and --near: every refusal that needs no store comes before any file is read */
+		const char *mode = opt.near.empty() ? "--index" : "--near";
+		if (storeMode || (!opt.index.empty() && !opt.near.empty())) ntsm::refuse("--pack, --against, --index and --near are four runs: give one of them");
+		if (!opt.debug.empty()) ntsm::refuse(std::string("-b with ") + mode + " is not part of this build");
+		if (!opt.merge.empty() || opt.onlyMerge) ntsm::refuse(std::string("merging (-e, -o) with ") + mode + " is not part of this build: the store does not hold the per-site sums");
+		if (!opt.near.empty()) {
+			if (!opt.pca.empty() || !opt.norm.empty()) ntsm::refuse("--near takes rotation and centre from the store's index: give no -p and no -n");
+			if (c.files.empty()) ntsm::refuse("--near needs input files");
+		} else {
+			if (!c.files.empty()) ntsm::refuse("--index takes no input files: it projects the samples of the store");
+			if (opt.pca.empty() || !std::ifstream(opt.pca).good()) ntsm::refuse("--index needs a readable rotation file (-p)");
+			if (opt.norm.empty() || !std::ifstream(opt.norm).good()) ntsm::refuse("--index needs a readable normalization file (-n)");
+			if (opt.dim == 0) ntsm::refuse("a PCA search with -d 0 is not part of this build");
+			return buildIndex(opt, std::chrono::steady_clock::now());
+		}
+	} else if (storeMode) {                              /* what --pack and --against do not go with: refused before any file is read */
 		const char *mode = opt.pack.empty() ? "--against" : "--pack";
 		if (!opt.pack.empty() && !opt.against.empty()) ntsm::refuse("--pack and --against are two runs: give one of them");
 		if (!opt.pca.empty()) ntsm::refuse(std::string("the PCA-guided search (-p) ") + (opt.pack.empty() ? "against a store" : "with --pack") + " is not part of this build");
@@ -435,7 +655,7 @@ int main(int argc, char **argv)
 		}
 	if (c.files.empty()) { std::cerr << "Error: Need Input File" << std::endl; die = true; }
 	/* the PCA path runs for one file (its PC columns) and for an analysis (not -o); refusals before any GPU work */
-	const bool pcaRuns = !opt.pca.empty() && !c.files.empty() && (c.files.size() == 1 || !opt.onlyMerge);
+	const bool pcaRuns = !nearMode && !opt.pca.empty() && !c.files.empty() && (c.files.size() == 1 || !opt.onlyMerge);
 	if (pcaRuns && !die) {
 		if (!std::ifstream(opt.norm).good()) {           /* src/ntSeqMatchEval.cpp:335-338; the reference then dies in an assert */
 			std::cerr << "Error: Need normalization file" << std::endl;
@@ -453,6 +673,7 @@ int main(int argc, char **argv)
 	const auto t0 = std::chrono::steady_clock::now();
 	if (!opt.pack.empty()) return packStore(c, opt);
 	if (!opt.against.empty()) return scoreAgainst(c, opt, t0);
+	if (!opt.near.empty()) return searchNear(c, opt, t0);
 	if (opt.verbose > 0) std::cerr << "Reading count files" << std::endl;
 	load(c);
 	std::vector<Genotype> g = summaries(c, opt);

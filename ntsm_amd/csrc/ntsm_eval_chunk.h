@@ -1,0 +1,95 @@
+/*
+ * ntsm_eval_chunk.h -- one chunk of a cohort store on the device, stated once for ntsm_eval_cross.hip (the dense rectangle)
+ * and ntsm_eval_near.hip (the projection of a store, the passes over listed samples): the chunk rule, the genotype tallies
+ * of the chunk's samples over the dense [chunk sample][site][2] buffer, and that buffer's transpose to at / cg / term
+ * [site][chunk sample] for the cross kernel.  Internal: not part of
+ * include/.  The kernels have internal linkage; each translation unit that includes this file carries its own copy.
+ */
+#ifndef NTSM_EVAL_CHUNK_H
+#define NTSM_EVAL_CHUNK_H
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+
+#include "ntsm_eval_score.h"
+
+namespace ntsm_eval_chunk {
+
+constexpr int kThreads = 256;
+constexpr int kTile = 64;                    /* the transpose moves 64 samples x 64 sites per workgroup */
+
+/* counts [sample][site][2] (dense) -> at / cg / term [site][sample] */
+static __global__ __launch_bounds__(kThreads) void prepare_kernel(const uint2 *__restrict__ counts, uint32_t n_samples, uint32_t n_sites,
+		uint32_t min_cov, uint32_t *__restrict__ at, uint32_t *__restrict__ cg, double *__restrict__ term)
+{
+	__shared__ uint2 tile[kTile][kTile + 1];
+	const uint32_t m0 = blockIdx.x * kTile, s0 = blockIdx.y * kTile;
+	const uint32_t lo = threadIdx.x % kTile, hi = threadIdx.x / kTile;              /* hi: 0 ... 3 */
+	for (uint32_t r = hi; r < (uint32_t) kTile; r += kThreads / kTile) {             /* lanes along the sites of one sample */
+		const uint32_t s = s0 + r, site = m0 + lo;
+		if (s < n_samples && site < n_sites) tile[r][lo] = counts[(uint64_t) s * n_sites + site];
+	}
+	__syncthreads();
+	for (uint32_t r = hi; r < (uint32_t) kTile; r += kThreads / kTile) {             /* lanes along the samples of one site */
+		const uint32_t s = s0 + lo, site = m0 + r;
+		if (s >= n_samples || site >= n_sites) continue;
+		const uint2 c = tile[lo][r];
+		const uint64_t cell = (uint64_t) site * n_samples + s;
+		at[cell] = c.x;
+		cg[cell] = c.y;
+		term[cell] = ntsm_eval_term(c.x, c.y, min_cov);
+	}
+}
+
+/* hets, homs, miss of every sample of the chunk (calcHomHetMiss, :742-767): one workgroup per sample; integer sums */
+static __global__ __launch_bounds__(kThreads) void tally_kernel(const uint2 *__restrict__ counts, uint32_t n_sites, uint32_t min_cov,
+		uint32_t *__restrict__ geno)
+{
+	__shared__ uint32_t sum[3];
+	if (threadIdx.x < 3) sum[threadIdx.x] = 0;
+	__syncthreads();
+	const uint2 *row = counts + (uint64_t) blockIdx.x * n_sites;
+	uint32_t hets = 0, homs = 0, miss = 0;
+	for (uint32_t site = threadIdx.x; site < n_sites; site += kThreads) {
+		const uint2 c = row[site];
+		const bool a = c.x > min_cov, b = c.y > min_cov;
+		hets += a && b;
+		homs += a != b;
+		miss += !a && !b;
+	}
+	atomicAdd(&sum[0], hets);
+	atomicAdd(&sum[1], homs);
+	atomicAdd(&sum[2], miss);
+	__syncthreads();
+	if (threadIdx.x < 3) geno[(uint64_t) blockIdx.x * 3 + threadIdx.x] = sum[threadIdx.x];
+}
+
+/* the launches; the caller checks hipGetLastError */
+inline void launch_prepare(const uint32_t *counts, uint32_t n_samples, uint32_t n_sites, uint32_t min_cov, uint32_t *at, uint32_t *cg, double *term)
+{
+	hipLaunchKernelGGL(prepare_kernel, dim3((n_sites + kTile - 1) / kTile, (n_samples + kTile - 1) / kTile), dim3(kThreads), 0, 0,
+			(const uint2 *) counts, n_samples, n_sites, min_cov, at, cg, term);
+}
+
+inline void launch_tally(const uint32_t *counts, uint32_t n_samples, uint32_t n_sites, uint32_t min_cov, uint32_t *geno)
+{
+	hipLaunchKernelGGL(tally_kernel, dim3(n_samples), dim3(kThreads), 0, 0, (const uint2 *) counts, n_sites, min_cov, geno);
+}
+
+/* The chunk rule: the caller's db_chunk, or, for 0, as many samples as fit in half of what is free
+ * on the device after `fixed` bytes, at `per_sample` bytes each -- fewer passes, fuller launches -- and at least 64. */
+inline uint32_t samples_per_pass(uint32_t db_chunk, uint32_t n_db, size_t free_bytes, uint64_t per_sample, uint64_t fixed)
+{
+	uint32_t chunk = db_chunk;
+	if (chunk == 0) {
+		const uint64_t budget = free_bytes / 2 > fixed ? free_bytes / 2 - fixed : 0;
+		chunk = (uint32_t) std::min<uint64_t>(n_db, std::max<uint64_t>(64, budget / per_sample));
+	}
+	return std::min(chunk, n_db);
+}
+
+}  // namespace ntsm_eval_chunk
+
+#endif

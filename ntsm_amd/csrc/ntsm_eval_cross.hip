@@ -13,7 +13,8 @@
  * Chunks.  The database is a host array with a fixed pitch between samples (a cohort store mapped from disk).  Per chunk:
  * one 2-D copy of the chunk's counts to a dense [chunk sample][site][2] buffer, the transpose (through LDS, so that both its
  * reads and its writes are coalesced), the genotype tallies of the chunk's samples (one workgroup per sample over the dense
- * buffer), the cross kernel, and one 2-D copy of the chunk's columns of `out` back.  One stream, no overlap.  Device memory is
+ * buffer) -- those two and the chunk rule are ntsm_eval_chunk.h's; the projection of a store
+ * (ntsm_eval_near.hip) takes the chunk rule and the tallies from there --, the cross kernel, and one 2-D copy of the chunk's columns of `out` back.  One stream, no overlap.  Device memory is
  * O((n_q + chunk) * n_sites + n_q * chunk).
  */
 #include <hip/hip_runtime.h>
@@ -24,63 +25,17 @@
 #include <cstring>
 
 #include "../../include/ntsm_eval_hip.h"
+#include "ntsm_eval_chunk.h"
 #include "ntsm_eval_score.h"
 #define NTSM_HIP_TAG "ntsm_eval_cross"
 #include "ntsm_hip_scope.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kTile = 64;                    /* the transpose moves 64 samples x 64 sites per workgroup */
+using ntsm_eval_chunk::kThreads;
 constexpr uint64_t kFillWaves = 1024;        /* one wave on every SIMD of the 256 CUs */
 
 uint32_t g_width = 0, g_query_group = 0;     /* ntsm_eval_cross_tune */
-
-/* counts [sample][site][2] (dense) -> at / cg / term [site][sample] */
-__global__ __launch_bounds__(kThreads) void ntsm_eval_cross_prepare(const uint2 *__restrict__ counts, uint32_t n_samples, uint32_t n_sites,
-		uint32_t min_cov, uint32_t *__restrict__ at, uint32_t *__restrict__ cg, double *__restrict__ term)
-{
-	__shared__ uint2 tile[kTile][kTile + 1];
-	const uint32_t m0 = blockIdx.x * kTile, s0 = blockIdx.y * kTile;
-	const uint32_t lo = threadIdx.x % kTile, hi = threadIdx.x / kTile;              /* hi: 0 ... 3 */
-	for (uint32_t r = hi; r < (uint32_t) kTile; r += kThreads / kTile) {             /* lanes along the sites of one sample */
-		const uint32_t s = s0 + r, site = m0 + lo;
-		if (s < n_samples && site < n_sites) tile[r][lo] = counts[(uint64_t) s * n_sites + site];
-	}
-	__syncthreads();
-	for (uint32_t r = hi; r < (uint32_t) kTile; r += kThreads / kTile) {             /* lanes along the samples of one site */
-		const uint32_t s = s0 + lo, site = m0 + r;
-		if (s >= n_samples || site >= n_sites) continue;
-		const uint2 c = tile[lo][r];
-		const uint64_t cell = (uint64_t) site * n_samples + s;
-		at[cell] = c.x;
-		cg[cell] = c.y;
-		term[cell] = ntsm_eval_term(c.x, c.y, min_cov);
-	}
-}
-
-/* hets, homs, miss of every sample of the chunk (calcHomHetMiss, :742-767): one workgroup per sample; integer sums */
-__global__ __launch_bounds__(kThreads) void ntsm_eval_cross_tally(const uint2 *__restrict__ counts, uint32_t n_sites, uint32_t min_cov,
-		uint32_t *__restrict__ geno)
-{
-	__shared__ uint32_t sum[3];
-	if (threadIdx.x < 3) sum[threadIdx.x] = 0;
-	__syncthreads();
-	const uint2 *row = counts + (uint64_t) blockIdx.x * n_sites;
-	uint32_t hets = 0, homs = 0, miss = 0;
-	for (uint32_t site = threadIdx.x; site < n_sites; site += kThreads) {
-		const uint2 c = row[site];
-		const bool a = c.x > min_cov, b = c.y > min_cov;
-		hets += a && b;
-		homs += a != b;
-		miss += !a && !b;
-	}
-	atomicAdd(&sum[0], hets);
-	atomicAdd(&sum[1], homs);
-	atomicAdd(&sum[2], miss);
-	__syncthreads();
-	if (threadIdx.x < 3) geno[(uint64_t) blockIdx.x * 3 + threadIdx.x] = sum[threadIdx.x];
-}
 
 /* grid (chunk samples / blockDim.x, queries / TQ); out [n_q][out_pitch], the chunk's sample d at column d */
 template <int TQ> __global__ __launch_bounds__(kThreads) void ntsm_eval_cross_kernel(const uint32_t *__restrict__ qat, const uint32_t *__restrict__ qcg,
@@ -104,14 +59,6 @@ template <int TQ> __global__ __launch_bounds__(kThreads) void ntsm_eval_cross_ke
 #pragma unroll
 	for (int k = 0; k < TQ; ++k)
 		if (q0 + k < n_q) out[(uint64_t) (q0 + k) * out_pitch + d] = acc[k].record();
-}
-
-int launch_prepare(const uint32_t *counts, uint32_t n_samples, uint32_t n_sites, uint32_t min_cov, uint32_t *at, uint32_t *cg, double *term)
-{
-	hipLaunchKernelGGL(ntsm_eval_cross_prepare, dim3((n_sites + kTile - 1) / kTile, (n_samples + kTile - 1) / kTile), dim3(kThreads), 0, 0,
-			(const uint2 *) counts, n_samples, n_sites, min_cov, at, cg, term);
-	HIPCHK(hipGetLastError());
-	return 0;
 }
 
 /* Workgroup width and query group of one launch.  A lane's walk over the sites is sequential, so the only parallelism is
@@ -152,15 +99,10 @@ extern "C" int ntsm_eval_cross(int device, const uint32_t *q_counts, uint32_t n_
 
 	const uint64_t row_bytes = 8ull * n_sites;
 	HIPCHK(hipSetDevice(device));
-	uint32_t chunk = db_chunk;
-	if (chunk == 0) {                                   /* as many samples as fit in half of what is free: fewer passes, fuller launches */
-		size_t free_b = 0, total_b = 0;
-		HIPCHK(hipMemGetInfo(&free_b, &total_b));
-		const uint64_t per_sample = 3 * row_bytes + (uint64_t) n_q * sizeof(ntsm_eval_record) + 12, fixed = 3ull * n_q * row_bytes;
-		const uint64_t budget = free_b / 2 > fixed ? free_b / 2 - fixed : 0;
-		chunk = (uint32_t) std::min<uint64_t>(n_db, std::max<uint64_t>(64, budget / per_sample));
-	}
-	chunk = std::min(chunk, n_db);
+	size_t free_b = 0, total_b = 0;
+	if (db_chunk == 0) HIPCHK(hipMemGetInfo(&free_b, &total_b));
+	const uint32_t chunk = ntsm_eval_chunk::samples_per_pass(db_chunk, n_db, free_b,
+			3 * row_bytes + (uint64_t) n_q * sizeof(ntsm_eval_record) + 12, 3ull * n_q * row_bytes);
 
 	ntsm_hip::Buffers b;
 	ntsm_hip::Events<3> ev;
@@ -187,7 +129,8 @@ extern "C" int ntsm_eval_cross(int device, const uint32_t *q_counts, uint32_t n_
 	HIPCHK(hipMemcpy(d_q, q_counts, qcells * 2 * sizeof(uint32_t), hipMemcpyHostToDevice));
 	tm.upload_ms += ms_since(t);
 	HIPCHK(hipEventRecord(ev[0], 0));
-	if (launch_prepare(d_q, n_q, n_sites, min_cov, d_qat, d_qcg, d_qterm)) return NTSM_HIP_FAIL;
+	ntsm_eval_chunk::launch_prepare(d_q, n_q, n_sites, min_cov, d_qat, d_qcg, d_qterm);
+	HIPCHK(hipGetLastError());
 	HIPCHK(hipEventRecord(ev[1], 0));
 	HIPCHK(hipEventSynchronize(ev[1]));
 	float ms = 0;
@@ -201,9 +144,10 @@ extern "C" int ntsm_eval_cross(int device, const uint32_t *q_counts, uint32_t n_
 				hipMemcpyHostToDevice));
 		tm.upload_ms += ms_since(t);
 		HIPCHK(hipEventRecord(ev[0], 0));
-		if (launch_prepare(d_raw, cn, n_sites, min_cov, d_at, d_cg, d_term)) return NTSM_HIP_FAIL;
+		ntsm_eval_chunk::launch_prepare(d_raw, cn, n_sites, min_cov, d_at, d_cg, d_term);
+		HIPCHK(hipGetLastError());
 		if (db_geno) {
-			hipLaunchKernelGGL(ntsm_eval_cross_tally, dim3(cn), dim3(kThreads), 0, 0, (const uint2 *) d_raw, n_sites, min_cov, d_geno);
+			ntsm_eval_chunk::launch_tally(d_raw, cn, n_sites, min_cov, d_geno);
 			HIPCHK(hipGetLastError());
 		}
 		HIPCHK(hipEventRecord(ev[1], 0));

@@ -1,0 +1,385 @@
+/*
+ * ntsm_eval_near.hip -- the PCA-guided search of new samples against a cohort store on one MI355X (include/ntsm_eval_hip.h:
+ * ntsm_eval_project_store, ntsm_eval_cross_candidates, ntsm_eval_cross_score_pairs; ntsmEval --index / --near; reference:
+ * src/CompareCounts.hpp:116-211 projectPCs, :285-398 computeScorePCA).  Indices follow the concatenation [queries; database]:
+ * query q is sample q, database sample d is sample n_q + d.
+ *
+ * Projection of a store.  The store is walked in chunks as ntsm_eval_cross walks it (one 2-D copy per chunk to a dense buffer,
+ * the chunk rule and the tallies of ntsm_eval_chunk.h) and each chunk is projected by the session's kernel (ntsm_eval_pca.h:
+ * one lane per (sample, component) over the dense rows), so cloud bits are ntsm_eval_project's by construction.  A kernel
+ * over the transposed [site][chunk sample] layout of the cross path -- samples across the lanes, coalesced loads, the table
+ * entry wave-uniform -- was built and measured first: 134.8 and 141.4 ms against 135.9 and 136.3 ms on 4,096 x 96,287 sites x
+ * 20 components.  The chain of integer x87 adds bounds both, not the loads, and the transposed form needs the transpose and
+ * three times the device memory per sample on top: a negative result (NOTEBOOK.md), the row form stays.
+ *
+ * Search.  One pass over the (n_q + n_db) columns k of the concatenation with the columns across the lanes and the queries
+ * wave-uniform: for each (query q, column k) evalMetric is formed once (it is symmetric bit for bit: (a - b)^2 = (b - a)^2)
+ * and the selection rule of ntsm_eval_pca.h is asked twice, for row q and, where k is a database sample, for row k.  A
+ * counting pass, the prefix sum over the rows on the host, a filling pass: a query row is filled through one wave-aggregated
+ * atomic per wave and query (its order does not matter: the host sorts), a database row by its own lane, queries ascending.
+ * The host orders a radius row by (evalMetric, k) and a search-all row by k, which is the session search's order.  The grid
+ * is (columns / 256): never one workgroup per database row.
+ *
+ * Scoring of listed pairs.  Every pair has a query in it, so it names at most one database sample.  The distinct database
+ * samples of the list are copied row by row from the mapped store, at most `chunk` per pass, to dense rows behind the
+ * queries' rows; a pass scores its pairs with the listed-pair kernel of ntsm_eval_pca.h over those rows (slot numbers in
+ * place of sample numbers) and its records are scattered back to list order.
+ */
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cfloat>
+#include <chrono>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+#include "../../include/ntsm_eval_hip.h"
+#include "ntsm_eval_chunk.h"
+#include "ntsm_eval_pca.h"
+#include "ntsm_eval_score.h"
+#define NTSM_HIP_TAG "ntsm_eval_near"
+#include "ntsm_hip_scope.h"
+#include "xprec.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+
+typedef std::chrono::steady_clock wall;
+double ms_since(wall::time_point t) { return std::chrono::duration<double, std::milli>(wall::now() - t).count(); }
+
+/* the point and radius of column k of the concatenation */
+struct Columns {
+	const double *q_cloud, *q_radius, *db_cloud, *db_radius;
+	uint32_t n_q, n_db, dim;
+	__device__ const double *point(uint32_t k) const { return k < n_q ? q_cloud + (uint64_t) k * dim : db_cloud + (uint64_t) (k - n_q) * dim; }
+	__device__ double radius(uint32_t k) const { return k < n_q ? q_radius[k] : db_radius[k - n_q]; }
+};
+
+/* what rows q and k say about the pair (q, k), q a query, k any column: bit 0 = row q takes k, bit 1 = row k takes q (only
+ * asked where k is a database sample: a query's row is asked when that query is the wave-uniform side) */
+__device__ inline uint32_t near_decide(const Columns &c, uint32_t q, uint32_t k, double rk, const double *pk, double *metric)
+{
+	const double rq = c.q_radius[q];
+	const double *pq = c.q_cloud + (uint64_t) q * c.dim;
+	const bool need = rq < DBL_MAX || (k >= c.n_q && rk < DBL_MAX);            /* a search-all row evaluates no metric */
+	const double dm = need ? ntsm_eval_pca::eval_metric(pq, pk, c.dim) : 0.0;
+	*metric = dm;
+	uint32_t bits = ntsm_eval_pca::take_with_metric(q, k, rq, rk, dm) ? 1u : 0u;
+	if (k >= c.n_q && ntsm_eval_pca::take_with_metric(k, q, rk, rq, dm)) bits |= 2u;
+	return bits;
+}
+
+/* pass 1: q_count[q] += the pairs of row q among this workgroup's columns; db_count[d] = the pairs of row n_q + d */
+__global__ __launch_bounds__(kThreads) void near_count_kernel(Columns c, uint32_t *__restrict__ q_count, uint32_t *__restrict__ db_count)
+{
+	const uint32_t n = c.n_q + c.n_db, k = blockIdx.x * kThreads + threadIdx.x;
+	const bool live = k < n;
+	const uint32_t kc = live ? k : n - 1;
+	const double rk = c.radius(kc);
+	const double *pk = c.point(kc);
+	uint32_t own = 0;
+	for (uint32_t q = 0; q < c.n_q; ++q) {
+		double dm;
+		const uint32_t bits = live ? near_decide(c, q, kc, rk, pk, &dm) : 0u;
+		const uint64_t ballot = __ballot(bits & 1u);
+		if ((threadIdx.x & 63) == 0 && ballot) atomicAdd(&q_count[q], (uint32_t) __popcll(ballot));
+		own += bits >> 1;
+	}
+	if (live && k >= c.n_q) db_count[k - c.n_q] = own;
+}
+
+/* pass 2: row q's pairs from q_offset[q] on through q_cursor[q] (any order), row n_q + d's at db_offset[d], queries ascending */
+__global__ __launch_bounds__(kThreads) void near_fill_kernel(Columns c, const uint64_t *__restrict__ q_offset, uint32_t *__restrict__ q_cursor,
+		const uint64_t *__restrict__ db_offset, uint32_t *__restrict__ other, double *__restrict__ metric, double *__restrict__ dist)
+{
+	const uint32_t n = c.n_q + c.n_db, k = blockIdx.x * kThreads + threadIdx.x, lane = threadIdx.x & 63;
+	const bool live = k < n;
+	const uint32_t kc = live ? k : n - 1;
+	const double rk = c.radius(kc);
+	const double *pk = c.point(kc);
+	uint64_t own = (live && k >= c.n_q) ? db_offset[k - c.n_q] : 0;
+	for (uint32_t q = 0; q < c.n_q; ++q) {
+		double dm = 0.0;
+		const uint32_t bits = live ? near_decide(c, q, kc, rk, pk, &dm) : 0u;
+		const uint64_t ballot = __ballot(bits & 1u);
+		uint32_t base = 0;
+		if (lane == 0 && ballot) base = atomicAdd(&q_cursor[q], (uint32_t) __popcll(ballot));
+		base = __shfl(base, 0, 64);
+		if (bits) {
+			const double dd = ntsm_eval_pca::calc_distance(c.q_cloud + (uint64_t) q * c.dim, pk, c.dim);
+			if (bits & 1u) {
+				const uint64_t p = q_offset[q] + base + (uint32_t) __popcll(ballot & ((1ull << lane) - 1));
+				other[p] = k; metric[p] = dm; dist[p] = dd;
+			}
+			if (bits & 2u) { other[own] = q; metric[own] = dm; dist[own] = dd; ++own; }
+		}
+	}
+}
+
+}  // namespace
+
+extern "C" int ntsm_eval_project_store(int device, const void *db_counts, uint64_t db_stride_bytes, uint32_t n_db, uint32_t n_sites, uint32_t min_cov,
+		const long double *norm, const long double *rot, uint32_t dim, uint32_t db_chunk, double *cloud, uint32_t *db_geno,
+		ntsm_eval_cross_times *times)
+{
+	if (times) *times = ntsm_eval_cross_times {};
+	if ((!db_counts && n_db && n_sites) || (n_sites && (!norm || (dim && !rot))) || (!cloud && n_db && dim)) return -1;
+	if (db_stride_bytes < 8ull * n_sites || db_stride_bytes % 4) return -1;
+	if (n_db && dim) memset(cloud, 0, (size_t) n_db * dim * sizeof(double));     /* no site: inner_product of nothing */
+	if (db_geno && n_db) memset(db_geno, 0, (size_t) n_db * 3 * sizeof(uint32_t));
+	if (n_db == 0 || n_sites == 0) return 0;
+
+	const std::vector<ntsm_x64> tab = ntsm_eval_pca::product_table(norm, rot, n_sites, dim);
+	const uint64_t row_bytes = 8ull * n_sites;
+	HIPCHK(hipSetDevice(device));
+	size_t free_b = 0, total_b = 0;
+	if (db_chunk == 0) HIPCHK(hipMemGetInfo(&free_b, &total_b));
+	const uint32_t chunk = ntsm_eval_chunk::samples_per_pass(db_chunk, n_db, free_b, row_bytes + 8ull * dim + 12, tab.size() * sizeof(ntsm_x64));
+
+	ntsm_hip::Buffers b;
+	ntsm_hip::Events<3> ev;
+	uint32_t *d_raw, *d_geno;
+	double *d_cloud;
+	ntsm_x64 *d_tab;
+	HIPCHK(b.alloc(&d_raw, (uint64_t) chunk * n_sites * 2));
+	HIPCHK(b.alloc(&d_geno, (uint64_t) chunk * 3));
+	HIPCHK(b.alloc(&d_cloud, (uint64_t) chunk * dim));
+	HIPCHK(b.alloc(&d_tab, tab.size()));
+	HIPCHK(ev.create());
+	ntsm_eval_cross_times tm {};
+	auto t = wall::now();
+	HIPCHK(hipMemcpy(d_tab, tab.data(), tab.size() * sizeof(ntsm_x64), hipMemcpyHostToDevice));
+	tm.upload_ms += ms_since(t);
+
+	for (uint32_t c0 = 0; c0 < n_db; c0 += chunk) {
+		const uint32_t cn = std::min(chunk, n_db - c0);
+		t = wall::now();
+		HIPCHK(hipMemcpy2D(d_raw, row_bytes, (const char *) db_counts + (uint64_t) c0 * db_stride_bytes, db_stride_bytes, row_bytes, cn,
+				hipMemcpyHostToDevice));
+		tm.upload_ms += ms_since(t);
+		HIPCHK(hipEventRecord(ev[0], 0));
+		if (db_geno) {
+			ntsm_eval_chunk::launch_tally(d_raw, cn, n_sites, min_cov, d_geno);
+			HIPCHK(hipGetLastError());
+		}
+		HIPCHK(hipEventRecord(ev[1], 0));
+		if (dim) {
+			ntsm_eval_pca::launch_project(d_raw, cn, n_sites, min_cov, d_tab, dim, d_cloud);
+			HIPCHK(hipGetLastError());
+		}
+		HIPCHK(hipEventRecord(ev[2], 0));
+		HIPCHK(hipEventSynchronize(ev[2]));
+		t = wall::now();
+		if (dim) HIPCHK(hipMemcpy(cloud + (uint64_t) c0 * dim, d_cloud, (size_t) cn * dim * sizeof(double), hipMemcpyDeviceToHost));
+		if (db_geno) HIPCHK(hipMemcpy(db_geno + (uint64_t) c0 * 3, d_geno, (size_t) cn * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+		tm.download_ms += ms_since(t);
+		float ms = 0;
+		HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+		tm.prepare_kernel_ms += ms;
+		HIPCHK(hipEventElapsedTime(&ms, ev[1], ev[2]));
+		tm.cross_kernel_ms += ms;
+		tm.chunks++;
+	}
+	if (times) *times = tm;
+	return 0;
+}
+
+extern "C" int ntsm_eval_cross_candidates(int device, const double *q_cloud, const double *q_radius, uint32_t n_q, const double *db_cloud,
+		const double *db_radius, uint32_t n_db, uint32_t dim, uint32_t *pi, uint32_t *pk, double *dist, uint64_t capacity, uint64_t *n_pairs,
+		double *kernel_ms)
+{
+	if (kernel_ms) *kernel_ms = 0;
+	if (!n_pairs || (n_q && (!q_radius || (dim && !q_cloud))) || (n_db && (!db_radius || (dim && !db_cloud))) || (capacity && (!pi || !pk || !dist)))
+		return -1;
+	*n_pairs = 0;
+	const uint64_t n64 = (uint64_t) n_q + n_db;
+	if (n64 > UINT32_MAX) return -1;
+	const uint32_t n = (uint32_t) n64;
+	if (n_q == 0 || n < 2) return 0;                                             /* no query: no pair has one */
+	HIPCHK(hipSetDevice(device));
+	ntsm_hip::Buffers b;
+	double *d_qc, *d_qr, *d_dc, *d_dr;
+	uint32_t *d_qcount, *d_dcount;
+	HIPCHK(b.alloc(&d_qc, (uint64_t) n_q * dim));
+	HIPCHK(b.alloc(&d_qr, n_q));
+	HIPCHK(b.alloc(&d_dc, (uint64_t) n_db * dim));
+	HIPCHK(b.alloc(&d_dr, n_db));
+	HIPCHK(b.alloc(&d_qcount, n_q));
+	HIPCHK(b.alloc(&d_dcount, n_db));
+	if (dim) HIPCHK(hipMemcpy(d_qc, q_cloud, (uint64_t) n_q * dim * sizeof(double), hipMemcpyHostToDevice));
+	HIPCHK(hipMemcpy(d_qr, q_radius, n_q * sizeof(double), hipMemcpyHostToDevice));
+	if (dim && n_db) HIPCHK(hipMemcpy(d_dc, db_cloud, (uint64_t) n_db * dim * sizeof(double), hipMemcpyHostToDevice));
+	if (n_db) HIPCHK(hipMemcpy(d_dr, db_radius, (uint64_t) n_db * sizeof(double), hipMemcpyHostToDevice));
+	HIPCHK(hipMemset(d_qcount, 0, n_q * sizeof(uint32_t)));
+	const Columns cols { d_qc, d_qr, d_dc, d_dr, n_q, n_db, dim };
+	const dim3 grid((n + kThreads - 1) / kThreads);
+	ntsm_hip::Events<2> ev;
+	HIPCHK(ev.create());
+	HIPCHK(hipEventRecord(ev[0], 0));
+	hipLaunchKernelGGL(near_count_kernel, grid, dim3(kThreads), 0, 0, cols, d_qcount, d_dcount);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(ev[1], 0));
+	std::vector<uint32_t> count(n, 0);
+	HIPCHK(hipMemcpy(count.data(), d_qcount, n_q * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	if (n_db) HIPCHK(hipMemcpy(count.data() + n_q, d_dcount, (uint64_t) n_db * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	float ms0 = 0;
+	HIPCHK(hipEventElapsedTime(&ms0, ev[0], ev[1]));
+	std::vector<uint64_t> offset((uint64_t) n + 1, 0);
+	for (uint32_t i = 0; i < n; ++i) offset[i + 1] = offset[i] + count[i];
+	const uint64_t total = offset[n];
+	*n_pairs = total;
+	if (kernel_ms) *kernel_ms = ms0;
+	if (total > capacity) return NTSM_EVAL_E_CAPACITY;
+	if (total == 0) return 0;
+	uint64_t *d_offset;
+	uint32_t *d_other;
+	double *d_metric, *d_dist;
+	HIPCHK(b.alloc(&d_offset, (uint64_t) n + 1));
+	HIPCHK(b.alloc(&d_other, total));
+	HIPCHK(b.alloc(&d_metric, total));
+	HIPCHK(b.alloc(&d_dist, total));
+	HIPCHK(hipMemcpy(d_offset, offset.data(), ((uint64_t) n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
+	HIPCHK(hipMemset(d_qcount, 0, n_q * sizeof(uint32_t)));                      /* now the rows' cursors */
+	HIPCHK(hipEventRecord(ev[0], 0));
+	hipLaunchKernelGGL(near_fill_kernel, grid, dim3(kThreads), 0, 0, cols, d_offset, d_qcount, d_offset + n_q, d_other, d_metric, d_dist);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(ev[1], 0));
+	std::vector<uint32_t> k(total);
+	std::vector<double> metric(total), dd(total);
+	HIPCHK(hipMemcpy(k.data(), d_other, total * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(metric.data(), d_metric, total * sizeof(double), hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(dd.data(), d_dist, total * sizeof(double), hipMemcpyDeviceToHost));
+	float ms1 = 0;
+	HIPCHK(hipEventElapsedTime(&ms1, ev[0], ev[1]));
+	if (kernel_ms) *kernel_ms = (double) ms0 + ms1;
+	/* a radius row by ascending evalMetric (nanoflann sorts its matches), exact ties by ascending k; a search-all row by k */
+	std::vector<uint64_t> ord;
+	for (uint32_t i = 0; i < n; ++i) {
+		const uint64_t lo = offset[i], hi = offset[i + 1];
+		if (lo == hi) continue;
+		ord.resize(hi - lo);
+		for (uint64_t p = lo; p < hi; ++p) ord[p - lo] = p;
+		const bool by_metric = (i < n_q ? q_radius[i] : db_radius[i - n_q]) < DBL_MAX;
+		std::sort(ord.begin(), ord.end(), [&](uint64_t x, uint64_t y) {
+			if (by_metric && metric[x] != metric[y]) return metric[x] < metric[y];
+			return k[x] < k[y];
+		});
+		for (uint64_t q = 0; q < ord.size(); ++q) {
+			pi[lo + q] = i;
+			pk[lo + q] = k[ord[q]];
+			dist[lo + q] = dd[ord[q]];
+		}
+	}
+	return 0;
+}
+
+extern "C" int ntsm_eval_cross_score_pairs(int device, const uint32_t *q_counts, uint32_t n_q, const void *db_counts, uint64_t db_stride_bytes,
+		uint32_t n_db, uint32_t n_sites, uint32_t min_cov, const uint32_t *pi, const uint32_t *pk, uint64_t n_pairs, uint32_t db_chunk,
+		ntsm_eval_record *out, ntsm_eval_cross_times *times)
+{
+	if (times) *times = ntsm_eval_cross_times {};
+	if ((!q_counts && n_q && n_sites) || (!db_counts && n_db && n_sites) || (n_pairs && (!pi || !pk || !out))) return -1;
+	if (db_stride_bytes < 8ull * n_sites || db_stride_bytes % 4) return -1;
+	const uint64_t n = (uint64_t) n_q + n_db;
+	if (n > UINT32_MAX) return -1;
+	for (uint64_t p = 0; p < n_pairs; ++p)
+		if (pi[p] >= n || pk[p] >= n || pi[p] == pk[p] || (pi[p] >= n_q && pk[p] >= n_q)) return -1;
+	if (n_pairs == 0) return 0;
+	memset(out, 0, n_pairs * sizeof(ntsm_eval_record));
+	if (n_sites == 0) return 0;
+
+	/* the distinct database samples of the list, ascending (the store is read front to back), and each pair's */
+	std::vector<uint32_t> named;
+	for (uint64_t p = 0; p < n_pairs; ++p) {
+		if (pi[p] >= n_q) named.push_back(pi[p] - n_q);
+		if (pk[p] >= n_q) named.push_back(pk[p] - n_q);
+	}
+	std::sort(named.begin(), named.end());
+	named.erase(std::unique(named.begin(), named.end()), named.end());
+	const uint64_t row_bytes = 8ull * n_sites;
+	HIPCHK(hipSetDevice(device));
+	size_t free_b = 0, total_b = 0;
+	if (db_chunk == 0) HIPCHK(hipMemGetInfo(&free_b, &total_b));
+	const uint32_t n_named = (uint32_t) named.size();
+	const uint32_t chunk = std::max(1u, ntsm_eval_chunk::samples_per_pass(db_chunk, n_named, free_b, 2 * row_bytes,
+			2ull * n_q * row_bytes + n_pairs * (sizeof(ntsm_eval_record) + 8)));
+	const uint32_t passes = std::max(1u, (n_named + chunk - 1) / chunk);         /* a list of query-query pairs still takes one */
+	/* pairs grouped by pass: a pair without a database sample goes with the first */
+	std::vector<std::vector<uint64_t>> of_pass(passes);
+	const auto rank = [&](uint32_t s) { return (uint32_t) (std::lower_bound(named.begin(), named.end(), s - n_q) - named.begin()); };
+	for (uint64_t p = 0; p < n_pairs; ++p) {
+		const uint32_t s = pi[p] >= n_q ? pi[p] : pk[p];
+		of_pass[s >= n_q ? rank(s) / chunk : 0].push_back(p);
+	}
+	uint64_t most = 0;
+	for (const auto &v : of_pass) most = std::max<uint64_t>(most, v.size());
+
+	ntsm_hip::Buffers b;
+	ntsm_hip::Events<3> ev;
+	uint32_t *d_rows, *d_pi, *d_pk;
+	double *d_term;
+	ntsm_eval_record *d_out;
+	const uint64_t slots = (uint64_t) n_q + chunk, qcells = (uint64_t) n_q * n_sites;
+	HIPCHK(b.alloc(&d_rows, slots * n_sites * 2));
+	HIPCHK(b.alloc(&d_term, slots * n_sites));
+	HIPCHK(b.alloc(&d_pi, most));
+	HIPCHK(b.alloc(&d_pk, most));
+	HIPCHK(b.alloc(&d_out, most));
+	HIPCHK(ev.create());
+	ntsm_eval_cross_times tm {};
+	auto t = wall::now();
+	if (qcells) HIPCHK(hipMemcpy(d_rows, q_counts, qcells * 2 * sizeof(uint32_t), hipMemcpyHostToDevice));
+	tm.upload_ms += ms_since(t);
+	float ms = 0;
+	if (qcells) {
+		HIPCHK(hipEventRecord(ev[0], 0));
+		ntsm_eval_pca::launch_term(d_rows, qcells, min_cov, d_term);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipEventRecord(ev[1], 0));
+		HIPCHK(hipEventSynchronize(ev[1]));
+		HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+		tm.prepare_kernel_ms += ms;
+	}
+	std::vector<uint32_t> a, c;
+	std::vector<ntsm_eval_record> rec;
+	for (uint32_t pass = 0; pass < passes; ++pass) {
+		const std::vector<uint64_t> &list = of_pass[pass];
+		if (list.empty()) continue;
+		const uint32_t r0 = pass * chunk, rn = r0 < n_named ? std::min(chunk, n_named - r0) : 0;
+		t = wall::now();
+		for (uint32_t r = 0; r < rn; ++r)                                        /* row by row from the mapped store */
+			HIPCHK(hipMemcpy(d_rows + ((uint64_t) n_q + r) * n_sites * 2, (const char *) db_counts + (uint64_t) named[r0 + r] * db_stride_bytes,
+					row_bytes, hipMemcpyHostToDevice));
+		a.resize(list.size());
+		c.resize(list.size());
+		const auto slot = [&](uint32_t s) { return s < n_q ? s : n_q + rank(s) - r0; };
+		for (uint64_t x = 0; x < list.size(); ++x) { a[x] = slot(pi[list[x]]); c[x] = slot(pk[list[x]]); }
+		HIPCHK(hipMemcpy(d_pi, a.data(), a.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+		HIPCHK(hipMemcpy(d_pk, c.data(), c.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+		tm.upload_ms += ms_since(t);
+		HIPCHK(hipEventRecord(ev[0], 0));
+		if (rn) {
+			ntsm_eval_pca::launch_term(d_rows + qcells * 2, (uint64_t) rn * n_sites, min_cov, d_term + qcells);
+			HIPCHK(hipGetLastError());
+		}
+		HIPCHK(hipEventRecord(ev[1], 0));
+		ntsm_eval_pca::launch_score(d_rows, d_term, n_sites, min_cov, d_pi, d_pk, list.size(), d_out);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipEventRecord(ev[2], 0));
+		HIPCHK(hipEventSynchronize(ev[2]));
+		HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+		tm.prepare_kernel_ms += ms;
+		HIPCHK(hipEventElapsedTime(&ms, ev[1], ev[2]));
+		tm.cross_kernel_ms += ms;
+		t = wall::now();
+		rec.resize(list.size());
+		HIPCHK(hipMemcpy(rec.data(), d_out, list.size() * sizeof(ntsm_eval_record), hipMemcpyDeviceToHost));
+		for (uint64_t x = 0; x < list.size(); ++x) out[list[x]] = rec[x];        /* back to list order */
+		tm.download_ms += ms_since(t);
+		tm.chunks++;
+	}
+	if (times) *times = tm;
+	return 0;
+}

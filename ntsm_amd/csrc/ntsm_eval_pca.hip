@@ -21,6 +21,9 @@
  *
  * Scoring.  One lane per listed pair, both rows gathered; the per-site update and the record are ntsm_eval_score.h's, the
  * ones ntsm_eval_pair_kernel calls, so a record is bit-identical to the all-pairs one (sample pi as sample 1).
+ *
+ * What the search against a cohort store (ntsm_eval_near.hip) needs as well -- the projection kernel and its product table,
+ * evalMetric, calcDistance, the selection rule, the term and scoring kernels -- is ntsm_eval_pca.h's.
  */
 #include <hip/hip_runtime.h>
 
@@ -30,6 +33,7 @@
 #include <vector>
 
 #include "../../include/ntsm_eval_hip.h"
+#include "ntsm_eval_pca.h"
 #include "ntsm_eval_score.h"
 #define NTSM_HIP_TAG "ntsm_eval"
 #include "ntsm_hip_scope.h"
@@ -44,78 +48,12 @@ struct ntsm_eval_session {
 
 namespace {
 
-constexpr int kThreads = 256;
+using ntsm_eval_pca::kThreads;
 
-__global__ __launch_bounds__(kThreads) void pca_term_kernel(const uint32_t *counts, uint64_t cells, uint32_t min_cov, double *term)
-{
-	const uint64_t cell = (uint64_t) blockIdx.x * kThreads + threadIdx.x;
-	if (cell >= cells) return;
-	term[cell] = ntsm_eval_term(counts[cell * 2], counts[cell * 2 + 1], min_cov);
-}
-
-/* m_cloud[i][d] (:166-211); tab[(site * dim + d) * 4 + code], code 0 / 1 / 2 = genotype 0 / 0.5 / 1, 3 = missing */
-__global__ __launch_bounds__(kThreads) void pca_project_kernel(const uint32_t *__restrict__ counts, uint32_t n, uint32_t m, uint32_t min_cov,
-		const ntsm_x64 *__restrict__ tab, uint32_t dim, double *__restrict__ cloud)
-{
-	const uint32_t i = blockIdx.x * kThreads + threadIdx.x, d = blockIdx.y;
-	if (i >= n) return;
-	const uint32_t *row = counts + (uint64_t) i * m * 2;
-	double acc = 0.0;
-	for (uint32_t j = 0; j < m; ++j) {
-		const uint32_t a0 = row[2 * j], a1 = row[2 * j + 1];
-		const uint32_t cAT = a0 > min_cov ? a0 : 0u, cCG = a1 > min_cov ? a1 : 0u;
-		const uint32_t den = cAT + cCG;                                         /* unsigned, as the reference's */
-		uint32_t code = 3;
-		if (den != 0) {
-			const double g = __ddiv_rn((double) cAT, (double) den);
-			code = g < 0.25 ? 0u : g < 0.75 ? 1u : 2u;                          /* (g - 0.25) < 0.0 has the sign of g - 0.25 */
-		}
-		acc = ntsm_x87_acc(acc, tab[((uint64_t) j * dim + d) * 4 + code]);
-	}
-	cloud[(uint64_t) i * dim + d] = acc;
-}
-
-/* nanoflann L2_Adaptor::evalMetric (vendor/nanoflann.hpp:452-486) */
-__device__ inline double eval_metric(const double *a, const double *b, uint32_t dim)
-{
-	double result = 0.0;
-	uint32_t t = 0;
-	for (; t + 4 <= dim; t += 4) {
-		const double d0 = __dsub_rn(a[t], b[t]), d1 = __dsub_rn(a[t + 1], b[t + 1]);
-		const double d2 = __dsub_rn(a[t + 2], b[t + 2]), d3 = __dsub_rn(a[t + 3], b[t + 3]);
-		result = __dadd_rn(result, __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(d0, d0), __dmul_rn(d1, d1)), __dmul_rn(d2, d2)), __dmul_rn(d3, d3)));
-	}
-	for (; t < dim; ++t) {
-		const double d0 = __dsub_rn(a[t], b[t]);
-		result = __dadd_rn(result, __dmul_rn(d0, d0));
-	}
-	return result;
-}
-
-/* calcDistance (:926-932): pow(x, 2) folds to x * x */
-__device__ inline double calc_distance(const double *a, const double *b, uint32_t dim)
-{
-	double dist = 0.0;
-	for (uint32_t t = 0; t < dim; ++t) {
-		const double x = a[t] < b[t] ? __dsub_rn(b[t], a[t]) : __dsub_rn(a[t], b[t]);
-		dist = __dadd_rn(dist, __dmul_rn(x, x));
-	}
-	return dist;
-}
-
-/* computeScorePCA's selection of pair (i, k) (:315-337 radius rows, :358-365 search-all rows) */
+/* computeScorePCA's selection of pair (i, k) of one cloud (ntsm_eval_pca.h) */
 __device__ inline bool pca_take(const double *cloud, const double *radius, uint32_t dim, uint32_t i, uint32_t k, double ri, double *metric)
 {
-	const double rk = radius[k];
-	if (!(ri < DBL_MAX)) {
-		*metric = 0.0;
-		return !(DBL_MAX == rk && k <= i);
-	}
-	const double dm = eval_metric(cloud + (uint64_t) i * dim, cloud + (uint64_t) k * dim, dim);
-	*metric = dm;
-	if (!(dm < ri)) return false;
-	if (ri == rk) return k > i;
-	return !(ri < rk);
+	return ntsm_eval_pca::take(cloud + (uint64_t) i * dim, cloud + (uint64_t) k * dim, dim, i, k, ri, radius[k], metric);
 }
 
 /* pass 1: count[i] = number of pairs of row i */
@@ -162,26 +100,11 @@ __global__ __launch_bounds__(kThreads) void pca_fill_kernel(const double *__rest
 			const uint64_t p = base + before + (uint32_t) __popcll(ballot & ((1ull << lane) - 1));
 			pk[p] = k;
 			metric[p] = dm;
-			dist[p] = calc_distance(cloud + (uint64_t) i * dim, cloud + (uint64_t) k * dim, dim);
+			dist[p] = ntsm_eval_pca::calc_distance(cloud + (uint64_t) i * dim, cloud + (uint64_t) k * dim, dim);
 		}
 		base += total;
 		__syncthreads();
 	}
-}
-
-/* one record per listed pair, sample pi as sample 1 */
-__global__ __launch_bounds__(kThreads) void pca_score_kernel(const uint32_t *__restrict__ counts, const double *__restrict__ term, uint32_t m, uint32_t min_cov,
-		const uint32_t *__restrict__ pi, const uint32_t *__restrict__ pk, uint64_t n_pairs, ntsm_eval_record *__restrict__ out)
-{
-	const uint64_t p = (uint64_t) blockIdx.x * kThreads + threadIdx.x;
-	if (p >= n_pairs) return;
-	const uint32_t *ra = counts + (uint64_t) pi[p] * m * 2, *rb = counts + (uint64_t) pk[p] * m * 2;
-	const double *ta = term + (uint64_t) pi[p] * m, *tb = term + (uint64_t) pk[p] * m;
-	ntsm_eval_acc acc;
-	for (uint32_t site = 0; site < m; ++site)
-		acc.add(ntsm_eval_side_of(ra[2 * site], ra[2 * site + 1], ta[site], min_cov),
-		        ntsm_eval_side_of(rb[2 * site], rb[2 * site + 1], tb[site], min_cov), min_cov);
-	out[p] = acc.record();
 }
 
 /* the session's device state: the upload and the term of every cell */
@@ -191,7 +114,7 @@ int session_upload(ntsm_eval_session *s, const uint32_t *counts, uint64_t cells)
 	HIPCHK(hipMalloc(&s->term, (cells ? cells : 1) * sizeof(double)));
 	if (cells == 0) return 0;
 	HIPCHK(hipMemcpy(s->counts, counts, cells * 2 * sizeof(uint32_t), hipMemcpyHostToDevice));
-	hipLaunchKernelGGL(pca_term_kernel, dim3((unsigned) ((cells + kThreads - 1) / kThreads)), dim3(kThreads), 0, 0, s->counts, cells, s->min_cov, s->term);
+	ntsm_eval_pca::launch_term(s->counts, cells, s->min_cov, s->term);
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipDeviceSynchronize());
 	return 0;
@@ -226,21 +149,7 @@ extern "C" int ntsm_eval_project(ntsm_eval_session *h, const long double *norm, 
 	if (!h || (h->m && (!norm || (dim && !rot))) || (h->n && dim && !cloud)) return -1;
 	const uint32_t n = h->n, m = h->m;
 	if ((uint64_t) n * dim == 0) return 0;
-	/* the x87 products RN64(v_c * rot[d][j]) (:190-210): v_c = double(c - norm[j]) for c = 0, 0.5, 1; +0.0 for a missing site */
-	std::vector<ntsm_x64> tab((uint64_t) m * dim * 4);
-	for (uint32_t j = 0; j < m; ++j) {
-		double v[4];
-		for (int c = 0; c < 3; ++c) {
-			volatile long double diff = (long double) (c * 0.5) - norm[j];
-			v[c] = (double) diff;
-		}
-		v[3] = 0.0;
-		for (uint32_t d = 0; d < dim; ++d)
-			for (int c = 0; c < 4; ++c) {
-				volatile long double prod = (long double) v[c] * rot[(uint64_t) d * m + j];
-				tab[((uint64_t) j * dim + d) * 4 + c] = ntsm_x64_from_ld(prod);
-			}
-	}
+	const std::vector<ntsm_x64> tab = ntsm_eval_pca::product_table(norm, rot, m, dim);
 	if (m == 0) {                                                               /* no site: inner_product of nothing */
 		for (uint64_t t = 0; t < (uint64_t) n * dim; ++t) cloud[t] = 0.0;
 		return 0;
@@ -255,7 +164,7 @@ extern "C" int ntsm_eval_project(ntsm_eval_session *h, const long double *norm, 
 	ntsm_hip::Events<2> ev;
 	HIPCHK(ev.create());
 	HIPCHK(hipEventRecord(ev[0], 0));
-	hipLaunchKernelGGL(pca_project_kernel, dim3((n + kThreads - 1) / kThreads, dim), dim3(kThreads), 0, 0, h->counts, n, m, h->min_cov, d_tab, dim, d_cloud);
+	ntsm_eval_pca::launch_project(h->counts, n, m, h->min_cov, d_tab, dim, d_cloud);
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipEventRecord(ev[1], 0));
 	HIPCHK(hipMemcpy(cloud, d_cloud, (uint64_t) n * dim * sizeof(double), hipMemcpyDeviceToHost));
@@ -361,8 +270,7 @@ extern "C" int ntsm_eval_score_pairs(ntsm_eval_session *h, const uint32_t *pi, c
 	ntsm_hip::Events<2> ev;
 	HIPCHK(ev.create());
 	HIPCHK(hipEventRecord(ev[0], 0));
-	hipLaunchKernelGGL(pca_score_kernel, dim3((unsigned) ((n_pairs + kThreads - 1) / kThreads)), dim3(kThreads), 0, 0, h->counts, h->term, h->m, h->min_cov,
-			d_pi, d_pk, n_pairs, d_out);
+	ntsm_eval_pca::launch_score(h->counts, h->term, h->m, h->min_cov, d_pi, d_pk, n_pairs, d_out);
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipEventRecord(ev[1], 0));
 	HIPCHK(hipMemcpy(out, d_out, n_pairs * sizeof(ntsm_eval_record), hipMemcpyDeviceToHost));

@@ -1,4 +1,5 @@
-"""ctypes plumbing for include/ntsm_eval_hip.h (all-pairs scoring of ntsmEval on the GPU); used by tests and tools.
+"""ctypes plumbing for include/ntsm_eval_hip.h (all-pairs scoring of ntsmEval on the GPU, its PCA-guided search, queries and
+that search against a cohort store); used by tests and tools.
 Loaded on demand: `import ntsm_amd.eval`.  Fails loudly when libntsm_eval_hip.so has not been built."""
 import ctypes as C
 import os
@@ -183,3 +184,114 @@ def cross(q, db, min_cov=1, db_chunk=0, device=0):
     if rc:
         raise RuntimeError("ntsm_eval_cross failed: %d" % rc)
     return out, geno, times
+
+
+# ---- the PCA-guided search against a cohort store (ntsmEval --index / --near; include/ntsm_eval_hip.h:
+# ntsm_eval_project_store, ntsm_eval_cross_candidates, ntsm_eval_cross_score_pairs).  Indices follow the concatenation
+# [queries; database]: database sample d is sample n_q + d.
+lib.ntsm_eval_project_store.restype = C.c_int
+lib.ntsm_eval_project_store.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_longdouble),
+                                        C.POINTER(C.c_longdouble), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(CrossTimes)]
+lib.ntsm_eval_cross_candidates.restype = C.c_int
+lib.ntsm_eval_cross_candidates.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+lib.ntsm_eval_cross_score_pairs.restype = C.c_int
+lib.ntsm_eval_cross_score_pairs.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
+                                            C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.POINTER(CrossTimes)]
+
+
+class Records:
+    """Database samples as a cohort store holds them: the counts of sample d, [n_sites][2] uint32, at `address + d * stride`
+    inside `buf`.  Records.of(db, head_bytes) lays a dense [n_db][n_sites][2] array out with head_bytes of filler in front
+    of every sample's counts (a store's record head is 1,056 bytes)."""
+
+    def __init__(self, buf, offset, stride, n, m):
+        self.buf, self.offset, self.stride, self.n, self.m = buf, offset, stride, n, m
+
+    @property
+    def address(self):
+        return self.buf.ctypes.data + self.offset
+
+    @classmethod
+    def of(cls, db, head_bytes=0):
+        db = np.ascontiguousarray(db, dtype=np.uint32)
+        if db.ndim != 3 or db.shape[2] != 2 or head_bytes % 4:
+            raise ValueError("database samples are [samples][sites][2]; the head is a multiple of 4 bytes")
+        n, m = db.shape[0], db.shape[1]
+        stride = head_bytes + 8 * m
+        buf = np.full(n * stride + 8, 0xAB, dtype=np.uint8)
+        if n and m:
+            rows = np.lib.stride_tricks.as_strided(buf[head_bytes:], shape=(n, 8 * m), strides=(stride, 1))
+            rows[:] = db.reshape(n, 2 * m).view(np.uint8)
+        return cls(buf, head_bytes, stride, n, m)
+
+
+def _records(db):
+    return db if isinstance(db, Records) else Records.of(db)
+
+
+def project_store(db, norm, rot, min_cov=1, db_chunk=0, device=0):
+    """db: uint32 [n_db][n_sites][2] or Records; norm, rot as Session.project.  Returns (cloud [n_db][dim] -- the bits of
+    project() on the dense samples --, geno [n_db][3] as cross()'s, times)."""
+    r = _records(db)
+    norm = np.ascontiguousarray(norm, dtype=np.longdouble)
+    rot = np.ascontiguousarray(rot, dtype=np.longdouble).reshape(-1, r.m) if r.m else np.zeros((np.shape(rot)[0], 0), dtype=np.longdouble)
+    dim = rot.shape[0]
+    cloud = np.zeros((r.n, dim), dtype=np.float64)
+    geno = np.zeros((r.n, 3), dtype=np.uint32)
+    times = CrossTimes()
+    rc = lib.ntsm_eval_project_store(device, r.address, r.stride, r.n, r.m, min_cov, _ld_ptr(norm), _ld_ptr(rot), dim, db_chunk,
+                                     cloud.ctypes.data, geno.ctypes.data, C.byref(times))
+    if rc:
+        raise RuntimeError("ntsm_eval_project_store failed: %d" % rc)
+    return cloud, geno, times
+
+
+def cross_candidates(q_cloud, q_radius, db_cloud, db_radius, capacity=None, device=0):
+    """The pairs of candidates() on the concatenated clouds and radii that have a query in them, in its order:
+    (pi, pk, calcDistance, kernel ms).  capacity as Session.candidates."""
+    q_cloud = np.ascontiguousarray(q_cloud, dtype=np.float64)
+    db_cloud = np.ascontiguousarray(db_cloud, dtype=np.float64)
+    q_radius = np.ascontiguousarray(q_radius, dtype=np.float64)
+    db_radius = np.ascontiguousarray(db_radius, dtype=np.float64)
+    n_q, n_db = len(q_radius), len(db_radius)
+    dim = q_cloud.shape[1] if q_cloud.ndim == 2 else 0
+    if n_q and n_db and (db_cloud.ndim != 2 or db_cloud.shape[1] != dim):
+        raise ValueError("cross_candidates: both clouds are [samples][dim]")
+    ms, n = C.c_double(), C.c_uint64()
+
+    def call(pi, pk, dist, cap):
+        return lib.ntsm_eval_cross_candidates(device, q_cloud.ctypes.data, q_radius.ctypes.data, n_q, db_cloud.ctypes.data, db_radius.ctypes.data, n_db,
+                                              dim, pi, pk, dist, cap, C.byref(n), C.byref(ms))
+    if capacity is None:
+        rc = call(None, None, None, 0)
+        if rc not in (0, E_CAPACITY):
+            raise RuntimeError("ntsm_eval_cross_candidates failed: %d" % rc)
+        capacity = n.value
+    pi, pk = np.zeros(capacity, dtype=np.uint32), np.zeros(capacity, dtype=np.uint32)
+    dist = np.zeros(capacity, dtype=np.float64)
+    rc = call(pi.ctypes.data, pk.ctypes.data, dist.ctypes.data, capacity)
+    if rc == E_CAPACITY:
+        raise ValueError("capacity %d < %d candidate pairs" % (capacity, n.value), n.value)
+    if rc:
+        raise RuntimeError("ntsm_eval_cross_candidates failed: %d" % rc)
+    k = n.value
+    return pi[:k], pk[:k], dist[:k], ms.value
+
+
+def cross_score_pairs(q, db, pi, pk, min_cov=1, db_chunk=0, device=0):
+    """q: uint32 [n_q][n_sites][2]; db: [n_db][n_sites][2] or Records; pi, pk in the concatenation's numbering, a query in
+    every pair.  Returns (records, sample pi as sample 1 -- the bits of score_pairs on the concatenation --, times)."""
+    q = np.ascontiguousarray(q, dtype=np.uint32)
+    r = _records(db)
+    if q.ndim != 3 or q.shape[2] != 2 or q.shape[1] != r.m:
+        raise ValueError("cross_score_pairs: q and db are [samples][sites][2] over the same sites")
+    pi = np.ascontiguousarray(pi, dtype=np.uint32)
+    pk = np.ascontiguousarray(pk, dtype=np.uint32)
+    out = np.zeros(len(pi), dtype=RECORD)
+    times = CrossTimes()
+    rc = lib.ntsm_eval_cross_score_pairs(device, q.ctypes.data, q.shape[0], r.address, r.stride, r.n, r.m, min_cov, pi.ctypes.data, pk.ctypes.data,
+                                         len(pi), db_chunk, out.ctypes.data, C.byref(times))
+    if rc:
+        raise RuntimeError("ntsm_eval_cross_score_pairs failed: %d" % rc)
+    return out, times

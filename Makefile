@@ -6,7 +6,8 @@
 #   build/ntsm_host_test      host-logic test driver (no GPU calls)
 #   ntsm_amd/libntsm_eval_hip.so, build/ntsmEval   all-pairs scoring of ntsmEval (HIP library + CLI mirror), its PCA-guided
 #                                                  search, queries against a cohort store (--pack / --against) and the
-#                                                  PCA-guided search against one (--index / --near)
+#                                                  PCA-guided search against one (--index / --near), and both runs over
+#                                                  the store's own samples (--within / --within-near)
 #   ntsm_amd/libntsm_vcf_hip.so, build/ntsmVCF     multi-sample VCF to PCA matrix + centre file (HIP library + CLI mirror);
 #                                                  with --rotation also the PCA, through libntsm_pca_hip.so
 #   ntsm_amd/libntsm_pca_hip.so, build/ntsmPCA     exact PCA of the ntsmVCF matrix: rotation for ntsmEval -p (HIP library + CLI)
@@ -78,11 +79,14 @@ xlib:
 # + queries against a cohort store (--against): ntsm_eval_cross.hip; the store itself is host code (host/eval_store.hpp)
 # + the PCA-guided search against a store (--index / --near): ntsm_eval_near.hip; it shares a chunk's preparation with the cross
 #   path (ntsm_eval_chunk.h) and the search's steps with the session search (ntsm_eval_pca.h); the index is host code (host/eval_index.hpp)
-EVALSRC := $(CSRC)/ntsm_eval.hip $(CSRC)/ntsm_eval_pca.hip $(CSRC)/ntsm_eval_cross.hip $(CSRC)/ntsm_eval_near.hip
-ntsm_amd/libntsm_eval_hip.so: $(EVALSRC) $(CSRC)/ntsm_eval_score.h $(CSRC)/ntsm_eval_chunk.h $(CSRC)/ntsm_eval_pca.h $(CSRC)/ntsm_hip_scope.h $(CSRC)/xprec.h include/ntsm_eval_hip.h
+# + the pairs inside a store (--within / --within-near): ntsm_eval_within.hip; the band and pass arithmetic is host code that
+#   the library and the CLI share (host/eval_within.hpp)
+EVALSRC := $(CSRC)/ntsm_eval.hip $(CSRC)/ntsm_eval_pca.hip $(CSRC)/ntsm_eval_cross.hip $(CSRC)/ntsm_eval_near.hip $(CSRC)/ntsm_eval_within.hip
+ntsm_amd/libntsm_eval_hip.so: $(EVALSRC) $(CSRC)/ntsm_eval_score.h $(CSRC)/ntsm_eval_chunk.h $(CSRC)/ntsm_eval_pca.h $(CSRC)/ntsm_hip_scope.h $(CSRC)/xprec.h \
+                              $(HOST)/eval_within.hpp include/ntsm_eval_hip.h
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -shared -o $@ $(EVALSRC)
 
-build/ntsmEval: $(HOST)/ntsm_eval_main.cpp $(HOST)/cli.hpp $(HOST)/eval_store.hpp $(HOST)/eval_index.hpp $(HOST)/crc32_fast.cpp $(HOST)/crc32_fast.hpp \
+build/ntsmEval: $(HOST)/ntsm_eval_main.cpp $(HOST)/cli.hpp $(HOST)/eval_store.hpp $(HOST)/eval_index.hpp $(HOST)/eval_within.hpp $(HOST)/crc32_fast.cpp $(HOST)/crc32_fast.hpp \
                 $(HOST)/gz_stream.hpp $(CSRC)/xprec.h include/ntsm_eval_hip.h ntsm_amd/libntsm_eval_hip.so
 	@mkdir -p build
 	$(CXX) $(CXXFLAGS) -ffp-contract=off -o $@ $(HOST)/ntsm_eval_main.cpp $(HOST)/crc32_fast.cpp -Lntsm_amd -lntsm_eval_hip -lz \
@@ -99,6 +103,14 @@ index_check: build/eval_index_check
 build/eval_index_check: tools/eval_index_check.cpp $(HOST)/eval_index.hpp $(HOST)/eval_store.hpp $(HOST)/crc32_fast.cpp $(HOST)/crc32_fast.hpp
 	@mkdir -p build
 	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ tools/eval_index_check.cpp $(HOST)/crc32_fast.cpp -lz
+
+# the band offsets, the band rule and the pass packing of --within / --within-near against brute force likewise
+# (tools/eval_within_check.cpp; not part of `all`)
+within_check: build/eval_within_check
+	build/eval_within_check
+build/eval_within_check: tools/eval_within_check.cpp $(HOST)/eval_within.hpp include/ntsm_eval_hip.h
+	@mkdir -p build
+	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ tools/eval_within_check.cpp
 
 # ntsmVCF (multi-sample VCF -> PCA matrix and centre file): own library, own CLI
 ntsm_amd/libntsm_vcf_hip.so: $(CSRC)/ntsm_vcf.hip $(CSRC)/ntsm_hip_scope.h include/ntsm_vcf_hip.h
@@ -183,4 +195,4 @@ build/gather_bench: tools/gather_bench.hip
 clean:
 	rm -rf build ntsm_amd/*.so
 	$(MAKE) -C oracle clean
-.PHONY: all oracle_all ref_gpu_binding clean ablation abl_tab tab m12 xlib store_check index_check
+.PHONY: all oracle_all ref_gpu_binding clean ablation abl_tab tab m12 xlib store_check index_check within_check

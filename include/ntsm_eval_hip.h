@@ -149,6 +149,44 @@ int ntsm_eval_cross_score_pairs(int device, const uint32_t *q_counts, uint32_t n
 		uint32_t n_db, uint32_t n_sites, uint32_t min_cov, const uint32_t *pi, const uint32_t *pk, uint64_t n_pairs, uint32_t db_chunk,
 		ntsm_eval_record *out, ntsm_eval_cross_times *times);
 
+/* ---- The pairs inside a cohort store (ntsmEval --within / --within-near; ntsm_amd/csrc/ntsm_eval_within.hip and
+ * ntsm_eval_near.hip): computeScore's triangle (src/CompareCounts.hpp:591-624) over a mapped store, in
+ * bands of rows, and the records of listed pairs that name two store samples.  db_counts / db_stride_bytes / db_chunk as for
+ * ntsm_eval_cross; the mapping must outlive the session.
+ *
+ * ntsm_eval_within_open: the store is resident when the chunk rule, asked at 24 bytes per sample and site (what
+ *   ntsm_eval_pairs holds), answers n_db: it is uploaded, transposed and tallied once, here.  Otherwise, or when a non-zero
+ *   db_chunk < n_db forces it, it is streamed: every _rows call uploads its band's rows and walks the columns from row_first on
+ *   in chunks of db_chunk; device memory is then O((n_rows + chunk) * n_sites + the band's records).
+ *   Returns 0, -1 bad argument, -2 HIP error.  n_db < 2 or n_sites == 0: a session without device work.
+ * ntsm_eval_within_rows: the records of the pairs (i, j), row_first <= i < row_first + n_rows, i < j < n_db, in
+ *   ntsm_eval_pair_index order: out[ntsm_eval_pair_index(i, j, n_db) - ntsm_eval_pair_index(row_first, row_first + 1, n_db)],
+ *   each bit for bit ntsm_eval_pairs' record on a dense copy of the store's samples.
+ *   db_geno (may be NULL): [n_db][3]; entries row_first ... n_db - 1 are written as ntsm_eval_cross writes them.
+ *   times (may be NULL): cross_kernel_ms is the pair kernel; chunks counts the column chunks this call uploaded, so it is 0
+ *   exactly when the store is resident; the first call on a resident store also reports the upload and preparation of open.
+ *   Returns 0, -1 (row_first + n_rows > n_db, n_rows == 0, a NULL it needs), -2.  n_db < 2 or n_sites == 0: zeroed outputs. */
+typedef struct ntsm_eval_within_session ntsm_eval_within_session;
+int ntsm_eval_within_open(int device, const void *db_counts, uint64_t db_stride_bytes, uint32_t n_db, uint32_t n_sites,
+		uint32_t min_cov, uint32_t db_chunk, ntsm_eval_within_session **h);
+int ntsm_eval_within_rows(ntsm_eval_within_session *h, uint32_t row_first, uint32_t n_rows, ntsm_eval_record *out,
+		uint32_t *db_geno, ntsm_eval_cross_times *times);
+void ntsm_eval_within_close(ntsm_eval_within_session *h);
+/* For measurements and tests only: force the workgroup width (64 or 256) of later _rows calls in this process; 0 = the
+ * library's rule (64 at every size: DESIGN.md section 9.3 has the measurement that moved it off ntsm_eval_pairs' rule).
+ * Returns 0, -1 for another value. */
+int ntsm_eval_within_tune(uint32_t width);
+
+/* ntsm_eval_store_score_pairs: out[p] is, bit for bit, the record ntsm_eval_score_pairs gives for (pi[p], pk[p]) on a dense
+ *   copy of the store (sample pi[p] as sample 1; either orientation).  A pair needs both of its samples on the device at once:
+ *   the list is cut in list order into passes of at most db_chunk distinct samples (ntsm_amd/csrc/host/eval_within.hpp;
+ *   0 = the library's choice from free memory, at 16 bytes per sample and site), rows are copied one by one from db_counts and
+ *   a sample may be copied in more than one pass; device memory is O(chunk * n_sites + n_pairs).
+ *   Returns 0, -1 (a bad argument, an index out of range, pi[p] == pk[p], db_chunk == 1), -2. */
+int ntsm_eval_store_score_pairs(int device, const void *db_counts, uint64_t db_stride_bytes, uint32_t n_db, uint32_t n_sites,
+		uint32_t min_cov, const uint32_t *pi, const uint32_t *pk, uint64_t n_pairs, uint32_t db_chunk,
+		ntsm_eval_record *out, ntsm_eval_cross_times *times);
+
 #ifdef __cplusplus
 }
 #endif

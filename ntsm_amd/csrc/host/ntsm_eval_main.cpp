@@ -10,7 +10,10 @@
  * projects the store's samples into STORE.pcaidx (eval_index.hpp, ntsm_eval_project_store) and --near STORE FILES... runs the
  * PCA-guided search of the files against the store through that index (ntsm_eval_cross_candidates, then ntsm_eval_cross for
  * the search-all queries and ntsm_eval_cross_score_pairs for the rest) and prints the rows of the -p run over [FILES...,
- * the store's samples] that name one of FILES.  Not built: -b (the debug
+ * the store's samples] that name one of FILES; --within STORE prints the all-to-all run over the store's own samples
+ * (ntsm_eval_within_open / _rows, in bands of rows) and --within-near STORE the -p run over them through the index
+ * (ntsm_eval_cross_candidates without a database side, then ntsm_eval_cross for the search-all samples' rows and
+ * ntsm_eval_store_score_pairs for the rest); neither reads a counts file.  Not built: -b (the debug
  * ground-truth mode) and -p without a normalization file (the reference dies in an assert); both are refused.  Pinned to
  * the reference: stdout equals, byte for byte, that of the unmodified scoring class (oracle/ref_eval_driver.cpp ->
  * oracle/_ref/ref_ntsmEval -t 1) and its recordings, tests/test_eval_reference.py.
@@ -34,6 +37,7 @@
 #include "cli.hpp"
 #include "eval_index.hpp"
 #include "eval_store.hpp"
+#include "eval_within.hpp"
 
 #define PROGRAM "ntsmEval"
 
@@ -48,6 +52,9 @@ struct Opt {                                 /* src/Options.h:44-55 */
 	std::string pca, merge, norm, debug;
 	std::string pack, against;               /* --pack STORE, --against STORE (this build only) */
 	std::string index, near;                 /* --index STORE, --near STORE: the PCA-guided search against a store */
+	std::string within, withinNear;          /* --within STORE, --within-near STORE: the store's samples against each other */
+	unsigned withinRows = 0;                 /* --within-rows N: rows per band of --within, 0 = the band rule */
+	bool withinRowsGiven = false;
 	bool minCovGiven = false, dimGiven = false;
 	bool onlyMerge = false;
 	unsigned dim = 20;                       /* src/Options.h:22, 35-39: the PCA search */
@@ -152,6 +159,14 @@ void printHelpDialog()
 	    "                             by the store's samples that name one of FILES. Rotation,\n"
 	    "                             centre, -d and -c come from the index. Not with -p, -n,\n"
 	    "                             -b, -e or -o.\n"
+	    "      --within = STORE       The all-to-all run over the samples of STORE, read from\n"
+	    "                             the store alone. Takes no FILES. Not with -p, -n, -b, -e\n"
+	    "                             or -o.\n"
+	    "      --within-near = STORE  The PCA-guided run (-p) over the samples of STORE through\n"
+	    "                             STORE.pcaidx. Takes no FILES; rotation, centre, -d and -c\n"
+	    "                             come from the index. Not with -p, -n, -b, -e or -o.\n"
+	    "      --within-rows = INT    Rows per band of --within [0: as many as fit in 1 GiB of\n"
+	    "                             records]. For tests and measurements.\n"
 	    "Not in this build: -b (debug mode of the PCA search); the PCA-guided search (-p)\n"
 	    "against a store (--index and --near are that search); merging (-e) from a store.\n" << std::endl;
 	exit(EXIT_SUCCESS);
@@ -320,7 +335,8 @@ int scorePCA(const Counts &c, std::vector<Genotype> &g, const Opt &opt, ntsm_eva
 	return 0;
 }
 
-constexpr int kOptPack = 1000, kOptAgainst = 1001, kOptIndex = 1002, kOptNear = 1003;   /* long-only: no letter of the reference's option string is taken */
+constexpr int kOptPack = 1000, kOptAgainst = 1001, kOptIndex = 1002, kOptNear = 1003, kOptWithin = 1004, kOptWithinNear = 1005,
+              kOptWithinRows = 1006;         /* long-only: no letter of the reference's option string is taken */
 
 /* --pack STORE FILES...: no GPU */
 int packStore(const Counts &c, const Opt &opt)
@@ -460,6 +476,27 @@ int buildIndex(const Opt &opt, std::chrono::steady_clock::time_point t0)
 	return 0;
 }
 
+/* What --near and --within-near open: the store and its index, valid, current and written with the run's -c and -d where
+ * those are given; -c and -d are then the index's.  Throws the refusal. */
+void openIndexedStore(const std::string &name, size_t nFiles, ntsm::eval_store::View &store, ntsm::eval_index::View &index, Opt &opt)
+{
+	namespace st = ntsm::eval_store;
+	const std::string path = ntsm::eval_index::path_of(name);
+	store.open(name);
+	if (store.h.n_samples == 0) throw st::Error(name + " holds no samples");
+	if (store.h.n_samples + nFiles > UINT32_MAX) throw st::Error(name + " holds more samples than one run scores");
+	struct stat sb;
+	if (stat(path.c_str(), &sb) != 0) throw st::Error("there is no index " + path + ": run --index on the store first");
+	index.open(path);
+	index.check_store(path, store, false);
+	if (opt.minCovGiven && opt.minCov != index.h.min_cov)
+		throw st::Error("-c " + std::to_string(opt.minCov) + ", but " + path + " was written with -c " + std::to_string(index.h.min_cov));
+	if (opt.dimGiven && opt.dim != index.h.dim)
+		throw st::Error("-d " + std::to_string(opt.dim) + ", but " + path + " was written with -d " + std::to_string(index.h.dim));
+	opt.minCov = index.h.min_cov;
+	opt.dim = index.h.dim;
+}
+
 /* --near STORE FILES...: the rows of computeScorePCA (:285-398) over [FILES..., the store's samples] in which sample 1 or
  * sample 2 is one of FILES, in that run's one-thread order.  The store's projections and tallies come from STORE.pcaidx, the
  * radii are formed here (scorePCA's), and only the counts of the candidates' samples leave the store -- except for a query
@@ -468,24 +505,11 @@ int searchNear(Counts &c, Opt &opt, std::chrono::steady_clock::time_point t0)
 {
 	namespace st = ntsm::eval_store;
 	namespace ix = ntsm::eval_index;
-	const std::string path = ix::path_of(opt.near);
 	st::View store;
 	ix::View index;
 	const auto tMap = std::chrono::steady_clock::now();
 	try {
-		store.open(opt.near);
-		if (store.h.n_samples == 0) throw st::Error(opt.near + " holds no samples");
-		if (store.h.n_samples + c.files.size() > UINT32_MAX) throw st::Error(opt.near + " holds more samples than one run scores");
-		struct stat sb;
-		if (stat(path.c_str(), &sb) != 0) throw st::Error("there is no index " + path + ": run --index on the store first");
-		index.open(path);
-		index.check_store(path, store, false);
-		if (opt.minCovGiven && opt.minCov != index.h.min_cov)
-			throw st::Error("-c " + std::to_string(opt.minCov) + ", but " + path + " was written with -c " + std::to_string(index.h.min_cov));
-		if (opt.dimGiven && opt.dim != index.h.dim)
-			throw st::Error("-d " + std::to_string(opt.dim) + ", but " + path + " was written with -d " + std::to_string(index.h.dim));
-		opt.minCov = index.h.min_cov;
-		opt.dim = index.h.dim;
+		openIndexedStore(opt.near, c.files.size(), store, index, opt);
 		if (opt.verbose > 0) std::cerr << "Reading count files" << std::endl;
 		c.locus = store.locus;
 		c.distinct.assign(store.distinct, store.distinct + 2 * (size_t) store.h.n_sites);
@@ -574,12 +598,168 @@ int searchNear(Counts &c, Opt &opt, std::chrono::steady_clock::time_point t0)
 	return 0;
 }
 
+struct WithinSession {                       /* closes the library session it holds when its scope ends */
+	ntsm_eval_within_session *h = nullptr;
+	~WithinSession() { if (h) ntsm_eval_within_close(h); }
+};
+
+/* the store's locus table and distinct columns play the part of the first file; a store of one sample has no pair */
+void storeAsRun(Counts &c, const ntsm::eval_store::View &store, const std::string &name)
+{
+	if (store.h.n_samples == 1) throw ntsm::eval_store::Error(name + " holds one sample: nothing to compare");
+	c.locus = store.locus;
+	c.distinct.assign(store.distinct, store.distinct + 2 * (size_t) store.h.n_sites);
+}
+
+/* --within STORE: computeScore's rows (:591-624) over the store's samples in store order -- the stdout of the all-to-all run
+ * over their files at one thread -- without reading a counts file.  The triangle comes in bands of rows (eval_within.hpp's
+ * rule, or --within-rows), printed band by band, which is the reference's order; the first band's call brings every
+ * sample's tallies. */
+int scoreWithin(const Opt &opt, std::chrono::steady_clock::time_point t0)
+{
+	namespace st = ntsm::eval_store;
+	namespace band = ntsm::eval_within;
+	st::View store;
+	Counts c;
+	const auto tMap = std::chrono::steady_clock::now();
+	try {
+		store.open(opt.within);
+		if (store.h.n_samples == 0) throw st::Error(opt.within + " holds no samples");
+		if (store.h.n_samples > UINT32_MAX) throw st::Error(opt.within + " holds more samples than one run scores");
+		storeAsRun(c, store, opt.within);
+	} catch (const std::exception &e) {
+		ntsm::refuse(e.what());
+	}
+	const double mapMs = msSince(tMap);
+	const uint32_t n = (uint32_t) store.h.n_samples, m = store.h.n_sites;
+	if (opt.verbose > 1) std::cerr << "Mapped " << opt.within << ". Now comparing its " << n << " samples." << std::endl;
+	std::cerr << "Performing all-to-all score computation.\nSpecify -p (--pca) to enable faster comparisons." << std::endl;
+	WithinSession session;
+	int rc = ntsm_eval_within_open(opt.device, store.counts(0), store.h.stride, n, m, opt.minCov, 0, &session.h);
+	if (rc) return gpuFail("opening the store", rc);
+	std::vector<uint32_t> geno((size_t) n * 3);
+	std::vector<Genotype> g;
+	std::vector<ntsm_eval_record> rec;
+	ntsm_eval_cross_times sum {};
+	uint32_t bands = 0;
+	double printMs = 0;
+	std::string temp;
+	for (uint32_t first = 0; first < n; ++bands) {
+		const uint32_t rows = opt.withinRows ? std::min(opt.withinRows, n - first) : band::band_rows(first, n, band::kBandRecords);
+		rec.resize(band::band_records(first, rows, n));
+		ntsm_eval_cross_times times {};
+		rc = ntsm_eval_within_rows(session.h, first, rows, rec.data(), first == 0 ? geno.data() : nullptr, &times);
+		if (rc) return gpuFail("scoring the store", rc);
+		sum.upload_ms += times.upload_ms; sum.prepare_kernel_ms += times.prepare_kernel_ms; sum.cross_kernel_ms += times.cross_kernel_ms;
+		sum.download_ms += times.download_ms; sum.chunks += times.chunks;
+		const auto tPrint = std::chrono::steady_clock::now();
+		if (first == 0) {
+			appendStoreSamples(c, g, store, opt, [&](uint32_t d, Genotype &s) { s.hets = geno[3 * d]; s.homs = geno[3 * d + 1]; s.miss = geno[3 * d + 2]; });
+			std::cout << kHeader << "\n";
+		}
+		for (uint32_t i = first; i < first + rows; ++i)
+			for (uint32_t j = i + 1; j < n; ++j) printRow(temp, c, g, opt, rec[band::band_offset(i, j, first, n)], i, j, "-1");
+		printMs += msSince(tPrint);
+		first += rows;
+	}
+	std::cout.flush();
+	if (opt.verbose > 1)
+		std::cerr << "store within: " << (sum.chunks ? "streamed" : "resident") << ", " << bands << " bands, " << sum.chunks << " chunks, map " << mapMs
+		          << " ms, upload " << sum.upload_ms << " ms, prepare " << sum.prepare_kernel_ms << " ms, pair kernel " << sum.cross_kernel_ms
+		          << " ms, download " << sum.download_ms << " ms, print " << printMs << " ms" << std::endl;
+	std::cerr << "Time: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << " s" << std::endl;
+	return 0;
+}
+
+/* --within-near STORE: computeScorePCA's rows (:285-398) over the store's samples -- the stdout of the -p run over their
+ * files with the index's rotation, centre, -d and -c.  Projections and tallies come from STORE.pcaidx and the radii are formed
+ * here, so the search is ntsm_eval_cross_candidates with every sample a query and no database side: by its contract
+ * ntsm_eval_candidates' list.  A sample whose radius is DBL_MAX owns whole rows: its counts go to a dense block that
+ * ntsm_eval_cross scores against the whole store (sample 1 is the owner); every other pair goes through the list. */
+int searchWithin(Opt &opt, std::chrono::steady_clock::time_point t0)
+{
+	namespace st = ntsm::eval_store;
+	namespace ix = ntsm::eval_index;
+	st::View store;
+	ix::View index;
+	Counts c;
+	const auto tMap = std::chrono::steady_clock::now();
+	try {
+		openIndexedStore(opt.withinNear, 0, store, index, opt);
+		storeAsRun(c, store, opt.withinNear);
+	} catch (const std::exception &e) {
+		ntsm::refuse(e.what());
+	}
+	const double mapMs = msSince(tMap);
+	const uint32_t n = (uint32_t) store.h.n_samples, m = store.h.n_sites, dim = opt.dim;
+	if (opt.verbose > 1) std::cerr << "Mapped " << opt.withinNear << " and its index. Now searching its " << n << " samples." << std::endl;
+
+	auto t = std::chrono::steady_clock::now();
+	std::vector<Genotype> g;
+	std::vector<double> cloud((size_t) n * dim);
+	appendStoreSamples(c, g, store, opt, [&](uint32_t d, Genotype &s) {
+		const ix::Entry e = index.entry(d);
+		s.hets = e.hets; s.homs = e.homs; s.miss = e.miss;
+		memcpy(&cloud[(size_t) d * dim], e.cloud, sizeof(double) * dim);
+	});
+	const std::vector<double> radius = searchRadii(g, m, opt);
+	if (opt.verbose > 1) std::cerr << "Starting Score Computation with PCA" << std::endl;
+	uint64_t np = 0;
+	double msSearch = 0;
+	int rc = ntsm_eval_cross_candidates(opt.device, cloud.data(), radius.data(), n, nullptr, nullptr, 0, dim, nullptr, nullptr, nullptr, 0, &np, &msSearch);
+	if (rc && rc != NTSM_EVAL_E_CAPACITY) return gpuFail("candidate search", rc);
+	std::vector<uint32_t> pi(np), pk(np);
+	std::vector<double> dist(np);
+	if (np) {
+		rc = ntsm_eval_cross_candidates(opt.device, cloud.data(), radius.data(), n, nullptr, nullptr, 0, dim, pi.data(), pk.data(), dist.data(), np, &np, &msSearch);
+		if (rc) return gpuFail("candidate search", rc);
+	}
+	const double searchMs = msSince(t);
+
+	t = std::chrono::steady_clock::now();
+	std::vector<uint32_t> dense, denseRow(n, UINT32_MAX);
+	for (uint32_t i = 0; i < n; ++i)
+		if (!(radius[i] < DBL_MAX)) { denseRow[i] = (uint32_t) dense.size(); dense.push_back(i); }
+	std::vector<ntsm_eval_record> rect((size_t) dense.size() * n), rec(np);
+	ntsm_eval_cross_times crossTimes {}, listTimes {};
+	if (!dense.empty()) {
+		std::vector<uint32_t> sub(dense.size() * (size_t) m * 2);
+		for (size_t r = 0; r < dense.size(); ++r) memcpy(&sub[r * m * 2], store.counts(dense[r]), sizeof(uint32_t) * m * 2);
+		rc = ntsm_eval_cross(opt.device, sub.data(), (uint32_t) dense.size(), store.counts(0), store.h.stride, n, m, opt.minCov, 0, rect.data(), nullptr, &crossTimes);
+		if (rc) return gpuFail("scoring against the store", rc);
+	}
+	std::vector<uint32_t> li, lk;
+	std::vector<uint64_t> where;
+	for (uint64_t p = 0; p < np; ++p) {
+		if (denseRow[pi[p]] != UINT32_MAX) rec[p] = rect[(size_t) denseRow[pi[p]] * n + pk[p]];
+		else { li.push_back(pi[p]); lk.push_back(pk[p]); where.push_back(p); }
+	}
+	std::vector<ntsm_eval_record> listed(li.size());
+	rc = ntsm_eval_store_score_pairs(opt.device, store.counts(0), store.h.stride, n, m, opt.minCov, li.data(), lk.data(), li.size(), 0, listed.data(), &listTimes);
+	if (rc) return gpuFail("scoring the candidate pairs", rc);
+	for (size_t x = 0; x < where.size(); ++x) rec[where[x]] = listed[x];
+	const double scoreMs = msSince(t);
+
+	const auto tPrint = std::chrono::steady_clock::now();
+	std::cout << kHeader << "\n";
+	std::string temp;
+	for (uint64_t p = 0; p < np; ++p) printRow(temp, c, g, opt, rec[p], pi[p], pk[p], std::to_string(dist[p]));
+	std::cout.flush();
+	if (opt.verbose > 1)
+		std::cerr << "store search: " << np << " pairs (" << li.size() << " listed, " << dense.size() << " dense rows), map+load " << mapMs << " ms, project "
+		          << 0.0 << " ms, search " << searchMs << " ms (kernels " << msSearch << " ms), score " << scoreMs << " ms (gather "
+		          << listTimes.upload_ms << " ms, list kernel " << listTimes.cross_kernel_ms << " ms in " << listTimes.chunks << " passes, dense upload "
+		          << crossTimes.upload_ms << " ms, dense kernel " << crossTimes.cross_kernel_ms << " ms), print " << msSince(tPrint) << " ms" << std::endl;
+	std::cerr << "Time: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << " s" << std::endl;
+	return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv)
 {
 	Opt opt;
-	bool die = false, storeMode = false, nearMode = false;
+	bool die = false, storeMode = false, nearMode = false, withinMode = false;
 	static struct option long_options[] = {
 		{ "score_thresh", required_argument, nullptr, 's' }, { "all", no_argument, nullptr, 'a' },
 		{ "min_cov", required_argument, nullptr, 'c' }, { "skew", required_argument, nullptr, 'w' },
@@ -591,7 +771,9 @@ int main(int argc, char **argv)
 		{ "large", required_argument, nullptr, 'l' }, { "debug", required_argument, nullptr, 'b' },
 		{ "gpu", required_argument, nullptr, 'G' }, { "verbose", no_argument, nullptr, 'v' },
 		{ "pack", required_argument, nullptr, kOptPack }, { "against", required_argument, nullptr, kOptAgainst },
-		{ "index", required_argument, nullptr, kOptIndex }, { "near", required_argument, nullptr, kOptNear }, { nullptr, 0, nullptr, 0 } };
+		{ "index", required_argument, nullptr, kOptIndex }, { "near", required_argument, nullptr, kOptNear },
+		{ "within", required_argument, nullptr, kOptWithin }, { "within-near", required_argument, nullptr, kOptWithinNear },
+		{ "within-rows", required_argument, nullptr, kOptWithinRows }, { nullptr, 0, nullptr, 0 } };
 	int ch;
 	while ((ch = getopt_long(argc, argv, "t:vhs:c:m:aw:g:p:n:d:r:e:o1:2:S:l:b:G:", long_options, nullptr)) != -1) {
 		switch (ch) {
@@ -619,12 +801,34 @@ int main(int argc, char **argv)
 		case kOptAgainst: opt.against = optarg; storeMode = true; break;
 		case kOptIndex: opt.index = optarg; nearMode = true; break;
 		case kOptNear: opt.near = optarg; nearMode = true; break;
+		case kOptWithin: opt.within = optarg; withinMode = true; break;
+		case kOptWithinNear: opt.withinNear = optarg; withinMode = true; break;
+		case kOptWithinRows:
+			if (!ntsm::read_whole(optarg, opt.withinRows)) ntsm::refuse(std::string("--within-rows takes a number of rows, not ") + optarg);
+			opt.withinRowsGiven = true;
+			break;
 		case '?': die = true; break;
 		default: break;                              /* m: read by the reference, without effect */
 		}
 	}
 	Counts c;
 	while (optind < argc) c.files.emplace_back(argv[optind++]);
+	if (withinMode) {                                    /* --within and --within-near: every refusal that needs no store, then the run */
+		const bool near = opt.within.empty();
+		const char *mode = near ? "--within-near" : "--within";
+		if (storeMode || nearMode || (!opt.within.empty() && !opt.withinNear.empty()))
+			ntsm::refuse("--pack, --against, --index, --near, --within and --within-near are six runs: give one of them");
+		if (!c.files.empty()) ntsm::refuse(std::string(mode) + " takes no input files: it compares the samples of the store with each other");
+		if (!opt.pca.empty() || !opt.norm.empty())
+			ntsm::refuse(near ? "--within-near takes rotation and centre from the store's index: give no -p and no -n"
+			                  : "--within is the all-to-all run and takes no -p and no -n: the PCA-guided search inside a store is --within-near");
+		if (!opt.debug.empty()) ntsm::refuse(std::string("-b with ") + mode + " is not part of this build");
+		if (!opt.merge.empty() || opt.onlyMerge) ntsm::refuse(std::string("merging (-e, -o) with ") + mode + " is not part of this build: the store does not hold the per-site sums");
+		if (opt.withinRowsGiven && near) ntsm::refuse("--within-rows sets the bands of --within: it does not go with --within-near");
+		const auto t0 = std::chrono::steady_clock::now();
+		return near ? searchWithin(opt, t0) : scoreWithin(opt, t0);
+	}
+	if (opt.withinRowsGiven) ntsm::refuse("--within-rows sets the bands of --within: give it with --within STORE");
 	if (nearMode) {                                      /* --index and --near: every refusal that needs no store comes before any file is read */
 		const char *mode = opt.near.empty() ? "--index" : "--near";
 		if (storeMode || (!opt.index.empty() && !opt.near.empty())) ntsm::refuse("--pack, --against, --index and --near are four runs: give one of them");

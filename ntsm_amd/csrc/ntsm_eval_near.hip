@@ -23,7 +23,8 @@
  * Scoring of listed pairs.  Every pair has a query in it, so it names at most one database sample.  The distinct database
  * samples of the list are copied row by row from the mapped store, at most `chunk` per pass, to dense rows behind the
  * queries' rows; a pass scores its pairs with the listed-pair kernel of ntsm_eval_pca.h over those rows (slot numbers in
- * place of sample numbers) and its records are scattered back to list order.
+ * place of sample numbers) and its records are scattered back to list order.  ntsm_eval_store_score_pairs, at the end of
+ * this file, is the same for pairs of two store samples (ntsmEval --within-near).
  */
 #include <hip/hip_runtime.h>
 
@@ -35,6 +36,7 @@
 #include <vector>
 
 #include "../../include/ntsm_eval_hip.h"
+#include "host/eval_within.hpp"
 #include "ntsm_eval_chunk.h"
 #include "ntsm_eval_pca.h"
 #include "ntsm_eval_score.h"
@@ -377,6 +379,79 @@ extern "C" int ntsm_eval_cross_score_pairs(int device, const uint32_t *q_counts,
 		rec.resize(list.size());
 		HIPCHK(hipMemcpy(rec.data(), d_out, list.size() * sizeof(ntsm_eval_record), hipMemcpyDeviceToHost));
 		for (uint64_t x = 0; x < list.size(); ++x) out[list[x]] = rec[x];        /* back to list order */
+		tm.download_ms += ms_since(t);
+		tm.chunks++;
+	}
+	if (times) *times = tm;
+	return 0;
+}
+
+/* Listed pairs of two store samples (ntsmEval --within-near): the scheme above with the query block removed.  Both samples of
+ * a pair have to be on the device at once, so the passes are eval_within.hpp's cut of the list -- contiguous pieces of it,
+ * each over at most `chunk` distinct samples -- and a pass's records go back to the list as one copy. */
+extern "C" int ntsm_eval_store_score_pairs(int device, const void *db_counts, uint64_t db_stride_bytes, uint32_t n_db, uint32_t n_sites,
+		uint32_t min_cov, const uint32_t *pi, const uint32_t *pk, uint64_t n_pairs, uint32_t db_chunk,
+		ntsm_eval_record *out, ntsm_eval_cross_times *times)
+{
+	if (times) *times = ntsm_eval_cross_times {};
+	if ((!db_counts && n_db && n_sites) || (n_pairs && (!pi || !pk || !out)) || db_chunk == 1) return -1;
+	if (db_stride_bytes < 8ull * n_sites || db_stride_bytes % 4) return -1;
+	for (uint64_t p = 0; p < n_pairs; ++p)
+		if (pi[p] >= n_db || pk[p] >= n_db || pi[p] == pk[p]) return -1;
+	if (n_pairs == 0) return 0;
+	memset(out, 0, n_pairs * sizeof(ntsm_eval_record));
+	if (n_sites == 0) return 0;
+
+	const uint64_t row_bytes = 8ull * n_sites;
+	HIPCHK(hipSetDevice(device));
+	size_t free_b = 0, total_b = 0;
+	if (db_chunk == 0) HIPCHK(hipMemGetInfo(&free_b, &total_b));
+	const uint32_t chunk = std::max(2u, ntsm_eval_chunk::samples_per_pass(db_chunk, n_db, free_b, 2 * row_bytes, n_pairs * (sizeof(ntsm_eval_record) + 8)));
+	const ntsm::eval_within::Passes cut = ntsm::eval_within::pack_passes(pi, pk, n_pairs, n_db, chunk);
+	uint64_t most = 0;
+	uint32_t slots = 0;
+	for (size_t x = 0; x < cut.passes(); ++x) {
+		most = std::max(most, cut.pair_begin[x + 1] - cut.pair_begin[x]);
+		slots = std::max(slots, (uint32_t) (cut.sample_begin[x + 1] - cut.sample_begin[x]));
+	}
+
+	ntsm_hip::Buffers b;
+	ntsm_hip::Events<3> ev;
+	uint32_t *d_rows, *d_pi, *d_pk;
+	double *d_term;
+	ntsm_eval_record *d_out;
+	HIPCHK(b.alloc(&d_rows, (uint64_t) slots * n_sites * 2));
+	HIPCHK(b.alloc(&d_term, (uint64_t) slots * n_sites));
+	HIPCHK(b.alloc(&d_pi, most));
+	HIPCHK(b.alloc(&d_pk, most));
+	HIPCHK(b.alloc(&d_out, most));
+	HIPCHK(ev.create());
+	ntsm_eval_cross_times tm {};
+	for (size_t x = 0; x < cut.passes(); ++x) {
+		const uint64_t p0 = cut.pair_begin[x], pn = cut.pair_begin[x + 1] - p0, s0 = cut.sample_begin[x];
+		const uint32_t rn = (uint32_t) (cut.sample_begin[x + 1] - s0);
+		auto t = wall::now();
+		for (uint32_t r = 0; r < rn; ++r)                                        /* row by row from the mapped store */
+			HIPCHK(hipMemcpy(d_rows + (uint64_t) r * n_sites * 2, (const char *) db_counts + (uint64_t) cut.sample[s0 + r] * db_stride_bytes, row_bytes,
+					hipMemcpyHostToDevice));
+		HIPCHK(hipMemcpy(d_pi, cut.slot_i.data() + p0, pn * sizeof(uint32_t), hipMemcpyHostToDevice));
+		HIPCHK(hipMemcpy(d_pk, cut.slot_k.data() + p0, pn * sizeof(uint32_t), hipMemcpyHostToDevice));
+		tm.upload_ms += ms_since(t);
+		HIPCHK(hipEventRecord(ev[0], 0));
+		ntsm_eval_pca::launch_term(d_rows, (uint64_t) rn * n_sites, min_cov, d_term);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipEventRecord(ev[1], 0));
+		ntsm_eval_pca::launch_score(d_rows, d_term, n_sites, min_cov, d_pi, d_pk, pn, d_out);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipEventRecord(ev[2], 0));
+		HIPCHK(hipEventSynchronize(ev[2]));
+		float ms = 0;
+		HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+		tm.prepare_kernel_ms += ms;
+		HIPCHK(hipEventElapsedTime(&ms, ev[1], ev[2]));
+		tm.cross_kernel_ms += ms;
+		t = wall::now();
+		HIPCHK(hipMemcpy(out + p0, d_out, pn * sizeof(ntsm_eval_record), hipMemcpyDeviceToHost));
 		tm.download_ms += ms_since(t);
 		tm.chunks++;
 	}

@@ -1,5 +1,5 @@
 """ctypes plumbing for include/ntsm_eval_hip.h (all-pairs scoring of ntsmEval on the GPU, its PCA-guided search, queries and
-that search against a cohort store); used by tests and tools.
+that search against a cohort store, the pairs inside a store); used by tests and tools.
 Loaded on demand: `import ntsm_amd.eval`.  Fails loudly when libntsm_eval_hip.so has not been built."""
 import ctypes as C
 import os
@@ -294,4 +294,83 @@ def cross_score_pairs(q, db, pi, pk, min_cov=1, db_chunk=0, device=0):
                                          len(pi), db_chunk, out.ctypes.data, C.byref(times))
     if rc:
         raise RuntimeError("ntsm_eval_cross_score_pairs failed: %d" % rc)
+    return out, times
+
+
+# ---- the pairs inside a cohort store (ntsmEval --within / --within-near; include/ntsm_eval_hip.h: ntsm_eval_within_open ...
+# ntsm_eval_store_score_pairs).  Sample numbers are the store's.
+lib.ntsm_eval_within_open.restype = C.c_int
+lib.ntsm_eval_within_open.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+lib.ntsm_eval_within_rows.restype = C.c_int
+lib.ntsm_eval_within_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(CrossTimes)]
+lib.ntsm_eval_within_close.restype = None
+lib.ntsm_eval_within_close.argtypes = [C.c_void_p]
+lib.ntsm_eval_within_tune.restype = C.c_int
+lib.ntsm_eval_within_tune.argtypes = [C.c_uint32]
+lib.ntsm_eval_store_score_pairs.restype = C.c_int
+lib.ntsm_eval_store_score_pairs.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
+                                            C.c_uint32, C.c_void_p, C.POINTER(CrossTimes)]
+
+
+def within_tune(width):
+    """Force the workgroup width (64 or 256) of later Within.rows calls in this process; 0 = the library's rule."""
+    rc = lib.ntsm_eval_within_tune(width)
+    if rc:
+        raise ValueError("ntsm_eval_within_tune(%r) failed: %d" % (width, rc))
+
+
+class Within:
+    """The pairs of a store's samples with each other (ntsm_eval_within_open): db is uint32 [n_db][n_sites][2] or Records,
+    which the session keeps alive.  db_chunk: 0 = resident if the store fits the device, else streamed; a value below n_db
+    streams the columns in chunks of it.  A context manager: `with Within(db) as w: rec, geno, times = w.rows(0, w.n)`."""
+
+    def __init__(self, db, min_cov=1, db_chunk=0, device=0):
+        self.records = _records(db)
+        self.n, self.m = self.records.n, self.records.m
+        self.h = C.c_void_p()
+        rc = lib.ntsm_eval_within_open(device, self.records.address, self.records.stride, self.n, self.m, min_cov, db_chunk, C.byref(self.h))
+        if rc:
+            raise RuntimeError("ntsm_eval_within_open failed: %d" % rc)
+
+    def rows(self, row_first, n_rows):
+        """The records of the pairs (i, j), row_first <= i < row_first + n_rows, i < j < n, in pair_index order (the slice
+        pairs()[pair_index(row_first, row_first + 1, n):pair_index(row_first + n_rows, ...)] of the dense samples); geno
+        [n][3] with the entries from row_first on written; times, a CrossTimes (chunks == 0: the store is resident)."""
+        base = lambda r: r * self.n - r * (r + 1) // 2  # noqa: E731
+        count = base(row_first + n_rows) - base(row_first) if 0 <= row_first and 0 < n_rows and row_first + n_rows <= self.n else 0
+        out = np.zeros(count, dtype=RECORD)
+        geno = np.zeros((self.n, 3), dtype=np.uint32)
+        times = CrossTimes()
+        rc = lib.ntsm_eval_within_rows(self.h, row_first, n_rows, out.ctypes.data, geno.ctypes.data, C.byref(times))
+        if rc:
+            raise RuntimeError("ntsm_eval_within_rows failed: %d" % rc)
+        return out, geno, times
+
+    def close(self):
+        if self.h:
+            lib.ntsm_eval_within_close(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+
+def store_score_pairs(db, pi, pk, min_cov=1, db_chunk=0, device=0):
+    """db: [n_db][n_sites][2] or Records; pi, pk: store sample numbers.  Returns (records, sample pi as sample 1 -- the bits
+    of score_pairs on the dense samples --, times; times.chunks = the passes)."""
+    r = _records(db)
+    pi = np.ascontiguousarray(pi, dtype=np.uint32)
+    pk = np.ascontiguousarray(pk, dtype=np.uint32)
+    out = np.zeros(len(pi), dtype=RECORD)
+    times = CrossTimes()
+    rc = lib.ntsm_eval_store_score_pairs(device, r.address, r.stride, r.n, r.m, min_cov, pi.ctypes.data, pk.ctypes.data, len(pi), db_chunk,
+                                         out.ctypes.data, C.byref(times))
+    if rc:
+        raise RuntimeError("ntsm_eval_store_score_pairs failed: %d" % rc)
     return out, times

@@ -37,8 +37,8 @@ build/ntsmCount: $(HOSTSRC) $(HOST)/feeder.cpp $(HOST)/fingerprint.cpp $(HOST)/e
 	$(CXX) $(CXXFLAGS) -o $@ $(HOSTSRC) $(HOST)/feeder.cpp $(HOST)/fingerprint.cpp $(HOST)/early_ingest.cpp $(HOST)/ntsm_count_main.cpp \
 	    -Lntsm_amd -lntsm_hip -lz -pthread -Wl,-rpath,'$$ORIGIN/../ntsm_amd' -Wl,-rpath,/opt/rocm/lib
 
-# libntsm_hip.so = three device translation units (the kernels + their launchers) and four host-only ones
-HIPLIB_DEV  := $(CSRC)/kernels_generic.hip $(CSRC)/kernels_mz.hip $(CSRC)/kernels_run.hip
+# libntsm_hip.so = four device translation units (the kernels + their launchers; kernels_sites.hip with its two entry points) and four host-only ones
+HIPLIB_DEV  := $(CSRC)/kernels_generic.hip $(CSRC)/kernels_mz.hip $(CSRC)/kernels_run.hip $(CSRC)/kernels_sites.hip
 HIPLIB_HOST := $(CSRC)/tables.cpp $(CSRC)/runtime.cpp $(CSRC)/rccl_bind.cpp $(CSRC)/capi.cpp
 HIPLIB_HDR  := $(CSRC)/ntsm_internal.h $(CSRC)/kernels_common.h $(CSRC)/ntsm_hooks.h $(CSRC)/ntsm_device.h include/ntsm_hip.h
 HIPLIB_TAB  := $(CSRC)/ntsm_tab_kernel.inc $(CSRC)/ntsm_tab_launch.inc $(CSRC)/ntsm_tab_runtime.inc $(CSRC)/ntsm_tab_tables.inc
@@ -111,6 +111,15 @@ within_check: build/eval_within_check
 build/eval_within_check: tools/eval_within_check.cpp $(HOST)/eval_within.hpp include/ntsm_eval_hip.h
 	@mkdir -p build
 	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ tools/eval_within_check.cpp
+
+# the host side of `ntsmCount --cohort` likewise: manifest parser, site lists, and the record builder against counts text +
+# --pack, byte for byte (tools/cohort_count_check.cpp; not part of `all`)
+cohort_check: build/cohort_count_check
+	@mkdir -p build/cohort_check_tmp
+	build/cohort_count_check build/cohort_check_tmp
+build/cohort_count_check: tools/cohort_count_check.cpp $(HOST)/cohort.hpp $(HOST)/eval_store.hpp $(HOST)/site_set.hpp $(HOST)/report.cpp $(HOST)/report.hpp
+	@mkdir -p build
+	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ tools/cohort_count_check.cpp $(HOST)/report.cpp
 
 # ntsmVCF (multi-sample VCF -> PCA matrix and centre file): own library, own CLI
 ntsm_amd/libntsm_vcf_hip.so: $(CSRC)/ntsm_vcf.hip $(CSRC)/ntsm_hip_scope.h include/ntsm_vcf_hip.h
@@ -195,4 +204,4 @@ build/gather_bench: tools/gather_bench.hip
 clean:
 	rm -rf build ntsm_amd/*.so
 	$(MAKE) -C oracle clean
-.PHONY: all oracle_all ref_gpu_binding clean ablation abl_tab tab m12 xlib store_check index_check within_check
+.PHONY: all oracle_all ref_gpu_binding clean ablation abl_tab tab m12 xlib store_check index_check within_check cohort_check

@@ -16,6 +16,7 @@
  *   processSingleRead's -m check (src/FingerPrint.hpp:473-488)  ntsm_sync -> ntsm_totals.early_stop
  *   m_totalKmers / m_totalCounts / m_totalBases                ntsm_sync -> ntsm_totals
  *   m_counts.at(hv) at print time (src/FingerPrint.hpp:282)    ntsm_counts (dense, key order)
+ *   per-site max / sum at print time (src/FingerPrint.hpp:281-294)  ntsm_sites_attach + ntsm_sites_reduce
  *   (none: single process)                                     ntsm_counts_device + RCCL SUM
  *
  * Flat read-stream layout consumed by submit/count: the reads of a batch are concatenated, each
@@ -183,6 +184,34 @@ int ntsm_allreduce(ntsm_ctx *const *ctxs, int n);
  * ncclGroupEnd, ncclAllReduce, ncclCommDestroy) and say whether it worked: NTSM_OK or NTSM_ERR_RCCL.  Touches no GPU.
  * A multi-device host calls it BEFORE counting, so that a missing RCCL shows up front rather than after the work. */
 int ntsm_rccl_probe(void);
+/* Per-site reduction of a context's counts on the device: what printCountsMax (src/FingerPrint.hpp:270-311) and the
+ * "Sites Covered" line of printInfoSummary (src/FingerPrint.hpp:313-349, through getSitesCoveredInSample) compute on the host
+ * from m_counts, for a caller that needs the per-site record of a sample and not its per-k-mer vector (`ntsmCount --cohort`:
+ * 16 bytes per site come back instead of 8 per k-mer).
+ *
+ * The site -> k-mer lists of the context's key set, uploaded once.  Site i's AT list is
+ * kmer_ix[offsets[2i] .. offsets[2i+1]), its CG list kmer_ix[offsets[2i+1] .. offsets[2i+2]);
+ * offsets has 2*n_sites + 1 entries, non-decreasing; every index < n_kmers.  A second call replaces the first.
+ * ntsm_reset keeps the lists (as it keeps the table), ntsm_destroy frees them.  n_sites = 0 is legal. */
+int ntsm_sites_attach(ntsm_ctx *ctx, const uint32_t *offsets, const uint32_t *kmer_ix, uint32_t n_sites);
+
+typedef struct { uint64_t total, sum_of_sums, sites_covered; } ntsm_site_totals;
+/* counts, sums: host arrays [n_sites][2] (sums may be NULL).  Implies ntsm_counts_device (a sync; an imported
+ * reduced vector is what gets reduced).  With f = (uint32_t) count of a list's k-mer (`unsigned freq`, :282):
+ *   counts[i][a] = max f (0 for an empty list)     sums[i][a] = sum of f mod 2^32            (:281-294)
+ *   total        = sum over i of (uint64_t)(uint32_t)(counts[i][0] + counts[i][1])   -- what ntsmEval adds up from the rows
+ *   sum_of_sums  = sum over i of (uint64_t)(uint32_t)(sums[i][0] + sums[i][1])          (src/CompareCounts.hpp:104-106, :1198-1216)
+ *   sites_covered: sites with a k-mer whose 64-bit count is not zero (a count of exactly 2^32 covers its site although its
+ *                  maximum reads 0).
+ * NTSM_ERR_ARG, before any HIP call: NULL ctx or counts, no lists attached (ntsm_sites_attach: NULL ctx or offsets, offsets
+ * that decrease, an index >= n_kmers, n_sites >= 2^31). */
+int ntsm_sites_reduce(ntsm_ctx *ctx, uint32_t *counts, uint32_t *sums, ntsm_site_totals *out);
+/* Test hook, host code only (no device needed): the argument check ntsm_sites_attach runs on its lists before any HIP call, for a
+ * key set of n_kmers keys: NTSM_OK or NTSM_ERR_ARG. */
+int ntsm_debug_sites_check(uint32_t n_kmers, const uint32_t *offsets, const uint32_t *kmer_ix, uint32_t n_sites);
+/* Device time of the last ntsm_sites_reduce's kernel in milliseconds, by hipEvents; 0 unless ntsm_set_timing is on. */
+int ntsm_sites_kernel_ms(ntsm_ctx *ctx, double *ms);
+
 /* Re-arm or disarm the -m stop of a context.  The threshold is compared (strict '>', after every whole read) with
  * the context's OWN cumulative total_hits, so a caller that orders reads across several contexts passes
  * total_hits_of_this_context + (global threshold - hits counted globally before the next batch); see

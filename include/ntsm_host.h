@@ -26,6 +26,11 @@ uint64_t ntsm_sites_n_keys(const ntsm_sites *s);          /* m_counts.size() */
 const uint64_t *ntsm_sites_keys(const ntsm_sites *s);     /* canonical codes, first-seen order */
 uint64_t ntsm_sites_n_sites(const ntsm_sites *s);         /* m_alleleIDs.size() */
 uint64_t ntsm_sites_n_erased(const ntsm_sites *s);        /* duplicates removed (no -d) */
+/* The site -> k-mer lists in the form ntsm_sites_attach takes (include/ntsm_hip.h): offsets[2 * n_sites + 1] into kmer_ix,
+ * site i's AT list first, then its CG list; indices into ntsm_sites_keys.  Both arrays are released with ntsm_host_free.
+ * Returns 1, with nothing allocated, for a set whose rows cannot be printed or packed (an erased k-mer in a list, a REF record
+ * without VAR, a repeated locus ID: host/cohort.hpp). */
+int ntsm_sites_lists(const ntsm_sites *s, uint32_t **offsets, uint32_t **kmer_ix, uint64_t *n_ix);
 
 /* m_maxCounts for a k-mer set size and the -m value (0 = disabled / never) */
 uint64_t ntsm_host_max_hits(uint64_t n_distinct, double cov_thresh);

@@ -38,6 +38,10 @@ class Totals(C.Structure):
                 ("reads_consumed", C.c_uint64), ("early_stop", C.c_int32), ("reserved", C.c_int32)]
 
 
+class SiteTotals(C.Structure):
+    _fields_ = [("total", C.c_uint64), ("sum_of_sums", C.c_uint64), ("sites_covered", C.c_uint64)]
+
+
 class SynthShortParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("read_len", C.c_uint32), ("n_sites", C.c_uint32), ("embed_thr", C.c_uint32),
                 ("sub_thr", C.c_uint32), ("n_thr", C.c_uint32), ("pad", C.c_uint32)]
@@ -83,6 +87,10 @@ _sig(H, "ntsm_import_reduced", C.c_int, [C.c_void_p])
 _sig(H, "ntsm_allreduce", C.c_int, [C.POINTER(C.c_void_p), C.c_int])
 _sig(H, "ntsm_rccl_probe", C.c_int, [])
 _sig(H, "ntsm_reset", C.c_int, [C.c_void_p])
+_sig(H, "ntsm_sites_attach", C.c_int, [C.c_void_p, u32p, u32p, C.c_uint32])
+_sig(H, "ntsm_sites_reduce", C.c_int, [C.c_void_p, u32p, u32p, C.POINTER(SiteTotals)])
+_sig(H, "ntsm_sites_kernel_ms", C.c_int, [C.c_void_p, C.POINTER(C.c_double)])
+_sig(H, "ntsm_debug_sites_check", C.c_int, [C.c_uint32, u32p, u32p, C.c_uint32])
 _sig(H, "ntsm_set_max_hits", C.c_int, [C.c_void_p, C.c_uint64, C.c_int])
 _sig(H, "ntsm_set_timing", C.c_int, [C.c_void_p, C.c_int])
 _sig(H, "ntsm_get_timing", C.c_int, [C.c_void_p, u64p, C.POINTER(C.c_double)])
@@ -107,6 +115,7 @@ _sig(HO, "ntsm_sites_n_keys", C.c_uint64, [C.c_void_p])
 _sig(HO, "ntsm_sites_keys", u64p, [C.c_void_p])
 _sig(HO, "ntsm_sites_n_sites", C.c_uint64, [C.c_void_p])
 _sig(HO, "ntsm_sites_n_erased", C.c_uint64, [C.c_void_p])
+_sig(HO, "ntsm_sites_lists", C.c_int, [C.c_void_p, C.POINTER(u32p), C.POINTER(u32p), u64p])
 _sig(HO, "ntsm_host_max_hits", C.c_uint64, [C.c_uint64, C.c_double])
 _sig(HO, "ntsm_host_flatten", C.c_int, [C.c_char_p, C.POINTER(u8p), u64p, C.POINTER(u64p), u64p, C.POINTER(C.c_int)])
 _sig(HO, "ntsm_host_free", None, [C.c_void_p])
@@ -182,6 +191,18 @@ class Sites:
         self.keys = np.ctypeslib.as_array(HO.ntsm_sites_keys(h), shape=(n,)).copy() if n else np.zeros(0, np.uint64)
         self.n_sites = int(HO.ntsm_sites_n_sites(h))
         self.n_erased = int(HO.ntsm_sites_n_erased(h))
+
+    def lists(self):
+        """(offsets uint32[2 * n_sites + 1], kmer_ix uint32[...]): the site -> k-mer lists as Context.sites_attach takes them; an
+        NtsmError for a set whose rows cannot be printed (erased k-mer, odd record count) or packed (repeated locus)."""
+        o, x, n = u32p(), u32p(), C.c_uint64()
+        if HO.ntsm_sites_lists(self._h, C.byref(o), C.byref(x), C.byref(n)) != 0:
+            raise NtsmError("the site set cannot be given as lists")
+        offsets = np.ctypeslib.as_array(o, shape=(2 * self.n_sites + 1,)).copy()
+        kmer_ix = np.ctypeslib.as_array(x, shape=(n.value,)).copy() if n.value else np.zeros(0, np.uint32)
+        HO.ntsm_host_free(o)
+        HO.ntsm_host_free(x)
+        return offsets, kmer_ix
 
     def format_counts(self, counts, total_kmers):
         counts = np.ascontiguousarray(counts, dtype=np.uint64)
@@ -395,6 +416,34 @@ class Context:
 
     def reset(self):
         _chk(H.ntsm_reset(self._h), "ntsm_reset")
+
+    def sites_attach(self, offsets, kmer_ix):
+        """ntsm_sites_attach: the site -> k-mer lists of this context's key set (offsets: 2 * n_sites + 1 entries)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
+        kmer_ix = np.ascontiguousarray(kmer_ix, dtype=np.uint32)
+        if offsets.size < 1 or offsets.size % 2 == 0:
+            raise NtsmError("sites_attach: offsets has 2 * n_sites + 1 entries")
+        _chk(H.ntsm_sites_attach(self._h, _p(offsets, u32p), _p(kmer_ix, u32p) if kmer_ix.size else None, (offsets.size - 1) // 2), "ntsm_sites_attach")
+        self.n_sites = (offsets.size - 1) // 2
+
+    def sites_reduce(self, want_sums=True):
+        """ntsm_sites_reduce: (counts uint32[n_sites, 2], sums uint32[n_sites, 2] or None, dict(total, sum_of_sums, sites_covered))."""
+        n = getattr(self, "n_sites", None)
+        if n is None:
+            _chk(H.ntsm_sites_reduce(self._h, None, None, None), "ntsm_sites_reduce")   # the library's own refusal
+        counts = np.zeros((n, 2), dtype=np.uint32)
+        sums = np.zeros((n, 2), dtype=np.uint32) if want_sums else None
+        t = SiteTotals()
+        # a one-element dummy keeps the pointers non-NULL for n_sites = 0
+        cbuf = counts if n else np.zeros(2, dtype=np.uint32)
+        sbuf = (sums if n else np.zeros(2, dtype=np.uint32)) if want_sums else None
+        _chk(H.ntsm_sites_reduce(self._h, _p(cbuf, u32p), _p(sbuf, u32p) if want_sums else None, C.byref(t)), "ntsm_sites_reduce")
+        return counts, sums, dict(total=int(t.total), sum_of_sums=int(t.sum_of_sums), sites_covered=int(t.sites_covered))
+
+    def sites_kernel_ms(self):
+        ms = C.c_double()
+        _chk(H.ntsm_sites_kernel_ms(self._h, C.byref(ms)), "ntsm_sites_kernel_ms")
+        return ms.value
 
     def set_timing(self, on):
         _chk(H.ntsm_set_timing(self._h, int(on)), "ntsm_set_timing")

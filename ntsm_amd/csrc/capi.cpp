@@ -159,6 +159,7 @@ void ntsm_destroy(ntsm_ctx *c)
 	}
 	tab_release(c);                                        /* no-op in the default build */
 	copy_pool_release(c);
+	sites_destroy(c);
 	for (auto &b : c->device_cache) (void) hipFree(b.first);
 	c->device_cache.clear();
 	void *ptrs[] = { c->d_rblocks, c->d_bloom, c->d_prefilter, c->d_lut64, c->d_blocks, c->d_filter, c->d_keys, c->d_slot_of, c->d_read_hits, c->d_totals, c->d_vec, c->d_lut };

@@ -225,6 +225,82 @@ inline bool write_all(int fd, const void *p, size_t n, uint64_t off)
 	return true;
 }
 
+/* ---- writing a store: the three steps --pack and `ntsmCount --cohort` (host/cohort.hpp) share ------------------------------ */
+
+/* the header of a store with these loci and no sample yet */
+inline Header new_header(const std::vector<std::string> &locus)
+{
+	Header h {};
+	memcpy(h.magic, kMagic, 8);
+	h.version = kVersion;
+	h.n_sites = (uint32_t) locus.size();
+	size_t at = kHeaderBytes;
+	for (const std::string &l : locus) at += l.size() + 1;
+	h.first = pad8(at) + 8ull * h.n_sites;
+	h.stride = kRecordHead + 8ull * h.n_sites;
+	return h;
+}
+
+/* header and locus section, bytes [0, h.first) of the file behind fd; distinct is [n_sites][2] */
+inline bool write_head(int fd, const Header &h, const std::vector<std::string> &locus, const uint32_t *distinct)
+{
+	std::vector<char> head(h.first, 0);
+	memcpy(head.data(), &h, kHeaderBytes);
+	size_t at = kHeaderBytes;
+	for (const std::string &l : locus) { memcpy(head.data() + at, l.c_str(), l.size() + 1); at += l.size() + 1; }
+	if (h.n_sites) memcpy(head.data() + pad8(at), distinct, 8ull * h.n_sites);
+	return write_all(fd, head.data(), head.size(), 0);
+}
+
+/* the head of a finished record; `rec` is h.stride zeroed bytes whose counts (from kRecordHead on) the caller fills */
+inline void fill_record_head(char *rec, const std::string &name, uint64_t raw_total, unsigned kmer_size, uint64_t total, uint64_t sum_of_sums)
+{
+	RecordHead *rh = (RecordHead *) rec;
+	rh->raw_total = raw_total;
+	rh->total = total;
+	rh->sum_of_sums = sum_of_sums;
+	rh->kmer_size = kmer_size;
+	memcpy(rh->name, name.data(), name.size());
+}
+
+inline void check_name(const std::string &f)
+{
+	if (f.size() >= kNameBytes) throw Error("the name " + f.substr(0, 40) + "... has " + std::to_string(f.size()) + " bytes; a store holds names of at most 1023");
+}
+
+/* Append finished records to an existing store: their bytes go behind the last record (write, any number of calls, whole
+ * records or pieces of them), then commit() writes n_samples -- records first, the count last, so that a run that ends in
+ * between leaves the store it found.  --pack commits once, with all its records; a cohort run commits every sample. */
+class Appender {
+	int fd_ = -1;
+	std::string path_;
+	uint64_t n_samples_ = 0, dst_ = 0;
+public:
+	Appender() = default;
+	Appender(const Appender &) = delete;
+	Appender &operator=(const Appender &) = delete;
+	~Appender() { if (fd_ >= 0) close(fd_); }
+	void open(const std::string &store, const Header &h)
+	{
+		path_ = store;
+		fd_ = ::open(store.c_str(), O_WRONLY);
+		if (fd_ < 0) throw Error("cannot write " + store);
+		n_samples_ = h.n_samples;
+		dst_ = h.first + h.n_samples * h.stride;
+	}
+	void write(const void *p, size_t n)
+	{
+		if (!write_all(fd_, p, n, dst_)) throw Error("cannot write " + path_);
+		dst_ += n;
+	}
+	uint64_t commit(uint64_t n_more)
+	{
+		n_samples_ += n_more;
+		if (!write_all(fd_, &n_samples_, 8, offsetof(Header, n_samples))) throw Error("cannot write " + path_);
+		return n_samples_;
+	}
+};
+
 /* --pack STORE FILES...: create the store, or append to it.  Every new record goes to STORE.tmp first, one sample in
  * memory at a time; only when all files have been read does STORE change (creation: the finished STORE.tmp is renamed;
  * append: the records are copied behind the last one, then n_samples is written).  Any refusal throws Error before that
@@ -247,16 +323,10 @@ inline uint64_t pack(const std::string &store, const std::vector<std::string> &f
 		for (uint64_t r = 0; r < h.n_samples; ++r) names.insert(v.name(r));
 	} else {
 		read_locus_table(files[0], index, locus, distinct);
-		memcpy(h.magic, kMagic, 8);
-		h.version = kVersion;
-		h.n_sites = (uint32_t) locus.size();
-		size_t at = kHeaderBytes;
-		for (const std::string &l : locus) at += l.size() + 1;
-		h.first = pad8(at) + 8ull * h.n_sites;
-		h.stride = kRecordHead + 8ull * h.n_sites;
+		h = new_header(locus);
 	}
 	for (const std::string &f : files) {
-		if (f.size() >= kNameBytes) throw Error("the name " + f.substr(0, 40) + "... has " + std::to_string(f.size()) + " bytes; a store holds names of at most 1023");
+		check_name(f);
 		if (!names.insert(f).second) throw Error("the name " + f + " is already in the store");
 	}
 	const size_t m = h.n_sites;
@@ -266,12 +336,7 @@ inline uint64_t pack(const std::string &store, const std::vector<std::string> &f
 	struct Cleanup { int fd; const std::string &path; bool keep = false; ~Cleanup() { close(fd); if (!keep) unlink(path.c_str()); } } tidy { fd, tmp };
 	uint64_t off = 0;
 	if (!exists) {                                   /* header (n_samples still 0) and locus section */
-		std::vector<char> head(h.first, 0);
-		memcpy(head.data(), &h, kHeaderBytes);
-		size_t at = kHeaderBytes;
-		for (const std::string &l : locus) { memcpy(head.data() + at, l.c_str(), l.size() + 1); at += l.size() + 1; }
-		if (m) memcpy(head.data() + pad8(at), distinct.data(), 8 * m);
-		if (!write_all(fd, head.data(), head.size(), 0)) throw Error("cannot write " + tmp);
+		if (!write_head(fd, h, locus, distinct.data())) throw Error("cannot write " + tmp);
 		off = h.first;
 	}
 	std::vector<char> rec(h.stride);
@@ -281,36 +346,27 @@ inline uint64_t pack(const std::string &store, const std::vector<std::string> &f
 		std::fill(sums.begin(), sums.end(), 0u);
 		Scalars sc;
 		parse_counts_file(f, index, (uint32_t *) (rec.data() + kRecordHead), sums.data(), sc, true);
-		RecordHead *rh = (RecordHead *) rec.data();
-		rh->raw_total = sc.raw_total;
-		rh->total = sc.total;
-		rh->sum_of_sums = sum_of_pairs(sums.data(), m);
-		rh->kmer_size = sc.kmer_size;
-		memcpy(rh->name, f.data(), f.size());
+		fill_record_head(rec.data(), f, sc.raw_total, sc.kmer_size, sc.total, sum_of_pairs(sums.data(), m));
 		if (!write_all(fd, rec.data(), rec.size(), off)) throw Error("cannot write " + tmp);
 		off += h.stride;
 	}
-	const uint64_t total = h.n_samples + files.size();
 	if (!exists) {
+		const uint64_t total = files.size();
 		if (!write_all(fd, &total, 8, offsetof(Header, n_samples))) throw Error("cannot write " + tmp);
 		if (rename(tmp.c_str(), store.c_str()) != 0) throw Error("cannot rename " + tmp + " to " + store);
 		tidy.keep = true;
 		return total;
 	}
-	const int sfd = ::open(store.c_str(), O_WRONLY);
-	if (sfd < 0) throw Error("cannot write " + store);
+	Appender to;
+	to.open(store, h);
 	std::vector<char> buf((size_t) 1 << 22);
-	uint64_t dst = h.first + h.n_samples * h.stride;
-	bool ok = true;
-	for (uint64_t src = 0; ok && src < off;) {
+	for (uint64_t src = 0; src < off;) {
 		const ssize_t n = pread(fd, buf.data(), (size_t) std::min<uint64_t>(buf.size(), off - src), (off_t) src);
-		ok = n > 0 && write_all(sfd, buf.data(), (size_t) n, dst);
-		if (ok) { src += (uint64_t) n; dst += (uint64_t) n; }
+		if (n <= 0) throw Error("cannot write " + store);
+		to.write(buf.data(), (size_t) n);
+		src += (uint64_t) n;
 	}
-	ok = ok && write_all(sfd, &total, 8, offsetof(Header, n_samples));      /* records first, the count last */
-	close(sfd);
-	if (!ok) throw Error("cannot write " + store);
-	return total;
+	return to.commit(files.size());
 }
 
 }  // namespace eval_store

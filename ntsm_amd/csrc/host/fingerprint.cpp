@@ -7,6 +7,7 @@
 #include <fstream>
 #include <iostream>
 #include <set>
+#include <sstream>
 #include <thread>
 #include <sys/stat.h>
 
@@ -86,7 +87,7 @@ void FingerPrint::quit(const std::string &message)
 	exit(1);
 }
 
-FingerPrint::FingerPrint(const Options &opt) : m_opt(opt)
+FingerPrint::FingerPrint(const Options &opt, const SiteCheck &check) : m_opt(opt)
 {
 	/* -t N is a ceiling: the threads that parse follow the CPUs this process is granted (affinity mask, cgroup quota), and the
 	 * decoder pools follow them (host_shape.hpp); counting into one table does not depend on the number */
@@ -94,11 +95,22 @@ FingerPrint::FingerPrint(const Options &opt) : m_opt(opt)
 	if (m_opt.threads > 1) m_opt.threads = std::max(2u, std::min(m_opt.threads, std::max(m_plan.feeders, 2u)));   /* 2 at least: keeps the lane path (and its tests) on a 1-CPU grant */
 	if (m_opt.devices.empty()) m_opt.devices.push_back(m_opt.device);
 	m_ctxDevice = m_opt.devices;                          /* one context per LISTED device: `-g 0,0` = two contexts on device 0, merged on the device (ntsm_allreduce) */
+	Lap lap;
+	const bool lanes = lanesPossible();
+	/* A caller with a say about the site set hears it before any device is touched: the sites are loaded first (their
+	 * warnings held back until the run is known to go on), and only then do the side threads below start. */
+	bool loaded = false;
+	if (check) {
+		std::ostringstream warnings;
+		if (!m_sites.load(m_opt.snp, m_opt.k, m_opt.dupes, warnings)) quit("file " + m_opt.snp + " cannot be opened");
+		const std::string refusal = check(m_sites);
+		if (!refusal.empty()) quit(refusal);
+		std::cerr << warnings.str();
+		loaded = true;
+	}
 	/* Side threads, one per device, prepare everything that does not depend on the sites while this thread parses
 	 * them: runtime + device context, the three streams of a context, the pinned staging pool (first device),
 	 * the two streams its lanes share.  They are joined when the first batch is about to be staged (computeCounts). */
-	Lap lap;
-	const bool lanes = lanesPossible();
 	{
 		const uint64_t slot = Feeder::slot_bytes(m_opt, false), lane_slot = Feeder::slot_bytes(m_opt, true);
 		const uint64_t pool_bytes = lanes ? (uint64_t) m_opt.threads * 2 * ((m_opt.pack ? lane_slot * 3 / 8 : lane_slot) + 8192)   /* packed lanes pin 3/8 byte per position */
@@ -128,7 +140,7 @@ FingerPrint::FingerPrint(const Options &opt) : m_opt(opt)
 		m_early.reset(new EarlyIngest(m_opt.inputs[0], (unsigned) parsers(), n_dec, blockBytes(), m_opt.gz_parallel_min_bytes, chunk_pos, max_chunks, m_opt.early_kinds));
 		if (!m_early->taken()) m_early.reset();
 	}
-	if (!m_sites.load(m_opt.snp, m_opt.k, m_opt.dupes, std::cerr)) quit("file " + m_opt.snp + " cannot be opened");   /* :493-499 */
+	if (!loaded && !m_sites.load(m_opt.snp, m_opt.k, m_opt.dupes, std::cerr)) quit("file " + m_opt.snp + " cannot be opened");   /* :493-499 */
 	const double t_sites = lap();
 	if (m_opt.verbose) std::cerr << "Opening " << m_opt.snp << std::endl;
 	m_maxCounts = threshold_from((double) m_sites.n_distinct(), m_opt.covThresh);
@@ -446,6 +458,52 @@ void FingerPrint::fetchResults()
 		fatal(std::string("ntsmCount: cannot fetch counts: ") + ntsm_strerror(rc));
 	}
 	m_fetched = true;
+}
+
+void FingerPrint::attachSites(const uint32_t *offsets, const uint32_t *kmer_ix, uint32_t n_sites)
+{
+	const int rc = ntsm_sites_attach(m_ctx[0], offsets, kmer_ix, n_sites);
+	if (rc) fatal(std::string("ntsmCount: cannot upload the site lists: ") + ntsm_strerror(rc));
+}
+
+void FingerPrint::nextSample()
+{
+	m_main.reset();
+	closeLanes();
+	for (auto &t : m_retire) if (t.joinable()) t.join();
+	m_retire.clear();
+	for (ntsm_ctx *c : m_ctx) {
+		int rc = ntsm_reset(c);
+		if (rc == 0 && m_maxCounts != 0) rc = ntsm_set_max_hits(c, m_maxCounts, 1);
+		if (rc) fatal(std::string("ntsmCount: cannot reset a GPU context: ") + ntsm_strerror(rc));
+	}
+	m_totals = ntsm_totals();
+	m_totalReads = 0;
+	m_fetched = false;
+	m_counts.clear();
+}
+
+FingerPrint::SiteRecord FingerPrint::siteRecord()
+{
+	SiteRecord r;
+	m_main.reset();
+	closeLanes();
+	Lap lap;
+	/* several contexts: the same SUM as fetchResults, after which context [0] holds the job-wide vector and totals */
+	int rc = m_ctx.size() > 1 ? ntsm_allreduce(m_ctx.data(), (int) m_ctx.size()) : NTSM_OK;
+	if (rc == 0) rc = ntsm_sync(m_ctx[0], &r.run);
+	r.wait_s = lap();
+	r.counts.assign(2 * m_sites.ids.size(), 0);
+	r.sums.assign(2 * m_sites.ids.size(), 0);
+	if (rc == 0 && m_opt.phase_times) rc = ntsm_set_timing(m_ctx[0], 1);
+	if (rc == 0) rc = ntsm_sites_reduce(m_ctx[0], r.counts.data(), r.sums.data(), &r.sites);
+	if (rc == 0 && m_opt.phase_times) {
+		rc = ntsm_sites_kernel_ms(m_ctx[0], &r.kernel_ms);
+		if (rc == 0) rc = ntsm_set_timing(m_ctx[0], 0);
+	}
+	r.reduce_s = lap();
+	if (rc) fatal(std::string("ntsmCount: cannot fetch the site record: ") + ntsm_strerror(rc));
+	return r;
 }
 
 void FingerPrint::printOptionalHeader(std::ostream &out) const

@@ -7,6 +7,7 @@
 #ifndef NTSM_FINGERPRINT_HPP
 #define NTSM_FINGERPRINT_HPP
 #include <cstdint>
+#include <functional>
 #include <iosfwd>
 #include <memory>
 #include <string>
@@ -21,13 +22,33 @@ namespace ntsm {
 
 class FingerPrint {
 public:
-	explicit FingerPrint(const Options &opt);            /* FingerPrint(), :35-44 */
+	/* What the caller has to say about the site set before any device is touched: a message refuses the run (one line on
+	 * stderr, exit status 1; the loader's collision warnings are printed only where the run goes on). */
+	typedef std::function<std::string(const SiteSet &)> SiteCheck;
+	explicit FingerPrint(const Options &opt, const SiteCheck &check = nullptr);   /* FingerPrint(), :35-44 */
 	~FingerPrint();
 	void computeCounts(const std::vector<std::string> &filenames);   /* :46-87 */
 	void printOptionalHeader(std::ostream &out) const;   /* :261-268 */
 	void printCountsMax(std::ostream &out) const;        /* :270-311 */
 	std::string printInfoSummary();                      /* :313-349 */
 	uint64_t maxCounts() const { return m_maxCounts; }
+	const SiteSet &sites() const { return m_sites; }
+	/* ---- more than one sample on the same contexts (`--cohort`; the reference counts one sample per process) ----
+	 * the site set's lists on the device (ntsm_sites_attach on context [0]: offsets has 2 * n_sites + 1 entries) */
+	void attachSites(const uint32_t *offsets, const uint32_t *kmer_ix, uint32_t n_sites);
+	/* Start the next sample: every context forgets its counts and totals (the tables and the attached lists stay), -m is
+	 * armed again, and computeCounts finds the feeders as it finds them in a fresh process. */
+	void nextSample();
+	/* The sample just counted as its per-site record, reduced on the device (ntsm_sites_reduce; after ntsm_allreduce where
+	 * there are several contexts): what printCountsMax's rows hold, the two sums ntsmEval forms from them, the covered
+	 * sites, and the run's totals (total_kmers is the #@TK value). */
+	struct SiteRecord {
+		std::vector<uint32_t> counts, sums;              /* [n_sites][2] */
+		ntsm_site_totals sites {};
+		ntsm_totals run {};
+		double wait_s = 0, reduce_s = 0, kernel_ms = 0;  /* NTSM_PHASE_TIMES: the sync, reduce + download, the kernel by HIP events */
+	};
+	SiteRecord siteRecord();
 
 private:
 	void fetchResults();

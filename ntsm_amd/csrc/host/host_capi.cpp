@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <zlib.h>
 
+#include "cohort.hpp"
 #include "gz_stream.hpp"
 #include "pack2.hpp"
 #include "early_ingest.hpp"
@@ -46,6 +47,19 @@ uint64_t ntsm_sites_n_keys(const ntsm_sites *s) { return s->set.keys.size(); }
 const uint64_t *ntsm_sites_keys(const ntsm_sites *s) { return s->set.keys.data(); }
 uint64_t ntsm_sites_n_sites(const ntsm_sites *s) { return s->set.ids.size(); }
 uint64_t ntsm_sites_n_erased(const ntsm_sites *s) { return s->set.n_erased; }
+
+int ntsm_sites_lists(const ntsm_sites *s, uint32_t **offsets, uint32_t **kmer_ix, uint64_t *n_ix)
+{
+	if (!s || !offsets || !kmer_ix || !n_ix) return -1;
+	ntsm::cohort::SiteLists l;
+	try { l = ntsm::cohort::site_lists(s->set); } catch (const ntsm::cohort::Error &) { return 1; }
+	*offsets = (uint32_t *) malloc(l.offsets.size() * sizeof(uint32_t));
+	*kmer_ix = (uint32_t *) malloc((l.kmer_ix.size() + 1) * sizeof(uint32_t));
+	memcpy(*offsets, l.offsets.data(), l.offsets.size() * sizeof(uint32_t));
+	memcpy(*kmer_ix, l.kmer_ix.data(), l.kmer_ix.size() * sizeof(uint32_t));
+	*n_ix = l.kmer_ix.size();
+	return 0;
+}
 
 uint64_t ntsm_host_max_hits(uint64_t n_distinct, double cov)
 {

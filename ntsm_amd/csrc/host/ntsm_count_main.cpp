@@ -6,6 +6,9 @@
  * New, optional: -g/--gpu INT[,INT...] selects the HIP device(s) (default 0): one context per listed device, with -t N the host
  * threads are spread round-robin over them and the per-k-mer counts are merged by one RCCL SUM (ntsm_allreduce).  A device listed
  * twice gets two contexts, merged on the device without RCCL -- `-g 0,0` runs the whole multi-context path on a one-GPU host.
+ * New, optional: --cohort MANIFEST --store STORE [--counts] [--resume] counts every sample of a manifest in this one process, on
+ * the same contexts, and appends each to a cohort store (the one `ntsmEval --pack` writes) as soon as it is finished: cohort_run
+ * below, host/cohort.hpp, DESIGN.md section 14.
  */
 #include <getopt.h>
 #include <sched.h>
@@ -23,9 +26,11 @@
 #include <string>
 #include <vector>
 
+#include "cohort.hpp"
 #include "fingerprint.hpp"
 #include "gz_stream.hpp"
 #include "pack2.hpp"
+#include "report.hpp"
 
 #define PROGRAM "ntsmCount"
 
@@ -66,7 +71,18 @@ static void printHelpDialog()
 		"                         threads are spread over them. [0]\n"
 		"  -h, --help             Display this dialog.\n"
 		"  -v, --verbose          Display verbose output.\n"
-		"      --version          Print version information.\n";
+		"      --version          Print version information.\n"
+		"This build only:\n"
+		"      --cohort = STR     Count every sample of a manifest in one run: one\n"
+		"                         line NAME<TAB>READS[<TAB>READS...] per sample, no\n"
+		"                         FILES on the command line. Needs --store.\n"
+		"      --store = STR      Cohort store (ntsmEval --pack / --against) the\n"
+		"                         samples are appended to, each as soon as it is\n"
+		"                         counted; created when missing.\n"
+		"      --counts           With --cohort: also write every sample's counts\n"
+		"                         text to the path NAME.\n"
+		"      --resume           With --cohort: skip the samples the store already\n"
+		"                         holds.\n";
 	std::cerr << dialog << std::endl;
 	exit(EXIT_SUCCESS);
 }
@@ -118,9 +134,134 @@ static bool hand_over_teardown()
 	return clone(teardown_child, stack + sizeof stack, CLONE_VM | CLONE_UNTRACED | SIGCHLD, (void *) (intptr_t) getpid()) > 0;
 }
 
+/* Environment switches of both forms of a run (staging sizes, A/B switches of the ingest) */
+static void options_from_environment(ntsm::Options &opt)
+{
+	if (const char *bb = getenv("NTSM_BATCH_BYTES")) opt.batch_bytes = strtoull(bb, nullptr, 10);   /* staging slot size */
+	if (getenv("NTSM_NO_PACK")) opt.pack = false;                                                  /* lanes send raw bytes instead of 2-bit codes + validity */
+	if (const char *pi = getenv("NTSM_PACK_IMPL")) ntsm::pack2_force_impl(atoi(pi));               /* A/B of the packer: 0 best the CPU has (AVX-512 VBMI), 1 portable, 2 at most AVX2 */
+	if (const char *pb = getenv("NTSM_BLOCK_BYTES")) opt.block_bytes = strtoull(pb, nullptr, 10);   /* block-parallel ingest block size */
+	if (const char *gm = getenv("NTSM_GZ_PARALLEL_MIN")) opt.gz_parallel_min_bytes = strtoull(gm, nullptr, 10);   /* smallest gzip file that takes the decoder pool + piece-parallel parse (-t N) */
+	if (const char *gd = getenv("NTSM_GZ_DECODERS")) opt.gz_decoders = (unsigned) strtoul(gd, nullptr, 10);     /* decoder threads of that route */
+	if (const char *gc = getenv("NTSM_GZ_CHUNK")) ntsm::GzStream::set_parallel_chunk(strtoull(gc, nullptr, 10));  /* compressed bytes per chunk of the parallel gzip decoder */
+}
+
+struct CohortArgs {
+	std::string manifest, store;
+	bool counts = false, resume = false;
+};
+
+static int refuse(const std::string &why)
+{
+	std::cerr << PROGRAM ": " << why << std::endl;
+	return 1;
+}
+
+/* ntsmCount -s SITES [flags] --cohort MANIFEST --store STORE [--counts] [--resume]: every sample of the manifest through the
+ * same FingerPrint, each appended to STORE as soon as it is counted.  Everything that can be known up front is checked before
+ * the first device call and before STORE or any NAME is touched; a refusal is one sentence and exit status 1. */
+static int cohort_run(ntsm::Options &opt, const CohortArgs &ca)
+{
+	namespace co = ntsm::cohort;
+	const auto t0 = std::chrono::steady_clock::now();
+	auto since = [](std::chrono::steady_clock::time_point &t) {
+		const auto was = t;
+		t = std::chrono::steady_clock::now();
+		return std::chrono::duration<double>(t - was).count();
+	};
+	std::vector<co::Sample> samples;
+	co::Store store;
+	co::SiteLists lists;
+	try {
+		std::ifstream mf(ca.manifest);
+		if (!mf.is_open()) throw co::Error("the manifest " + ca.manifest + " cannot be opened");
+		samples = co::parse_manifest(mf, ca.manifest);
+		co::check_reads_exist(samples);
+		store.open_existing(ca.store);
+		if (ca.resume) {
+			std::vector<co::Sample> left;
+			for (co::Sample &s : samples) if (!store.holds(s.name)) left.push_back(std::move(s));
+			samples.swap(left);
+		} else {
+			for (const co::Sample &s : samples) if (store.holds(s.name)) throw co::Error("the name " + s.name + " is already in the store");
+		}
+	} catch (const std::exception &e) {
+		return refuse(e.what());
+	}
+	options_from_environment(opt);
+	opt.phase_times = getenv("NTSM_PHASE_TIMES") != nullptr;
+	opt.early = false;                                     /* there is no first input file to parse beside the start-up */
+	/* the site set's turn: loaded by the FingerPrint, judged here before it touches a device */
+	ntsm::FingerPrint fp(opt, [&](const ntsm::SiteSet &sites) -> std::string {
+		try {
+			lists = co::site_lists(sites);
+			store.check(sites.ids, lists.distinct);
+		} catch (const std::exception &e) {
+			return std::string(PROGRAM ": ") + e.what();
+		}
+		return std::string();
+	});
+	const ntsm::SiteSet &sites = fp.sites();
+	try {
+		store.begin(sites.ids, lists.distinct);
+	} catch (const std::exception &e) {
+		return refuse(e.what());
+	}
+	fp.attachSites(lists.offsets.data(), lists.kmer_ix.data(), (uint32_t) sites.ids.size());
+	if (opt.phase_times) std::cerr << "[phase] cohort: start-up (manifest, store, sites, contexts, lists) " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << " s" << std::endl;
+	std::vector<char> rec;
+	bool first = true;
+	for (const co::Sample &s : samples) {
+		auto t = std::chrono::steady_clock::now();
+		if (!first) fp.nextSample();
+		first = false;
+		const double t_reset = since(t);
+		fp.computeCounts(s.reads);
+		const double t_count = since(t);
+		const ntsm::FingerPrint::SiteRecord r = fp.siteRecord();
+		(void) since(t);
+		if (ca.counts) {                                   /* the bytes `ntsmCount [same flags] READS... > NAME` writes */
+			std::ofstream out(s.name, std::ios::binary | std::ios::trunc);
+			ntsm::print_optional_header(out, r.run.total_kmers, opt.k);
+			ntsm::print_counts_rows(out, sites.ids, r.counts.data(), r.sums.data(), lists.distinct.data());
+			out.flush();
+			if (!out) return refuse("cannot write " + s.name);
+		}
+		const double t_text = since(t);
+		co::build_record(rec, store.header(), s.name, r.run.total_kmers, opt.k, r.counts.data(), r.sites.total, r.sites.sum_of_sums);
+		try {
+			store.append(rec, s.name);
+		} catch (const std::exception &e) {
+			return refuse(e.what());
+		}
+		const double t_store = since(t);
+		std::cout << s.name << '\t' << r.run.total_bases << '\t' << r.run.total_kmers << '\t' << r.run.total_hits << '\t' << r.sites.sites_covered << std::endl;
+		if (opt.verbose)
+			std::cerr << "== " << s.name << "\n"
+			          << ntsm::info_summary_lines(sites.n_distinct(), sites.ref.size(), r.sites.sites_covered, r.run.total_bases, r.run.total_kmers, r.run.total_hits) << std::endl;
+		const double covPer = double(r.sites.sites_covered) / double(sites.ref.size());
+		if (covPer < opt.siteCovThreshold)
+			std::cerr << s.name << ": Warning: site coverage is : " << covPer
+			          << "(<75%). Data may be sorted or sparse along the genome. Any PCA projection may be inaccurate." << std::endl;
+		if (opt.phase_times)
+			std::cerr << "[phase] cohort sample " << s.name << ": reset " << t_reset << " s, count " << t_count << " s, wait " << r.wait_s << " s, reduce+download "
+			          << r.reduce_s << " s (kernel " << r.kernel_ms << " ms), counts text " << t_text << " s, store " << t_store << " s" << std::endl;
+	}
+	if (opt.verbose)
+		std::cerr << "Time: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << " s Memory: " << rss_kb() << " kbytes" << std::endl;
+	if (!getenv("NTSM_CLEAN_EXIT")) {                      /* as the single run leaves: everything is written, the driver reclaims the rest */
+		std::cout.flush();
+		std::cerr.flush();
+		fflush(nullptr);
+		_exit(0);
+	}
+	return 0;
+}
+
 int main(int argc, char *argv[])
 {
 	ntsm::Options opt;
+	CohortArgs cohort;
 	bool die = false;
 	int OPT_VERSION = 0;
 	/* "dupes" takes an argument in its long form only, as in the reference (:66 vs :75) */
@@ -132,6 +273,8 @@ int main(int argc, char *argv[])
 		{ "version", no_argument, &OPT_VERSION, 1 }, { "verbose", no_argument, NULL, 'v' },
 		{ "debug-fault", required_argument, NULL, 1000 },      /* tests only, not in the help text: KIND:NTH -> ntsm_debug_fail_after */
 		{ "debug-kernel", required_argument, NULL, 1001 },     /* tests only: force a kernel variant (ntsm_set_kernel) */
+		{ "cohort", required_argument, NULL, 1002 }, { "store", required_argument, NULL, 1003 },
+		{ "counts", no_argument, NULL, 1004 },       { "resume", no_argument, NULL, 1005 },
 		{ NULL, 0, NULL, 0 } };
 	int c, option_index = 0;
 	while ((c = getopt_long(argc, argv, "s:t:vhk:m:do:g:", long_options, &option_index)) != -1) {
@@ -170,10 +313,22 @@ int main(int argc, char *argv[])
 		case 1001:                                     /* tools/soak.py: the same inputs through every kernel form, against the oracle */
 			if (!parse(optarg, opt.debug_kernel) || opt.debug_kernel < 0) { std::cerr << "Error - Invalid parameter debug-kernel: " << optarg << std::endl; return 0; }
 			break;
+		case 1002: cohort.manifest = optarg; break;
+		case 1003: cohort.store = optarg; break;
+		case 1004: cohort.counts = true; break;
+		case 1005: cohort.resume = true; break;
 		case '?': die = true; break;
 		}
 	}
 	if (OPT_VERSION) printVersion();
+	const bool cohort_mode = !cohort.manifest.empty() || !cohort.store.empty();
+	if (!die) {                                            /* the four options of a cohort run go together or not at all */
+		if (cohort.manifest.empty() != cohort.store.empty()) return refuse(cohort.store.empty() ? "--cohort needs --store" : "--store needs --cohort");
+		if (!cohort_mode && cohort.counts) return refuse("--counts needs --cohort");
+		if (!cohort_mode && cohort.resume) return refuse("--resume needs --cohort");
+		if (cohort_mode && optind < argc) return refuse("with --cohort the read files come from the manifest, not from the command line");
+		if (cohort_mode && !opt.summary.empty()) return refuse("-o writes one sample's summary and cannot be combined with --cohort");
+	}
 	if (opt.k > 32) {
 		die = true;
 		std::cerr << "Error: k cannot be greater than 32" << std::endl;
@@ -195,7 +350,7 @@ int main(int argc, char *argv[])
 		}
 		optind++;
 	}
-	if (inputFiles.size() == 0) {
+	if (inputFiles.size() == 0 && !cohort_mode) {
 		std::cerr << "Error: Need input files" << std::endl;
 		die = true;
 	}
@@ -203,13 +358,8 @@ int main(int argc, char *argv[])
 		std::cerr << "Try '--help' for more information.\n";
 		exit(EXIT_FAILURE);
 	}
-	if (const char *bb = getenv("NTSM_BATCH_BYTES")) opt.batch_bytes = strtoull(bb, nullptr, 10);   /* staging slot size */
-	if (getenv("NTSM_NO_PACK")) opt.pack = false;                                                  /* lanes send raw bytes instead of 2-bit codes + validity */
-	if (const char *pi = getenv("NTSM_PACK_IMPL")) ntsm::pack2_force_impl(atoi(pi));               /* A/B of the packer: 0 best the CPU has (AVX-512 VBMI), 1 portable, 2 at most AVX2 */
-	if (const char *pb = getenv("NTSM_BLOCK_BYTES")) opt.block_bytes = strtoull(pb, nullptr, 10);   /* block-parallel ingest block size */
-	if (const char *gm = getenv("NTSM_GZ_PARALLEL_MIN")) opt.gz_parallel_min_bytes = strtoull(gm, nullptr, 10);   /* smallest gzip file that takes the decoder pool + piece-parallel parse (-t N) */
-	if (const char *gd = getenv("NTSM_GZ_DECODERS")) opt.gz_decoders = (unsigned) strtoul(gd, nullptr, 10);     /* decoder threads of that route */
-	if (const char *gc = getenv("NTSM_GZ_CHUNK")) ntsm::GzStream::set_parallel_chunk(strtoull(gc, nullptr, 10));  /* compressed bytes per chunk of the parallel gzip decoder */
+	if (cohort_mode) return cohort_run(opt, cohort);
+	options_from_environment(opt);
 	const auto t0 = std::chrono::steady_clock::now();
 	const bool phases = opt.phase_times = getenv("NTSM_PHASE_TIMES") != nullptr;
 	if (phases) {                                          /* time between exec and main: loader + static initialisers of the HIP runtime */

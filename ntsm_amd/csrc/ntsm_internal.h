@@ -6,6 +6,7 @@
  *   kernels_generic.hip  generic-k count kernel + helper kernels, launch_generic / launch_gather / ...
  *   kernels_mz.hip       minimizer-blocked count kernels, launch_mz (+ the tabulated kernel in `make tab` builds)
  *   kernels_run.hip      run-anchored count kernel (k = 19, one filter test per minimizer run), launch_run
+ *   kernels_sites.hip    per-site reduction of the dense count vector (ntsm_sites_attach / ntsm_sites_reduce: kernel and entry points)
  *   tables.cpp           host-side construction of the cuckoo key table and the filters (no HIP call, no device code)
  *   runtime.cpp          pools, the staging slot's lifecycle (slot_acquire / slot_release), table upload, launch_count, the one enqueue
  *                        step of a batch (enqueue_batch) and a context's use of it (submit_slot), the exact -m early stop (armed_batch)
@@ -210,6 +211,14 @@ struct ntsm_ctx {
 	static constexpr size_t kDeviceCacheMax = 128;
 	hipStream_t lane_stream[2] = { nullptr, nullptr };   /* shared by all lanes (round robin): a stream costs 14 ms to create */
 	unsigned lanes_opened = 0;
+	/* site -> k-mer lists of the key set (ntsm_sites_attach, kernels_sites.hip): kept across ntsm_reset like the tables */
+	uint32_t *d_site_off = nullptr, *d_site_ix = nullptr;    /* 2 * n_sites + 1 offsets into d_site_ix; indices into d_vec */
+	uint32_t *d_site_out = nullptr;                          /* counts[n_sites][2], then sums[n_sites][2] */
+	unsigned long long *d_site_totals = nullptr;             /* total, sum_of_sums, sites_covered of the reduce in flight */
+	uint32_t n_sites = 0;
+	bool sites_attached = false;
+	hipEvent_t site_ev[2] = { nullptr, nullptr };            /* around the reduce kernel while ntsm_set_timing is on */
+	double site_kernel_ms = 0;                               /* the last reduce's kernel time (ntsm_sites_kernel_ms) */
 };
 
 /* One producer thread's private staging: two pinned slots + their device mirrors and streams.  All lanes of a
@@ -242,6 +251,9 @@ hipError_t launch_zero_counts(uint64_t *table, unsigned long long n_buckets, hip
 /* the whole tabulated launch (queue / list buffers of this stream, segments, look-up kernels, the list walker); caller holds c->mu */
 int launch_tab(ntsm_ctx *c, hipStream_t st, const NtsmCountParams &p, uint64_t hi);
 #endif
+
+/* ---- kernels_sites.hip */
+void sites_destroy(ntsm_ctx *c);             /* ntsm_destroy: the lists, the outputs and the two timing events */
 
 /* ---- tables.cpp: the four (five) structures as host images; no HIP call */
 struct TableImages {

@@ -10,6 +10,7 @@
 #                                                  the store's own samples (--within / --within-near)
 #   ntsm_amd/libntsm_vcf_hip.so, build/ntsmVCF     multi-sample VCF to PCA matrix + centre file (HIP library + CLI mirror);
 #                                                  with --rotation also the PCA, through libntsm_pca_hip.so
+#                                                  with --counts / --store the genotypes as counts files and cohort-store records
 #   ntsm_amd/libntsm_pca_hip.so, build/ntsmPCA     exact PCA of the ntsmVCF matrix: rotation for ntsmEval -p (HIP library + CLI)
 #   ntsm_amd/libntsm_sitegen_hip.so, build/ntsmSiteGen   sites files from a genome and a VCF of SNPs (HIP library + CLI)
 #   ntsm_amd/libntsm_sitegen_gap_hip.so                  the device step of `ntsmSiteGen -g`: one-base gapped places as well
@@ -121,7 +122,7 @@ build/cohort_count_check: tools/cohort_count_check.cpp $(HOST)/cohort.hpp $(HOST
 	@mkdir -p build
 	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ tools/cohort_count_check.cpp $(HOST)/report.cpp
 
-# ntsmVCF (multi-sample VCF -> PCA matrix and centre file): own library, own CLI
+# ntsmVCF (multi-sample VCF -> PCA matrix and centre file; --counts / --store: counts files and cohort-store records): own library, own CLI
 ntsm_amd/libntsm_vcf_hip.so: $(CSRC)/ntsm_vcf.hip $(CSRC)/ntsm_hip_scope.h include/ntsm_vcf_hip.h
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -shared -o $@ $(CSRC)/ntsm_vcf.hip
 

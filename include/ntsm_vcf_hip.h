@@ -71,6 +71,44 @@ int ntsm_vcf_run(int device, uint32_t n_samples, uint32_t multi,
 		uint16_t *cells, double *sums, uint32_t *first_undef,
 		ntsm_vcf_warning *warn, uint64_t warn_cap, uint64_t *n_warn, ntsm_vcf_times *times);
 
+/*
+ * The counts records of a window of samples (MultiCount::printCountsMax, MultiCount.hpp:93-138): per (sample, site) the
+ * two maxima of ntsm_vcf_run's cell and the two sums of the same final state bytes, sample-major, plus each sample's two
+ * totals as a cohort store's record holds them (ntsm_amd/csrc/host/eval_store.hpp).  The insert rule is ntsm_vcf_run's;
+ * warnings are not reported here (ntsm_vcf_run is their source).  All results are exact integers; the order in which the
+ * device adds the totals cannot change them.
+ */
+typedef struct ntsm_vcf_records_times {   /* milliseconds; upload / download wall clock, the kernel from HIP events */
+	double upload_ms, kernel_ms, download_ms;
+	uint64_t kernel_bytes;           /* bytes the kernel reads and writes at least once (the window's G columns, lists, records) */
+	uint64_t upload_bytes, download_bytes;
+} ntsm_vcf_records_times;
+
+/*
+ * n_samples, multi, n_lines, geno, g_stride, n_keys, key_off, n_events, ev_ord, ev_ls, n_sites, site_off, site_keys:
+ *            as for ntsm_vcf_run, with the same checks (ev_ord is not read: the lists are already in ordinal order).
+ * s_begin:   first sample of the window, a multiple of 16.
+ * s_count:   samples in the window, >= 1, s_begin + s_count <= n_samples.  Only the window's columns of geno are
+ *            uploaded (one 2-D copy of s_count rounded up to 16 bytes per line).
+ * counts:    host out: for sample j of the window (j = 0 is sample s_begin), n_sites pairs of uint32 (maxREF, maxVAR)
+ *            at (char *) counts + j * counts_pitch.  Bytes of a row past 8 * n_sites are not written.
+ * counts_pitch: bytes from one sample's row to the next; a multiple of 8, >= 8 * n_sites.
+ * sums:      host out, may be NULL: the same shape, (sumREF, sumVAR) = the 32-bit sums over the site's REF / VAR keys
+ *            of the final state bytes (the truncated uint8 values).
+ * sums_pitch: as counts_pitch, for sums; not read when sums is NULL.
+ * total:     host out [s_count]: sum over the sites of uint32(maxREF + maxVAR).
+ * sum_of_sums: host out [s_count]: sum over the sites of uint32(sumREF + sumVAR); written whether or not sums is NULL.
+ * times:     may be NULL.
+ * Returns 0, -1 bad argument, -2 HIP error.
+ */
+int ntsm_vcf_records(int device, uint32_t n_samples, uint32_t multi,
+		uint64_t n_lines, const uint8_t *geno, uint32_t g_stride,
+		uint64_t n_keys, const uint64_t *key_off, uint64_t n_events, const uint32_t *ev_ord, const uint32_t *ev_ls,
+		uint64_t n_sites, const uint64_t *site_off, const uint32_t *site_keys,
+		uint32_t s_begin, uint32_t s_count,
+		uint32_t *counts, uint64_t counts_pitch, uint32_t *sums, uint64_t sums_pitch,
+		uint64_t *total, uint64_t *sum_of_sums, ntsm_vcf_records_times *times);
+
 #ifdef __cplusplus
 }
 #endif

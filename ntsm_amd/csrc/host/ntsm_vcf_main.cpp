@@ -17,12 +17,18 @@
  *                to libntsm_pca_hip.so with the double every cell's text reads back as (include/ntsm_pca_hip.h,
  *                ntsm_pca_run_cells), and NAME_rotationalMatrix.tsv and NAME_components.tsv are written as ntsmPCA
  *                writes them (pca_text.hpp); -M leaves NAME_matrix.tsv out
+ *   counts       --counts DIR / --store STORE (this build only): what the reference's VCFConvert::outputCounts would write
+ *                (:176-187, MultiCount::printCountsMax, MultiCount.hpp:93-138; its main never calls it), per sample a
+ *                counts file and / or a record of a cohort store (eval_store.hpp), from ntsm_vcf_records, in windows of
+ *                samples so that memory does not grow with the cohort
  * Whatever -t is, the result is the one-thread result.  Inputs where the reference throws, asserts or has undefined
  * behaviour are refused with "Error: ..." and exit status 1.  A VCF that starts with the gzip
  * magic is decoded (ntsm::GzStream); the reference reads it as text and finds no samples.
  */
 #include <getopt.h>
 #include <sys/resource.h>
+#include <sys/stat.h>
+#include <unistd.h>
 
 #include <algorithm>
 #include <cstdio>
@@ -34,17 +40,26 @@
 #include <stdexcept>
 #include <string>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include "../../../include/ntsm_pca_hip.h"
 #include "../../../include/ntsm_vcf_hip.h"
 #include "cli.hpp"
+#include "eval_store.hpp"
 #include "kmer.hpp"
 #include "pca_text.hpp"
 #include "seq_reader.hpp"
 #include "site_set.hpp"
 
 #define PROGRAM "ntsmVCF"
+
+/* Referenced weakly: a program linked against a device library without the records step (the CPU stand-in of
+ * tests/test_vcf.py) still links, and refuses --counts / --store */
+extern "C" __attribute__((weak)) int ntsm_vcf_records(int device, uint32_t n_samples, uint32_t multi, uint64_t n_lines, const uint8_t *geno,
+		uint32_t g_stride, uint64_t n_keys, const uint64_t *key_off, uint64_t n_events, const uint32_t *ev_ord, const uint32_t *ev_ls,
+		uint64_t n_sites, const uint64_t *site_off, const uint32_t *site_keys, uint32_t s_begin, uint32_t s_count, uint32_t *counts,
+		uint64_t counts_pitch, uint32_t *sums, uint64_t sums_pitch, uint64_t *total, uint64_t *sum_of_sums, ntsm_vcf_records_times *times);
 
 namespace {
 
@@ -55,6 +70,9 @@ struct Opt {                                 /* src/Options.h: the members ntsmV
 	bool rotation = false, no_matrix = false, dims_given = false;   /* -R, -M, -n (this build only) */
 	long long numComp = 20;                                         /* ntsmPCA's -n and its default */
 	std::string snp, ref, pca;
+	std::string counts_dir, store;                                  /* --counts, --store (this build only) */
+	bool want_counts = false, want_store = false;
+	bool records() const { return want_counts || want_store; }
 	std::vector<std::string> inputs;                                /* the arguments after the flags */
 	unsigned T = 1;                                                 /* ntsm::thread_count(threads) */
 };
@@ -84,6 +102,11 @@ void printHelpDialog()
 	    "                         ntsmEval -p and the components. (this build only)\n"
 	    "  -n, --dims = INT       With -R: number of components. [" << std::to_string(d.numComp) << "]\n"
 	    "  -M, --no-matrix        With -R: do not write the matrix file.\n"
+	    "      --counts = DIR     Write DIR/SAMPLE.counts.txt for every sample.\n"
+	    "                         (this build only)\n"
+	    "      --store = STR      Create this cohort store for ntsmEval --against,\n"
+	    "                         or append to it: one record per sample.\n"
+	    "                         (this build only)\n"
 	    "  -h, --help             Display this dialog.\n"
 	    "  -v, --verbose          Display verbose output.\n"
 	    "      --version          Print version information.\n" << std::endl;
@@ -287,6 +310,7 @@ Opt read_options(int argc, char **argv)
 	Opt opt;
 	bool die = false;
 	int OPT_VERSION = 0;
+	enum { kOptCounts = 1000, kOptStore };                           /* long options only: none of the reference's letters */
 	static struct option long_options[] = {
 		{ "threads", required_argument, nullptr, 't' }, { "dupes", no_argument, nullptr, 'd' },
 		{ "snp", required_argument, nullptr, 's' }, { "pca", required_argument, nullptr, 'p' },
@@ -295,7 +319,8 @@ Opt read_options(int argc, char **argv)
 		{ "help", no_argument, nullptr, 'h' }, { "version", no_argument, &OPT_VERSION, 1 },
 		{ "verbose", no_argument, nullptr, 'v' }, { "gpu", required_argument, nullptr, 'G' },
 		{ "rotation", no_argument, nullptr, 'R' }, { "dims", required_argument, nullptr, 'n' },
-		{ "no-matrix", no_argument, nullptr, 'M' }, { nullptr, 0, nullptr, 0 } };
+		{ "no-matrix", no_argument, nullptr, 'M' }, { "counts", required_argument, nullptr, kOptCounts },
+		{ "store", required_argument, nullptr, kOptStore }, { nullptr, 0, nullptr, 0 } };
 	int ch;
 	while ((ch = getopt_long(argc, argv, "s:t:vhk:dr:w:m:p:G:Rn:M", long_options, nullptr)) != -1) {
 		switch (ch) {                            /* src/ntSeqMatchVCF.cpp:82-156 */
@@ -313,6 +338,8 @@ Opt read_options(int argc, char **argv)
 		case 'M': opt.no_matrix = true; break;
 		case 'n': opt.dims_given = true; ntsm::whole_flag('n', optarg, opt.numComp, die); break;   /* as ntsmPCA reads its -n */
 		case 'v': opt.verbose++; break;
+		case kOptCounts: opt.want_counts = true; opt.counts_dir = optarg; break;
+		case kOptStore: opt.want_store = true; opt.store = optarg; break;
 		case '?': die = true; break;
 		default: break;
 		}
@@ -332,6 +359,7 @@ Opt read_options(int argc, char **argv)
 	if (opt.rotation && opt.numComp < 1) refuse(ntsm::pca_dims_low_error(opt.numComp));
 	if (opt.inputs.size() > 1) refuse("ntsmVCF takes one VCF file, " + std::to_string(opt.inputs.size()) + " were given");   /* :199 asserts */
 	if (opt.k == 0 || opt.k == 32) refuse("-k " + std::to_string(opt.k) + " is not supported (k must be 1 to 31)");
+	if (opt.records() && !ntsm_vcf_records) refuse("--counts / --store: the device library of this build lacks the records step (ntsm_vcf_records)");
 	if (opt.window >= kMaxWindow) refuse("-w " + std::to_string(opt.window) + " is too large (at most " + std::to_string(kMaxWindow - 1) + ")");
 	opt.T = ntsm::thread_count(opt.threads);
 	return opt;
@@ -348,14 +376,20 @@ ntsm::SiteSet load_sites(const Opt &opt)         /* VCFConvert's constructor, fi
 	if (sites.ref.size() != sites.var.size())
 		refuse("the sites file has an odd number of records (" + std::to_string(sites.ref.size() + sites.var.size()) + "): site " +
 		    sites.ids.back() + " has no VAR record");
-	if (!opt.pca.empty() && !opt.dupes && sites.n_erased) {
+	if ((!opt.pca.empty() || opt.records()) && !opt.dupes && sites.n_erased) {
 		/* without -d a shared k-mer is erased from the keys but stays in its first allele list: the reference's
-		 * printNormMatrix throws at that site (m_kmerToHash.at), after rows that overlap the next sample's */
+		 * printNormMatrix throws at that site (m_kmerToHash.at), after rows that overlap the next sample's, and so does
+		 * printCountsMax (--counts / --store) */
 		size_t s = 0;
 		auto has = [](const std::vector<int64_t> &l) { return std::find(l.begin(), l.end(), ntsm::SiteSet::kErased) != l.end(); };
 		while (s < n_sites && !has(sites.ref[s]) && !has(sites.var[s])) ++s;
 		refuse("the sites file has k-mers shared between sites (first at site " + sites.ids[std::min(s, n_sites - 1)] +
-		    "); -p needs -d for such a file");
+		    "); " + (opt.pca.empty() ? "--counts / --store need" : "-p needs") + " -d for such a file");
+	}
+	if (opt.want_store) {                                           /* a store finds a locus by its ID (eval_store::LocusIndex) */
+		std::unordered_set<std::string> seen;
+		for (const std::string &id : sites.ids)
+			if (!seen.insert(id).second) refuse("the sites file has the locus ID " + id + " twice; --store needs distinct IDs");
 	}
 	return sites;
 }
@@ -634,6 +668,183 @@ void write_outputs(const Opt &opt, const std::string &head, const std::vector<st
 	if (fclose(cf) != 0 || !ok) refuse("writing " + opt.pca + "_matrix.tsv / _center.txt failed");
 }
 
+/* ---- --counts / --store: the records of ntsm_vcf_records as counts files and as a cohort store ------------------------------ */
+
+namespace store = ntsm::eval_store;
+
+struct RecordsPlan {                         /* what --counts / --store decide from the inputs alone, before the device */
+	std::vector<std::string> paths;          /* --counts: DIR/SAMPLE.counts.txt per sample */
+	std::vector<std::string> names;          /* --store: the record names (those paths, or the sample IDs) */
+	std::vector<uint32_t> distinct;          /* [n_sites][2]: the sizes of the allele lists (printCountsMax's last columns) */
+	store::Header head {};                   /* of the store as it is now (n_samples = 0 for one to create) */
+	bool store_exists = false;
+	uint32_t window = 16;                    /* samples per call of the device step */
+};
+
+constexpr uint64_t kWindowBytes = 256ull << 20;   /* records of one window: the host buffer does not grow with the cohort */
+
+RecordsPlan plan_records(const Opt &opt, const ntsm::SiteSet &sites, const std::vector<std::string> &samples)
+{
+	RecordsPlan plan;
+	if (samples.empty()) refuse("the VCF's header has no samples: --counts / --store have nothing to write");
+	struct stat st;
+	if (opt.want_counts) {
+		for (const std::string &id : samples)
+			if (id.empty() || id.find('/') != std::string::npos)
+				refuse("the sample ID '" + id + "' cannot name a counts file (it is empty or contains '/')");
+		if (stat(opt.counts_dir.c_str(), &st) != 0 || !S_ISDIR(st.st_mode)) refuse("--counts: " + opt.counts_dir + " is not a directory");
+		for (const std::string &id : samples) plan.paths.push_back(opt.counts_dir + "/" + id + ".counts.txt");
+	}
+	const std::vector<std::string> &names = opt.want_counts ? plan.paths : samples;
+	std::unordered_set<std::string> seen;
+	try {
+		for (const std::string &n : names) {
+			store::check_name(n);
+			if (!seen.insert(n).second) refuse("two samples are named " + n);
+		}
+		const size_t n_sites = sites.ids.size();
+		for (size_t s = 0; s < n_sites; ++s) {
+			plan.distinct.push_back((uint32_t) sites.ref[s].size());
+			plan.distinct.push_back((uint32_t) sites.var[s].size());
+		}
+		plan.head = store::new_header(sites.ids);
+		if (opt.want_store) {
+			plan.names = names;
+			plan.store_exists = stat(opt.store.c_str(), &st) == 0;
+			if (plan.store_exists) {
+				store::View v;
+				v.open(opt.store);
+				if (v.locus != sites.ids || (n_sites && memcmp(v.distinct, plan.distinct.data(), 8 * n_sites) != 0))
+					refuse("the loci of the store " + opt.store + " (IDs and distinct columns) are not those of " + opt.snp);
+				for (uint64_t r = 0; r < v.h.n_samples; ++r)
+					if (seen.count(v.name(r))) refuse("the name " + v.name(r) + " is already in the store");
+				plan.head = v.h;
+			}
+		}
+	} catch (const store::Error &e) {
+		refuse(e.what());
+	}
+	const bool dir_writable = !opt.want_counts || access(opt.counts_dir.c_str(), W_OK | X_OK) == 0;
+	for (const std::string &p : plan.paths)                      /* a counts file that cannot be written, as far as a look tells */
+		if (!dir_writable || (stat(p.c_str(), &st) == 0 && !S_ISREG(st.st_mode))) refuse("cannot write " + p);
+	uint64_t window = std::max<uint64_t>(16, kWindowBytes / plan.head.stride / 16 * 16);
+	if (const char *w = getenv("NTSM_VCF_STORE_WINDOW")) {       /* samples; a test forces several windows with it */
+		unsigned long long v = 0;
+		if (!ntsm::read_whole(w, v) || v < 1) refuse("NTSM_VCF_STORE_WINDOW=" + std::string(w) + " is not a number of samples");
+		window = std::max<uint64_t>(16, std::min<uint64_t>(v, 1u << 30) / 16 * 16);
+	}
+	plan.window = (uint32_t) std::min<uint64_t>(window, (samples.size() + 15) / 16 * 16);
+	return plan;
+}
+
+inline void append_number(std::string &o, uint32_t v)       /* std::to_string's digits, without its temporary */
+{
+	char b[10];
+	int n = 0;
+	do { b[n++] = (char) ('0' + v % 10); v /= 10; } while (v);
+	while (n) o += b[--n];
+}
+
+/* printCountsMax's bytes for one sample (MultiCount.hpp:93-138); counts and sums are the sample's [n_sites][2] */
+void counts_text(std::string &o, const std::vector<std::string> &ids, const uint32_t *counts, const uint32_t *sums, const uint32_t *distinct)
+{
+	o = "\n#locusID\tcountAT\tcountCG\tsumAT\tsumCG\tdistinctAT\tdistinctCG\n";
+	for (size_t s = 0; s < ids.size(); ++s) {
+		o += ids[s];
+		for (const uint32_t *v : { counts, sums, distinct })
+			for (int c = 0; c < 2; ++c) { o += '\t'; append_number(o, v[2 * s + c]); }
+		o += '\n';
+	}
+}
+
+/* The samples in windows: device step, then the window's counts files (formatted and written on T threads) and its store
+ * records.  The store changes last: a new one is STORE.tmp until it is renamed, an old one gets its sample count when
+ * every record is behind the last one; a failure on the way removes STORE.tmp or cuts the old store back to its size. */
+void write_records(const Opt &opt, const RecordsPlan &plan, const Events &ev, const std::vector<std::string> &ids, uint32_t n_samples, bool prof)
+{
+	const size_t n_sites = ids.size();
+	const uint64_t stride = plan.head.stride, old_size = plan.head.first + plan.head.n_samples * stride;
+	const std::string tmp = opt.store + ".tmp", &target = plan.store_exists ? opt.store : tmp;
+	bool store_open = false;
+	const auto fail = [&](const std::string &why) {
+		if (store_open && !plan.store_exists) unlink(tmp.c_str());
+		if (store_open && plan.store_exists && truncate(opt.store.c_str(), (off_t) old_size) != 0) std::cerr << "cannot restore " << opt.store << std::endl;
+		refuse(why);
+	};
+	store::Appender to;
+	std::vector<char> recs((size_t) plan.window * stride);
+	std::vector<uint32_t> sums(opt.want_counts ? (size_t) plan.window * 2 * n_sites : 0);
+	std::vector<uint64_t> total(plan.window), sum_of_sums(plan.window);
+	std::vector<std::string> text(opt.T), failed(opt.T);
+	double dev_s[3] = { 0, 0, 0 }, text_s = 0, store_s = 0;
+	uint64_t kernel_bytes = 0, n_windows = 0;
+	const auto now = [] { return std::chrono::steady_clock::now(); };
+	const auto since = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double>(now() - t).count(); };
+	try {
+		if (opt.want_store) {
+			if (!plan.store_exists) {                                /* header (n_samples still 0) and locus section */
+				const int fd = open(tmp.c_str(), O_CREAT | O_TRUNC | O_RDWR, 0644);
+				if (fd < 0) refuse("cannot write " + tmp);
+				store_open = true;
+				const bool ok = store::write_head(fd, plan.head, ids, plan.distinct.data());
+				close(fd);
+				if (!ok) fail("cannot write " + tmp);
+			}
+			to.open(target, plan.head);
+			store_open = true;
+		}
+		for (uint32_t s_begin = 0; s_begin < n_samples; s_begin += plan.window, ++n_windows) {
+			const uint32_t cnt = std::min(plan.window, n_samples - s_begin);
+			std::fill(recs.begin(), recs.begin() + (size_t) cnt * stride, 0);
+			ntsm_vcf_records_times tm {};
+			const int rc = ntsm_vcf_records(opt.device, n_samples, opt.multi, ev.n_lines, ev.geno.data(), ev.g_stride, ev.n_keys, ev.key_off.data(),
+			    ev.n_events, ev.ev_ord.data(), ev.ev_ls.data(), ev.n_sites, ev.site_off.data(), ev.site_keys.data(), s_begin, cnt,
+			    (uint32_t *) (recs.data() + store::kRecordHead), stride, opt.want_counts ? sums.data() : nullptr, 8 * n_sites, total.data(),
+			    sum_of_sums.data(), &tm);
+			if (rc) fail("the HIP records step failed (" + std::to_string(rc) + ")");
+			dev_s[0] += tm.upload_ms / 1e3; dev_s[1] += tm.kernel_ms / 1e3; dev_s[2] += tm.download_ms / 1e3;
+			kernel_bytes += tm.kernel_bytes;
+			auto t0 = now();
+			if (opt.want_counts) {
+				on_threads(opt.T, [&](unsigned t) {
+					for (uint32_t j = t; j < cnt && failed[t].empty(); j += opt.T) {
+						counts_text(text[t], ids, (const uint32_t *) (recs.data() + (size_t) j * stride + store::kRecordHead),
+						    sums.data() + (size_t) j * 2 * n_sites, plan.distinct.data());
+						const std::string &path = plan.paths[s_begin + j];
+						FILE *f = fopen(path.c_str(), "wb");
+						const bool ok = f && fwrite(text[t].data(), 1, text[t].size(), f) == text[t].size();
+						if ((f && fclose(f) != 0) || !ok) failed[t] = path;
+					}
+				});
+				for (const std::string &path : failed)
+					if (!path.empty()) fail("cannot write " + path);
+				text_s += since(t0);
+				t0 = now();
+			}
+			if (opt.want_store) {
+				for (uint32_t j = 0; j < cnt; ++j)                       /* no #@TK / #@KS line in such a file: raw_total = kmer_size = 0 */
+					store::fill_record_head(recs.data() + (size_t) j * stride, plan.names[s_begin + j], 0, 0, total[j], sum_of_sums[j]);
+				to.write(recs.data(), (size_t) cnt * stride);
+				store_s += since(t0);
+			}
+		}
+		if (opt.want_store) {
+			const auto t0 = now();
+			to.commit(n_samples);
+			if (!plan.store_exists && rename(tmp.c_str(), opt.store.c_str()) != 0) fail("cannot rename " + tmp + " to " + opt.store);
+			store_s += since(t0);
+		}
+	} catch (const store::Error &e) {
+		fail(e.what());
+	}
+	if (prof) {
+		fprintf(stderr, "[vcf] records device: windows %llu of %u samples, upload %.4f s, kernel %.6f s, download %.4f s, kernel bytes %llu\n",
+		    (unsigned long long) n_windows, plan.window, dev_s[0], dev_s[1], dev_s[2], (unsigned long long) kernel_bytes);
+		if (opt.want_counts) fprintf(stderr, "[vcf] counts format + write: %.4f s\n", text_s);
+		if (opt.want_store) fprintf(stderr, "[vcf] store write: %.4f s\n", store_s);
+	}
+}
+
 } // namespace
 
 /* The order is the contract: every refusal of the inputs before the device, nothing written before -R's PCA has succeeded */
@@ -651,6 +862,7 @@ int main(int argc, char **argv)
 	const Header header = read_header(vcf);
 	const uint32_t n_samples = (uint32_t) header.samples.size(), stride = (n_samples + 15) / 16 * 16;
 	if (opt.verbose > 1) std::cerr << "Starting multicount of each rsID for " << n_samples << " samples." << std::endl;
+	const RecordsPlan plan = opt.records() ? plan_records(opt, sites, header.samples) : RecordsPlan();
 	const KeyTable table(sites.keys);
 	std::vector<Part> parts = parse_body(Ctx { opt, genome, table, n_samples, stride }, header, opt.T);
 	timer.lap("parse");
@@ -679,6 +891,10 @@ int main(int argc, char **argv)
 			if (!bad_path.empty()) refuse("cannot write " + bad_path);
 			timer.lap("rotation + components write");
 		}
+	}
+	if (opt.records()) {                         /* after -p's files: nothing of these is written before a -R PCA has succeeded */
+		write_records(opt, plan, events, sites.ids, n_samples, timer.on);
+		timer.lap("records (total)");
 	}
 	std::cerr << "Time: " << timer.total() << " s Memory: " << rss_kbytes() << " kbytes" << std::endl;
 	return 0;

@@ -76,3 +76,78 @@ def run(geno, multi, key_events, site_ref, site_var, device=0, warn_cap=1 << 16)
         break
     warn = np.sort(warn[:n_warn.value], order=["event", "sample"])
     return cells, sums, first, warn, times
+
+
+class RecordsTimes(C.Structure):
+    _fields_ = [("upload_ms", C.c_double), ("kernel_ms", C.c_double), ("download_ms", C.c_double),
+                ("kernel_bytes", C.c_uint64), ("upload_bytes", C.c_uint64), ("download_bytes", C.c_uint64)]
+
+
+lib.ntsm_vcf_records.restype = C.c_int
+lib.ntsm_vcf_records.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint32,
+                                 C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                 C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                 C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(RecordsTimes)]
+
+FILL = 0xA5   # records() fills its row buffers with this byte first: what the library does not write keeps it
+
+
+def _lists(geno, key_events, site_ref, site_var):
+    """The host arrays of include/ntsm_vcf_hip.h from Python lists (as run() builds them)."""
+    geno = np.asarray(geno, dtype=np.uint8)
+    n_lines, n = geno.shape
+    stride = (n + 15) // 16 * 16
+    g = np.full((max(n_lines, 1), max(stride, 16)), PAD, dtype=np.uint8)
+    g[:n_lines, :n] = geno
+    key_off = np.zeros(len(key_events) + 1, dtype=np.uint64)
+    key_off[1:] = np.cumsum([len(e) for e in key_events])
+    flat = [ev for evs in key_events for ev in evs]
+    ev_ord = np.array([e[0] for e in flat] + [0], dtype=np.uint32)
+    ev_ls = np.array([e[1] * 2 + e[2] for e in flat] + [0], dtype=np.uint32)
+    site_off = np.zeros(2 * len(site_ref) + 1, dtype=np.uint64)
+    keys = []
+    for s in range(len(site_ref)):
+        keys += list(site_ref[s])
+        site_off[2 * s + 1] = len(keys)
+        keys += list(site_var[s])
+        site_off[2 * s + 2] = len(keys)
+    site_keys = np.array(keys + [0], dtype=np.uint32)
+    return g, max(stride, 16), key_off, len(flat), ev_ord, ev_ls, site_off, site_keys
+
+
+class Records:
+    """What records() returns.  counts / sums: uint32 [s_count][n_sites][2] views into raw_counts / raw_sums, the uint8
+    [s_count][pitch] buffers the library wrote into (filled with FILL before the call); sums and raw_sums are None without
+    want_sums.  total, sum_of_sums: uint64 [s_count].  times: RecordsTimes."""
+    def __init__(self, counts, sums, total, sum_of_sums, times, raw_counts, raw_sums):
+        self.counts, self.sums, self.total, self.sum_of_sums, self.times = counts, sums, total, sum_of_sums, times
+        self.raw_counts, self.raw_sums = raw_counts, raw_sums
+
+
+def records(geno, multi, key_events, site_ref, site_var, s_begin=0, s_count=None, pitch=None, want_sums=True, device=0):
+    """The counts records of the samples [s_begin, s_begin + s_count) (ntsm_vcf_records); the lists as for run().
+    s_count None: up to the last sample.  pitch: bytes between two samples' rows, for counts and sums alike (None:
+    8 * n_sites, no gap)."""
+    g, stride, key_off, n_ev, ev_ord, ev_ls, site_off, site_keys = _lists(geno, key_events, site_ref, site_var)
+    n_lines, n = np.asarray(geno).shape
+    m = len(site_ref)
+    if s_count is None:
+        s_count = n - s_begin
+    if pitch is None:
+        pitch = 8 * m
+    rows = max(int(s_count), 0)
+    raw_counts = np.full((rows, pitch), FILL, dtype=np.uint8)
+    raw_sums = np.full((rows, pitch), FILL, dtype=np.uint8) if want_sums else None
+    total = np.zeros(rows, dtype=np.uint64)
+    sos = np.zeros(rows, dtype=np.uint64)
+    times = RecordsTimes()
+    rc = lib.ntsm_vcf_records(device, n, multi, n_lines, g.ctypes.data, stride, len(key_events), key_off.ctypes.data,
+                              n_ev, ev_ord.ctypes.data, ev_ls.ctypes.data, m, site_off.ctypes.data, site_keys.ctypes.data,
+                              s_begin, s_count, raw_counts.ctypes.data, pitch, raw_sums.ctypes.data if want_sums else None, pitch,
+                              total.ctypes.data, sos.ctypes.data, C.byref(times))
+    if rc:
+        raise RuntimeError("ntsm_vcf_records failed: %d" % rc)
+
+    def view(raw):
+        return np.ascontiguousarray(raw[:, :8 * m]).view("<u4").reshape(rows, m, 2)
+    return Records(view(raw_counts), view(raw_sums) if want_sums else None, total, sos, times, raw_counts, raw_sums)

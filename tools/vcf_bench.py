@@ -10,9 +10,13 @@ directory that is removed afterwards, unless --dir names one to keep the inputs 
 --rotation measures the three routes from the VCF to the rotation on the same inputs instead and prints one JSON line
 per leg: `ntsmVCF -p`, then `ntsmPCA` on its matrix; `ntsmVCF -R`; `ntsmVCF -R -M` -- wall time of every program and its
 lap lines (--raw-out DIR keeps every program's stderr laps as text).
+--store measures the route from the VCF to a cohort store instead and prints one JSON line per leg: `ntsmVCF --store`
+(lap lines, the records kernel's bytes over its time), then, for scale, the two-step route `ntsmVCF --counts DIR` and
+`ntsmEval --pack` of DIR's files (--no-two-step leaves that leg out: at full size it writes about 10 GB of text).
 
   python3 tools/vcf_bench.py [--sites 96287] [--samples 3202] [--threads 16] [--seed 1] [--dir DIR]
                              [--rocprof --rocprof-out DIR] [--rotation [--dims 20] [--raw-out DIR]]
+                             [--store [--no-two-step] [--raw-out DIR]]
 """
 import argparse
 import json
@@ -29,6 +33,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 VCF = os.path.join(ROOT, "build", "ntsmVCF")
 PCA = os.path.join(ROOT, "build", "ntsmPCA")
+EVAL = os.path.join(ROOT, "build", "ntsmEval")
 ALT = {65: 71, 67: 84, 71: 65, 84: 67}
 
 
@@ -125,6 +130,52 @@ def rotation_legs(a, d, tmp):
             f.write("".join(raw))
 
 
+def store_legs(a, d, tmp):
+    """The VCF to a cohort store: in one run, and through counts files and ntsmEval --pack"""
+    env = dict(os.environ, NTSM_VCF_PROF="1")
+    common = [VCF, "-d", "-t", str(a.threads), "-s", os.path.join(d, "sites.fa"), "-r", os.path.join(d, "genome.fa")]
+    vcf = os.path.join(d, "cohort.vcf")
+    one, two, cdir = os.path.join(tmp, "one.store"), os.path.join(tmp, "two.store"), os.path.join(tmp, "counts")
+    os.makedirs(cdir)
+    files = [os.path.join(cdir, "HG%05d.counts.txt" % i) for i in range(a.samples)]
+    legs = [("store", [common + ["--store", one, vcf]])]
+    if not a.no_two_step:
+        legs.append(("counts_then_pack", [common + ["--counts", cdir, vcf], [EVAL, "--pack", two] + files]))
+    raw = []
+    for name, cmds in legs:
+        res = dict(leg=name, sites=a.sites, samples=a.samples, threads=a.threads, programs=[])
+        total = 0.0
+        for cmd in cmds:
+            t0 = time.time()
+            p = subprocess.run(cmd, env=env, capture_output=True)
+            wall = time.time() - t0
+            err = p.stderr.decode(errors="replace")
+            if p.returncode != 0:
+                sys.stderr.write(err[-3000:])
+                sys.exit(p.returncode)
+            phases, device = laps(err)
+            rec = re.search(r"^\[vcf\] records device: windows (\d+) of (\d+) samples, upload ([0-9.]+) s, kernel ([0-9.]+) s, "
+                            r"download ([0-9.]+) s, kernel bytes (\d+)$", err, re.M)
+            prog = dict(program=os.path.basename(cmd[0]), wall_s=round(wall, 3), laps_s=phases, device=device)
+            if rec:
+                w, ws, up, ks, down, nb = (float(x) for x in rec.groups())
+                prog.update(records_windows=int(w), records_window_samples=int(ws), records_upload_s=up, records_kernel_s=ks,
+                            records_download_s=down, records_kernel_bytes=int(nb), records_kernel_gbps=round(nb / ks / 1e9, 1) if ks > 0 else None)
+            total += wall
+            res["programs"].append(prog)
+            raw.append("== %s: %s\n" % (name, " ".join(os.path.basename(c) if os.sep in c else c for c in cmd[:12])) +
+                       "".join(l + "\n" for l in err.splitlines() if l.startswith(("[vcf]", "Time:"))))
+        res["wall_s"] = round(total, 3)
+        res["store_bytes"] = os.path.getsize(one if name == "store" else two)
+        if name != "store":
+            res["counts_text_bytes"] = sum(os.path.getsize(f) for f in files)
+        print(json.dumps(res), flush=True)
+    if a.raw_out:
+        os.makedirs(a.raw_out, exist_ok=True)
+        with open(os.path.join(a.raw_out, "laps.txt"), "w") as f:
+            f.write("".join(raw))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--sites", type=int, default=96287)
@@ -137,6 +188,8 @@ def main():
     ap.add_argument("--rotation", action="store_true", help="measure the routes to the rotation instead (three legs)")
     ap.add_argument("--dims", type=int, default=20)
     ap.add_argument("--raw-out", default=None)
+    ap.add_argument("--store", action="store_true", help="measure the routes to a cohort store instead (two legs)")
+    ap.add_argument("--no-two-step", action="store_true", help="with --store: leave the --counts + --pack leg out")
     a = ap.parse_args()
     tmp = tempfile.mkdtemp(prefix="vcf_bench_")
     d = a.dir or tmp
@@ -148,6 +201,9 @@ def main():
         gen_s = time.time() - t0
         if a.rotation:
             rotation_legs(a, d, tmp)
+            return
+        if a.store:
+            store_legs(a, d, tmp)
             return
         prefix = os.path.join(tmp, "out")
         cmd = [VCF, "-d", "-t", str(a.threads), "-s", os.path.join(d, "sites.fa"), "-r", os.path.join(d, "genome.fa"), "-p", prefix,

@@ -78,10 +78,10 @@ xlib:
 # ntsmEval all-pairs scoring: own library, own CLI
 # + the PCA-guided pair search (-p / -n): ntsm_eval_pca.hip with the x87 add of xprec.h
 # + queries against a cohort store (--against): ntsm_eval_cross.hip; the store itself is host code (host/eval_store.hpp)
-# + the PCA-guided search against a store (--index / --near): ntsm_eval_near.hip; it shares a chunk's preparation with the cross
+# + the PCA-guided search against a store (--index / --near): ntsm_eval_near.hip; it shares the staging of a chunk with the cross
 #   path (ntsm_eval_chunk.h) and the search's steps with the session search (ntsm_eval_pca.h); the index is host code (host/eval_index.hpp)
-# + the pairs inside a store (--within / --within-near): ntsm_eval_within.hip; the band and pass arithmetic is host code that
-#   the library and the CLI share (host/eval_within.hpp)
+# + the pairs inside a store (--within / --within-near): ntsm_eval_within.hip, staging through ntsm_eval_chunk.h too; the band and
+#   pass arithmetic is host code that the library and the CLI share (host/eval_within.hpp)
 EVALSRC := $(CSRC)/ntsm_eval.hip $(CSRC)/ntsm_eval_pca.hip $(CSRC)/ntsm_eval_cross.hip $(CSRC)/ntsm_eval_near.hip $(CSRC)/ntsm_eval_within.hip
 ntsm_amd/libntsm_eval_hip.so: $(EVALSRC) $(CSRC)/ntsm_eval_score.h $(CSRC)/ntsm_eval_chunk.h $(CSRC)/ntsm_eval_pca.h $(CSRC)/ntsm_hip_scope.h $(CSRC)/xprec.h \
                               $(HOST)/eval_within.hpp include/ntsm_eval_hip.h

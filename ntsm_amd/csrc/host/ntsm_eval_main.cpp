@@ -1,22 +1,25 @@
 /*
  * ntsm_eval_main.cpp -- host mirror of the reference's ntsmEval (src/ntSeqMatchEval.cpp:86-349, src/CompareCounts.hpp):
- * same flags, same stdout bytes; the pair loop of CompareCounts::computeScore (:591-624) is one call into the HIP library
- * (include/ntsm_eval_hip.h).  A single input file prints the QC table (computeScoreSingle, :541-585) without touching the
- * GPU unless -p asks for its PC columns; -e FILE writes the merged counts (mergeCounts, :626-674), -o skips the analysis.
- * -p ROT -n NORM is the PCA-guided search (projectPCs, :116-211, computeScorePCA, :285-398): projection, candidate pairs
- * and their scoring in the library's session calls, printed in the one-thread order.  This build only: --pack STORE FILES...
- * writes or extends a cohort store (eval_store.hpp, no GPU), --against STORE FILES... scores the files against the store's
- * samples (ntsm_eval_cross) and against each other and prints computeScore's rows for them; --index STORE -p ROT -n NORM
- * projects the store's samples into STORE.pcaidx (eval_index.hpp, ntsm_eval_project_store) and --near STORE FILES... runs the
- * PCA-guided search of the files against the store through that index (ntsm_eval_cross_candidates, then ntsm_eval_cross for
- * the search-all queries and ntsm_eval_cross_score_pairs for the rest) and prints the rows of the -p run over [FILES...,
- * the store's samples] that name one of FILES; --within STORE prints the all-to-all run over the store's own samples
- * (ntsm_eval_within_open / _rows, in bands of rows) and --within-near STORE the -p run over them through the index
- * (ntsm_eval_cross_candidates without a database side, then ntsm_eval_cross for the search-all samples' rows and
- * ntsm_eval_store_score_pairs for the rest); neither reads a counts file.  Not built: -b (the debug
- * ground-truth mode) and -p without a normalization file (the reference dies in an assert); both are refused.  Pinned to
- * the reference: stdout equals, byte for byte, that of the unmodified scoring class (oracle/ref_eval_driver.cpp ->
- * oracle/_ref/ref_ntsmEval -t 1) and its recordings, tests/test_eval_reference.py.
+ * same flags, same stdout bytes; the scoring is the HIP library's (include/ntsm_eval_hip.h).  The runs and their calls:
+ *   FILES...                  all pairs, computeScore (:591-624): ntsm_eval_pairs
+ *   FILE                      the QC table, computeScoreSingle (:541-585): no GPU unless -p asks for its PC columns
+ *   -e FILE [-o]              the merged counts, mergeCounts (:626-674), after the analysis or (-o) in its place: no GPU
+ *   -p ROT -n NORM FILES...   the PCA-guided search, projectPCs (:116-211) + computeScorePCA (:285-398), printed in the
+ *                             one-thread order: ntsm_eval_open, _project, _candidates, _score_pairs
+ * This build only:
+ *   --pack STORE FILES...     writes or extends a cohort store (eval_store.hpp): no GPU
+ *   --against STORE FILES...  computeScore's rows of FILES against the store's samples and each other: ntsm_eval_cross, ntsm_eval_pairs
+ *   --index STORE -p -n       projects the store's samples into STORE.pcaidx (eval_index.hpp): ntsm_eval_project_store
+ *   --near STORE FILES...     the rows of the -p run over [FILES..., the store's samples] that name one of FILES, through that
+ *                             index: ntsm_eval_cross_candidates, then ntsm_eval_cross for the search-all queries' rows and
+ *                             ntsm_eval_cross_score_pairs for the rest
+ *   --within STORE            the all-to-all run over the store's own samples, in bands of rows: ntsm_eval_within_open / _rows
+ *   --within-near STORE       the -p run over them through the index: ntsm_eval_cross_candidates without a database side, then
+ *                             ntsm_eval_cross for the search-all samples' rows and ntsm_eval_store_score_pairs for the rest
+ * --within and --within-near read no counts file.  Not built, and refused: -b (the debug ground-truth mode) and -p without a
+ * normalization file (the reference dies in an assert).  Pinned to the reference: stdout equals, byte for byte, that of the
+ * unmodified scoring class (oracle/ref_eval_driver.cpp -> oracle/_ref/ref_ntsmEval -t 1) and its recordings,
+ * tests/test_eval_reference.py.
  */
 #include <getopt.h>
 
@@ -276,10 +279,20 @@ int gpuFail(const char *what, int rc)
 	return 3;
 }
 
-struct Session {                             /* closes the library session it holds when its scope ends */
-	ntsm_eval_session *h = nullptr;
-	~Session() { if (h) ntsm_eval_close(h); }
+template <typename H, void (*Close)(H *)> struct Handle {   /* closes the library session it holds when its scope ends */
+	H *h = nullptr;
+	~Handle() { if (h) Close(h); }
 };
+typedef Handle<ntsm_eval_session, ntsm_eval_close> Session;
+typedef Handle<ntsm_eval_within_session, ntsm_eval_within_close> WithinSession;
+
+typedef std::chrono::steady_clock Clock;
+double msSince(Clock::time_point t) { return std::chrono::duration<double, std::milli>(Clock::now() - t).count(); }
+
+void printTime(Clock::time_point t0)         /* the last line of every run's stderr */
+{
+	std::cerr << "Time: " << std::chrono::duration<double>(Clock::now() - t0).count() << " s" << std::endl;
+}
 
 /* projectPCs (:166-211) on the device: cloud [n][dim] */
 int project(const Counts &c, const Opt &opt, ntsm_eval_session *h, const std::vector<long double> &norm, const std::vector<long double> &rot,
@@ -309,29 +322,43 @@ std::vector<double> searchRadii(std::vector<Genotype> &g, size_t m, const Opt &o
 	return radius;
 }
 
+/* A candidate list and the two calls that fetch it: ask the size with no room, allocate, ask again.  `call` is the library's
+ * search with its inputs bound: (pi, pk, dist, capacity, &n_pairs, &kernel_ms). */
+struct Candidates {
+	std::vector<uint32_t> pi, pk;
+	std::vector<double> dist;
+	double kernelMs = 0;
+	int search(const std::function<int(uint32_t *, uint32_t *, double *, uint64_t, uint64_t *, double *)> &call)
+	{
+		uint64_t np = 0;
+		int rc = call(nullptr, nullptr, nullptr, 0, &np, &kernelMs);
+		if (rc && rc != NTSM_EVAL_E_CAPACITY) return gpuFail("candidate search", rc);
+		pi.resize(np); pk.resize(np); dist.resize(np);
+		if (np && (rc = call(pi.data(), pk.data(), dist.data(), np, &np, &kernelMs)) != 0) return gpuFail("candidate search", rc);
+		return 0;
+	}
+};
+
 /* computeScorePCA (:285-398), the one-thread order of its rows */
 int scorePCA(const Counts &c, std::vector<Genotype> &g, const Opt &opt, ntsm_eval_session *h, const std::vector<double> &cloud)
 {
 	if (opt.verbose > 1) std::cerr << "Generating kd-tree" << std::endl;
 	const std::vector<double> radius = searchRadii(g, c.nSites(), opt);
 	if (opt.verbose > 1) std::cerr << "Starting Score Computation with PCA" << std::endl;
-	uint64_t np = 0;
-	double msSearch = 0, msScore = 0;
-	int rc = ntsm_eval_candidates(h, cloud.data(), opt.dim, radius.data(), nullptr, nullptr, nullptr, 0, &np, &msSearch);
-	if (rc && rc != NTSM_EVAL_E_CAPACITY) return gpuFail("candidate search", rc);
-	std::vector<uint32_t> pi(np), pk(np);
-	std::vector<double> dist(np);
-	if (np) {
-		rc = ntsm_eval_candidates(h, cloud.data(), opt.dim, radius.data(), pi.data(), pk.data(), dist.data(), np, &np, &msSearch);
-		if (rc) return gpuFail("candidate search", rc);
-	}
+	Candidates cand;
+	int rc = cand.search([&](uint32_t *pi, uint32_t *pk, double *dist, uint64_t capacity, uint64_t *np, double *ms) {
+		return ntsm_eval_candidates(h, cloud.data(), opt.dim, radius.data(), pi, pk, dist, capacity, np, ms);
+	});
+	if (rc) return rc;
+	const uint64_t np = cand.pi.size();
+	double msScore = 0;
 	std::vector<ntsm_eval_record> rec(np);
-	rc = ntsm_eval_score_pairs(h, pi.data(), pk.data(), np, rec.data(), &msScore);
+	rc = ntsm_eval_score_pairs(h, cand.pi.data(), cand.pk.data(), np, rec.data(), &msScore);
 	if (rc) return gpuFail("scoring", rc);
-	if (opt.verbose > 1) std::cerr << "search kernels: " << msSearch << " ms, scoring kernel: " << msScore << " ms for " << np << " pairs" << std::endl;
+	if (opt.verbose > 1) std::cerr << "search kernels: " << cand.kernelMs << " ms, scoring kernel: " << msScore << " ms for " << np << " pairs" << std::endl;
 	std::cout << kHeader << "\n";
 	std::string temp;
-	for (uint64_t p = 0; p < np; ++p) printRow(temp, c, g, opt, rec[p], pi[p], pk[p], std::to_string(dist[p]));
+	for (uint64_t p = 0; p < np; ++p) printRow(temp, c, g, opt, rec[p], cand.pi[p], cand.pk[p], std::to_string(cand.dist[p]));
 	return 0;
 }
 
@@ -350,7 +377,19 @@ int packStore(const Counts &c, const Opt &opt)
 	return 0;
 }
 
-double msSince(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); }
+/* What every store run opens: the mapped store, refused when it is empty or holds more samples than a run with nFiles
+ * further ones numbers ("... one run scores" / "... one run projects").  With c, its locus table and distinct columns play
+ * the part of the first file.  Throws the refusal. */
+void openStore(const std::string &name, size_t nFiles, const char *does, ntsm::eval_store::View &store, Counts *c)
+{
+	namespace st = ntsm::eval_store;
+	store.open(name);
+	if (store.h.n_samples == 0) throw st::Error(name + " holds no samples");
+	if (store.h.n_samples + nFiles > UINT32_MAX) throw st::Error(name + " holds more samples than one run " + does);
+	if (!c) return;
+	c->locus = store.locus;
+	c->distinct.assign(store.distinct, store.distinct + 2 * (size_t) store.h.n_sites);
+}
 
 /* the store's samples as samples nq ... of a run: names, summaries from the record scalars and the given tallies */
 void appendStoreSamples(Counts &c, std::vector<Genotype> &g, const ntsm::eval_store::View &store, const Opt &opt,
@@ -373,18 +412,13 @@ void appendStoreSamples(Counts &c, std::vector<Genotype> &g, const ntsm::eval_st
 
 /* --against STORE FILES...: the rows of computeScore (:591-624) over [FILES..., the store's samples] whose sample 1 is one
  * of FILES -- a prefix of that run's output.  The store's locus table and distinct columns play the part of the first file. */
-int scoreAgainst(Counts &c, const Opt &opt, std::chrono::steady_clock::time_point t0)
+int scoreAgainst(Counts &c, const Opt &opt, Clock::time_point t0)
 {
-	namespace st = ntsm::eval_store;
-	st::View store;
-	const auto tMap = std::chrono::steady_clock::now();
+	ntsm::eval_store::View store;
+	const auto tMap = Clock::now();
 	try {
-		store.open(opt.against);
-		if (store.h.n_samples == 0) throw st::Error(opt.against + " holds no samples");
-		if (store.h.n_samples + c.files.size() > UINT32_MAX) throw st::Error(opt.against + " holds more samples than one run scores");
+		openStore(opt.against, c.files.size(), "scores", store, &c);
 		if (opt.verbose > 0) std::cerr << "Reading count files" << std::endl;
-		c.locus = store.locus;
-		c.distinct.assign(store.distinct, store.distinct + 2 * (size_t) store.h.n_sites);
 		load(c, store.index(), true);
 	} catch (const std::exception &e) {
 		ntsm::refuse(e.what());
@@ -403,7 +437,7 @@ int scoreAgainst(Counts &c, const Opt &opt, std::chrono::steady_clock::time_poin
 	rc = ntsm_eval_cross(opt.device, c.counts.data(), nq, store.counts(0), store.h.stride, nd, m, opt.minCov, 0, cross.data(), geno.data(), &times);
 	if (rc) return gpuFail("scoring against the store", rc);
 	appendStoreSamples(c, g, store, opt, [&](uint32_t d, Genotype &s) { s.hets = geno[3 * d]; s.homs = geno[3 * d + 1]; s.miss = geno[3 * d + 2]; });
-	const auto tPrint = std::chrono::steady_clock::now();
+	const auto tPrint = Clock::now();
 	std::cout << kHeader << "\n";
 	std::string temp;
 	for (uint32_t q = 0; q < nq; ++q) {
@@ -415,12 +449,12 @@ int scoreAgainst(Counts &c, const Opt &opt, std::chrono::steady_clock::time_poin
 		std::cerr << "store query: " << times.chunks << " chunks, map+load " << mapMs << " ms, query pairs " << ms << " ms, upload " << times.upload_ms
 		          << " ms, prepare " << times.prepare_kernel_ms << " ms, cross kernel " << times.cross_kernel_ms << " ms, download " << times.download_ms
 		          << " ms, print " << msSince(tPrint) << " ms" << std::endl;
-	std::cerr << "Time: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << " s" << std::endl;
+	printTime(t0);
 	return 0;
 }
 
 /* --index STORE -p ROT -n NORM [-d -c]: project the store's samples, or the tail an append added, into STORE.pcaidx */
-int buildIndex(const Opt &opt, std::chrono::steady_clock::time_point t0)
+int buildIndex(const Opt &opt, Clock::time_point t0)
 {
 	namespace st = ntsm::eval_store;
 	namespace ix = ntsm::eval_index;
@@ -431,9 +465,7 @@ int buildIndex(const Opt &opt, std::chrono::steady_clock::time_point t0)
 	std::vector<char> matrices;
 	std::vector<long double> norm, rot;
 	try {
-		store.open(opt.index);
-		if (store.h.n_samples == 0) throw st::Error(opt.index + " holds no samples");
-		if (store.h.n_samples > UINT32_MAX) throw st::Error(opt.index + " holds more samples than one run projects");
+		openStore(opt.index, 0, "projects", store, nullptr);
 		loadPCA(opt, store.h.n_sites, norm, rot);
 		matrices = ix::matrix_bytes(norm, rot);
 		struct stat sb;
@@ -472,19 +504,17 @@ int buildIndex(const Opt &opt, std::chrono::steady_clock::time_point t0)
 	if (opt.verbose > 1)
 		std::cerr << "store index: " << times.chunks << " chunks, upload " << times.upload_ms << " ms, prepare " << times.prepare_kernel_ms
 		          << " ms, projection kernel " << times.cross_kernel_ms << " ms, download " << times.download_ms << " ms" << std::endl;
-	std::cerr << "Time: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << " s" << std::endl;
+	printTime(t0);
 	return 0;
 }
 
-/* What --near and --within-near open: the store and its index, valid, current and written with the run's -c and -d where
- * those are given; -c and -d are then the index's.  Throws the refusal. */
-void openIndexedStore(const std::string &name, size_t nFiles, ntsm::eval_store::View &store, ntsm::eval_index::View &index, Opt &opt)
+/* What --near and --within-near open: the store (openStore) and its index, valid, current and written with the run's -c and
+ * -d where those are given; -c and -d are then the index's.  Throws the refusal. */
+void openIndexedStore(const std::string &name, Counts &c, ntsm::eval_store::View &store, ntsm::eval_index::View &index, Opt &opt)
 {
 	namespace st = ntsm::eval_store;
 	const std::string path = ntsm::eval_index::path_of(name);
-	store.open(name);
-	if (store.h.n_samples == 0) throw st::Error(name + " holds no samples");
-	if (store.h.n_samples + nFiles > UINT32_MAX) throw st::Error(name + " holds more samples than one run scores");
+	openStore(name, c.files.size(), "scores", store, &c);
 	struct stat sb;
 	if (stat(path.c_str(), &sb) != 0) throw st::Error("there is no index " + path + ": run --index on the store first");
 	index.open(path);
@@ -497,22 +527,95 @@ void openIndexedStore(const std::string &name, size_t nFiles, ntsm::eval_store::
 	opt.dim = index.h.dim;
 }
 
+/* a store of one sample has no pair */
+void refuseOneSample(const ntsm::eval_store::View &store, const std::string &name)
+{
+	if (store.h.n_samples == 1) throw ntsm::eval_store::Error(name + " holds one sample: nothing to compare");
+}
+
+/* the store's samples appended from the index: tallies into the summaries, projections into cloud [n_samples][dim] */
+std::vector<double> appendIndexedSamples(Counts &c, std::vector<Genotype> &g, const ntsm::eval_store::View &store, const ntsm::eval_index::View &index,
+		const Opt &opt)
+{
+	std::vector<double> cloud((size_t) store.h.n_samples * opt.dim);
+	appendStoreSamples(c, g, store, opt, [&](uint32_t d, Genotype &s) {
+		const ntsm::eval_index::Entry e = index.entry(d);
+		s.hets = e.hets; s.homs = e.homs; s.miss = e.miss;
+		memcpy(&cloud[(size_t) d * opt.dim], e.cloud, sizeof(double) * opt.dim);
+	});
+	return cloud;
+}
+
+/* What differs between the two store searches once the candidates are known. */
+struct Route {
+	uint32_t nOwners;                        /* samples 0 ... nOwners - 1 may own a dense row: the query files, or every store sample */
+	uint32_t col0;                           /* the store's sample d is sample col0 + d of the run: after the queries, or at 0 */
+	const void *owners; uint64_t ownerStride; /* owner i's counts [site][2] lie at owners + i * ownerStride bytes */
+	std::function<int(const uint32_t *, const uint32_t *, uint64_t, ntsm_eval_record *, ntsm_eval_cross_times *)> scoreList;   /* the list scorer */
+};
+
+/* The second half of --near and --within-near.  A sample whose radius is DBL_MAX owns whole rows of the store: the owners'
+ * counts go to a dense block that ntsm_eval_cross scores against the whole store (the owner is sample 1; identical records by
+ * its contract), so the store is never gathered for them; every other pair goes through the list scorer and its records are
+ * scattered back to list order.  Then the rows, the report line (mapMs, projectMs, searchMs: the caller's first half) and
+ * the time. */
+int routeAndScore(const Counts &c, const std::vector<Genotype> &g, const Opt &opt, const ntsm::eval_store::View &store, const std::vector<double> &radius,
+		const Candidates &cand, const Route &route, double mapMs, double projectMs, double searchMs, Clock::time_point t0)
+{
+	const auto t = Clock::now();
+	const uint32_t nd = (uint32_t) store.h.n_samples, m = store.h.n_sites;
+	const uint64_t np = cand.pi.size();
+	std::vector<uint32_t> dense, denseRow(route.nOwners, UINT32_MAX);
+	for (uint32_t i = 0; i < route.nOwners; ++i)
+		if (!(radius[i] < DBL_MAX)) { denseRow[i] = (uint32_t) dense.size(); dense.push_back(i); }
+	std::vector<ntsm_eval_record> rect((size_t) dense.size() * nd), rec(np);
+	ntsm_eval_cross_times crossTimes {}, listTimes {};
+	if (!dense.empty()) {
+		std::vector<uint32_t> sub(dense.size() * (size_t) m * 2);
+		for (size_t r = 0; r < dense.size(); ++r) memcpy(&sub[r * m * 2], (const char *) route.owners + dense[r] * route.ownerStride, sizeof(uint32_t) * m * 2);
+		const int rc = ntsm_eval_cross(opt.device, sub.data(), (uint32_t) dense.size(), store.counts(0), store.h.stride, nd, m, opt.minCov, 0, rect.data(), nullptr,
+				&crossTimes);
+		if (rc) return gpuFail("scoring against the store", rc);
+	}
+	std::vector<uint32_t> li, lk;
+	std::vector<uint64_t> where;
+	for (uint64_t p = 0; p < np; ++p) {
+		const uint32_t i = cand.pi[p], k = cand.pk[p];
+		if (i < route.nOwners && k >= route.col0 && denseRow[i] != UINT32_MAX) rec[p] = rect[(size_t) denseRow[i] * nd + (k - route.col0)];
+		else { li.push_back(i); lk.push_back(k); where.push_back(p); }
+	}
+	std::vector<ntsm_eval_record> listed(li.size());
+	const int rc = route.scoreList(li.data(), lk.data(), li.size(), listed.data(), &listTimes);
+	if (rc) return gpuFail("scoring the candidate pairs", rc);
+	for (size_t x = 0; x < where.size(); ++x) rec[where[x]] = listed[x];
+	const double scoreMs = msSince(t);
+
+	const auto tPrint = Clock::now();
+	std::cout << kHeader << "\n";
+	std::string temp;
+	for (uint64_t p = 0; p < np; ++p) printRow(temp, c, g, opt, rec[p], cand.pi[p], cand.pk[p], std::to_string(cand.dist[p]));
+	std::cout.flush();
+	if (opt.verbose > 1)
+		std::cerr << "store search: " << np << " pairs (" << li.size() << " listed, " << dense.size() << " dense rows), map+load " << mapMs << " ms, project "
+		          << projectMs << " ms, search " << searchMs << " ms (kernels " << cand.kernelMs << " ms), score " << scoreMs << " ms (gather "
+		          << listTimes.upload_ms << " ms, list kernel " << listTimes.cross_kernel_ms << " ms in " << listTimes.chunks << " passes, dense upload "
+		          << crossTimes.upload_ms << " ms, dense kernel " << crossTimes.cross_kernel_ms << " ms), print " << msSince(tPrint) << " ms" << std::endl;
+	printTime(t0);
+	return 0;
+}
+
 /* --near STORE FILES...: the rows of computeScorePCA (:285-398) over [FILES..., the store's samples] in which sample 1 or
  * sample 2 is one of FILES, in that run's one-thread order.  The store's projections and tallies come from STORE.pcaidx, the
  * radii are formed here (scorePCA's), and only the counts of the candidates' samples leave the store -- except for a query
- * whose radius is DBL_MAX: it owns a whole row of the store, which ntsm_eval_cross scores as the dense rectangle it is. */
-int searchNear(Counts &c, Opt &opt, std::chrono::steady_clock::time_point t0)
+ * whose radius is DBL_MAX: it owns a whole row of the store (routeAndScore). */
+int searchNear(Counts &c, Opt &opt, Clock::time_point t0)
 {
-	namespace st = ntsm::eval_store;
-	namespace ix = ntsm::eval_index;
-	st::View store;
-	ix::View index;
-	const auto tMap = std::chrono::steady_clock::now();
+	ntsm::eval_store::View store;
+	ntsm::eval_index::View index;
+	const auto tMap = Clock::now();
 	try {
-		openIndexedStore(opt.near, c.files.size(), store, index, opt);
+		openIndexedStore(opt.near, c, store, index, opt);
 		if (opt.verbose > 0) std::cerr << "Reading count files" << std::endl;
-		c.locus = store.locus;
-		c.distinct.assign(store.distinct, store.distinct + 2 * (size_t) store.h.n_sites);
 		load(c, store.index(), true);
 	} catch (const std::exception &e) {
 		ntsm::refuse(e.what());
@@ -522,7 +625,7 @@ int searchNear(Counts &c, Opt &opt, std::chrono::steady_clock::time_point t0)
 	const uint32_t nq = (uint32_t) c.files.size(), nd = (uint32_t) store.h.n_samples, m = store.h.n_sites, dim = opt.dim;
 	if (opt.verbose > 1) std::cerr << "Finished loading files. Now searching " << nq << " samples against the " << nd << " of " << opt.near << "." << std::endl;
 
-	auto t = std::chrono::steady_clock::now();
+	auto t = Clock::now();
 	std::vector<double> qCloud;
 	{
 		std::vector<long double> norm, rot;
@@ -534,99 +637,36 @@ int searchNear(Counts &c, Opt &opt, std::chrono::steady_clock::time_point t0)
 	}
 	const double projectMs = msSince(t);
 
-	t = std::chrono::steady_clock::now();
-	std::vector<double> dbCloud((size_t) nd * dim);
-	appendStoreSamples(c, g, store, opt, [&](uint32_t d, Genotype &s) {
-		const ix::Entry e = index.entry(d);
-		s.hets = e.hets; s.homs = e.homs; s.miss = e.miss;
-		memcpy(&dbCloud[(size_t) d * dim], e.cloud, sizeof(double) * dim);
-	});
+	t = Clock::now();
+	const std::vector<double> dbCloud = appendIndexedSamples(c, g, store, index, opt);
 	const std::vector<double> radius = searchRadii(g, m, opt);
 	if (opt.verbose > 1) std::cerr << "Starting Score Computation with PCA" << std::endl;
-	uint64_t np = 0;
-	double msSearch = 0;
-	int rc = ntsm_eval_cross_candidates(opt.device, qCloud.data(), radius.data(), nq, dbCloud.data(), radius.data() + nq, nd, dim, nullptr, nullptr, nullptr,
-			0, &np, &msSearch);
-	if (rc && rc != NTSM_EVAL_E_CAPACITY) return gpuFail("candidate search", rc);
-	std::vector<uint32_t> pi(np), pk(np);
-	std::vector<double> dist(np);
-	if (np) {
-		rc = ntsm_eval_cross_candidates(opt.device, qCloud.data(), radius.data(), nq, dbCloud.data(), radius.data() + nq, nd, dim, pi.data(), pk.data(),
-				dist.data(), np, &np, &msSearch);
-		if (rc) return gpuFail("candidate search", rc);
-	}
+	Candidates cand;
+	const int rc = cand.search([&](uint32_t *pi, uint32_t *pk, double *dist, uint64_t capacity, uint64_t *np, double *ms) {
+		return ntsm_eval_cross_candidates(opt.device, qCloud.data(), radius.data(), nq, dbCloud.data(), radius.data() + nq, nd, dim, pi, pk, dist, capacity, np, ms);
+	});
+	if (rc) return rc;
 	const double searchMs = msSince(t);
-
-	/* routing: the search-all queries' rows of the store through the dense rectangle, every other pair through the list */
-	t = std::chrono::steady_clock::now();
-	std::vector<uint32_t> dense, denseRow(nq, UINT32_MAX);
-	for (uint32_t q = 0; q < nq; ++q)
-		if (!(radius[q] < DBL_MAX)) { denseRow[q] = (uint32_t) dense.size(); dense.push_back(q); }
-	std::vector<ntsm_eval_record> rect((size_t) dense.size() * nd), rec(np);
-	ntsm_eval_cross_times crossTimes {}, listTimes {};
-	if (!dense.empty()) {
-		std::vector<uint32_t> sub(dense.size() * (size_t) m * 2);
-		for (size_t r = 0; r < dense.size(); ++r) memcpy(&sub[r * m * 2], &c.counts[(size_t) dense[r] * m * 2], sizeof(uint32_t) * m * 2);
-		rc = ntsm_eval_cross(opt.device, sub.data(), (uint32_t) dense.size(), store.counts(0), store.h.stride, nd, m, opt.minCov, 0, rect.data(), nullptr,
-				&crossTimes);
-		if (rc) return gpuFail("scoring against the store", rc);
-	}
-	std::vector<uint32_t> li, lk;
-	std::vector<uint64_t> where;
-	for (uint64_t p = 0; p < np; ++p) {
-		if (pi[p] < nq && pk[p] >= nq && denseRow[pi[p]] != UINT32_MAX) rec[p] = rect[(size_t) denseRow[pi[p]] * nd + (pk[p] - nq)];
-		else { li.push_back(pi[p]); lk.push_back(pk[p]); where.push_back(p); }
-	}
-	std::vector<ntsm_eval_record> listed(li.size());
-	rc = ntsm_eval_cross_score_pairs(opt.device, c.counts.data(), nq, store.counts(0), store.h.stride, nd, m, opt.minCov, li.data(), lk.data(), li.size(), 0,
-			listed.data(), &listTimes);
-	if (rc) return gpuFail("scoring the candidate pairs", rc);
-	for (size_t x = 0; x < where.size(); ++x) rec[where[x]] = listed[x];
-	const double scoreMs = msSince(t);
-
-	const auto tPrint = std::chrono::steady_clock::now();
-	std::cout << kHeader << "\n";
-	std::string temp;
-	for (uint64_t p = 0; p < np; ++p) printRow(temp, c, g, opt, rec[p], pi[p], pk[p], std::to_string(dist[p]));
-	std::cout.flush();
-	if (opt.verbose > 1)
-		std::cerr << "store search: " << np << " pairs (" << li.size() << " listed, " << dense.size() << " dense rows), map+load " << mapMs << " ms, project "
-		          << projectMs << " ms, search " << searchMs << " ms (kernels " << msSearch << " ms), score " << scoreMs << " ms (gather "
-		          << listTimes.upload_ms << " ms, list kernel " << listTimes.cross_kernel_ms << " ms in " << listTimes.chunks << " passes, dense upload "
-		          << crossTimes.upload_ms << " ms, dense kernel " << crossTimes.cross_kernel_ms << " ms), print " << msSince(tPrint) << " ms" << std::endl;
-	std::cerr << "Time: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << " s" << std::endl;
-	return 0;
-}
-
-struct WithinSession {                       /* closes the library session it holds when its scope ends */
-	ntsm_eval_within_session *h = nullptr;
-	~WithinSession() { if (h) ntsm_eval_within_close(h); }
-};
-
-/* the store's locus table and distinct columns play the part of the first file; a store of one sample has no pair */
-void storeAsRun(Counts &c, const ntsm::eval_store::View &store, const std::string &name)
-{
-	if (store.h.n_samples == 1) throw ntsm::eval_store::Error(name + " holds one sample: nothing to compare");
-	c.locus = store.locus;
-	c.distinct.assign(store.distinct, store.distinct + 2 * (size_t) store.h.n_sites);
+	const Route route { nq, nq, c.counts.data(), 8ull * m,
+		[&](const uint32_t *li, const uint32_t *lk, uint64_t n, ntsm_eval_record *out, ntsm_eval_cross_times *times) {
+			return ntsm_eval_cross_score_pairs(opt.device, c.counts.data(), nq, store.counts(0), store.h.stride, nd, m, opt.minCov, li, lk, n, 0, out, times);
+		} };
+	return routeAndScore(c, g, opt, store, radius, cand, route, mapMs, projectMs, searchMs, t0);
 }
 
 /* --within STORE: computeScore's rows (:591-624) over the store's samples in store order -- the stdout of the all-to-all run
  * over their files at one thread -- without reading a counts file.  The triangle comes in bands of rows (eval_within.hpp's
  * rule, or --within-rows), printed band by band, which is the reference's order; the first band's call brings every
  * sample's tallies. */
-int scoreWithin(const Opt &opt, std::chrono::steady_clock::time_point t0)
+int scoreWithin(const Opt &opt, Clock::time_point t0)
 {
-	namespace st = ntsm::eval_store;
 	namespace band = ntsm::eval_within;
-	st::View store;
+	ntsm::eval_store::View store;
 	Counts c;
-	const auto tMap = std::chrono::steady_clock::now();
+	const auto tMap = Clock::now();
 	try {
-		store.open(opt.within);
-		if (store.h.n_samples == 0) throw st::Error(opt.within + " holds no samples");
-		if (store.h.n_samples > UINT32_MAX) throw st::Error(opt.within + " holds more samples than one run scores");
-		storeAsRun(c, store, opt.within);
+		openStore(opt.within, 0, "scores", store, &c);
+		refuseOneSample(store, opt.within);
 	} catch (const std::exception &e) {
 		ntsm::refuse(e.what());
 	}
@@ -652,7 +692,7 @@ int scoreWithin(const Opt &opt, std::chrono::steady_clock::time_point t0)
 		if (rc) return gpuFail("scoring the store", rc);
 		sum.upload_ms += times.upload_ms; sum.prepare_kernel_ms += times.prepare_kernel_ms; sum.cross_kernel_ms += times.cross_kernel_ms;
 		sum.download_ms += times.download_ms; sum.chunks += times.chunks;
-		const auto tPrint = std::chrono::steady_clock::now();
+		const auto tPrint = Clock::now();
 		if (first == 0) {
 			appendStoreSamples(c, g, store, opt, [&](uint32_t d, Genotype &s) { s.hets = geno[3 * d]; s.homs = geno[3 * d + 1]; s.miss = geno[3 * d + 2]; });
 			std::cout << kHeader << "\n";
@@ -667,26 +707,23 @@ int scoreWithin(const Opt &opt, std::chrono::steady_clock::time_point t0)
 		std::cerr << "store within: " << (sum.chunks ? "streamed" : "resident") << ", " << bands << " bands, " << sum.chunks << " chunks, map " << mapMs
 		          << " ms, upload " << sum.upload_ms << " ms, prepare " << sum.prepare_kernel_ms << " ms, pair kernel " << sum.cross_kernel_ms
 		          << " ms, download " << sum.download_ms << " ms, print " << printMs << " ms" << std::endl;
-	std::cerr << "Time: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << " s" << std::endl;
+	printTime(t0);
 	return 0;
 }
 
 /* --within-near STORE: computeScorePCA's rows (:285-398) over the store's samples -- the stdout of the -p run over their
  * files with the index's rotation, centre, -d and -c.  Projections and tallies come from STORE.pcaidx and the radii are formed
  * here, so the search is ntsm_eval_cross_candidates with every sample a query and no database side: by its contract
- * ntsm_eval_candidates' list.  A sample whose radius is DBL_MAX owns whole rows: its counts go to a dense block that
- * ntsm_eval_cross scores against the whole store (sample 1 is the owner); every other pair goes through the list. */
-int searchWithin(Opt &opt, std::chrono::steady_clock::time_point t0)
+ * ntsm_eval_candidates' list.  Any sample may own whole rows (routeAndScore); the other pairs are pairs of two store samples. */
+int searchWithin(Opt &opt, Clock::time_point t0)
 {
-	namespace st = ntsm::eval_store;
-	namespace ix = ntsm::eval_index;
-	st::View store;
-	ix::View index;
+	ntsm::eval_store::View store;
+	ntsm::eval_index::View index;
 	Counts c;
-	const auto tMap = std::chrono::steady_clock::now();
+	const auto tMap = Clock::now();
 	try {
-		openIndexedStore(opt.withinNear, 0, store, index, opt);
-		storeAsRun(c, store, opt.withinNear);
+		openIndexedStore(opt.withinNear, c, store, index, opt);
+		refuseOneSample(store, opt.withinNear);
 	} catch (const std::exception &e) {
 		ntsm::refuse(e.what());
 	}
@@ -694,64 +731,29 @@ int searchWithin(Opt &opt, std::chrono::steady_clock::time_point t0)
 	const uint32_t n = (uint32_t) store.h.n_samples, m = store.h.n_sites, dim = opt.dim;
 	if (opt.verbose > 1) std::cerr << "Mapped " << opt.withinNear << " and its index. Now searching its " << n << " samples." << std::endl;
 
-	auto t = std::chrono::steady_clock::now();
+	const auto t = Clock::now();
 	std::vector<Genotype> g;
-	std::vector<double> cloud((size_t) n * dim);
-	appendStoreSamples(c, g, store, opt, [&](uint32_t d, Genotype &s) {
-		const ix::Entry e = index.entry(d);
-		s.hets = e.hets; s.homs = e.homs; s.miss = e.miss;
-		memcpy(&cloud[(size_t) d * dim], e.cloud, sizeof(double) * dim);
-	});
+	const std::vector<double> cloud = appendIndexedSamples(c, g, store, index, opt);
 	const std::vector<double> radius = searchRadii(g, m, opt);
 	if (opt.verbose > 1) std::cerr << "Starting Score Computation with PCA" << std::endl;
-	uint64_t np = 0;
-	double msSearch = 0;
-	int rc = ntsm_eval_cross_candidates(opt.device, cloud.data(), radius.data(), n, nullptr, nullptr, 0, dim, nullptr, nullptr, nullptr, 0, &np, &msSearch);
-	if (rc && rc != NTSM_EVAL_E_CAPACITY) return gpuFail("candidate search", rc);
-	std::vector<uint32_t> pi(np), pk(np);
-	std::vector<double> dist(np);
-	if (np) {
-		rc = ntsm_eval_cross_candidates(opt.device, cloud.data(), radius.data(), n, nullptr, nullptr, 0, dim, pi.data(), pk.data(), dist.data(), np, &np, &msSearch);
-		if (rc) return gpuFail("candidate search", rc);
-	}
+	Candidates cand;
+	const int rc = cand.search([&](uint32_t *pi, uint32_t *pk, double *dist, uint64_t capacity, uint64_t *np, double *ms) {
+		return ntsm_eval_cross_candidates(opt.device, cloud.data(), radius.data(), n, nullptr, nullptr, 0, dim, pi, pk, dist, capacity, np, ms);
+	});
+	if (rc) return rc;
 	const double searchMs = msSince(t);
+	const Route route { n, 0, store.counts(0), store.h.stride,
+		[&](const uint32_t *li, const uint32_t *lk, uint64_t np, ntsm_eval_record *out, ntsm_eval_cross_times *times) {
+			return ntsm_eval_store_score_pairs(opt.device, store.counts(0), store.h.stride, n, m, opt.minCov, li, lk, np, 0, out, times);
+		} };
+	return routeAndScore(c, g, opt, store, radius, cand, route, mapMs, 0.0, searchMs, t0);
+}
 
-	t = std::chrono::steady_clock::now();
-	std::vector<uint32_t> dense, denseRow(n, UINT32_MAX);
-	for (uint32_t i = 0; i < n; ++i)
-		if (!(radius[i] < DBL_MAX)) { denseRow[i] = (uint32_t) dense.size(); dense.push_back(i); }
-	std::vector<ntsm_eval_record> rect((size_t) dense.size() * n), rec(np);
-	ntsm_eval_cross_times crossTimes {}, listTimes {};
-	if (!dense.empty()) {
-		std::vector<uint32_t> sub(dense.size() * (size_t) m * 2);
-		for (size_t r = 0; r < dense.size(); ++r) memcpy(&sub[r * m * 2], store.counts(dense[r]), sizeof(uint32_t) * m * 2);
-		rc = ntsm_eval_cross(opt.device, sub.data(), (uint32_t) dense.size(), store.counts(0), store.h.stride, n, m, opt.minCov, 0, rect.data(), nullptr, &crossTimes);
-		if (rc) return gpuFail("scoring against the store", rc);
-	}
-	std::vector<uint32_t> li, lk;
-	std::vector<uint64_t> where;
-	for (uint64_t p = 0; p < np; ++p) {
-		if (denseRow[pi[p]] != UINT32_MAX) rec[p] = rect[(size_t) denseRow[pi[p]] * n + pk[p]];
-		else { li.push_back(pi[p]); lk.push_back(pk[p]); where.push_back(p); }
-	}
-	std::vector<ntsm_eval_record> listed(li.size());
-	rc = ntsm_eval_store_score_pairs(opt.device, store.counts(0), store.h.stride, n, m, opt.minCov, li.data(), lk.data(), li.size(), 0, listed.data(), &listTimes);
-	if (rc) return gpuFail("scoring the candidate pairs", rc);
-	for (size_t x = 0; x < where.size(); ++x) rec[where[x]] = listed[x];
-	const double scoreMs = msSince(t);
-
-	const auto tPrint = std::chrono::steady_clock::now();
-	std::cout << kHeader << "\n";
-	std::string temp;
-	for (uint64_t p = 0; p < np; ++p) printRow(temp, c, g, opt, rec[p], pi[p], pk[p], std::to_string(dist[p]));
-	std::cout.flush();
-	if (opt.verbose > 1)
-		std::cerr << "store search: " << np << " pairs (" << li.size() << " listed, " << dense.size() << " dense rows), map+load " << mapMs << " ms, project "
-		          << 0.0 << " ms, search " << searchMs << " ms (kernels " << msSearch << " ms), score " << scoreMs << " ms (gather "
-		          << listTimes.upload_ms << " ms, list kernel " << listTimes.cross_kernel_ms << " ms in " << listTimes.chunks << " passes, dense upload "
-		          << crossTimes.upload_ms << " ms, dense kernel " << crossTimes.cross_kernel_ms << " ms), print " << msSince(tPrint) << " ms" << std::endl;
-	std::cerr << "Time: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << " s" << std::endl;
-	return 0;
+/* what no store run goes with */
+void refuseDebugAndMerge(const Opt &opt, const char *mode)
+{
+	if (!opt.debug.empty()) ntsm::refuse(std::string("-b with ") + mode + " is not part of this build");
+	if (!opt.merge.empty() || opt.onlyMerge) ntsm::refuse(std::string("merging (-e, -o) with ") + mode + " is not part of this build: the store does not hold the per-site sums");
 }
 
 }  // namespace
@@ -822,18 +824,16 @@ int main(int argc, char **argv)
 		if (!opt.pca.empty() || !opt.norm.empty())
 			ntsm::refuse(near ? "--within-near takes rotation and centre from the store's index: give no -p and no -n"
 			                  : "--within is the all-to-all run and takes no -p and no -n: the PCA-guided search inside a store is --within-near");
-		if (!opt.debug.empty()) ntsm::refuse(std::string("-b with ") + mode + " is not part of this build");
-		if (!opt.merge.empty() || opt.onlyMerge) ntsm::refuse(std::string("merging (-e, -o) with ") + mode + " is not part of this build: the store does not hold the per-site sums");
+		refuseDebugAndMerge(opt, mode);
 		if (opt.withinRowsGiven && near) ntsm::refuse("--within-rows sets the bands of --within: it does not go with --within-near");
-		const auto t0 = std::chrono::steady_clock::now();
+		const auto t0 = Clock::now();
 		return near ? searchWithin(opt, t0) : scoreWithin(opt, t0);
 	}
 	if (opt.withinRowsGiven) ntsm::refuse("--within-rows sets the bands of --within: give it with --within STORE");
 	if (nearMode) {                                      /* --index and --near: every refusal that needs no store comes before any file is read */
 		const char *mode = opt.near.empty() ? "--index" : "--near";
 		if (storeMode || (!opt.index.empty() && !opt.near.empty())) ntsm::refuse("--pack, --against, --index and --near are four runs: give one of them");
-		if (!opt.debug.empty()) ntsm::refuse(std::string("-b with ") + mode + " is not part of this build");
-		if (!opt.merge.empty() || opt.onlyMerge) ntsm::refuse(std::string("merging (-e, -o) with ") + mode + " is not part of this build: the store does not hold the per-site sums");
+		refuseDebugAndMerge(opt, mode);
 		if (!opt.near.empty()) {
 			if (!opt.pca.empty() || !opt.norm.empty()) ntsm::refuse("--near takes rotation and centre from the store's index: give no -p and no -n");
 			if (c.files.empty()) ntsm::refuse("--near needs input files");
@@ -842,14 +842,13 @@ int main(int argc, char **argv)
 			if (opt.pca.empty() || !std::ifstream(opt.pca).good()) ntsm::refuse("--index needs a readable rotation file (-p)");
 			if (opt.norm.empty() || !std::ifstream(opt.norm).good()) ntsm::refuse("--index needs a readable normalization file (-n)");
 			if (opt.dim == 0) ntsm::refuse("a PCA search with -d 0 is not part of this build");
-			return buildIndex(opt, std::chrono::steady_clock::now());
+			return buildIndex(opt, Clock::now());
 		}
 	} else if (storeMode) {                              /* what --pack and --against do not go with: refused before any file is read */
 		const char *mode = opt.pack.empty() ? "--against" : "--pack";
 		if (!opt.pack.empty() && !opt.against.empty()) ntsm::refuse("--pack and --against are two runs: give one of them");
 		if (!opt.pca.empty()) ntsm::refuse(std::string("the PCA-guided search (-p) ") + (opt.pack.empty() ? "against a store" : "with --pack") + " is not part of this build");
-		if (!opt.debug.empty()) ntsm::refuse(std::string("-b with ") + mode + " is not part of this build");
-		if (!opt.merge.empty() || opt.onlyMerge) ntsm::refuse(std::string("merging (-e, -o) with ") + mode + " is not part of this build: the store does not hold the per-site sums");
+		refuseDebugAndMerge(opt, mode);
 		if (c.files.empty()) ntsm::refuse(std::string(mode) + " needs input files");
 	}
 	for (const std::string &f : c.files)
@@ -874,7 +873,7 @@ int main(int argc, char **argv)
 		}
 	}
 	ntsm::try_help_if(die);
-	const auto t0 = std::chrono::steady_clock::now();
+	const auto t0 = Clock::now();
 	if (!opt.pack.empty()) return packStore(c, opt);
 	if (!opt.against.empty()) return scoreAgainst(c, opt, t0);
 	if (!opt.near.empty()) return searchNear(c, opt, t0);
@@ -916,7 +915,7 @@ int main(int argc, char **argv)
 		std::vector<ntsm_eval_record> rec((size_t) n * (n - 1) / 2);
 		double ms = 0;
 		const int rc = ntsm_eval_pairs(opt.device, c.counts.data(), n, (uint32_t) c.nSites(), opt.minCov, rec.data(), &ms);
-		if (rc) { std::cerr << PROGRAM ": scoring on the GPU failed (" << rc << "); there is no CPU path" << std::endl; return 3; }
+		if (rc) return gpuFail("scoring", rc);
 		if (opt.verbose > 1) std::cerr << "pair kernel: " << ms << " ms for " << rec.size() << " pairs" << std::endl;
 		std::cout << kHeader;
 		std::cout << "\n";
@@ -944,6 +943,6 @@ int main(int argc, char **argv)
 			out << c.locus[s] << "\t" << cAT << "\t" << cCG << "\t" << sAT << "\t" << sCG << "\t" << c.distinct[2 * s] << "\t" << c.distinct[2 * s + 1] << "\n";
 		}
 	}
-	std::cerr << "Time: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << " s" << std::endl;
+	printTime(t0);
 	return 0;
 }

@@ -1,9 +1,11 @@
 /*
- * ntsm_eval_chunk.h -- one chunk of a cohort store on the device, stated once for ntsm_eval_cross.hip (the dense rectangle)
- * and ntsm_eval_near.hip (the projection of a store, the passes over listed samples): the chunk rule, the genotype tallies
- * of the chunk's samples over the dense [chunk sample][site][2] buffer, and that buffer's transpose to at / cg / term
- * [site][chunk sample] for the cross kernel.  Internal: not part of
- * include/.  The kernels have internal linkage; each translation unit that includes this file carries its own copy.
+ * ntsm_eval_chunk.h -- one chunk of a cohort store on the device, stated once for ntsm_eval_cross.hip (the dense rectangle),
+ * ntsm_eval_near.hip (the projection of a store) and ntsm_eval_within.hip (the triangle, resident or streamed): the chunk
+ * rule; the kernels -- the genotype tallies of the chunk's samples over the dense [chunk sample][site][2] buffer and that
+ * buffer's transpose to at / cg / term [site][chunk sample] --; and the step that stages a chunk: the 2-D copy from the
+ * host pitch, those kernels, the wall clock and the events that time them.  Internal: not part of include/.  The kernels
+ * have internal linkage; each translation unit that includes this file carries its own copy, and names itself first
+ * (NTSM_HIP_TAG, ntsm_hip_scope.h).
  */
 #ifndef NTSM_EVAL_CHUNK_H
 #define NTSM_EVAL_CHUNK_H
@@ -11,9 +13,12 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cstdint>
 
+#include "../../include/ntsm_eval_hip.h"
 #include "ntsm_eval_score.h"
+#include "ntsm_hip_scope.h"
 
 namespace ntsm_eval_chunk {
 
@@ -88,6 +93,42 @@ inline uint32_t samples_per_pass(uint32_t db_chunk, uint32_t n_db, size_t free_b
 		chunk = (uint32_t) std::min<uint64_t>(n_db, std::max<uint64_t>(64, budget / per_sample));
 	}
 	return std::min(chunk, n_db);
+}
+
+typedef std::chrono::steady_clock wall;
+static inline double ms_since(wall::time_point t) { return std::chrono::duration<double, std::milli>(wall::now() - t).count(); }
+
+/* the interval between two events that have completed, added to *ms */
+static inline int add_interval(hipEvent_t e0, hipEvent_t e1, double *ms)
+{
+	float f = 0;
+	HIPCHK(hipEventElapsedTime(&f, e0, e1));
+	*ms += f;
+	return 0;
+}
+
+/* Samples first ... first + count - 1 of the store: one 2-D copy from the host pitch to d_raw [count][site][2], timed into
+ * tm.upload_ms (added); then, between e0 and e1, with d_at the transpose to at / cg / term [site][count] and with d_geno
+ * the tallies.  It waits for nothing: a caller adds the interval (e0, e1) to tm.prepare_kernel_ms once it has waited for e1
+ * or for a later event of its own, so a walk over chunks keeps the one wait per chunk it has. */
+static inline int stage(const void *db, uint64_t stride, uint32_t first, uint32_t count, uint32_t n_sites, uint32_t min_cov, uint32_t *d_raw, uint32_t *d_at,
+		uint32_t *d_cg, double *d_term, uint32_t *d_geno, hipEvent_t e0, hipEvent_t e1, ntsm_eval_cross_times &tm)
+{
+	const uint64_t row_bytes = 8ull * n_sites;
+	const auto t = wall::now();
+	HIPCHK(hipMemcpy2D(d_raw, row_bytes, (const char *) db + (uint64_t) first * stride, stride, row_bytes, count, hipMemcpyHostToDevice));
+	tm.upload_ms += ms_since(t);
+	HIPCHK(hipEventRecord(e0, 0));
+	if (d_at) {
+		launch_prepare(d_raw, count, n_sites, min_cov, d_at, d_cg, d_term);
+		HIPCHK(hipGetLastError());
+	}
+	if (d_geno) {
+		launch_tally(d_raw, count, n_sites, min_cov, d_geno);
+		HIPCHK(hipGetLastError());
+	}
+	HIPCHK(hipEventRecord(e1, 0));
+	return 0;
 }
 
 }  // namespace ntsm_eval_chunk

@@ -11,23 +11,22 @@
  * record is mirrored; the query is sample 1 of every record.
  *
  * Chunks.  The database is a host array with a fixed pitch between samples (a cohort store mapped from disk).  Per chunk:
- * one 2-D copy of the chunk's counts to a dense [chunk sample][site][2] buffer, the transpose (through LDS, so that both its
- * reads and its writes are coalesced), the genotype tallies of the chunk's samples (one workgroup per sample over the dense
- * buffer) -- those two and the chunk rule are ntsm_eval_chunk.h's; the projection of a store
- * (ntsm_eval_near.hip) takes the chunk rule and the tallies from there --, the cross kernel, and one 2-D copy of the chunk's columns of `out` back.  One stream, no overlap.  Device memory is
- * O((n_q + chunk) * n_sites + n_q * chunk).
+ * the staging step of ntsm_eval_chunk.h -- one 2-D copy of the chunk's counts to a dense [chunk sample][site][2] buffer, the
+ * transpose (through LDS, so that both its reads and its writes are coalesced) and the genotype tallies of the chunk's
+ * samples (one workgroup per sample over the dense buffer), both reported as "prepare" --, the cross kernel, one wait, and
+ * one 2-D copy of the chunk's columns of `out` back.  The chunk rule is that header's too.  One stream, no overlap.  Device
+ * memory is O((n_q + chunk) * n_sites + n_q * chunk).
  */
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstdint>
 #include <cstring>
 
 #include "../../include/ntsm_eval_hip.h"
+#define NTSM_HIP_TAG "ntsm_eval_cross"
 #include "ntsm_eval_chunk.h"
 #include "ntsm_eval_score.h"
-#define NTSM_HIP_TAG "ntsm_eval_cross"
 #include "ntsm_hip_scope.h"
 
 namespace {
@@ -122,10 +121,10 @@ extern "C" int ntsm_eval_cross(int device, const uint32_t *q_counts, uint32_t n_
 	HIPCHK(b.alloc(&d_out, (uint64_t) n_q * chunk));
 	HIPCHK(ev.create());
 
-	typedef std::chrono::steady_clock clock;
-	const auto ms_since = [](clock::time_point t) { return std::chrono::duration<double, std::milli>(clock::now() - t).count(); };
+	using ntsm_eval_chunk::ms_since;
+	using ntsm_eval_chunk::wall;
 	ntsm_eval_cross_times tm {};
-	auto t = clock::now();
+	auto t = wall::now();
 	HIPCHK(hipMemcpy(d_q, q_counts, qcells * 2 * sizeof(uint32_t), hipMemcpyHostToDevice));
 	tm.upload_ms += ms_since(t);
 	HIPCHK(hipEventRecord(ev[0], 0));
@@ -133,24 +132,13 @@ extern "C" int ntsm_eval_cross(int device, const uint32_t *q_counts, uint32_t n_
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipEventRecord(ev[1], 0));
 	HIPCHK(hipEventSynchronize(ev[1]));
-	float ms = 0;
-	HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-	tm.prepare_kernel_ms += ms;
+	int rc = ntsm_eval_chunk::add_interval(ev[0], ev[1], &tm.prepare_kernel_ms);
+	if (rc) return rc;
 
 	for (uint32_t c0 = 0; c0 < n_db; c0 += chunk) {
 		const uint32_t cn = std::min(chunk, n_db - c0);
-		t = clock::now();
-		HIPCHK(hipMemcpy2D(d_raw, row_bytes, (const char *) db_counts + (uint64_t) c0 * db_stride_bytes, db_stride_bytes, row_bytes, cn,
-				hipMemcpyHostToDevice));
-		tm.upload_ms += ms_since(t);
-		HIPCHK(hipEventRecord(ev[0], 0));
-		ntsm_eval_chunk::launch_prepare(d_raw, cn, n_sites, min_cov, d_at, d_cg, d_term);
-		HIPCHK(hipGetLastError());
-		if (db_geno) {
-			ntsm_eval_chunk::launch_tally(d_raw, cn, n_sites, min_cov, d_geno);
-			HIPCHK(hipGetLastError());
-		}
-		HIPCHK(hipEventRecord(ev[1], 0));
+		rc = ntsm_eval_chunk::stage(db_counts, db_stride_bytes, c0, cn, n_sites, min_cov, d_raw, d_at, d_cg, d_term, db_geno ? d_geno : nullptr, ev[0], ev[1], tm);
+		if (rc) return rc;
 		uint32_t width, tq;
 		launch_shape(n_q, cn, width, tq);
 		const dim3 grid((cn + width - 1) / width, (n_q + tq - 1) / tq);
@@ -159,15 +147,13 @@ extern "C" int ntsm_eval_cross(int device, const uint32_t *q_counts, uint32_t n_
 		HIPCHK(hipGetLastError());
 		HIPCHK(hipEventRecord(ev[2], 0));
 		HIPCHK(hipEventSynchronize(ev[2]));
-		t = clock::now();
+		t = wall::now();
 		HIPCHK(hipMemcpy2D(out + c0, (size_t) n_db * sizeof(ntsm_eval_record), d_out, (size_t) chunk * sizeof(ntsm_eval_record),
 				(size_t) cn * sizeof(ntsm_eval_record), n_q, hipMemcpyDeviceToHost));
 		if (db_geno) HIPCHK(hipMemcpy(db_geno + (uint64_t) c0 * 3, d_geno, (size_t) cn * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost));
 		tm.download_ms += ms_since(t);
-		HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-		tm.prepare_kernel_ms += ms;
-		HIPCHK(hipEventElapsedTime(&ms, ev[1], ev[2]));
-		tm.cross_kernel_ms += ms;
+		if ((rc = ntsm_eval_chunk::add_interval(ev[0], ev[1], &tm.prepare_kernel_ms)) != 0) return rc;
+		if ((rc = ntsm_eval_chunk::add_interval(ev[1], ev[2], &tm.cross_kernel_ms)) != 0) return rc;
 		tm.chunks++;
 	}
 	if (times) *times = tm;

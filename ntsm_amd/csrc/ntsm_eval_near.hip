@@ -4,8 +4,8 @@
  * src/CompareCounts.hpp:116-211 projectPCs, :285-398 computeScorePCA).  Indices follow the concatenation [queries; database]:
  * query q is sample q, database sample d is sample n_q + d.
  *
- * Projection of a store.  The store is walked in chunks as ntsm_eval_cross walks it (one 2-D copy per chunk to a dense buffer,
- * the chunk rule and the tallies of ntsm_eval_chunk.h) and each chunk is projected by the session's kernel (ntsm_eval_pca.h:
+ * Projection of a store.  The store is walked in chunks as ntsm_eval_cross walks it (the chunk rule and the staging step of
+ * ntsm_eval_chunk.h, here without the transpose) and each chunk is projected by the session's kernel (ntsm_eval_pca.h:
  * one lane per (sample, component) over the dense rows), so cloud bits are ntsm_eval_project's by construction.  A kernel
  * over the transposed [site][chunk sample] layout of the cross path -- samples across the lanes, coalesced loads, the table
  * entry wave-uniform -- was built and measured first: 134.8 and 141.4 ms against 135.9 and 136.3 ms on 4,096 x 96,287 sites x
@@ -17,30 +17,30 @@
  * and the selection rule of ntsm_eval_pca.h is asked twice, for row q and, where k is a database sample, for row k.  A
  * counting pass, the prefix sum over the rows on the host, a filling pass: a query row is filled through one wave-aggregated
  * atomic per wave and query (its order does not matter: the host sorts), a database row by its own lane, queries ascending.
- * The host orders a radius row by (evalMetric, k) and a search-all row by k, which is the session search's order.  The grid
- * is (columns / 256): never one workgroup per database row.
+ * The host half is ntsm_eval_pca.h's finish_candidates: a radius row by (evalMetric, k) and a search-all row by k, which is
+ * the session search's order.  The grid is (columns / 256): never one workgroup per database row.
  *
  * Scoring of listed pairs.  Every pair has a query in it, so it names at most one database sample.  The distinct database
  * samples of the list are copied row by row from the mapped store, at most `chunk` per pass, to dense rows behind the
  * queries' rows; a pass scores its pairs with the listed-pair kernel of ntsm_eval_pca.h over those rows (slot numbers in
  * place of sample numbers) and its records are scattered back to list order.  ntsm_eval_store_score_pairs, at the end of
- * this file, is the same for pairs of two store samples (ntsmEval --within-near).
+ * this file, is the same for pairs of two store samples (ntsmEval --within-near); one pass is stated once for both
+ * (PairPass), the cut of a list into passes is each caller's own.
  */
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cfloat>
-#include <chrono>
 #include <cstdint>
 #include <cstring>
 #include <vector>
 
 #include "../../include/ntsm_eval_hip.h"
 #include "host/eval_within.hpp"
+#define NTSM_HIP_TAG "ntsm_eval_near"
 #include "ntsm_eval_chunk.h"
 #include "ntsm_eval_pca.h"
 #include "ntsm_eval_score.h"
-#define NTSM_HIP_TAG "ntsm_eval_near"
 #include "ntsm_hip_scope.h"
 #include "xprec.h"
 
@@ -48,8 +48,9 @@ namespace {
 
 constexpr int kThreads = 256;
 
-typedef std::chrono::steady_clock wall;
-double ms_since(wall::time_point t) { return std::chrono::duration<double, std::milli>(wall::now() - t).count(); }
+using ntsm_eval_chunk::add_interval;
+using ntsm_eval_chunk::ms_since;
+using ntsm_eval_chunk::wall;
 
 /* the point and radius of column k of the concatenation */
 struct Columns {
@@ -120,6 +121,63 @@ __global__ __launch_bounds__(kThreads) void near_fill_kernel(Columns c, const ui
 	}
 }
 
+/* One pass of a list scorer: dense rows [slot][site][2] with their terms, the pass's pairs as slot numbers, its records. */
+struct PairPass {
+	ntsm_hip::Buffers b;
+	ntsm_hip::Events<3> ev;
+	uint32_t *d_rows, *d_pi, *d_pk;
+	double *d_term;
+	ntsm_eval_record *d_out;
+	uint32_t n_sites, min_cov;
+
+	/* room for `slots` rows and passes of at most `most` pairs */
+	int alloc(uint64_t slots, uint64_t most, uint32_t sites, uint32_t cov)
+	{
+		n_sites = sites;
+		min_cov = cov;
+		HIPCHK(b.alloc(&d_rows, slots * n_sites * 2));
+		HIPCHK(b.alloc(&d_term, slots * n_sites));
+		HIPCHK(b.alloc(&d_pi, most));
+		HIPCHK(b.alloc(&d_pk, most));
+		HIPCHK(b.alloc(&d_out, most));
+		HIPCHK(ev.create());
+		return 0;
+	}
+
+	/* Store samples sample[0 ... rn - 1] go to slots slot0 ... (row by row from the mapped store) and get their terms; the pn
+	 * pairs (slot_i[x], slot_k[x]) are scored into out[0 ... pn - 1]; one wait, after the scoring kernel; timed into tm (added) */
+	int run(const void *db_counts, uint64_t db_stride_bytes, uint32_t slot0, const uint32_t *sample, uint32_t rn, const uint32_t *slot_i,
+			const uint32_t *slot_k, uint64_t pn, ntsm_eval_record *out, ntsm_eval_cross_times &tm)
+	{
+		const uint64_t first = (uint64_t) slot0 * n_sites;
+		auto t = wall::now();
+		for (uint32_t r = 0; r < rn; ++r)
+			HIPCHK(hipMemcpy(d_rows + (first + (uint64_t) r * n_sites) * 2, (const char *) db_counts + (uint64_t) sample[r] * db_stride_bytes, 8ull * n_sites,
+					hipMemcpyHostToDevice));
+		HIPCHK(hipMemcpy(d_pi, slot_i, pn * sizeof(uint32_t), hipMemcpyHostToDevice));
+		HIPCHK(hipMemcpy(d_pk, slot_k, pn * sizeof(uint32_t), hipMemcpyHostToDevice));
+		tm.upload_ms += ms_since(t);
+		HIPCHK(hipEventRecord(ev[0], 0));
+		if (rn) {
+			ntsm_eval_pca::launch_term(d_rows + first * 2, (uint64_t) rn * n_sites, min_cov, d_term + first);
+			HIPCHK(hipGetLastError());
+		}
+		HIPCHK(hipEventRecord(ev[1], 0));
+		ntsm_eval_pca::launch_score(d_rows, d_term, n_sites, min_cov, d_pi, d_pk, pn, d_out);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipEventRecord(ev[2], 0));
+		HIPCHK(hipEventSynchronize(ev[2]));
+		int rc = add_interval(ev[0], ev[1], &tm.prepare_kernel_ms);
+		if (!rc) rc = add_interval(ev[1], ev[2], &tm.cross_kernel_ms);
+		if (rc) return rc;
+		t = wall::now();
+		HIPCHK(hipMemcpy(out, d_out, pn * sizeof(ntsm_eval_record), hipMemcpyDeviceToHost));
+		tm.download_ms += ms_since(t);
+		tm.chunks++;
+		return 0;
+	}
+};
+
 }  // namespace
 
 extern "C" int ntsm_eval_project_store(int device, const void *db_counts, uint64_t db_stride_bytes, uint32_t n_db, uint32_t n_sites, uint32_t min_cov,
@@ -157,16 +215,9 @@ extern "C" int ntsm_eval_project_store(int device, const void *db_counts, uint64
 
 	for (uint32_t c0 = 0; c0 < n_db; c0 += chunk) {
 		const uint32_t cn = std::min(chunk, n_db - c0);
-		t = wall::now();
-		HIPCHK(hipMemcpy2D(d_raw, row_bytes, (const char *) db_counts + (uint64_t) c0 * db_stride_bytes, db_stride_bytes, row_bytes, cn,
-				hipMemcpyHostToDevice));
-		tm.upload_ms += ms_since(t);
-		HIPCHK(hipEventRecord(ev[0], 0));
-		if (db_geno) {
-			ntsm_eval_chunk::launch_tally(d_raw, cn, n_sites, min_cov, d_geno);
-			HIPCHK(hipGetLastError());
-		}
-		HIPCHK(hipEventRecord(ev[1], 0));
+		int rc = ntsm_eval_chunk::stage(db_counts, db_stride_bytes, c0, cn, n_sites, min_cov, d_raw, nullptr, nullptr, nullptr, db_geno ? d_geno : nullptr,
+				ev[0], ev[1], tm);
+		if (rc) return rc;
 		if (dim) {
 			ntsm_eval_pca::launch_project(d_raw, cn, n_sites, min_cov, d_tab, dim, d_cloud);
 			HIPCHK(hipGetLastError());
@@ -177,11 +228,8 @@ extern "C" int ntsm_eval_project_store(int device, const void *db_counts, uint64
 		if (dim) HIPCHK(hipMemcpy(cloud + (uint64_t) c0 * dim, d_cloud, (size_t) cn * dim * sizeof(double), hipMemcpyDeviceToHost));
 		if (db_geno) HIPCHK(hipMemcpy(db_geno + (uint64_t) c0 * 3, d_geno, (size_t) cn * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost));
 		tm.download_ms += ms_since(t);
-		float ms = 0;
-		HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-		tm.prepare_kernel_ms += ms;
-		HIPCHK(hipEventElapsedTime(&ms, ev[1], ev[2]));
-		tm.cross_kernel_ms += ms;
+		if ((rc = add_interval(ev[0], ev[1], &tm.prepare_kernel_ms)) != 0) return rc;
+		if ((rc = add_interval(ev[1], ev[2], &tm.cross_kernel_ms)) != 0) return rc;
 		tm.chunks++;
 	}
 	if (times) *times = tm;
@@ -203,18 +251,18 @@ extern "C" int ntsm_eval_cross_candidates(int device, const double *q_cloud, con
 	HIPCHK(hipSetDevice(device));
 	ntsm_hip::Buffers b;
 	double *d_qc, *d_qr, *d_dc, *d_dr;
-	uint32_t *d_qcount, *d_dcount;
+	uint32_t *d_qcount, *d_dcount;                                               /* d_qcount: the queries' counts, then their rows' cursors */
 	HIPCHK(b.alloc(&d_qc, (uint64_t) n_q * dim));
 	HIPCHK(b.alloc(&d_qr, n_q));
 	HIPCHK(b.alloc(&d_dc, (uint64_t) n_db * dim));
 	HIPCHK(b.alloc(&d_dr, n_db));
-	HIPCHK(b.alloc(&d_qcount, n_q));
+	HIPCHK(b.alloc(&d_qcount, 2ull * n_q));
 	HIPCHK(b.alloc(&d_dcount, n_db));
 	if (dim) HIPCHK(hipMemcpy(d_qc, q_cloud, (uint64_t) n_q * dim * sizeof(double), hipMemcpyHostToDevice));
 	HIPCHK(hipMemcpy(d_qr, q_radius, n_q * sizeof(double), hipMemcpyHostToDevice));
 	if (dim && n_db) HIPCHK(hipMemcpy(d_dc, db_cloud, (uint64_t) n_db * dim * sizeof(double), hipMemcpyHostToDevice));
 	if (n_db) HIPCHK(hipMemcpy(d_dr, db_radius, (uint64_t) n_db * sizeof(double), hipMemcpyHostToDevice));
-	HIPCHK(hipMemset(d_qcount, 0, n_q * sizeof(uint32_t)));
+	HIPCHK(hipMemset(d_qcount, 0, 2ull * n_q * sizeof(uint32_t)));
 	const Columns cols { d_qc, d_qr, d_dc, d_dr, n_q, n_db, dim };
 	const dim3 grid((n + kThreads - 1) / kThreads);
 	ntsm_hip::Events<2> ev;
@@ -226,55 +274,11 @@ extern "C" int ntsm_eval_cross_candidates(int device, const double *q_cloud, con
 	std::vector<uint32_t> count(n, 0);
 	HIPCHK(hipMemcpy(count.data(), d_qcount, n_q * sizeof(uint32_t), hipMemcpyDeviceToHost));
 	if (n_db) HIPCHK(hipMemcpy(count.data() + n_q, d_dcount, (uint64_t) n_db * sizeof(uint32_t), hipMemcpyDeviceToHost));
-	float ms0 = 0;
-	HIPCHK(hipEventElapsedTime(&ms0, ev[0], ev[1]));
-	std::vector<uint64_t> offset((uint64_t) n + 1, 0);
-	for (uint32_t i = 0; i < n; ++i) offset[i + 1] = offset[i] + count[i];
-	const uint64_t total = offset[n];
-	*n_pairs = total;
-	if (kernel_ms) *kernel_ms = ms0;
-	if (total > capacity) return NTSM_EVAL_E_CAPACITY;
-	if (total == 0) return 0;
-	uint64_t *d_offset;
-	uint32_t *d_other;
-	double *d_metric, *d_dist;
-	HIPCHK(b.alloc(&d_offset, (uint64_t) n + 1));
-	HIPCHK(b.alloc(&d_other, total));
-	HIPCHK(b.alloc(&d_metric, total));
-	HIPCHK(b.alloc(&d_dist, total));
-	HIPCHK(hipMemcpy(d_offset, offset.data(), ((uint64_t) n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
-	HIPCHK(hipMemset(d_qcount, 0, n_q * sizeof(uint32_t)));                      /* now the rows' cursors */
-	HIPCHK(hipEventRecord(ev[0], 0));
-	hipLaunchKernelGGL(near_fill_kernel, grid, dim3(kThreads), 0, 0, cols, d_offset, d_qcount, d_offset + n_q, d_other, d_metric, d_dist);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(ev[1], 0));
-	std::vector<uint32_t> k(total);
-	std::vector<double> metric(total), dd(total);
-	HIPCHK(hipMemcpy(k.data(), d_other, total * sizeof(uint32_t), hipMemcpyDeviceToHost));
-	HIPCHK(hipMemcpy(metric.data(), d_metric, total * sizeof(double), hipMemcpyDeviceToHost));
-	HIPCHK(hipMemcpy(dd.data(), d_dist, total * sizeof(double), hipMemcpyDeviceToHost));
-	float ms1 = 0;
-	HIPCHK(hipEventElapsedTime(&ms1, ev[0], ev[1]));
-	if (kernel_ms) *kernel_ms = (double) ms0 + ms1;
-	/* a radius row by ascending evalMetric (nanoflann sorts its matches), exact ties by ascending k; a search-all row by k */
-	std::vector<uint64_t> ord;
-	for (uint32_t i = 0; i < n; ++i) {
-		const uint64_t lo = offset[i], hi = offset[i + 1];
-		if (lo == hi) continue;
-		ord.resize(hi - lo);
-		for (uint64_t p = lo; p < hi; ++p) ord[p - lo] = p;
-		const bool by_metric = (i < n_q ? q_radius[i] : db_radius[i - n_q]) < DBL_MAX;
-		std::sort(ord.begin(), ord.end(), [&](uint64_t x, uint64_t y) {
-			if (by_metric && metric[x] != metric[y]) return metric[x] < metric[y];
-			return k[x] < k[y];
-		});
-		for (uint64_t q = 0; q < ord.size(); ++q) {
-			pi[lo + q] = i;
-			pk[lo + q] = k[ord[q]];
-			dist[lo + q] = dd[ord[q]];
-		}
-	}
-	return 0;
+	return ntsm_eval_pca::finish_candidates(b, ev[0], ev[1], count,
+			[&](const uint64_t *d_offset, uint32_t *d_k, double *d_metric, double *d_dist) {
+				hipLaunchKernelGGL(near_fill_kernel, grid, dim3(kThreads), 0, 0, cols, d_offset, d_qcount + n_q, d_offset + n_q, d_k, d_metric, d_dist);
+			},
+			[&](uint32_t i) { return i < n_q ? q_radius[i] : db_radius[i - n_q]; }, pi, pk, dist, capacity, n_pairs, kernel_ms);
 }
 
 extern "C" int ntsm_eval_cross_score_pairs(int device, const uint32_t *q_counts, uint32_t n_q, const void *db_counts, uint64_t db_stride_bytes,
@@ -318,31 +322,21 @@ extern "C" int ntsm_eval_cross_score_pairs(int device, const uint32_t *q_counts,
 	uint64_t most = 0;
 	for (const auto &v : of_pass) most = std::max<uint64_t>(most, v.size());
 
-	ntsm_hip::Buffers b;
-	ntsm_hip::Events<3> ev;
-	uint32_t *d_rows, *d_pi, *d_pk;
-	double *d_term;
-	ntsm_eval_record *d_out;
-	const uint64_t slots = (uint64_t) n_q + chunk, qcells = (uint64_t) n_q * n_sites;
-	HIPCHK(b.alloc(&d_rows, slots * n_sites * 2));
-	HIPCHK(b.alloc(&d_term, slots * n_sites));
-	HIPCHK(b.alloc(&d_pi, most));
-	HIPCHK(b.alloc(&d_pk, most));
-	HIPCHK(b.alloc(&d_out, most));
-	HIPCHK(ev.create());
+	PairPass d;
+	const uint64_t qcells = (uint64_t) n_q * n_sites;
+	int rc = d.alloc((uint64_t) n_q + chunk, most, n_sites, min_cov);
+	if (rc) return rc;
 	ntsm_eval_cross_times tm {};
 	auto t = wall::now();
-	if (qcells) HIPCHK(hipMemcpy(d_rows, q_counts, qcells * 2 * sizeof(uint32_t), hipMemcpyHostToDevice));
+	if (qcells) HIPCHK(hipMemcpy(d.d_rows, q_counts, qcells * 2 * sizeof(uint32_t), hipMemcpyHostToDevice));
 	tm.upload_ms += ms_since(t);
-	float ms = 0;
-	if (qcells) {
-		HIPCHK(hipEventRecord(ev[0], 0));
-		ntsm_eval_pca::launch_term(d_rows, qcells, min_cov, d_term);
+	if (qcells) {                                                                /* the queries' terms: once, in front of the passes */
+		HIPCHK(hipEventRecord(d.ev[0], 0));
+		ntsm_eval_pca::launch_term(d.d_rows, qcells, min_cov, d.d_term);
 		HIPCHK(hipGetLastError());
-		HIPCHK(hipEventRecord(ev[1], 0));
-		HIPCHK(hipEventSynchronize(ev[1]));
-		HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-		tm.prepare_kernel_ms += ms;
+		HIPCHK(hipEventRecord(d.ev[1], 0));
+		HIPCHK(hipEventSynchronize(d.ev[1]));
+		if ((rc = add_interval(d.ev[0], d.ev[1], &tm.prepare_kernel_ms)) != 0) return rc;
 	}
 	std::vector<uint32_t> a, c;
 	std::vector<ntsm_eval_record> rec;
@@ -350,37 +344,15 @@ extern "C" int ntsm_eval_cross_score_pairs(int device, const uint32_t *q_counts,
 		const std::vector<uint64_t> &list = of_pass[pass];
 		if (list.empty()) continue;
 		const uint32_t r0 = pass * chunk, rn = r0 < n_named ? std::min(chunk, n_named - r0) : 0;
-		t = wall::now();
-		for (uint32_t r = 0; r < rn; ++r)                                        /* row by row from the mapped store */
-			HIPCHK(hipMemcpy(d_rows + ((uint64_t) n_q + r) * n_sites * 2, (const char *) db_counts + (uint64_t) named[r0 + r] * db_stride_bytes,
-					row_bytes, hipMemcpyHostToDevice));
 		a.resize(list.size());
 		c.resize(list.size());
+		rec.resize(list.size());
 		const auto slot = [&](uint32_t s) { return s < n_q ? s : n_q + rank(s) - r0; };
 		for (uint64_t x = 0; x < list.size(); ++x) { a[x] = slot(pi[list[x]]); c[x] = slot(pk[list[x]]); }
-		HIPCHK(hipMemcpy(d_pi, a.data(), a.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-		HIPCHK(hipMemcpy(d_pk, c.data(), c.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-		tm.upload_ms += ms_since(t);
-		HIPCHK(hipEventRecord(ev[0], 0));
-		if (rn) {
-			ntsm_eval_pca::launch_term(d_rows + qcells * 2, (uint64_t) rn * n_sites, min_cov, d_term + qcells);
-			HIPCHK(hipGetLastError());
-		}
-		HIPCHK(hipEventRecord(ev[1], 0));
-		ntsm_eval_pca::launch_score(d_rows, d_term, n_sites, min_cov, d_pi, d_pk, list.size(), d_out);
-		HIPCHK(hipGetLastError());
-		HIPCHK(hipEventRecord(ev[2], 0));
-		HIPCHK(hipEventSynchronize(ev[2]));
-		HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-		tm.prepare_kernel_ms += ms;
-		HIPCHK(hipEventElapsedTime(&ms, ev[1], ev[2]));
-		tm.cross_kernel_ms += ms;
+		if ((rc = d.run(db_counts, db_stride_bytes, n_q, named.data() + r0, rn, a.data(), c.data(), list.size(), rec.data(), tm)) != 0) return rc;
 		t = wall::now();
-		rec.resize(list.size());
-		HIPCHK(hipMemcpy(rec.data(), d_out, list.size() * sizeof(ntsm_eval_record), hipMemcpyDeviceToHost));
 		for (uint64_t x = 0; x < list.size(); ++x) out[list[x]] = rec[x];        /* back to list order */
 		tm.download_ms += ms_since(t);
-		tm.chunks++;
 	}
 	if (times) *times = tm;
 	return 0;
@@ -415,46 +387,15 @@ extern "C" int ntsm_eval_store_score_pairs(int device, const void *db_counts, ui
 		slots = std::max(slots, (uint32_t) (cut.sample_begin[x + 1] - cut.sample_begin[x]));
 	}
 
-	ntsm_hip::Buffers b;
-	ntsm_hip::Events<3> ev;
-	uint32_t *d_rows, *d_pi, *d_pk;
-	double *d_term;
-	ntsm_eval_record *d_out;
-	HIPCHK(b.alloc(&d_rows, (uint64_t) slots * n_sites * 2));
-	HIPCHK(b.alloc(&d_term, (uint64_t) slots * n_sites));
-	HIPCHK(b.alloc(&d_pi, most));
-	HIPCHK(b.alloc(&d_pk, most));
-	HIPCHK(b.alloc(&d_out, most));
-	HIPCHK(ev.create());
+	PairPass d;
+	int rc = d.alloc(slots, most, n_sites, min_cov);
 	ntsm_eval_cross_times tm {};
-	for (size_t x = 0; x < cut.passes(); ++x) {
-		const uint64_t p0 = cut.pair_begin[x], pn = cut.pair_begin[x + 1] - p0, s0 = cut.sample_begin[x];
-		const uint32_t rn = (uint32_t) (cut.sample_begin[x + 1] - s0);
-		auto t = wall::now();
-		for (uint32_t r = 0; r < rn; ++r)                                        /* row by row from the mapped store */
-			HIPCHK(hipMemcpy(d_rows + (uint64_t) r * n_sites * 2, (const char *) db_counts + (uint64_t) cut.sample[s0 + r] * db_stride_bytes, row_bytes,
-					hipMemcpyHostToDevice));
-		HIPCHK(hipMemcpy(d_pi, cut.slot_i.data() + p0, pn * sizeof(uint32_t), hipMemcpyHostToDevice));
-		HIPCHK(hipMemcpy(d_pk, cut.slot_k.data() + p0, pn * sizeof(uint32_t), hipMemcpyHostToDevice));
-		tm.upload_ms += ms_since(t);
-		HIPCHK(hipEventRecord(ev[0], 0));
-		ntsm_eval_pca::launch_term(d_rows, (uint64_t) rn * n_sites, min_cov, d_term);
-		HIPCHK(hipGetLastError());
-		HIPCHK(hipEventRecord(ev[1], 0));
-		ntsm_eval_pca::launch_score(d_rows, d_term, n_sites, min_cov, d_pi, d_pk, pn, d_out);
-		HIPCHK(hipGetLastError());
-		HIPCHK(hipEventRecord(ev[2], 0));
-		HIPCHK(hipEventSynchronize(ev[2]));
-		float ms = 0;
-		HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-		tm.prepare_kernel_ms += ms;
-		HIPCHK(hipEventElapsedTime(&ms, ev[1], ev[2]));
-		tm.cross_kernel_ms += ms;
-		t = wall::now();
-		HIPCHK(hipMemcpy(out + p0, d_out, pn * sizeof(ntsm_eval_record), hipMemcpyDeviceToHost));
-		tm.download_ms += ms_since(t);
-		tm.chunks++;
+	for (size_t x = 0; x < cut.passes() && !rc; ++x) {
+		const uint64_t p0 = cut.pair_begin[x], s0 = cut.sample_begin[x];
+		rc = d.run(db_counts, db_stride_bytes, 0, cut.sample.data() + s0, (uint32_t) (cut.sample_begin[x + 1] - s0), cut.slot_i.data() + p0,
+				cut.slot_k.data() + p0, cut.pair_begin[x + 1] - p0, out + p0, tm);
 	}
+	if (rc) return rc;
 	if (times) *times = tm;
 	return 0;
 }

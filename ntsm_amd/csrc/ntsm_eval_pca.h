@@ -2,19 +2,23 @@
  * ntsm_eval_pca.h -- the steps of the PCA-guided search that its two forms share, each stated once: ntsm_eval_pca.hip (one
  * run's samples against each other) and ntsm_eval_near.hip (new samples against a cohort store).  The projection kernel,
  * the genotype code of a site and the host's product table (src/CompareCounts.hpp:166-211), nanoflann's evalMetric, calcDistance
- * and computeScorePCA's selection of a pair (:285-398), and the scoring of listed pairs over [sample][site][2] rows.
- * Internal: not part of include/.  The kernels have internal linkage.
+ * and computeScorePCA's selection of a pair (:285-398), the host half of a candidate search (from the rows' counts to the
+ * ordered list), and the scoring of listed pairs over [sample][site][2] rows.  Internal: not part of include/.  The kernels
+ * have internal linkage; a translation unit names itself (NTSM_HIP_TAG, ntsm_hip_scope.h) before it includes this file.
  */
 #ifndef NTSM_EVAL_PCA_H
 #define NTSM_EVAL_PCA_H
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cfloat>
 #include <cstdint>
 #include <vector>
 
+#include "../../include/ntsm_eval_hip.h"
 #include "ntsm_eval_score.h"
+#include "ntsm_hip_scope.h"
 #include "xprec.h"
 
 namespace ntsm_eval_pca {
@@ -147,6 +151,69 @@ inline void launch_score(const uint32_t *counts, const double *term, uint32_t m,
 		uint64_t n_pairs, ntsm_eval_record *out)
 {
 	hipLaunchKernelGGL(score_kernel, dim3((unsigned) ((n_pairs + kThreads - 1) / kThreads)), dim3(kThreads), 0, 0, counts, term, m, min_cov, pi, pk, n_pairs, out);
+}
+
+/* The host half of a candidate search.  count[i] is the number of pairs of row i, from a counting pass that ran between e0
+ * and e1 and is complete.  Prefix sum, *n_pairs, the capacity protocol (NTSM_EVAL_E_CAPACITY with the size reported; nothing
+ * further for an empty list), then fill(d_offset, d_k, d_metric, d_dist) launches the caller's filling pass over device
+ * arrays allocated here in b -- row i's pairs from d_offset[i] on -- and each row is ordered and written to pi / pk / dist.
+ * radius_of(i) < DBL_MAX says that row i is a radius row.  *kernel_ms = count + fill.
+ *
+ * Order: a radius row by ascending evalMetric (nanoflann sorts its matches), exact ties by ascending k; a search-all row by
+ * k.  The session search used to say this as a stable sort by metric alone; its fill writes k ascending within a row, and a
+ * stable sort keeps that order among equal metrics, which is what the second key says.  A fill that writes a row in any
+ * order (a query row of the search against a store) needs the key, so the total order is the one spelling. */
+template <typename Fill, typename RadiusOf>
+int finish_candidates(ntsm_hip::Buffers &b, hipEvent_t e0, hipEvent_t e1, const std::vector<uint32_t> &count, Fill fill, RadiusOf radius_of, uint32_t *pi,
+		uint32_t *pk, double *dist, uint64_t capacity, uint64_t *n_pairs, double *kernel_ms)
+{
+	const uint32_t n = (uint32_t) count.size();
+	float ms0 = 0, ms1 = 0;
+	HIPCHK(hipEventElapsedTime(&ms0, e0, e1));
+	std::vector<uint64_t> offset((uint64_t) n + 1, 0);
+	for (uint32_t i = 0; i < n; ++i) offset[i + 1] = offset[i] + count[i];
+	const uint64_t total = offset[n];
+	*n_pairs = total;
+	if (kernel_ms) *kernel_ms = ms0;
+	if (total > capacity) return NTSM_EVAL_E_CAPACITY;
+	if (total == 0) return 0;
+	uint64_t *d_offset;
+	uint32_t *d_k;
+	double *d_metric, *d_dist;
+	HIPCHK(b.alloc(&d_offset, (uint64_t) n + 1));
+	HIPCHK(b.alloc(&d_k, total));
+	HIPCHK(b.alloc(&d_metric, total));
+	HIPCHK(b.alloc(&d_dist, total));
+	HIPCHK(hipMemcpy(d_offset, offset.data(), ((uint64_t) n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
+	HIPCHK(hipEventRecord(e0, 0));
+	fill(d_offset, d_k, d_metric, d_dist);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(e1, 0));
+	std::vector<uint32_t> k(total);
+	std::vector<double> metric(total), dd(total);
+	HIPCHK(hipMemcpy(k.data(), d_k, total * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(metric.data(), d_metric, total * sizeof(double), hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(dd.data(), d_dist, total * sizeof(double), hipMemcpyDeviceToHost));
+	HIPCHK(hipEventElapsedTime(&ms1, e0, e1));
+	if (kernel_ms) *kernel_ms = (double) ms0 + ms1;
+	std::vector<uint64_t> ord;
+	for (uint32_t i = 0; i < n; ++i) {
+		const uint64_t lo = offset[i], hi = offset[i + 1];
+		ord.resize(hi - lo);
+		for (uint64_t p = lo; p < hi; ++p) ord[p - lo] = p;
+		const bool by_metric = radius_of(i) < DBL_MAX;
+		const auto before = [&](uint64_t x, uint64_t y) {
+			if (by_metric && metric[x] != metric[y]) return metric[x] < metric[y];
+			return k[x] < k[y];
+		};
+		if (!std::is_sorted(ord.begin(), ord.end(), before)) std::sort(ord.begin(), ord.end(), before);   /* a search-all row that came in k order is left alone */
+		for (uint64_t q = 0; q < ord.size(); ++q) {
+			pi[lo + q] = i;
+			pk[lo + q] = k[ord[q]];
+			dist[lo + q] = dd[ord[q]];
+		}
+	}
+	return 0;
 }
 
 }  // namespace ntsm_eval_pca

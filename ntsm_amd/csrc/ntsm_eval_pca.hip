@@ -16,7 +16,8 @@
  *
  * Search.  Brute force over all pairs: one workgroup per row i, the row's point read wave-uniformly, lanes over k.  A
  * counting pass, a prefix sum over the rows on the host, then a filling pass that compacts each row in k order (wave
- * ballots + an LDS scan across the four waves).  The host sorts each radius row by evalMetric (stable: ties keep k order).
+ * ballots + an LDS scan across the four waves).  The host half -- offsets, capacity, the order of a radius row by (evalMetric,
+ * k) -- is ntsm_eval_pca.h's finish_candidates, shared with the search against a store.
  * IEEE double with __dadd_rn / __dsub_rn / __dmul_rn: the reference is built without contraction.
  *
  * Scoring.  One lane per listed pair, both rows gathered; the per-site update and the record are ntsm_eval_score.h's, the
@@ -27,15 +28,13 @@
  */
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cfloat>
 #include <cstdint>
 #include <vector>
 
 #include "../../include/ntsm_eval_hip.h"
+#define NTSM_HIP_TAG "ntsm_eval"
 #include "ntsm_eval_pca.h"
 #include "ntsm_eval_score.h"
-#define NTSM_HIP_TAG "ntsm_eval"
 #include "ntsm_hip_scope.h"
 #include "xprec.h"
 
@@ -199,51 +198,11 @@ extern "C" int ntsm_eval_candidates(ntsm_eval_session *h, const double *cloud, u
 	HIPCHK(hipEventRecord(ev[1], 0));
 	std::vector<uint32_t> count(n);
 	HIPCHK(hipMemcpy(count.data(), d_count, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-	float ms0 = 0;
-	HIPCHK(hipEventElapsedTime(&ms0, ev[0], ev[1]));
-	std::vector<uint64_t> offset(n + 1, 0);
-	for (uint32_t i = 0; i < n; ++i) offset[i + 1] = offset[i] + count[i];
-	const uint64_t total = offset[n];
-	*n_pairs = total;
-	if (kernel_ms) *kernel_ms = ms0;
-	if (total > capacity) return NTSM_EVAL_E_CAPACITY;
-	if (total == 0) return 0;
-	uint64_t *d_offset;
-	uint32_t *d_pk;
-	double *d_metric, *d_dist;
-	HIPCHK(b.alloc(&d_offset, n + 1));
-	HIPCHK(b.alloc(&d_pk, total));
-	HIPCHK(b.alloc(&d_metric, total));
-	HIPCHK(b.alloc(&d_dist, total));
-	HIPCHK(hipMemcpy(d_offset, offset.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
-	HIPCHK(hipEventRecord(ev[0], 0));
-	hipLaunchKernelGGL(pca_fill_kernel, dim3(n), dim3(kThreads), 0, 0, d_cloud, d_radius, n, dim, d_offset, d_pk, d_metric, d_dist);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(ev[1], 0));
-	std::vector<uint32_t> k(total);
-	std::vector<double> metric(total), dd(total);
-	HIPCHK(hipMemcpy(k.data(), d_pk, total * sizeof(uint32_t), hipMemcpyDeviceToHost));
-	HIPCHK(hipMemcpy(metric.data(), d_metric, total * sizeof(double), hipMemcpyDeviceToHost));
-	HIPCHK(hipMemcpy(dd.data(), d_dist, total * sizeof(double), hipMemcpyDeviceToHost));
-	float ms1 = 0;
-	HIPCHK(hipEventElapsedTime(&ms1, ev[0], ev[1]));
-	if (kernel_ms) *kernel_ms = (double) ms0 + ms1;
-	/* radius rows in ascending evalMetric (nanoflann sorts its matches); the fill wrote k ascending, so a stable sort
-	 * orders exact ties by k */
-	std::vector<uint64_t> ord;
-	for (uint32_t i = 0; i < n; ++i) {
-		const uint64_t lo = offset[i], hi = offset[i + 1];
-		ord.resize(hi - lo);
-		for (uint64_t p = lo; p < hi; ++p) ord[p - lo] = p;
-		if (radius[i] < DBL_MAX)
-			std::stable_sort(ord.begin(), ord.end(), [&](uint64_t x, uint64_t y) { return metric[x] < metric[y]; });
-		for (uint64_t q = 0; q < ord.size(); ++q) {
-			pi[lo + q] = i;
-			pk[lo + q] = k[ord[q]];
-			dist[lo + q] = dd[ord[q]];
-		}
-	}
-	return 0;
+	return ntsm_eval_pca::finish_candidates(b, ev[0], ev[1], count,
+			[&](const uint64_t *d_offset, uint32_t *d_k, double *d_metric, double *d_dist) {
+				hipLaunchKernelGGL(pca_fill_kernel, dim3(n), dim3(kThreads), 0, 0, d_cloud, d_radius, n, dim, d_offset, d_k, d_metric, d_dist);
+			},
+			[&](uint32_t i) { return radius[i]; }, pi, pk, dist, capacity, n_pairs, kernel_ms);
 }
 
 extern "C" int ntsm_eval_score_pairs(ntsm_eval_session *h, const uint32_t *pi, const uint32_t *pk, uint64_t n_pairs, ntsm_eval_record *out,

@@ -14,13 +14,12 @@
  * ntsm_eval_pairs holds); it is uploaded, transposed and tallied once at open, and a band's rows and columns are offsets
  * into the same arrays.  Streamed: each call uploads and transposes its band's rows into a buffer of their own (pitch =
  * n_rows) and walks the columns row_first ... n_db - 1 in chunks of db_chunk, as ntsm_eval_cross walks a store; the columns
- * before row_first never leave the host.  The chunk rule, the transpose and the tallies are ntsm_eval_chunk.h's.  One
- * stream, no overlap.
+ * before row_first never leave the host.  The chunk rule and the staging of a window (copy, transpose, tallies) are
+ * ntsm_eval_chunk.h's.  One stream, no overlap.
  */
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstdint>
 #include <cstring>
 #include <memory>
@@ -28,14 +27,16 @@
 
 #include "../../include/ntsm_eval_hip.h"
 #include "host/eval_within.hpp"
+#define NTSM_HIP_TAG "ntsm_eval_within"
 #include "ntsm_eval_chunk.h"
 #include "ntsm_eval_score.h"
-#define NTSM_HIP_TAG "ntsm_eval_within"
 #include "ntsm_hip_scope.h"
 
 namespace {
 
 using ntsm_eval_chunk::kThreads;
+using ntsm_eval_chunk::ms_since;
+using ntsm_eval_chunk::wall;
 namespace band = ntsm::eval_within;
 constexpr int kTI = 4;                       /* rows i per workgroup, as in ntsm_eval.hip */
 
@@ -73,9 +74,6 @@ __global__ __launch_bounds__(kThreads) void ntsm_eval_within_kernel(const uint32
 	}
 }
 
-typedef std::chrono::steady_clock wall;
-double ms_since(wall::time_point t) { return std::chrono::duration<double, std::milli>(wall::now() - t).count(); }
-
 /* a window of transposed samples on the device */
 struct Window { const uint32_t *at, *cg; const double *term; uint32_t pitch, first, count; };
 
@@ -94,34 +92,17 @@ int launch_within(const Window &rows, const Window &cols, uint32_t n_db, uint32_
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipEventRecord(e1, 0));
 	HIPCHK(hipEventSynchronize(e1));
-	float f = 0;
-	HIPCHK(hipEventElapsedTime(&f, e0, e1));
-	*ms += f;
-	return 0;
+	return ntsm_eval_chunk::add_interval(e0, e1, ms);
 }
 
-/* samples first ... first + count - 1 of the store: one 2-D copy from the host pitch to d_raw [count][site][2], the transpose
- * to at / cg / term [site][count] and, with d_geno, their tallies; timed into tm (added) */
+/* ntsm_eval_chunk::stage and the wait for it: the pair kernel's launch records the same two events next */
 int stage(const char *db, uint64_t stride, uint32_t first, uint32_t count, uint32_t n_sites, uint32_t min_cov, uint32_t *d_raw, uint32_t *d_at, uint32_t *d_cg,
 		double *d_term, uint32_t *d_geno, hipEvent_t e0, hipEvent_t e1, ntsm_eval_cross_times &tm)
 {
-	const uint64_t row_bytes = 8ull * n_sites;
-	const auto t = wall::now();
-	HIPCHK(hipMemcpy2D(d_raw, row_bytes, db + (uint64_t) first * stride, stride, row_bytes, count, hipMemcpyHostToDevice));
-	tm.upload_ms += ms_since(t);
-	HIPCHK(hipEventRecord(e0, 0));
-	ntsm_eval_chunk::launch_prepare(d_raw, count, n_sites, min_cov, d_at, d_cg, d_term);
-	HIPCHK(hipGetLastError());
-	if (d_geno) {
-		ntsm_eval_chunk::launch_tally(d_raw, count, n_sites, min_cov, d_geno);
-		HIPCHK(hipGetLastError());
-	}
-	HIPCHK(hipEventRecord(e1, 0));
+	const int rc = ntsm_eval_chunk::stage(db, stride, first, count, n_sites, min_cov, d_raw, d_at, d_cg, d_term, d_geno, e0, e1, tm);
+	if (rc) return rc;
 	HIPCHK(hipEventSynchronize(e1));
-	float f = 0;
-	HIPCHK(hipEventElapsedTime(&f, e0, e1));
-	tm.prepare_kernel_ms += f;
-	return 0;
+	return ntsm_eval_chunk::add_interval(e0, e1, &tm.prepare_kernel_ms);
 }
 
 }  // namespace

@@ -7,7 +7,8 @@
 #   ntsm_amd/libntsm_eval_hip.so, build/ntsmEval   all-pairs scoring of ntsmEval (HIP library + CLI mirror), its PCA-guided
 #                                                  search, queries against a cohort store (--pack / --against) and the
 #                                                  PCA-guided search against one (--index / --near), and both runs over
-#                                                  the store's own samples (--within / --within-near)
+#                                                  the store's own samples (--within / --within-near), and one store
+#                                                  against another (--between)
 #   ntsm_amd/libntsm_vcf_hip.so, build/ntsmVCF     multi-sample VCF to PCA matrix + centre file (HIP library + CLI mirror);
 #                                                  with --rotation also the PCA, through libntsm_pca_hip.so
 #                                                  with --counts / --store the genotypes as counts files and cohort-store records
@@ -82,12 +83,15 @@ xlib:
 #   path (ntsm_eval_chunk.h) and the search's steps with the session search (ntsm_eval_pca.h); the index is host code (host/eval_index.hpp)
 # + the pairs inside a store (--within / --within-near): ntsm_eval_within.hip, staging through ntsm_eval_chunk.h too; the band and
 #   pass arithmetic is host code that the library and the CLI share (host/eval_within.hpp)
-EVALSRC := $(CSRC)/ntsm_eval.hip $(CSRC)/ntsm_eval_pca.hip $(CSRC)/ntsm_eval_cross.hip $(CSRC)/ntsm_eval_near.hip $(CSRC)/ntsm_eval_within.hip
+# + one store against another (--between): ntsm_eval_between.hip, the rectangle tile and the staging of a store whose locus table
+#   differs; the locus map and the band rule are host code that the library and the CLI share (host/eval_between.hpp)
+EVALSRC := $(CSRC)/ntsm_eval.hip $(CSRC)/ntsm_eval_pca.hip $(CSRC)/ntsm_eval_cross.hip $(CSRC)/ntsm_eval_near.hip $(CSRC)/ntsm_eval_within.hip \
+           $(CSRC)/ntsm_eval_between.hip
 ntsm_amd/libntsm_eval_hip.so: $(EVALSRC) $(CSRC)/ntsm_eval_score.h $(CSRC)/ntsm_eval_chunk.h $(CSRC)/ntsm_eval_pca.h $(CSRC)/ntsm_hip_scope.h $(CSRC)/xprec.h \
-                              $(HOST)/eval_within.hpp include/ntsm_eval_hip.h
+                              $(HOST)/eval_within.hpp $(HOST)/eval_between.hpp $(HOST)/eval_store.hpp include/ntsm_eval_hip.h
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -shared -o $@ $(EVALSRC)
 
-build/ntsmEval: $(HOST)/ntsm_eval_main.cpp $(HOST)/cli.hpp $(HOST)/eval_store.hpp $(HOST)/eval_index.hpp $(HOST)/eval_within.hpp $(HOST)/crc32_fast.cpp $(HOST)/crc32_fast.hpp \
+build/ntsmEval: $(HOST)/ntsm_eval_main.cpp $(HOST)/cli.hpp $(HOST)/eval_store.hpp $(HOST)/eval_index.hpp $(HOST)/eval_within.hpp $(HOST)/eval_between.hpp $(HOST)/crc32_fast.cpp $(HOST)/crc32_fast.hpp \
                 $(HOST)/gz_stream.hpp $(CSRC)/xprec.h include/ntsm_eval_hip.h ntsm_amd/libntsm_eval_hip.so
 	@mkdir -p build
 	$(CXX) $(CXXFLAGS) -ffp-contract=off -o $@ $(HOST)/ntsm_eval_main.cpp $(HOST)/crc32_fast.cpp -Lntsm_amd -lntsm_eval_hip -lz \
@@ -112,6 +116,13 @@ within_check: build/eval_within_check
 build/eval_within_check: tools/eval_within_check.cpp $(HOST)/eval_within.hpp include/ntsm_eval_hip.h
 	@mkdir -p build
 	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ tools/eval_within_check.cpp
+
+# the locus map and the band rule of --between on their cases likewise (tools/eval_between_check.cpp; not part of `all`)
+between_check: build/eval_between_check
+	build/eval_between_check
+build/eval_between_check: tools/eval_between_check.cpp $(HOST)/eval_between.hpp $(HOST)/eval_store.hpp
+	@mkdir -p build
+	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ tools/eval_between_check.cpp
 
 # the host side of `ntsmCount --cohort` likewise: manifest parser, site lists, and the record builder against counts text +
 # --pack, byte for byte (tools/cohort_count_check.cpp; not part of `all`)
@@ -205,4 +216,4 @@ build/gather_bench: tools/gather_bench.hip
 clean:
 	rm -rf build ntsm_amd/*.so
 	$(MAKE) -C oracle clean
-.PHONY: all oracle_all ref_gpu_binding clean ablation abl_tab tab m12 xlib store_check index_check within_check cohort_check
+.PHONY: all oracle_all ref_gpu_binding clean ablation abl_tab tab m12 xlib store_check index_check within_check between_check cohort_check

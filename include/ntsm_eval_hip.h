@@ -187,6 +187,42 @@ int ntsm_eval_store_score_pairs(int device, const void *db_counts, uint64_t db_s
 		uint32_t min_cov, const uint32_t *pi, const uint32_t *pk, uint64_t n_pairs, uint32_t db_chunk,
 		ntsm_eval_record *out, ntsm_eval_cross_times *times);
 
+/* ---- One cohort store against another (ntsmEval --between; ntsm_amd/csrc/ntsm_eval_between.hip): the
+ * n_a x n_b rectangle of pairs (a sample of store A, a sample of store B) over two mapped stores, in bands of rows of A.  A's
+ * site table is the run's: B's sites are matched to it by site_map.  a_counts / a_stride_bytes and b_counts / b_stride_bytes
+ * as db_counts / db_stride_bytes of ntsm_eval_cross, over n_sites_a and n_sites_b sites; both mappings must outlive the session.
+ *
+ * ntsm_eval_between_open:
+ *   site_map: [n_sites_a]; site_map[s] is the index among B's sites of A's site s, UINT32_MAX where B lacks it (it then counts
+ *     0 / 0 for every sample of B).  NULL = the two tables are identical (n_sites_b == n_sites_a).
+ *   b_chunk: samples of B per pass, 0 = the library's choice.  B is resident when the chunk rule, asked at 24 bytes per sample
+ *     and site of A, answers n_b: it is uploaded, remapped, transposed and tallied once, here.  Otherwise, or when a non-zero
+ *     b_chunk < n_b forces it, it is streamed: every _rows call walks B in chunks of b_chunk.  Device memory is
+ *     O((n_rows + chunk) * n_sites_a + chunk * n_sites_b + n_rows * n_b).
+ *   Returns 0, -2 HIP error, -1 bad argument: a NULL pointer the call needs, a stride below 8 * its n_sites or not a multiple
+ *     of 4, a map entry >= n_sites_b that is not UINT32_MAX, a map that names one site of B twice, no map although
+ *     n_sites_b != n_sites_a.  n_a == 0, n_b == 0 or n_sites_a == 0: a session without device work.
+ * ntsm_eval_between_rows: rows row_first ... row_first + n_rows - 1 of A against every sample of B.
+ *   out: [n_rows][n_b].  out[(a - row_first) * n_b + b] is, bit for bit, the record ntsm_eval_pairs gives for pair (a, n_a + b)
+ *     of the dense concatenation [A; B remapped to A's sites] -- the sample of A is sample 1.
+ *   a_geno (may be NULL): [n_rows][3], b_geno (may be NULL): [n_b][3] = hets, homs, miss (calcHomHetMiss, :742-767) over A's
+ *     n_sites_a sites, as ntsm_eval_cross writes db_geno: a site B lacks is a missing site of its samples.
+ *   times (may be NULL): cross_kernel_ms is the rectangle kernel; chunks counts the chunks of B this call uploaded, so it is 0
+ *     exactly when B is resident; the first call on a resident B also reports the upload and preparation of open.
+ *   Returns 0, -2, -1 (row_first + n_rows > n_a, n_rows == 0, a NULL it needs).  n_a == 0, n_b == 0 or n_sites_a == 0: zeroed
+ *     outputs, no device work and no HIP call; of an A without samples the one range there is, (0, 0), is taken. */
+typedef struct ntsm_eval_between_session ntsm_eval_between_session;
+int ntsm_eval_between_open(int device, const void *a_counts, uint64_t a_stride_bytes, uint32_t n_a, const void *b_counts,
+		uint64_t b_stride_bytes, uint32_t n_b, uint32_t n_sites_a, uint32_t n_sites_b, const uint32_t *site_map,
+		uint32_t min_cov, uint32_t b_chunk, ntsm_eval_between_session **h);
+int ntsm_eval_between_rows(ntsm_eval_between_session *h, uint32_t row_first, uint32_t n_rows, ntsm_eval_record *out,
+		uint32_t *a_geno, uint32_t *b_geno, ntsm_eval_cross_times *times);
+void ntsm_eval_between_close(ntsm_eval_between_session *h);
+/* For measurements and tests only: force the workgroup width (64 or 256) of later _rows calls in this process; 0 = the
+ * library's rule (256 where a launch has more than 256 columns, else 64: DESIGN.md section 9.4 has the measurement).
+ * Returns 0, -1 for another value. */
+int ntsm_eval_between_tune(uint32_t width);
+
 #ifdef __cplusplus
 }
 #endif

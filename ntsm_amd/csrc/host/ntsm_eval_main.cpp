@@ -16,7 +16,9 @@
  *   --within STORE            the all-to-all run over the store's own samples, in bands of rows: ntsm_eval_within_open / _rows
  *   --within-near STORE       the -p run over them through the index: ntsm_eval_cross_candidates without a database side, then
  *                             ntsm_eval_cross for the search-all samples' rows and ntsm_eval_store_score_pairs for the rest
- * --within and --within-near read no counts file.  Not built, and refused: -b (the debug ground-truth mode) and -p without a
+ *   --between STORE_A STORE_B the rows of the all-to-all run over [A's samples, B's samples] that pair a sample of A with one of
+ *                             B, B's loci matched to A's by ID, in bands of rows of A: ntsm_eval_between_open / _rows
+ * --within, --within-near and --between read no counts file.  Not built, and refused: -b (the debug ground-truth mode) and -p without a
  * normalization file (the reference dies in an assert).  Pinned to the reference: stdout equals, byte for byte, that of the
  * unmodified scoring class (oracle/ref_eval_driver.cpp -> oracle/_ref/ref_ntsmEval -t 1) and its recordings,
  * tests/test_eval_reference.py.
@@ -38,6 +40,7 @@
 
 #include "../../../include/ntsm_eval_hip.h"
 #include "cli.hpp"
+#include "eval_between.hpp"
 #include "eval_index.hpp"
 #include "eval_store.hpp"
 #include "eval_within.hpp"
@@ -58,6 +61,9 @@ struct Opt {                                 /* src/Options.h:44-55 */
 	std::string within, withinNear;          /* --within STORE, --within-near STORE: the store's samples against each other */
 	unsigned withinRows = 0;                 /* --within-rows N: rows per band of --within, 0 = the band rule */
 	bool withinRowsGiven = false;
+	std::string between;                     /* --between STORE_A; STORE_B is the one positional argument */
+	unsigned betweenRows = 0;                /* --between-rows N: rows of A per band of --between, 0 = the band rule */
+	bool betweenRowsGiven = false;
 	bool minCovGiven = false, dimGiven = false;
 	bool onlyMerge = false;
 	unsigned dim = 20;                       /* src/Options.h:22, 35-39: the PCA search */
@@ -170,6 +176,17 @@ void printHelpDialog()
 	    "                             come from the index. Not with -p, -n, -b, -e or -o.\n"
 	    "      --within-rows = INT    Rows per band of --within [0: as many as fit in 1 GiB of\n"
 	    "                             records]. For tests and measurements.\n"
+	    "      --between = STORE_A STORE_B\n"
+	    "                             Score every sample of STORE_A against every sample of\n"
+	    "                             STORE_B: the rows of the all-to-all run over A's samples\n"
+	    "                             followed by B's that pair a sample of A (sample1) with\n"
+	    "                             one of B (sample2). STORE_B is the one positional\n"
+	    "                             argument; there are no FILES. B's loci are matched to A's\n"
+	    "                             by ID: a locus B lacks counts 0 / 0, a locus A lacks is\n"
+	    "                             refused. Not with -p, -n, -b, -e or -o.\n"
+	    "      --between-rows = INT   Rows of STORE_A per band of --between [0 is refused;\n"
+	    "                             absent: as many as fit in 1 GiB of records]. For tests\n"
+	    "                             and measurements.\n"
 	    "Not in this build: -b (debug mode of the PCA search); the PCA-guided search (-p)\n"
 	    "against a store (--index and --near are that search); merging (-e) from a store.\n" << std::endl;
 	exit(EXIT_SUCCESS);
@@ -285,6 +302,7 @@ template <typename H, void (*Close)(H *)> struct Handle {   /* closes the librar
 };
 typedef Handle<ntsm_eval_session, ntsm_eval_close> Session;
 typedef Handle<ntsm_eval_within_session, ntsm_eval_within_close> WithinSession;
+typedef Handle<ntsm_eval_between_session, ntsm_eval_between_close> BetweenSession;
 
 typedef std::chrono::steady_clock Clock;
 double msSince(Clock::time_point t) { return std::chrono::duration<double, std::milli>(Clock::now() - t).count(); }
@@ -363,7 +381,7 @@ int scorePCA(const Counts &c, std::vector<Genotype> &g, const Opt &opt, ntsm_eva
 }
 
 constexpr int kOptPack = 1000, kOptAgainst = 1001, kOptIndex = 1002, kOptNear = 1003, kOptWithin = 1004, kOptWithinNear = 1005,
-              kOptWithinRows = 1006;         /* long-only: no letter of the reference's option string is taken */
+              kOptWithinRows = 1006, kOptBetween = 1007, kOptBetweenRows = 1008;   /* long-only: no letter of the reference's option string is taken */
 
 /* --pack STORE FILES...: no GPU */
 int packStore(const Counts &c, const Opt &opt)
@@ -391,12 +409,13 @@ void openStore(const std::string &name, size_t nFiles, const char *does, ntsm::e
 	c->distinct.assign(store.distinct, store.distinct + 2 * (size_t) store.h.n_sites);
 }
 
-/* the store's samples as samples nq ... of a run: names, summaries from the record scalars and the given tallies */
+/* the store's samples as samples nq ... of a run: names, summaries from the record scalars and the given tallies.  The sites
+ * are the run's (c.locus: the table of the store that openStore gave c, which under --between is not this store's). */
 void appendStoreSamples(Counts &c, std::vector<Genotype> &g, const ntsm::eval_store::View &store, const Opt &opt,
 		const std::function<void(uint32_t, Genotype &)> &tallies)
 {
 	namespace st = ntsm::eval_store;
-	const uint32_t nq = (uint32_t) c.files.size(), nd = (uint32_t) store.h.n_samples, m = store.h.n_sites;
+	const uint32_t nq = (uint32_t) c.files.size(), nd = (uint32_t) store.h.n_samples, m = (uint32_t) c.nSites();
 	const uint64_t distinctSum = st::sum_of_pairs(c.distinct.data(), m);
 	g.resize((size_t) nq + nd);
 	c.files.reserve((size_t) nq + nd);
@@ -749,6 +768,73 @@ int searchWithin(Opt &opt, Clock::time_point t0)
 	return routeAndScore(c, g, opt, store, radius, cand, route, mapMs, 0.0, searchMs, t0);
 }
 
+/* --between STORE_A STORE_B: computeScore's rows (:591-624) over [A's samples, B's samples] whose sample 1 is of A and whose
+ * sample 2 is of B, in that run's order, without reading a counts file.  A's locus table and distinct columns play the first
+ * file's part and B's samples are later files of that run: their loci are matched to A's by ID (eval_between.hpp), on the
+ * device.  The rectangle comes in bands of rows of A (that header's rule, or --between-rows), printed band by band; a band's
+ * call brings the tallies of its rows and the first one those of B's samples, taken over A's sites. */
+int scoreBetween(const Opt &opt, const std::string &storeB, Clock::time_point t0)
+{
+	namespace band = ntsm::eval_between;
+	ntsm::eval_store::View a, b;
+	band::LocusMap map;
+	Counts c;
+	const auto tMap = Clock::now();
+	try {
+		openStore(opt.between, 0, "scores", a, &c);
+		openStore(storeB, a.h.n_samples, "scores", b, nullptr);
+		map = band::map_loci(a, b, opt.between, storeB);
+	} catch (const std::exception &e) {
+		ntsm::refuse(e.what());
+	}
+	const double mapMs = msSince(tMap);
+	const uint32_t na = (uint32_t) a.h.n_samples, nb = (uint32_t) b.h.n_samples;
+	if (opt.verbose > 1) std::cerr << "Mapped " << opt.between << " and " << storeB << ". Now comparing " << na << " samples against " << nb << "." << std::endl;
+	std::cerr << "Performing all-to-all score computation.\nSpecify -p (--pca) to enable faster comparisons." << std::endl;
+	BetweenSession session;
+	int rc = ntsm_eval_between_open(opt.device, a.counts(0), a.h.stride, na, b.counts(0), b.h.stride, nb, a.h.n_sites, b.h.n_sites, map.data(), opt.minCov, 0,
+			&session.h);
+	if (rc) return gpuFail("opening the stores", rc);
+	std::vector<Genotype> g;
+	appendStoreSamples(c, g, a, opt, [](uint32_t, Genotype &) {});                /* A's tallies come with their bands */
+	std::vector<uint32_t> genoA, genoB((size_t) nb * 3);
+	std::vector<ntsm_eval_record> rec;
+	ntsm_eval_cross_times sum {};
+	uint32_t bands = 0;
+	double printMs = 0;
+	std::string temp;
+	for (uint32_t first = 0; first < na; ++bands) {
+		const uint32_t rows = opt.betweenRows ? std::min(opt.betweenRows, na - first) : band::band_rows(first, na, nb, band::kBandRecords);
+		rec.resize((size_t) rows * nb);
+		genoA.resize((size_t) rows * 3);
+		ntsm_eval_cross_times times {};
+		rc = ntsm_eval_between_rows(session.h, first, rows, rec.data(), genoA.data(), first == 0 ? genoB.data() : nullptr, &times);
+		if (rc) return gpuFail("scoring the stores", rc);
+		sum.upload_ms += times.upload_ms; sum.prepare_kernel_ms += times.prepare_kernel_ms; sum.cross_kernel_ms += times.cross_kernel_ms;
+		sum.download_ms += times.download_ms; sum.chunks += times.chunks;
+		const auto tPrint = Clock::now();
+		if (first == 0) {
+			appendStoreSamples(c, g, b, opt, [&](uint32_t d, Genotype &s) { s.hets = genoB[3 * d]; s.homs = genoB[3 * d + 1]; s.miss = genoB[3 * d + 2]; });
+			std::cout << kHeader << "\n";
+		}
+		for (uint32_t r = 0; r < rows; ++r) {
+			Genotype &s = g[first + r];
+			s.hets = genoA[3 * r]; s.homs = genoA[3 * r + 1]; s.miss = genoA[3 * r + 2];
+			for (uint32_t d = 0; d < nb; ++d) printRow(temp, c, g, opt, rec[(size_t) r * nb + d], first + r, na + d, "-1");
+		}
+		printMs += msSince(tPrint);
+		first += rows;
+	}
+	std::cout.flush();
+	if (opt.verbose > 1)
+		std::cerr << "store between: loci " << (map.identical ? "identical" : "mapped") << " (" << map.lacking << " of " << a.h.n_sites << " absent from " << storeB
+		          << "), B " << (sum.chunks ? "streamed" : "resident") << ", " << bands << " bands, " << sum.chunks << " chunks, map " << mapMs << " ms, upload "
+		          << sum.upload_ms << " ms, prepare " << sum.prepare_kernel_ms << " ms, pair kernel " << sum.cross_kernel_ms << " ms, download " << sum.download_ms
+		          << " ms, print " << printMs << " ms" << std::endl;
+	printTime(t0);
+	return 0;
+}
+
 /* what no store run goes with */
 void refuseDebugAndMerge(const Opt &opt, const char *mode)
 {
@@ -761,7 +847,7 @@ void refuseDebugAndMerge(const Opt &opt, const char *mode)
 int main(int argc, char **argv)
 {
 	Opt opt;
-	bool die = false, storeMode = false, nearMode = false, withinMode = false;
+	bool die = false, storeMode = false, nearMode = false, withinMode = false, betweenMode = false;
 	static struct option long_options[] = {
 		{ "score_thresh", required_argument, nullptr, 's' }, { "all", no_argument, nullptr, 'a' },
 		{ "min_cov", required_argument, nullptr, 'c' }, { "skew", required_argument, nullptr, 'w' },
@@ -775,7 +861,8 @@ int main(int argc, char **argv)
 		{ "pack", required_argument, nullptr, kOptPack }, { "against", required_argument, nullptr, kOptAgainst },
 		{ "index", required_argument, nullptr, kOptIndex }, { "near", required_argument, nullptr, kOptNear },
 		{ "within", required_argument, nullptr, kOptWithin }, { "within-near", required_argument, nullptr, kOptWithinNear },
-		{ "within-rows", required_argument, nullptr, kOptWithinRows }, { nullptr, 0, nullptr, 0 } };
+		{ "within-rows", required_argument, nullptr, kOptWithinRows }, { "between", required_argument, nullptr, kOptBetween },
+		{ "between-rows", required_argument, nullptr, kOptBetweenRows }, { nullptr, 0, nullptr, 0 } };
 	int ch;
 	while ((ch = getopt_long(argc, argv, "t:vhs:c:m:aw:g:p:n:d:r:e:o1:2:S:l:b:G:", long_options, nullptr)) != -1) {
 		switch (ch) {
@@ -809,17 +896,34 @@ int main(int argc, char **argv)
 			if (!ntsm::read_whole(optarg, opt.withinRows)) ntsm::refuse(std::string("--within-rows takes a number of rows, not ") + optarg);
 			opt.withinRowsGiven = true;
 			break;
+		case kOptBetween: opt.between = optarg; betweenMode = true; break;
+		case kOptBetweenRows:
+			if (!ntsm::read_whole(optarg, opt.betweenRows) || opt.betweenRows == 0)
+				ntsm::refuse(std::string("--between-rows takes a number of rows of at least 1, not ") + optarg);
+			opt.betweenRowsGiven = true;
+			break;
 		case '?': die = true; break;
 		default: break;                              /* m: read by the reference, without effect */
 		}
 	}
 	Counts c;
 	while (optind < argc) c.files.emplace_back(argv[optind++]);
+	const char *sevenRuns = "--pack, --against, --index, --near, --within, --within-near and --between are seven runs: give one of them";
+	if (opt.betweenRowsGiven && !betweenMode) ntsm::refuse("--between-rows sets the bands of --between: give it with --between STORE_A STORE_B");
+	if (betweenMode) {                                   /* --between: every refusal that needs no store, then the run */
+		if (storeMode || nearMode || withinMode) ntsm::refuse(sevenRuns);
+		if (opt.withinRowsGiven) ntsm::refuse("--within-rows sets the bands of --within: the bands of --between are --between-rows");
+		if (c.files.empty()) ntsm::refuse("--between needs the second store: --between STORE_A STORE_B");
+		if (c.files.size() > 1) ntsm::refuse("--between takes STORE_B and no input files: it compares the samples of two stores");
+		if (!opt.pca.empty() || !opt.norm.empty())
+			ntsm::refuse("--between is the all-to-all run and takes no -p and no -n: a PCA-guided search between two stores is not part of this build");
+		refuseDebugAndMerge(opt, "--between");
+		return scoreBetween(opt, c.files[0], Clock::now());
+	}
 	if (withinMode) {                                    /* --within and --within-near: every refusal that needs no store, then the run */
 		const bool near = opt.within.empty();
 		const char *mode = near ? "--within-near" : "--within";
-		if (storeMode || nearMode || (!opt.within.empty() && !opt.withinNear.empty()))
-			ntsm::refuse("--pack, --against, --index, --near, --within and --within-near are six runs: give one of them");
+		if (storeMode || nearMode || (!opt.within.empty() && !opt.withinNear.empty())) ntsm::refuse(sevenRuns);
 		if (!c.files.empty()) ntsm::refuse(std::string(mode) + " takes no input files: it compares the samples of the store with each other");
 		if (!opt.pca.empty() || !opt.norm.empty())
 			ntsm::refuse(near ? "--within-near takes rotation and centre from the store's index: give no -p and no -n"

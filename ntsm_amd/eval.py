@@ -1,5 +1,5 @@
 """ctypes plumbing for include/ntsm_eval_hip.h (all-pairs scoring of ntsmEval on the GPU, its PCA-guided search, queries and
-that search against a cohort store, the pairs inside a store); used by tests and tools.
+that search against a cohort store, the pairs inside a store, one store against another); used by tests and tools.
 Loaded on demand: `import ntsm_amd.eval`.  Fails loudly when libntsm_eval_hip.so has not been built."""
 import ctypes as C
 import os
@@ -374,3 +374,69 @@ def store_score_pairs(db, pi, pk, min_cov=1, db_chunk=0, device=0):
     if rc:
         raise RuntimeError("ntsm_eval_store_score_pairs failed: %d" % rc)
     return out, times
+
+
+# ---- one cohort store against another (ntsmEval --between; include/ntsm_eval_hip.h: ntsm_eval_between_open ... _tune).  Rows are
+# samples of A, columns samples of B; B's sites are matched to A's by site_map.
+LACKS = 0xFFFFFFFF
+lib.ntsm_eval_between_open.restype = C.c_int
+lib.ntsm_eval_between_open.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
+                                       C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+lib.ntsm_eval_between_rows.restype = C.c_int
+lib.ntsm_eval_between_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CrossTimes)]
+lib.ntsm_eval_between_close.restype = None
+lib.ntsm_eval_between_close.argtypes = [C.c_void_p]
+lib.ntsm_eval_between_tune.restype = C.c_int
+lib.ntsm_eval_between_tune.argtypes = [C.c_uint32]
+
+
+def between_tune(width):
+    """Force the workgroup width (64 or 256) of later Between.rows calls in this process; 0 = the library's rule."""
+    rc = lib.ntsm_eval_between_tune(width)
+    if rc:
+        raise ValueError("ntsm_eval_between_tune(%r) failed: %d" % (width, rc))
+
+
+class Between:
+    """The samples of store A against those of store B (ntsm_eval_between_open): a and b are uint32 [n][n_sites][2] or Records,
+    which the session keeps alive.  site_map: uint32 [n_sites_a], the index among B's sites of each site of A, LACKS where B
+    has none; None = identical tables.  b_chunk: 0 = B resident if it fits the device, else streamed; a value below n_b
+    streams B in chunks of it.  A context manager: `with Between(a, b) as s: rec, a_geno, b_geno, times = s.rows(0, s.n_a)`."""
+
+    def __init__(self, a, b, site_map=None, min_cov=1, b_chunk=0, device=0):
+        self.a, self.b = _records(a), _records(b)
+        self.n_a, self.n_b = self.a.n, self.b.n
+        self.site_map = None if site_map is None else np.ascontiguousarray(site_map, dtype=np.uint32)
+        self.h = C.c_void_p()
+        rc = lib.ntsm_eval_between_open(device, self.a.address, self.a.stride, self.n_a, self.b.address, self.b.stride, self.n_b, self.a.m, self.b.m,
+                                        None if self.site_map is None else self.site_map.ctypes.data, min_cov, b_chunk, C.byref(self.h))
+        if rc:
+            raise RuntimeError("ntsm_eval_between_open failed: %d" % rc)
+
+    def rows(self, row_first, n_rows):
+        """Rows row_first ... row_first + n_rows - 1 of A against every sample of B: (records [n_rows, n_b], the record of
+        (a, b) being that of pair (a, n_a + b) of pairs(concatenate([A, B remapped to A's sites])); a_geno [n_rows, 3] and
+        b_geno [n_b, 3] over A's sites; times, a CrossTimes (chunks == 0: B is resident))."""
+        count = n_rows if 0 <= row_first and 0 <= n_rows and row_first + n_rows <= self.n_a else 0
+        out = np.zeros((count, self.n_b), dtype=RECORD)
+        a_geno = np.zeros((count, 3), dtype=np.uint32)
+        b_geno = np.zeros((self.n_b, 3), dtype=np.uint32)
+        times = CrossTimes()
+        rc = lib.ntsm_eval_between_rows(self.h, row_first, n_rows, out.ctypes.data, a_geno.ctypes.data, b_geno.ctypes.data, C.byref(times))
+        if rc:
+            raise RuntimeError("ntsm_eval_between_rows failed: %d" % rc)
+        return out, a_geno, b_geno, times
+
+    def close(self):
+        if self.h:
+            lib.ntsm_eval_between_close(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()

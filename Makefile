@@ -8,7 +8,8 @@
 #                                                  search, queries against a cohort store (--pack / --against) and the
 #                                                  PCA-guided search against one (--index / --near), and both runs over
 #                                                  the store's own samples (--within / --within-near), and one store
-#                                                  against another (--between)
+#                                                  against another (--between) and the PCA-guided search between
+#                                                  two (--between-near)
 #   ntsm_amd/libntsm_vcf_hip.so, build/ntsmVCF     multi-sample VCF to PCA matrix + centre file (HIP library + CLI mirror);
 #                                                  with --rotation also the PCA, through libntsm_pca_hip.so
 #                                                  with --counts / --store the genotypes as counts files and cohort-store records
@@ -85,8 +86,10 @@ xlib:
 #   pass arithmetic is host code that the library and the CLI share (host/eval_within.hpp)
 # + one store against another (--between): ntsm_eval_between.hip, the rectangle tile and the staging of a store whose locus table
 #   differs; the locus map and the band rule are host code that the library and the CLI share (host/eval_between.hpp)
+# + the PCA-guided search between two stores (--between-near): ntsm_eval_between_near.hip, the row remap of a store whose locus
+#   table differs in front of the projection and the listed-pair scorer; its candidate search is ntsm_eval_near.hip's kernels
 EVALSRC := $(CSRC)/ntsm_eval.hip $(CSRC)/ntsm_eval_pca.hip $(CSRC)/ntsm_eval_cross.hip $(CSRC)/ntsm_eval_near.hip $(CSRC)/ntsm_eval_within.hip \
-           $(CSRC)/ntsm_eval_between.hip
+           $(CSRC)/ntsm_eval_between.hip $(CSRC)/ntsm_eval_between_near.hip
 ntsm_amd/libntsm_eval_hip.so: $(EVALSRC) $(CSRC)/ntsm_eval_score.h $(CSRC)/ntsm_eval_chunk.h $(CSRC)/ntsm_eval_pca.h $(CSRC)/ntsm_hip_scope.h $(CSRC)/xprec.h \
                               $(HOST)/eval_within.hpp $(HOST)/eval_between.hpp $(HOST)/eval_store.hpp include/ntsm_eval_hip.h
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -shared -o $@ $(EVALSRC)
@@ -123,6 +126,14 @@ between_check: build/eval_between_check
 build/eval_between_check: tools/eval_between_check.cpp $(HOST)/eval_between.hpp $(HOST)/eval_store.hpp
 	@mkdir -p build
 	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ tools/eval_between_check.cpp
+
+# what --between-near decides on the host likewise: whether B's index serves, the runs of dense rows, and the pass cut over
+# lists that name two stores (tools/eval_between_near_check.cpp; not part of `all`)
+between_near_check: build/eval_between_near_check
+	build/eval_between_near_check
+build/eval_between_near_check: tools/eval_between_near_check.cpp $(HOST)/eval_between.hpp $(HOST)/eval_within.hpp $(HOST)/eval_store.hpp
+	@mkdir -p build
+	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ tools/eval_between_near_check.cpp
 
 # the host side of `ntsmCount --cohort` likewise: manifest parser, site lists, and the record builder against counts text +
 # --pack, byte for byte (tools/cohort_count_check.cpp; not part of `all`)
@@ -216,4 +227,4 @@ build/gather_bench: tools/gather_bench.hip
 clean:
 	rm -rf build ntsm_amd/*.so
 	$(MAKE) -C oracle clean
-.PHONY: all oracle_all ref_gpu_binding clean ablation abl_tab tab m12 xlib store_check index_check within_check between_check cohort_check
+.PHONY: all oracle_all ref_gpu_binding clean ablation abl_tab tab m12 xlib store_check index_check within_check between_check between_near_check cohort_check

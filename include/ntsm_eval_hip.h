@@ -223,6 +223,41 @@ void ntsm_eval_between_close(ntsm_eval_between_session *h);
  * Returns 0, -1 for another value. */
 int ntsm_eval_between_tune(uint32_t width);
 
+/* ---- The PCA-guided search between two cohort stores (ntsmEval --between-near; ntsm_amd/csrc/ntsm_eval_between_near.hip and
+ * ntsm_eval_near.hip): projectPCs (src/CompareCounts.hpp:116-211) of store B over store A's site table,
+ * computeScorePCA's pairs (:285-398) that name one sample of each store, and their records.  Indices follow the concatenation
+ * [A; B] throughout: sample a of A is sample a, sample b of B is sample n_a + b.  Stores, strides and site_map as for
+ * ntsm_eval_between_open, with its validity rules (-1 before any HIP call); times as for ntsm_eval_project_store.
+ *
+ * ntsm_eval_project_store_mapped: cloud [n_b][dim] is, bit for bit, what ntsm_eval_project gives on the dense copy of B
+ *   remapped to A's sites (site s of A = B's site site_map[s], 0 / 0 where B lacks it), and b_geno (may be NULL) [n_b][3] what
+ *   ntsm_eval_cross gives as db_geno on that copy.  norm [n_sites_a], rot [dim][n_sites_a].  A chunk of B arrives by one 2-D
+ *   copy, a kernel remaps its rows to A's sites, and the projection and tally kernels of ntsm_eval_project_store run on the
+ *   remapped rows.  b_chunk: 0 = the chunk rule at 8 * (n_sites_a + n_sites_b) bytes per sample.  site_map == NULL is exactly
+ *   ntsm_eval_project_store.  Returns 0, -1, -2.  n_b == 0 or n_sites_a == 0: zeroed outputs, no device work. */
+int ntsm_eval_project_store_mapped(int device, const void *b_counts, uint64_t b_stride_bytes, uint32_t n_b, uint32_t n_sites_a, uint32_t n_sites_b,
+		const uint32_t *site_map, uint32_t min_cov, const long double *norm, const long double *rot, uint32_t dim, uint32_t b_chunk, double *cloud,
+		uint32_t *b_geno, ntsm_eval_cross_times *times);
+
+/* ntsm_eval_between_candidates: exactly the sublist of ntsm_eval_candidates' output on the concatenated clouds and radii in
+ *   which one index is < n_a and the other >= n_a -- order, indices and dist the same; a pair stands in the row of the sample
+ *   with the larger radius, so pi is often a sample of B.  Samples of B across the lanes, samples of A wave-uniform; the
+ *   columns of A are never walked.  Capacity protocol and return codes as ntsm_eval_candidates.  n_a == 0 or n_b == 0: no
+ *   pairs, no device work. */
+int ntsm_eval_between_candidates(int device, const double *a_cloud, const double *a_radius, uint32_t n_a, const double *b_cloud,
+		const double *b_radius, uint32_t n_b, uint32_t dim, uint32_t *pi, uint32_t *pk, double *dist, uint64_t capacity, uint64_t *n_pairs,
+		double *kernel_ms);
+
+/* ntsm_eval_between_score_pairs: out[p] is, bit for bit, the record ntsm_eval_score_pairs gives for (pi[p], pk[p]) on the dense
+ *   concatenation [A; B remapped to A's sites] (sample pi[p] as sample 1; either orientation).  The list is cut in list order
+ *   into passes of at most `chunk` distinct samples of both stores together (ntsm_amd/csrc/host/eval_within.hpp; 0 = the
+ *   library's choice from free memory); rows of A are copied to their slots as they lie, rows of B through a staging area and
+ *   the remap kernel (without a map, straight in); neighbouring samples are one 2-D copy.  times->chunks = the passes.
+ *   Returns 0, -2, -1 (a bad argument, an index out of range, a pair of two samples of A or of two of B, chunk == 1). */
+int ntsm_eval_between_score_pairs(int device, const void *a_counts, uint64_t a_stride_bytes, uint32_t n_a, const void *b_counts,
+		uint64_t b_stride_bytes, uint32_t n_b, uint32_t n_sites_a, uint32_t n_sites_b, const uint32_t *site_map, uint32_t min_cov, const uint32_t *pi,
+		const uint32_t *pk, uint64_t n_pairs, uint32_t chunk, ntsm_eval_record *out, ntsm_eval_cross_times *times);
+
 #ifdef __cplusplus
 }
 #endif

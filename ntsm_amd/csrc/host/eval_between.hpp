@@ -1,16 +1,20 @@
 /*
  * eval_between.hpp -- the host arithmetic of one cohort store scored against another (ntsmEval --between, DESIGN.md section
  * 9.4), stated once for the device library (ntsm_eval_between.hip) and the CLI: how the loci of store B map onto the site
- * table of store A, what a map handed to the library must satisfy, and how many rows of A a band takes.  Header only, host
- * only, no HIP; tools/eval_between_check.cpp holds it against its cases under the host sanitizers (`make between_check`).
+ * table of store A, what a map handed to the library must satisfy, and how many rows of A a band takes; for the PCA-guided
+ * search between two stores (--between-near, section 9.5) also which rows of A are scored dense and whether B's index serves.
+ * Header only, host only, no HIP; tools/eval_between_check.cpp and tools/eval_between_near_check.cpp hold it against its cases
+ * under the host sanitizers (`make between_check`, `make between_near_check`).
  */
 #ifndef NTSM_EVAL_BETWEEN_HPP
 #define NTSM_EVAL_BETWEEN_HPP
 
 #include <algorithm>
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "eval_store.hpp"
@@ -77,6 +81,41 @@ inline uint32_t band_rows(uint32_t row_first, uint32_t n_a, uint32_t n_b, uint64
 }
 
 constexpr uint64_t kBandRecords = (1ull << 30) / 64;                            /* 1 GiB of 64-byte records */
+
+/* The dense rows of --between-near: a sample of A whose squared radius is not below `all` (DBL_MAX,
+ * "search all") owns its whole row of B.  The runs of consecutive such samples, (first, count) ascending: each goes through
+ * ntsm_eval_between_rows as one range, cut by band_rows where it passes the band rule. */
+inline std::vector<std::pair<uint32_t, uint32_t>> dense_runs(const double *radius, uint32_t n_a, double all)
+{
+	std::vector<std::pair<uint32_t, uint32_t>> runs;
+	for (uint32_t a = 0; a < n_a; ++a) {
+		if (radius[a] < all) continue;
+		if (!runs.empty() && runs.back().first + runs.back().second == a) ++runs.back().second;
+		else runs.emplace_back(a, 1u);
+	}
+	return runs;
+}
+
+/* Where the projections and tallies of B's samples come from in --between-near.  B.pcaidx holds them over B's own site table
+ * and with the matrices of the run that wrote it; they are those of this run exactly when that table is A's and those
+ * matrices are A's index's.  What the caller found out about B's index, and the two indexes' parameters: */
+struct BIndexFacts {
+	bool exists = false;                     /* there is a file B.pcaidx */
+	bool valid = false;                      /* it opens as an index (eval_index.hpp: magic, version, offsets, size) */
+	bool current = false;                    /* it was written for B's loci and holds every sample of B */
+	bool identical_loci = false;             /* LocusMap::identical: B's locus table is A's */
+	uint32_t dim_a = 0, min_cov_a = 0, dim_b = 0, min_cov_b = 0;
+	const char *matrices_a = nullptr, *matrices_b = nullptr;   /* norm and rot as the files hold them */
+	size_t matrix_size_a = 0, matrix_size_b = 0;
+};
+
+/* Does B.pcaidx serve?  Where it does not, B is projected and tallied in the run, through the map, and nothing is written.
+ * Every condition alone says no. */
+inline bool b_index_usable(const BIndexFacts &f)
+{
+	return f.exists && f.valid && f.current && f.identical_loci && f.dim_b == f.dim_a && f.min_cov_b == f.min_cov_a && f.matrices_a && f.matrices_b
+	       && f.matrix_size_b == f.matrix_size_a && memcmp(f.matrices_a, f.matrices_b, f.matrix_size_a) == 0;
+}
 
 }  // namespace eval_between
 }  // namespace ntsm

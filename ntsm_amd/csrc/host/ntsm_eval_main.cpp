@@ -18,7 +18,11 @@
  *                             ntsm_eval_cross for the search-all samples' rows and ntsm_eval_store_score_pairs for the rest
  *   --between STORE_A STORE_B the rows of the all-to-all run over [A's samples, B's samples] that pair a sample of A with one of
  *                             B, B's loci matched to A's by ID, in bands of rows of A: ntsm_eval_between_open / _rows
- * --within, --within-near and --between read no counts file.  Not built, and refused: -b (the debug ground-truth mode) and -p without a
+ *   --between-near STORE_A STORE_B   the rows of the -p run over them that pair a sample of A with one of B, through A's index:
+ *                             B's projections from its own index where that serves, else ntsm_eval_project_store_mapped; then
+ *                             ntsm_eval_between_candidates, ntsm_eval_between_rows for the search-all rows of A and
+ *                             ntsm_eval_between_score_pairs for the rest
+ * --within, --within-near, --between and --between-near read no counts file.  Not built, and refused: -b (the debug ground-truth mode) and -p without a
  * normalization file (the reference dies in an assert).  Pinned to the reference: stdout equals, byte for byte, that of the
  * unmodified scoring class (oracle/ref_eval_driver.cpp -> oracle/_ref/ref_ntsmEval -t 1) and its recordings,
  * tests/test_eval_reference.py.
@@ -64,6 +68,7 @@ struct Opt {                                 /* src/Options.h:44-55 */
 	std::string between;                     /* --between STORE_A; STORE_B is the one positional argument */
 	unsigned betweenRows = 0;                /* --between-rows N: rows of A per band of --between, 0 = the band rule */
 	bool betweenRowsGiven = false;
+	std::string betweenNear;                 /* --between-near STORE_A; STORE_B is the one positional argument */
 	bool minCovGiven = false, dimGiven = false;
 	bool onlyMerge = false;
 	unsigned dim = 20;                       /* src/Options.h:22, 35-39: the PCA search */
@@ -187,6 +192,16 @@ void printHelpDialog()
 	    "      --between-rows = INT   Rows of STORE_A per band of --between [0 is refused;\n"
 	    "                             absent: as many as fit in 1 GiB of records]. For tests\n"
 	    "                             and measurements.\n"
+	    "      --between-near = STORE_A STORE_B\n"
+	    "                             The PCA-guided run (-p) over the samples of STORE_A\n"
+	    "                             followed by those of STORE_B, through STORE_A.pcaidx: the\n"
+	    "                             rows that pair a sample of one store with a sample of the\n"
+	    "                             other. STORE_B is the one positional argument; loci as\n"
+	    "                             for --between. Rotation, centre, -d and -c come from A's\n"
+	    "                             index; B's projections from STORE_B.pcaidx where it was\n"
+	    "                             written over the same loci with the same matrices, else\n"
+	    "                             they are computed in the run. Not with -p, -n, -b, -e or\n"
+	    "                             -o.\n"
 	    "Not in this build: -b (debug mode of the PCA search); the PCA-guided search (-p)\n"
 	    "against a store (--index and --near are that search); merging (-e) from a store.\n" << std::endl;
 	exit(EXIT_SUCCESS);
@@ -381,7 +396,7 @@ int scorePCA(const Counts &c, std::vector<Genotype> &g, const Opt &opt, ntsm_eva
 }
 
 constexpr int kOptPack = 1000, kOptAgainst = 1001, kOptIndex = 1002, kOptNear = 1003, kOptWithin = 1004, kOptWithinNear = 1005,
-              kOptWithinRows = 1006, kOptBetween = 1007, kOptBetweenRows = 1008;   /* long-only: no letter of the reference's option string is taken */
+              kOptWithinRows = 1006, kOptBetween = 1007, kOptBetweenRows = 1008, kOptBetweenNear = 1009;   /* long-only: no letter of the reference's option string is taken */
 
 /* --pack STORE FILES...: no GPU */
 int packStore(const Counts &c, const Opt &opt)
@@ -527,13 +542,12 @@ int buildIndex(const Opt &opt, Clock::time_point t0)
 	return 0;
 }
 
-/* What --near and --within-near open: the store (openStore) and its index, valid, current and written with the run's -c and
- * -d where those are given; -c and -d are then the index's.  Throws the refusal. */
-void openIndexedStore(const std::string &name, Counts &c, ntsm::eval_store::View &store, ntsm::eval_index::View &index, Opt &opt)
+/* What --near, --within-near and --between-near open: the store (openStore) and its index, valid, current and written with the
+ * run's -c and -d where those are given; -c and -d are then the index's.  Throws the refusal. */
+void openIndexOf(const std::string &name, const ntsm::eval_store::View &store, ntsm::eval_index::View &index, Opt &opt)
 {
 	namespace st = ntsm::eval_store;
 	const std::string path = ntsm::eval_index::path_of(name);
-	openStore(name, c.files.size(), "scores", store, &c);
 	struct stat sb;
 	if (stat(path.c_str(), &sb) != 0) throw st::Error("there is no index " + path + ": run --index on the store first");
 	index.open(path);
@@ -544,6 +558,12 @@ void openIndexedStore(const std::string &name, Counts &c, ntsm::eval_store::View
 		throw st::Error("-d " + std::to_string(opt.dim) + ", but " + path + " was written with -d " + std::to_string(index.h.dim));
 	opt.minCov = index.h.min_cov;
 	opt.dim = index.h.dim;
+}
+
+void openIndexedStore(const std::string &name, Counts &c, ntsm::eval_store::View &store, ntsm::eval_index::View &index, Opt &opt)
+{
+	openStore(name, c.files.size(), "scores", store, &c);
+	openIndexOf(name, store, index, opt);
 }
 
 /* a store of one sample has no pair */
@@ -835,6 +855,134 @@ int scoreBetween(const Opt &opt, const std::string &storeB, Clock::time_point t0
 	return 0;
 }
 
+/* --between-near STORE_A STORE_B: computeScorePCA's rows (:285-398) over [A's samples, B's samples] that pair a sample of one
+ * store with a sample of the other, in that run's one-thread order, with the rotation, centre, -d and -c of A's index.  A's
+ * locus table and distinct columns play the first file's part, as in --between.  A's projections and tallies come from its
+ * index; B's from B's index where eval_between.hpp's rule says it serves, else from ntsm_eval_project_store_mapped, and
+ * nothing is written.  A sample of A whose radius is DBL_MAX owns its whole row of B: runs of such rows go through
+ * --between's session (identical records by its contract; B is never gathered for them); every other pair -- those owned by
+ * a search-all sample of B among them, as (b, a) -- goes through ntsm_eval_between_score_pairs. */
+int searchBetween(Opt &opt, const std::string &storeB, Clock::time_point t0)
+{
+	namespace st = ntsm::eval_store;
+	namespace ix = ntsm::eval_index;
+	namespace band = ntsm::eval_between;
+	st::View a, b;
+	ix::View indexA, indexB;
+	band::LocusMap map;
+	band::BIndexFacts facts;
+	Counts c;
+	const auto tMap = Clock::now();
+	try {
+		openStore(opt.betweenNear, 0, "scores", a, &c);
+		openStore(storeB, a.h.n_samples, "scores", b, nullptr);
+		map = band::map_loci(a, b, opt.betweenNear, storeB);
+		try {
+			openIndexOf(opt.betweenNear, a, indexA, opt);
+		} catch (const st::Error &e) {                       /* absent, invalid, stale, or another -c / -d */
+			throw st::Error(std::string(e.what()) + " (--between-near searches through the index of store A: --index " + opt.betweenNear + " -p ROT -n NORM)");
+		}
+		const std::string pathB = ix::path_of(storeB);
+		struct stat sb;
+		facts.exists = stat(pathB.c_str(), &sb) == 0;
+		if (facts.exists)
+			try {
+				indexB.open(pathB);
+				facts.valid = true;
+				indexB.check_store(pathB, b, false);
+				facts.current = true;
+			} catch (const st::Error &) {                    /* B is projected in the run instead */
+			}
+		facts.identical_loci = map.identical;
+		facts.dim_a = indexA.h.dim; facts.min_cov_a = indexA.h.min_cov; facts.matrices_a = indexA.matrices(); facts.matrix_size_a = indexA.matrix_size();
+		if (facts.valid) { facts.dim_b = indexB.h.dim; facts.min_cov_b = indexB.h.min_cov; facts.matrices_b = indexB.matrices(); facts.matrix_size_b = indexB.matrix_size(); }
+	} catch (const std::exception &e) {
+		ntsm::refuse(e.what());
+	}
+	const bool fromIndex = band::b_index_usable(facts);
+	const double mapMs = msSince(tMap);
+	const uint32_t na = (uint32_t) a.h.n_samples, nb = (uint32_t) b.h.n_samples, m = a.h.n_sites, dim = opt.dim;
+	if (opt.verbose > 1)
+		std::cerr << "Mapped " << opt.betweenNear << ", its index and " << storeB << ". Now searching " << na << " samples against " << nb << "." << std::endl;
+
+	auto t = Clock::now();
+	std::vector<Genotype> g;
+	const std::vector<double> cloudA = appendIndexedSamples(c, g, a, indexA, opt);
+	std::vector<double> cloudB;
+	if (fromIndex) cloudB = appendIndexedSamples(c, g, b, indexB, opt);
+	else {
+		std::vector<long double> norm, rot;
+		indexA.matrices(norm, rot);
+		cloudB.assign((size_t) nb * dim, 0.0);
+		std::vector<uint32_t> geno((size_t) nb * 3);
+		const int rc = ntsm_eval_project_store_mapped(opt.device, b.counts(0), b.h.stride, nb, m, b.h.n_sites, map.data(), opt.minCov, norm.data(), rot.data(), dim, 0,
+				cloudB.data(), geno.data(), nullptr);
+		if (rc) return gpuFail("projecting the second store", rc);
+		appendStoreSamples(c, g, b, opt, [&](uint32_t d, Genotype &s) { s.hets = geno[3 * d]; s.homs = geno[3 * d + 1]; s.miss = geno[3 * d + 2]; });
+	}
+	const double projectMs = msSince(t);
+
+	t = Clock::now();
+	const std::vector<double> radius = searchRadii(g, m, opt);
+	if (opt.verbose > 1) std::cerr << "Starting Score Computation with PCA" << std::endl;
+	Candidates cand;
+	int rc = cand.search([&](uint32_t *pi, uint32_t *pk, double *dist, uint64_t capacity, uint64_t *np, double *ms) {
+		return ntsm_eval_between_candidates(opt.device, cloudA.data(), radius.data(), na, cloudB.data(), radius.data() + na, nb, dim, pi, pk, dist, capacity, np, ms);
+	});
+	if (rc) return rc;
+	const double searchMs = msSince(t);
+
+	t = Clock::now();
+	const uint64_t np = cand.pi.size();
+	const std::vector<std::pair<uint32_t, uint32_t>> runs = band::dense_runs(radius.data(), na, DBL_MAX);
+	std::vector<uint32_t> denseRow(na, UINT32_MAX);
+	uint32_t nDense = 0;
+	for (const auto &run : runs)
+		for (uint32_t r = 0; r < run.second; ++r) denseRow[run.first + r] = nDense++;
+	std::vector<ntsm_eval_record> rect((size_t) nDense * nb), rec(np);
+	if (nDense) {
+		BetweenSession session;
+		rc = ntsm_eval_between_open(opt.device, a.counts(0), a.h.stride, na, b.counts(0), b.h.stride, nb, m, b.h.n_sites, map.data(), opt.minCov, 0, &session.h);
+		if (rc) return gpuFail("opening the stores", rc);
+		for (const auto &run : runs)
+			for (uint32_t first = run.first, end = run.first + run.second; first < end;) {
+				const uint32_t rows = band::band_rows(first, end, nb, band::kBandRecords);
+				rc = ntsm_eval_between_rows(session.h, first, rows, rect.data() + (size_t) denseRow[first] * nb, nullptr, nullptr, nullptr);
+				if (rc) return gpuFail("scoring the stores", rc);
+				first += rows;
+			}
+	}
+	std::vector<uint32_t> li, lk;
+	std::vector<uint64_t> where;
+	for (uint64_t p = 0; p < np; ++p) {
+		const uint32_t i = cand.pi[p], k = cand.pk[p];
+		if (i < na && denseRow[i] != UINT32_MAX) rec[p] = rect[(size_t) denseRow[i] * nb + (k - na)];
+		else { li.push_back(i); lk.push_back(k); where.push_back(p); }
+	}
+	std::vector<ntsm_eval_record> listed(li.size());
+	ntsm_eval_cross_times listTimes {};
+	rc = ntsm_eval_between_score_pairs(opt.device, a.counts(0), a.h.stride, na, b.counts(0), b.h.stride, nb, m, b.h.n_sites, map.data(), opt.minCov, li.data(),
+			lk.data(), li.size(), 0, listed.data(), &listTimes);
+	if (rc) return gpuFail("scoring the candidate pairs", rc);
+	for (size_t x = 0; x < where.size(); ++x) rec[where[x]] = listed[x];
+	const double scoreMs = msSince(t);
+
+	const auto tPrint = Clock::now();
+	std::cout << kHeader << "\n";
+	std::string temp;
+	for (uint64_t p = 0; p < np; ++p) printRow(temp, c, g, opt, rec[p], cand.pi[p], cand.pk[p], std::to_string(cand.dist[p]));
+	std::cout.flush();
+	if (opt.verbose > 1)
+		std::cerr << "store between-near: loci " << (map.identical ? "identical" : "mapped") << " (" << map.lacking << " of " << m << " absent from " << storeB
+		          << "), B's projections " << (fromIndex ? "from index" : "projected") << ", " << np << " candidates (" << li.size() << " listed pairs in "
+		          << listTimes.chunks << " passes, " << nDense << " dense rows of A in " << runs.size() << " runs), map " << mapMs << " ms, project " << projectMs
+		          << " ms, search " << searchMs << " ms (kernels " << cand.kernelMs << " ms), score " << scoreMs << " ms (gather " << listTimes.upload_ms
+		          << " ms, remap+terms " << listTimes.prepare_kernel_ms << " ms, list kernel " << listTimes.cross_kernel_ms << " ms), print " << msSince(tPrint)
+		          << " ms" << std::endl;
+	printTime(t0);
+	return 0;
+}
+
 /* what no store run goes with */
 void refuseDebugAndMerge(const Opt &opt, const char *mode)
 {
@@ -847,7 +995,7 @@ void refuseDebugAndMerge(const Opt &opt, const char *mode)
 int main(int argc, char **argv)
 {
 	Opt opt;
-	bool die = false, storeMode = false, nearMode = false, withinMode = false, betweenMode = false;
+	bool die = false, storeMode = false, nearMode = false, withinMode = false, betweenMode = false, betweenNearMode = false;
 	static struct option long_options[] = {
 		{ "score_thresh", required_argument, nullptr, 's' }, { "all", no_argument, nullptr, 'a' },
 		{ "min_cov", required_argument, nullptr, 'c' }, { "skew", required_argument, nullptr, 'w' },
@@ -862,7 +1010,8 @@ int main(int argc, char **argv)
 		{ "index", required_argument, nullptr, kOptIndex }, { "near", required_argument, nullptr, kOptNear },
 		{ "within", required_argument, nullptr, kOptWithin }, { "within-near", required_argument, nullptr, kOptWithinNear },
 		{ "within-rows", required_argument, nullptr, kOptWithinRows }, { "between", required_argument, nullptr, kOptBetween },
-		{ "between-rows", required_argument, nullptr, kOptBetweenRows }, { nullptr, 0, nullptr, 0 } };
+		{ "between-rows", required_argument, nullptr, kOptBetweenRows }, { "between-near", required_argument, nullptr, kOptBetweenNear },
+		{ nullptr, 0, nullptr, 0 } };
 	int ch;
 	while ((ch = getopt_long(argc, argv, "t:vhs:c:m:aw:g:p:n:d:r:e:o1:2:S:l:b:G:", long_options, nullptr)) != -1) {
 		switch (ch) {
@@ -897,6 +1046,7 @@ int main(int argc, char **argv)
 			opt.withinRowsGiven = true;
 			break;
 		case kOptBetween: opt.between = optarg; betweenMode = true; break;
+		case kOptBetweenNear: opt.betweenNear = optarg; betweenNearMode = true; break;
 		case kOptBetweenRows:
 			if (!ntsm::read_whole(optarg, opt.betweenRows) || opt.betweenRows == 0)
 				ntsm::refuse(std::string("--between-rows takes a number of rows of at least 1, not ") + optarg);
@@ -909,6 +1059,17 @@ int main(int argc, char **argv)
 	Counts c;
 	while (optind < argc) c.files.emplace_back(argv[optind++]);
 	const char *sevenRuns = "--pack, --against, --index, --near, --within, --within-near and --between are seven runs: give one of them";
+	if (betweenNearMode) {                               /* --between-near: every refusal that needs no store, then the run */
+		if (storeMode || nearMode || withinMode || betweenMode)
+			ntsm::refuse("--pack, --against, --index, --near, --within, --within-near, --between and --between-near are eight runs: give one of them");
+		if (opt.betweenRowsGiven) ntsm::refuse("--between-rows sets the bands of --between: it does not go with --between-near");
+		if (opt.withinRowsGiven) ntsm::refuse("--within-rows sets the bands of --within: it does not go with --between-near");
+		if (c.files.empty()) ntsm::refuse("--between-near needs the second store: --between-near STORE_A STORE_B");
+		if (c.files.size() > 1) ntsm::refuse("--between-near takes STORE_B and no input files: it searches between the samples of two stores");
+		if (!opt.pca.empty() || !opt.norm.empty()) ntsm::refuse("--between-near takes rotation and centre from the store's index: give no -p and no -n");
+		refuseDebugAndMerge(opt, "--between-near");
+		return searchBetween(opt, c.files[0], Clock::now());
+	}
 	if (opt.betweenRowsGiven && !betweenMode) ntsm::refuse("--between-rows sets the bands of --between: give it with --between STORE_A STORE_B");
 	if (betweenMode) {                                   /* --between: every refusal that needs no store, then the run */
 		if (storeMode || nearMode || withinMode) ntsm::refuse(sevenRuns);
@@ -916,7 +1077,8 @@ int main(int argc, char **argv)
 		if (c.files.empty()) ntsm::refuse("--between needs the second store: --between STORE_A STORE_B");
 		if (c.files.size() > 1) ntsm::refuse("--between takes STORE_B and no input files: it compares the samples of two stores");
 		if (!opt.pca.empty() || !opt.norm.empty())
-			ntsm::refuse("--between is the all-to-all run and takes no -p and no -n: a PCA-guided search between two stores is not part of this build");
+			ntsm::refuse("--between is the all-to-all run and takes no -p and no -n: a PCA-guided search between two stores is not part of this build "
+			             "under this flag; it is --between-near STORE_A STORE_B");
 		refuseDebugAndMerge(opt, "--between");
 		return scoreBetween(opt, c.files[0], Clock::now());
 	}

@@ -18,7 +18,9 @@
  * counting pass, the prefix sum over the rows on the host, a filling pass: a query row is filled through one wave-aggregated
  * atomic per wave and query (its order does not matter: the host sorts), a database row by its own lane, queries ascending.
  * The host half is ntsm_eval_pca.h's finish_candidates: a radius row by (evalMetric, k) and a search-all row by k, which is
- * the session search's order.  The grid is (columns / 256): never one workgroup per database row.
+ * the session search's order.  The grid is (columns / 256): never one workgroup per database row.  The search between two
+ * stores (ntsm_eval_between_candidates; ntsmEval --between-near) is the same two kernels launched over
+ * the database columns alone, store A in the queries' place: no pair of two samples of A is ever evaluated.
  *
  * Scoring of listed pairs.  Every pair has a query in it, so it names at most one database sample.  The distinct database
  * samples of the list are copied row by row from the mapped store, at most `chunk` per pass, to dense rows behind the
@@ -74,10 +76,11 @@ __device__ inline uint32_t near_decide(const Columns &c, uint32_t q, uint32_t k,
 	return bits;
 }
 
-/* pass 1: q_count[q] += the pairs of row q among this workgroup's columns; db_count[d] = the pairs of row n_q + d */
-__global__ __launch_bounds__(kThreads) void near_count_kernel(Columns c, uint32_t *__restrict__ q_count, uint32_t *__restrict__ db_count)
+/* Both passes walk the columns from k_first on: 0 for the whole concatenation, n_q for the database columns alone.
+ * pass 1: q_count[q] += the pairs of row q among this workgroup's columns; db_count[d] = the pairs of row n_q + d */
+__global__ __launch_bounds__(kThreads) void near_count_kernel(Columns c, uint32_t k_first, uint32_t *__restrict__ q_count, uint32_t *__restrict__ db_count)
 {
-	const uint32_t n = c.n_q + c.n_db, k = blockIdx.x * kThreads + threadIdx.x;
+	const uint32_t n = c.n_q + c.n_db, k = k_first + blockIdx.x * kThreads + threadIdx.x;
 	const bool live = k < n;
 	const uint32_t kc = live ? k : n - 1;
 	const double rk = c.radius(kc);
@@ -94,10 +97,10 @@ __global__ __launch_bounds__(kThreads) void near_count_kernel(Columns c, uint32_
 }
 
 /* pass 2: row q's pairs from q_offset[q] on through q_cursor[q] (any order), row n_q + d's at db_offset[d], queries ascending */
-__global__ __launch_bounds__(kThreads) void near_fill_kernel(Columns c, const uint64_t *__restrict__ q_offset, uint32_t *__restrict__ q_cursor,
+__global__ __launch_bounds__(kThreads) void near_fill_kernel(Columns c, uint32_t k_first, const uint64_t *__restrict__ q_offset, uint32_t *__restrict__ q_cursor,
 		const uint64_t *__restrict__ db_offset, uint32_t *__restrict__ other, double *__restrict__ metric, double *__restrict__ dist)
 {
-	const uint32_t n = c.n_q + c.n_db, k = blockIdx.x * kThreads + threadIdx.x, lane = threadIdx.x & 63;
+	const uint32_t n = c.n_q + c.n_db, k = k_first + blockIdx.x * kThreads + threadIdx.x, lane = threadIdx.x & 63;
 	const bool live = k < n;
 	const uint32_t kc = live ? k : n - 1;
 	const double rk = c.radius(kc);
@@ -236,9 +239,12 @@ extern "C" int ntsm_eval_project_store(int device, const void *db_counts, uint64
 	return 0;
 }
 
-extern "C" int ntsm_eval_cross_candidates(int device, const double *q_cloud, const double *q_radius, uint32_t n_q, const double *db_cloud,
-		const double *db_radius, uint32_t n_db, uint32_t dim, uint32_t *pi, uint32_t *pk, double *dist, uint64_t capacity, uint64_t *n_pairs,
-		double *kernel_ms)
+namespace {
+
+/* The search of both entry points below.  `rectangle`: only the database columns are walked, so a pair is listed exactly
+ * when one of its samples is a query and the other a database sample; otherwise all columns, query-query pairs included. */
+int search_columns(int device, const double *q_cloud, const double *q_radius, uint32_t n_q, const double *db_cloud, const double *db_radius, uint32_t n_db,
+		uint32_t dim, bool rectangle, uint32_t *pi, uint32_t *pk, double *dist, uint64_t capacity, uint64_t *n_pairs, double *kernel_ms)
 {
 	if (kernel_ms) *kernel_ms = 0;
 	if (!n_pairs || (n_q && (!q_radius || (dim && !q_cloud))) || (n_db && (!db_radius || (dim && !db_cloud))) || (capacity && (!pi || !pk || !dist)))
@@ -247,7 +253,7 @@ extern "C" int ntsm_eval_cross_candidates(int device, const double *q_cloud, con
 	const uint64_t n64 = (uint64_t) n_q + n_db;
 	if (n64 > UINT32_MAX) return -1;
 	const uint32_t n = (uint32_t) n64;
-	if (n_q == 0 || n < 2) return 0;                                             /* no query: no pair has one */
+	if (n_q == 0 || n < 2 || (rectangle && n_db == 0)) return 0;                 /* no query: no pair has one; no database sample: nor has the rectangle */
 	HIPCHK(hipSetDevice(device));
 	ntsm_hip::Buffers b;
 	double *d_qc, *d_qr, *d_dc, *d_dr;
@@ -264,11 +270,12 @@ extern "C" int ntsm_eval_cross_candidates(int device, const double *q_cloud, con
 	if (n_db) HIPCHK(hipMemcpy(d_dr, db_radius, (uint64_t) n_db * sizeof(double), hipMemcpyHostToDevice));
 	HIPCHK(hipMemset(d_qcount, 0, 2ull * n_q * sizeof(uint32_t)));
 	const Columns cols { d_qc, d_qr, d_dc, d_dr, n_q, n_db, dim };
-	const dim3 grid((n + kThreads - 1) / kThreads);
+	const uint32_t k_first = rectangle ? n_q : 0;
+	const dim3 grid((n - k_first + kThreads - 1) / kThreads);
 	ntsm_hip::Events<2> ev;
 	HIPCHK(ev.create());
 	HIPCHK(hipEventRecord(ev[0], 0));
-	hipLaunchKernelGGL(near_count_kernel, grid, dim3(kThreads), 0, 0, cols, d_qcount, d_dcount);
+	hipLaunchKernelGGL(near_count_kernel, grid, dim3(kThreads), 0, 0, cols, k_first, d_qcount, d_dcount);
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipEventRecord(ev[1], 0));
 	std::vector<uint32_t> count(n, 0);
@@ -276,9 +283,27 @@ extern "C" int ntsm_eval_cross_candidates(int device, const double *q_cloud, con
 	if (n_db) HIPCHK(hipMemcpy(count.data() + n_q, d_dcount, (uint64_t) n_db * sizeof(uint32_t), hipMemcpyDeviceToHost));
 	return ntsm_eval_pca::finish_candidates(b, ev[0], ev[1], count,
 			[&](const uint64_t *d_offset, uint32_t *d_k, double *d_metric, double *d_dist) {
-				hipLaunchKernelGGL(near_fill_kernel, grid, dim3(kThreads), 0, 0, cols, d_offset, d_qcount + n_q, d_offset + n_q, d_k, d_metric, d_dist);
+				hipLaunchKernelGGL(near_fill_kernel, grid, dim3(kThreads), 0, 0, cols, k_first, d_offset, d_qcount + n_q, d_offset + n_q, d_k, d_metric, d_dist);
 			},
 			[&](uint32_t i) { return i < n_q ? q_radius[i] : db_radius[i - n_q]; }, pi, pk, dist, capacity, n_pairs, kernel_ms);
+}
+
+}  // namespace
+
+extern "C" int ntsm_eval_cross_candidates(int device, const double *q_cloud, const double *q_radius, uint32_t n_q, const double *db_cloud,
+		const double *db_radius, uint32_t n_db, uint32_t dim, uint32_t *pi, uint32_t *pk, double *dist, uint64_t capacity, uint64_t *n_pairs,
+		double *kernel_ms)
+{
+	return search_columns(device, q_cloud, q_radius, n_q, db_cloud, db_radius, n_db, dim, false, pi, pk, dist, capacity, n_pairs, kernel_ms);
+}
+
+/* The search between two stores (ntsmEval --between-near): store A's samples are the wave-uniform side, store B's run across
+ * the lanes, and the columns of A are never walked -- their (n_a)^2 / 2 metric evaluations would all be thrown away. */
+extern "C" int ntsm_eval_between_candidates(int device, const double *a_cloud, const double *a_radius, uint32_t n_a, const double *b_cloud,
+		const double *b_radius, uint32_t n_b, uint32_t dim, uint32_t *pi, uint32_t *pk, double *dist, uint64_t capacity, uint64_t *n_pairs,
+		double *kernel_ms)
+{
+	return search_columns(device, a_cloud, a_radius, n_a, b_cloud, b_radius, n_b, dim, true, pi, pk, dist, capacity, n_pairs, kernel_ms);
 }
 
 extern "C" int ntsm_eval_cross_score_pairs(int device, const uint32_t *q_counts, uint32_t n_q, const void *db_counts, uint64_t db_stride_bytes,

@@ -1,5 +1,6 @@
 """ctypes plumbing for include/ntsm_eval_hip.h (all-pairs scoring of ntsmEval on the GPU, its PCA-guided search, queries and
-that search against a cohort store, the pairs inside a store, one store against another); used by tests and tools.
+that search against a cohort store, the pairs inside a store, one store against another and the search between two); used by
+tests and tools.
 Loaded on demand: `import ntsm_amd.eval`.  Fails loudly when libntsm_eval_hip.so has not been built."""
 import ctypes as C
 import os
@@ -440,3 +441,89 @@ class Between:
 
     def __del__(self):
         self.close()
+
+
+# ---- the PCA-guided search between two stores (ntsmEval --between-near; ntsm_eval_project_store_mapped, ntsm_eval_between_candidates,
+# ntsm_eval_between_score_pairs).  Indices follow the concatenation [A; B]: sample b of B is sample n_a + b.
+lib.ntsm_eval_project_store_mapped.restype = C.c_int
+lib.ntsm_eval_project_store_mapped.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
+                                               C.POINTER(C.c_longdouble), C.POINTER(C.c_longdouble), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                               C.POINTER(CrossTimes)]
+lib.ntsm_eval_between_candidates.restype = C.c_int
+lib.ntsm_eval_between_candidates.argtypes = lib.ntsm_eval_cross_candidates.argtypes
+lib.ntsm_eval_between_score_pairs.restype = C.c_int
+lib.ntsm_eval_between_score_pairs.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
+                                              C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.POINTER(CrossTimes)]
+
+
+def _site_map(site_map):
+    return None if site_map is None else np.ascontiguousarray(site_map, dtype=np.uint32)
+
+
+def project_store_mapped(b, n_sites_a, site_map, norm, rot, min_cov=1, b_chunk=0, device=0):
+    """The PCA-guided search between two stores (ntsmEval --between-near): b is uint32 [n_b][n_sites_b][2] or Records; site_map
+    as Between's (None = identical tables: project_store); norm [n_sites_a], rot [dim][n_sites_a].  Returns (cloud [n_b][dim]
+    -- the bits of project() on B remapped to A's sites --, geno [n_b][3] as cross()'s on that copy, times)."""
+    r = _records(b)
+    site_map = _site_map(site_map)
+    norm = np.ascontiguousarray(norm, dtype=np.longdouble)
+    rot = np.ascontiguousarray(rot, dtype=np.longdouble).reshape(-1, n_sites_a) if n_sites_a else np.zeros((np.shape(rot)[0], 0), dtype=np.longdouble)
+    dim = rot.shape[0]
+    cloud = np.zeros((r.n, dim), dtype=np.float64)
+    geno = np.zeros((r.n, 3), dtype=np.uint32)
+    times = CrossTimes()
+    rc = lib.ntsm_eval_project_store_mapped(device, r.address, r.stride, r.n, n_sites_a, r.m, None if site_map is None else site_map.ctypes.data, min_cov,
+                                            _ld_ptr(norm), _ld_ptr(rot), dim, b_chunk, cloud.ctypes.data, geno.ctypes.data, C.byref(times))
+    if rc:
+        raise RuntimeError("ntsm_eval_project_store_mapped failed: %d" % rc)
+    return cloud, geno, times
+
+
+def between_candidates(a_cloud, a_radius, b_cloud, b_radius, capacity=None, device=0):
+    """The pairs of candidates() on the concatenated clouds and radii [A; B] that name one sample of each store, in its order:
+    (pi, pk, calcDistance, kernel ms).  capacity as Session.candidates."""
+    a_cloud = np.ascontiguousarray(a_cloud, dtype=np.float64)
+    b_cloud = np.ascontiguousarray(b_cloud, dtype=np.float64)
+    a_radius = np.ascontiguousarray(a_radius, dtype=np.float64)
+    b_radius = np.ascontiguousarray(b_radius, dtype=np.float64)
+    n_a, n_b = len(a_radius), len(b_radius)
+    dim = a_cloud.shape[1] if a_cloud.ndim == 2 else 0
+    if n_a and n_b and (b_cloud.ndim != 2 or b_cloud.shape[1] != dim):
+        raise ValueError("between_candidates: both clouds are [samples][dim]")
+    ms, n = C.c_double(), C.c_uint64()
+
+    def call(pi, pk, dist, cap):
+        return lib.ntsm_eval_between_candidates(device, a_cloud.ctypes.data, a_radius.ctypes.data, n_a, b_cloud.ctypes.data, b_radius.ctypes.data, n_b,
+                                                dim, pi, pk, dist, cap, C.byref(n), C.byref(ms))
+    if capacity is None:
+        rc = call(None, None, None, 0)
+        if rc not in (0, E_CAPACITY):
+            raise RuntimeError("ntsm_eval_between_candidates failed: %d" % rc)
+        capacity = n.value
+    pi, pk = np.zeros(capacity, dtype=np.uint32), np.zeros(capacity, dtype=np.uint32)
+    dist = np.zeros(capacity, dtype=np.float64)
+    rc = call(pi.ctypes.data, pk.ctypes.data, dist.ctypes.data, capacity)
+    if rc == E_CAPACITY:
+        raise ValueError("capacity %d < %d candidate pairs" % (capacity, n.value), n.value)
+    if rc:
+        raise RuntimeError("ntsm_eval_between_candidates failed: %d" % rc)
+    k = n.value
+    return pi[:k], pk[:k], dist[:k], ms.value
+
+
+def between_score_pairs(a, b, pi, pk, site_map=None, min_cov=1, chunk=0, device=0):
+    """a, b: [n][n_sites][2] or Records; pi, pk in the numbering of [A; B], one sample of each store in every pair; site_map as
+    Between's.  Returns (records, sample pi as sample 1 -- the bits of score_pairs on [A; B remapped to A's sites] --, times;
+    times.chunks = the passes)."""
+    ra, rb = _records(a), _records(b)
+    site_map = _site_map(site_map)
+    pi = np.ascontiguousarray(pi, dtype=np.uint32)
+    pk = np.ascontiguousarray(pk, dtype=np.uint32)
+    out = np.zeros(len(pi), dtype=RECORD)
+    times = CrossTimes()
+    rc = lib.ntsm_eval_between_score_pairs(device, ra.address, ra.stride, ra.n, rb.address, rb.stride, rb.n, ra.m, rb.m,
+                                           None if site_map is None else site_map.ctypes.data, min_cov, pi.ctypes.data, pk.ctypes.data, len(pi), chunk,
+                                           out.ctypes.data, C.byref(times))
+    if rc:
+        raise RuntimeError("ntsm_eval_between_score_pairs failed: %d" % rc)
+    return out, times

@@ -158,7 +158,11 @@ build/ntsmVCF: $(VCFSRC) $(HOST)/ntsm_vcf_main.cpp $(HOSTHDR) include/ntsm_vcf_h
 
 # ntsmPCA (NAME_matrix.tsv -> NAME_rotationalMatrix.tsv, NAME_components.tsv): own library, own CLI.  rocSOLVER is bound with
 # dlopen on first use (the rpath lets a bare `librocsolver.so.0` resolve), so nothing links against it
-ntsm_amd/libntsm_pca_hip.so: $(CSRC)/ntsm_pca.hip $(CSRC)/ntsm_hip_scope.h include/ntsm_pca_hip.h
+# + the matrix from a cohort store (ntsmPCA --store): the genotype step shares the chunk rule and the 2-D copy with the store
+#   paths of ntsmEval (ntsm_eval_chunk.h), the genotype code with its projection (ntsm_eval_pca.h) and the centre's text with
+#   ntsmVCF (host/pca_text.hpp)
+ntsm_amd/libntsm_pca_hip.so: $(CSRC)/ntsm_pca.hip $(CSRC)/ntsm_hip_scope.h include/ntsm_pca_hip.h $(CSRC)/ntsm_eval_chunk.h $(CSRC)/ntsm_eval_pca.h \
+                             $(CSRC)/ntsm_eval_score.h $(CSRC)/xprec.h include/ntsm_eval_hip.h $(HOST)/pca_text.hpp $(HOST)/cli.hpp $(HOST)/gz_stream.hpp
 	$(HIPCC) $(HIPFLAGS) -fvisibility=hidden -ffp-contract=off -shared -o $@ $(CSRC)/ntsm_pca.hip -ldl -Wl,-rpath,/opt/rocm/lib
 
 PCASRC := $(HOST)/inflate.cpp $(HOST)/inflate_spec.cpp $(HOST)/gz_stream.cpp $(HOST)/gz_parallel.cpp $(HOST)/crc32_fast.cpp

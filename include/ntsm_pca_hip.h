@@ -19,6 +19,9 @@
  * The matrix may also be given as the 16-bit cells of ntsm_vcf_run (include/ntsm_vcf_hip.h) with the value of every cell
  * code, the form `ntsmVCF --rotation` hands over: the *_cells entry points below.  The doubles then exist on the device
  * only: step (0), ntsm_pca_expand, writes the whole padded buffer from the cells, and steps (1) to (4) follow unchanged.
+ *
+ * Or as the first n records of a cohort store (`ntsmPCA --store`): the *_store entry points at the
+ * end.  The cells are then made on the device from the store's counts, chunk by chunk, and never cross the host.
  */
 #ifndef NTSM_PCA_HIP_H
 #define NTSM_PCA_HIP_H
@@ -98,6 +101,45 @@ int ntsm_pca_gram_cells(int device, uint64_t p, uint32_t n, const uint16_t *cell
 int ntsm_pca_run_cells(int device, uint64_t p, uint32_t n, const uint16_t *cells, const double *value,
 		const double *row_fill, uint64_t first_undef_cell, uint32_t d, uint32_t split,
 		double *eigval, double *rot, double *comp, uint32_t *bad_component, ntsm_pca_times *times, double *expand_ms);
+
+/*
+ * The matrix from a cohort store: the genotypes that ntsmEval's projection derives from the counts
+ * of the store's samples, with every site centred over the samples that call it.
+ *
+ * db_counts: host; the counts of sample j, uint32 [n_sites][2] (AT, CG), at db_counts + j * db_stride_bytes -- a mapped
+ *            store's records (host/eval_store.hpp), or any buffer of that pitch.  db_stride_bytes >= 8 * n_sites, a
+ *            multiple of 4.
+ * n:         samples taken, the first n records.  p of the entry points above is n_sites.
+ * min_cov:   a count at or below it reads as 0 (ntsmEval -c).
+ * db_chunk:  samples uploaded per pass; 0 = as many as fit in half of the free device memory.
+ * The cell of (site s, sample j) is code + 1 with code the genotype code of the two counts (0 / 1 / 2 for genotype
+ * 0 / 0.5 / 1), and 0 where the sample does not call the site.  tallies[s] = { n_half, n_one, n_called }: the samples of
+ * genotype 0.5, of genotype 1, and all that call the site.  The value table of the cells is value[0][1..3] = { 0, 0.5, 1 },
+ * first_undef_cell = ~0, and row_fill[s] is what ntsmPCA reads back from the text of (n_one + 0.5 n_half) / n_called as
+ * NAME_center.txt holds it ("0" where n_called = 0): host/pca_text.hpp, store_centre_text.
+ *
+ * Contract: ntsm_pca_run_store(...) returns the same bits as ntsm_pca_run_cells on the cells ntsm_pca_store_cells returned
+ * with that table and those fills -- for the same `split`, in the same process, for every db_chunk.  Cells and tallies
+ * are integers (the tallies summed with integer atomics), so they do not depend on db_chunk or on the order of anything.
+ * Argument checks and return codes are those of the entry points above.
+ */
+typedef struct ntsm_pca_store_times {   /* milliseconds */
+	double upload_ms;                    /* the 2-D copies of the chunks' counts, wall clock */
+	double genotype_ms;                  /* the genotype kernel over all chunks, HIP events */
+	double fill_ms;                      /* tallies down, centre texts and fills on the host, fills and value table up: wall clock */
+	double expand_ms;                    /* ntsm_pca_expand, HIP events (ntsm_pca_run_store only) */
+	uint32_t chunks, chunk;              /* passes, and samples per pass */
+} ntsm_pca_store_times;
+
+/* The genotype step on its own.  cells: host out [n_sites][n] row-major; tallies: host out [n_sites][3]. */
+int ntsm_pca_store_cells(int device, const void *db_counts, uint64_t db_stride_bytes, uint32_t n, uint64_t n_sites, uint32_t min_cov,
+		uint32_t db_chunk, uint16_t *cells, uint32_t *tallies, ntsm_pca_store_times *store_times);
+
+/* The whole PCA of a store's first n samples; eigval, rot, comp, bad_component, times as ntsm_pca_run.  times->upload_ms is
+ * store_times->upload_ms.  tallies: host out [n_sites][3]; store_times: may be NULL. */
+int ntsm_pca_run_store(int device, const void *db_counts, uint64_t db_stride_bytes, uint32_t n, uint64_t n_sites, uint32_t min_cov,
+		uint32_t db_chunk, uint32_t d, uint32_t split, double *eigval, double *rot, double *comp, uint32_t *tallies,
+		uint32_t *bad_component, ntsm_pca_times *times, ntsm_pca_store_times *store_times);
 
 #ifdef __cplusplus
 }

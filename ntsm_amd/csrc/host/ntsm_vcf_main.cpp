@@ -287,14 +287,7 @@ std::string cell_text(unsigned r, unsigned v, int prec)     /* a defined cell: i
 	return std::string(b);
 }
 
-std::string centre_text(double sum, uint32_t n_samples)     /* a row's centre, also the text of its undefined cells */
-{
-	char b[128];
-	const long double sizeFloat = n_samples;
-	const long double center = sum / sizeFloat;
-	snprintf(b, sizeof b, "%.19Lg", center);
-	return std::string(b);
-}
+using ntsm::centre_text;                                    /* a row's centre, also the text of its undefined cells: pca_text.hpp */
 
 constexpr int kShortDigits = 6, kLongDigits = 19;           /* the stream's precision up to / after the first undefined cell */
 

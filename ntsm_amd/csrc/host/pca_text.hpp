@@ -34,6 +34,33 @@ inline bool parse_cell(const char *b, const char *e, double &x)
 	return r.ec == std::errc() && r.ptr == e && std::isfinite(x);
 }
 
+/* a row's centre as NAME_center.txt holds it, also the text of the row's undefined cells in NAME_matrix.tsv: the long double
+ * quotient printed %.19Lg (printNormMatrix, MultiCount.hpp:148-201) */
+inline std::string centre_text(double sum, uint32_t n_samples)
+{
+	char b[128];
+	const long double sizeFloat = n_samples;
+	const long double center = sum / sizeFloat;
+	snprintf(b, sizeof b, "%.19Lg", center);
+	return std::string(b);
+}
+
+/* The centre of a site of a cohort store from its tallies: n_half samples of genotype 0.5, n_one of
+ * genotype 1 among the n_called that call the site.  n_one + 0.5 n_half is exact in a double; a site nobody calls is "0". */
+inline std::string store_centre_text(uint32_t n_half, uint32_t n_one, uint32_t n_called)
+{
+	return n_called ? centre_text((double) n_one + 0.5 * (double) n_half, n_called) : std::string("0");
+}
+
+/* the value of that site's missing cells in the training matrix: what ntsmPCA would read back from the text */
+inline double store_centre_value(uint32_t n_half, uint32_t n_one, uint32_t n_called)
+{
+	const std::string text = store_centre_text(n_half, n_one, n_called);
+	double x = 0.0;
+	(void) parse_cell(text.data(), text.data() + text.size(), x);                  /* %.19Lg of a quotient in [0, 1] always parses */
+	return x;
+}
+
 /* the sample names of the header line [b, e) (no '\n'): alleleID <TAB> sample ... */
 inline std::vector<Name> header_samples(const char *b, const char *e)
 {

@@ -7,6 +7,9 @@
  *   ntsm_pca_expand        the cells of ntsm_vcf_run into that buffer, padding included: a wave per row, one 16-byte store per
  *                          lane (two samples), the lanes side by side along the sample dimension; a cell's value from a table
  *                          by its code
+ *   ntsm_pca_store_genotype  the cells from a chunk of a cohort store instead: counts [sample][site][2]
+ *                          read along the sites, the genotype code of each pair, a byte per cell transposed through LDS,
+ *                          16-bit cells written along the samples, the per-site tallies of the called genotypes added
  *   ntsm_pca_centre        one workgroup per site: the row sum in a fixed order (per-thread strided partial sums, then a
  *                          binary tree in LDS), mean = sum / n, and the row rewritten as Ac (padding stays 0)
  *   ntsm_pca_gram_tiles    the hot path: one workgroup per (upper 128 x 128 tile, piece of the site dimension); 4 waves,
@@ -32,6 +35,9 @@
 #define NTSM_HIP_TAG "ntsm_pca"
 #define NTSM_HIP_FAIL NTSM_PCA_E_HIP
 #include "ntsm_hip_scope.h"
+#include "ntsm_eval_chunk.h"                 /* a chunk of a cohort store on the device: the chunk rule and the 2-D copy */
+#include "ntsm_eval_pca.h"                   /* genotype_code */
+#include "host/pca_text.hpp"                 /* store_centre_value: a site's centre as its text reads back */
 
 namespace {
 
@@ -47,9 +53,10 @@ typedef double v4d __attribute__((ext_vector_type(4)));
  * the samples 2 l and 2 l + 1 of every 128-sample piece, so each store instruction writes 1 KiB of the row, 16 bytes per lane
  * (ld is a multiple of 128), and nothing but the row's base is computed in 64 bits.  A live cell is
  * value[lin > first_undef][code] with lin = row * n + sample, row_fill[row] for code 0; padding is zero.  Rows of cells are
- * 2 n bytes apart, so the two codes are loaded as two 16-bit values. */
+ * cell_ld cells apart: n for cells that came from the host, so the two codes are loaded as two 16-bit values; the padded
+ * leading dimension of the genotype step for cells that were made on the device (the linear index stays row * n + sample). */
 __global__ __launch_bounds__(256) void ntsm_pca_expand(const uint16_t *__restrict__ cells, const double *__restrict__ value,
-		const double *__restrict__ row_fill, uint64_t first_undef, uint64_t p, uint32_t n, uint64_t p_pad, uint32_t ld,
+		const double *__restrict__ row_fill, uint64_t first_undef, uint64_t p, uint32_t n, uint32_t cell_ld, uint64_t p_pad, uint32_t ld,
 		double *__restrict__ a)
 {
 	const uint32_t lane = threadIdx.x & 63;
@@ -61,7 +68,7 @@ __global__ __launch_bounds__(256) void ntsm_pca_expand(const uint16_t *__restric
 			continue;
 		}
 		const uint64_t base = row * n;
-		const uint16_t *in_row = cells + base;
+		const uint16_t *in_row = cells + row * cell_ld;
 		const double fill = row_fill[row];
 #pragma unroll 2
 		for (uint32_t col = lane * 2; col < ld; col += 128) {
@@ -77,6 +84,81 @@ __global__ __launch_bounds__(256) void ntsm_pca_expand(const uint16_t *__restric
 			*reinterpret_cast<double2 *>(out_row + col) = out;
 		}
 	}
+}
+
+/* The genotype step of a cohort store's chunk.  counts: the chunk, dense [count][n_sites] pairs;
+ * sample i of it is column first + i of the cell matrix [n_sites][cell_ld].  A workgroup takes 64 sites x 256 columns, the
+ * columns counted from col0 = first rounded down to a multiple of 64, so that a tile's row pieces start on 128-byte
+ * boundaries whatever column the chunk starts at (cell_ld is a multiple of 64).
+ *   read:   lane l of wave w is site l of the tile for the columns 64 w ... 64 w + 63, four at a time: four independent
+ *           8-byte loads, side by side along the sites of one sample (512 B per wave-instruction), the code of each pair,
+ *           and one ds_write_b32 of the four cells code + 1 (0: missing or outside the chunk) -- a byte per cell, so the
+ *           tile is 16.25 KiB.  Rows are 65 dwords apart: the 32 lanes of a store's group fall on 32 banks.
+ *           A lane is a site here, so the site's tallies over the wave's 64 columns add up in three registers, without a
+ *           cross-lane step; the four waves add theirs in LDS and the workgroup adds 64 x 3 integers to the global tallies.
+ *   write:  wave w takes the tile's sites w, w + 4, ...: a ds_read_b32 per lane (consecutive dwords), the four cells widened
+ *           to 16 bits and stored as 8 bytes, 512 B of the cell row per wave-instruction.  A group of four columns that
+ *           the chunk covers only in part (its first and last column need not be multiples of 4) is stored cell by cell,
+ *           so nothing outside the chunk's columns is written and chunks may be processed in any order.
+ * Integer atomics only: cells and tallies are the same for every chunk size. */
+constexpr int kGenoSites = 64, kGenoCols = 256, kGenoPitch = kGenoCols + 4;
+
+__global__ __launch_bounds__(256) void ntsm_pca_store_genotype(const uint2 *__restrict__ counts, uint32_t first, uint32_t count, uint32_t col0,
+		uint32_t n_sites, uint32_t min_cov, uint16_t *__restrict__ cells, uint32_t cell_ld, uint32_t *__restrict__ tally)
+{
+	__shared__ __attribute__((aligned(16))) uint8_t tile[kGenoSites][kGenoPitch];
+	__shared__ uint32_t sum[kGenoSites * 3];
+	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const uint32_t site0 = blockIdx.x * kGenoSites, tile_col = col0 + blockIdx.y * kGenoCols, end = first + count;
+	if (threadIdx.x < kGenoSites * 3) sum[threadIdx.x] = 0;
+
+	const bool site_ok = site0 + lane < n_sites;
+	const uint2 *column = counts + (site_ok ? site0 + lane : 0u);
+	uint32_t n_half = 0, n_one = 0, n_called = 0;
+#pragma unroll 2
+	for (uint32_t g = 0; g < 64; g += 4) {
+		const uint32_t col = tile_col + wave * 64 + g;
+		uint2 c[4];
+		bool ok[4];
+#pragma unroll
+		for (int k = 0; k < 4; ++k) {                               /* unconditional loads of a row of the chunk: they stay in flight together */
+			ok[k] = site_ok && col + k >= first && col + k < end;
+			c[k] = column[(uint64_t) (ok[k] ? col + k - first : 0u) * n_sites];
+		}
+		uint32_t four = 0;
+#pragma unroll
+		for (int k = 0; k < 4; ++k) {
+			const uint32_t code = ntsm_eval_pca::genotype_code(c[k].x, c[k].y, min_cov);
+			const bool called = ok[k] && code != 3;
+			n_half += called && code == 1;
+			n_one += called && code == 2;
+			n_called += called;
+			four |= (called ? code + 1 : 0u) << (8 * k);
+		}
+		*reinterpret_cast<uint32_t *>(&tile[lane][wave * 64 + g]) = four;
+	}
+	__syncthreads();                                               /* sum is zero, the tile is written */
+	if (n_called) {
+		atomicAdd(&sum[lane * 3], n_half);
+		atomicAdd(&sum[lane * 3 + 1], n_one);
+		atomicAdd(&sum[lane * 3 + 2], n_called);
+	}
+
+	for (uint32_t r = wave; r < (uint32_t) kGenoSites && site0 + r < n_sites; r += 4) {
+		const uint32_t four = *reinterpret_cast<const uint32_t *>(&tile[r][lane * 4]);
+		const uint32_t col = tile_col + lane * 4;
+		uint16_t *out = cells + (uint64_t) (site0 + r) * cell_ld + col;
+		if (col >= first && col + 4 <= end) {
+			*reinterpret_cast<uint2 *>(out) = uint2 { (four & 0xFFu) | (four & 0xFF00u) << 8, (four >> 16 & 0xFFu) | (four >> 24) << 16 };
+		} else {
+#pragma unroll
+			for (int k = 0; k < 4; ++k)
+				if (col + k >= first && col + k < end) out[k] = (uint16_t) (four >> (8 * k) & 0xFFu);
+		}
+	}
+	__syncthreads();
+	if (threadIdx.x < kGenoSites * 3 && site0 + threadIdx.x / 3 < n_sites && sum[threadIdx.x])
+		atomicAdd(&tally[(uint64_t) site0 * 3 + threadIdx.x], sum[threadIdx.x]);
 }
 
 __global__ __launch_bounds__(256) void ntsm_pca_centre(double *a, size_t ld, uint32_t n, double *means, int subtract)
@@ -275,6 +357,10 @@ struct Device {
 	ntsm_hip::Buffers buf;
 	ntsm_hip::Events<5> ev;
 	uint16_t *cells = nullptr;
+	uint32_t cell_ld = 0;                    /* cells per row of `cells`: n for host cells, padded for a store's */
+	uint32_t *tally = nullptr;               /* a store's [p][3] */
+	std::vector<uint32_t> tallies;           /* ... on the host */
+	ntsm_pca_store_times st = {};
 	double *value = nullptr, *row_fill = nullptr;
 	double expand_ms = 0.0;
 	double *a = nullptr, *means = nullptr, *partial = nullptr, *g = nullptr;
@@ -293,12 +379,16 @@ struct Handle {
 	~Handle() { if (h) (void) sv.destroy_handle(h); }
 };
 
-/* where the matrix comes from: host doubles [p][n], or the cells of ntsm_vcf_run with the values of their codes */
+/* where the matrix comes from: host doubles [p][n], the cells of ntsm_vcf_run with the values of their codes, or the first
+ * n records of a cohort store (the cells and the fills are then made here, section 11.1) */
 struct Source {
 	const double *a = nullptr;
 	const uint16_t *cells = nullptr;
 	const double *value = nullptr, *row_fill = nullptr;
 	uint64_t first_undef_cell = ~0ull;
+	const void *db = nullptr;
+	uint64_t db_stride = 0;
+	uint32_t min_cov = 0, db_chunk = 0;
 };
 
 bool shape_ok(uint64_t p, uint32_t n)
@@ -311,15 +401,57 @@ bool args_ok(uint64_t p, uint32_t n, const double *a)
 }
 bool args_ok(uint64_t p, uint32_t n, const Source &src)
 {
+	if (src.db) return shape_ok(p, n) && src.db_stride >= 8 * p && src.db_stride % 4 == 0;
 	return src.cells && src.value && src.row_fill && shape_ok(p, n);
+}
+
+/* The cells and the tallies of a store's first n records, on the device (dev.cells [p][dev.cell_ld], dev.tally) and the
+ * tallies on the host as well (dev.tallies): per chunk ntsm_eval_chunk::stage with neither transpose nor tally asked for --
+ * the 2-D copy from the store's pitch into a dense [chunk][site][2] buffer -- and ntsm_pca_store_genotype.  One stream, one
+ * wait per chunk.  The device is set and dev.ev exists. */
+int store_cells_on_device(Device &dev, uint64_t p, uint32_t n, const Source &src)
+{
+	const uint32_t m = (uint32_t) p;
+	uint32_t *d_raw = nullptr;
+	size_t free_b = 0, total_b = 0;
+	ntsm_eval_cross_times ctm {};
+	dev.cell_ld = (n + 63u) / 64u * 64u;
+	HIPCHK(dev.buf.alloc(&dev.cells, p * dev.cell_ld));
+	HIPCHK(dev.buf.alloc(&dev.tally, p * 3));
+	HIPCHK(hipMemset(dev.tally, 0, p * 3 * sizeof(uint32_t)));
+	if (src.db_chunk == 0) HIPCHK(hipMemGetInfo(&free_b, &total_b));
+	const uint32_t chunk = std::min(1u << 23, ntsm_eval_chunk::samples_per_pass(src.db_chunk, n, free_b, 8ull * p, 0));   /* grid.y <= 32,769 */
+	HIPCHK(dev.buf.alloc(&d_raw, (uint64_t) chunk * p * 2));
+	dev.st.chunk = chunk;
+	for (uint32_t c0 = 0; c0 < n; c0 += chunk) {
+		const uint32_t cn = std::min(chunk, n - c0), col0 = c0 & ~63u;
+		if (const int rc = ntsm_eval_chunk::stage(src.db, src.db_stride, c0, cn, m, src.min_cov, d_raw, nullptr, nullptr, nullptr, nullptr, dev.ev[0],
+		        dev.ev[1], ctm))
+			return rc;
+		ntsm_pca_store_genotype<<<dim3((m + kGenoSites - 1) / kGenoSites, (c0 + cn - col0 + kGenoCols - 1) / kGenoCols), dim3(256)>>>(
+		    (const uint2 *) d_raw, c0, cn, col0, m, src.min_cov, dev.cells, dev.cell_ld, dev.tally);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipEventRecord(dev.ev[2], 0));
+		HIPCHK(hipEventSynchronize(dev.ev[2]));                   /* the next chunk's copy overwrites d_raw */
+		if (const int rc = ntsm_eval_chunk::add_interval(dev.ev[1], dev.ev[2], &dev.st.genotype_ms)) return rc;
+		dev.st.chunks++;
+	}
+	dev.st.upload_ms = ctm.upload_ms;
+	HIPCHK(dev.buf.release(&d_raw));
+	const auto t0 = std::chrono::steady_clock::now();
+	dev.tallies.resize(p * 3);
+	HIPCHK(hipMemcpy(dev.tallies.data(), dev.tally, p * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	dev.st.fill_ms = ms_since(t0);
+	return 0;
 }
 bool run_args_ok(uint64_t p, uint32_t n, uint32_t d, const double *eigval, const double *rot, const double *comp)
 {
 	return n >= 2 && d >= 1 && d <= n && d <= p && eigval && rot && comp;
 }
 
-/* the matrix into the padded buffer dev.a: host doubles are copied into a zeroed buffer; cells are uploaded as they are
- * and expanded by ntsm_pca_expand, which writes the padding too (dev.expand_ms, HIP events) */
+/* the matrix into the padded buffer dev.a: host doubles are copied into a zeroed buffer; cells are uploaded as they are, or
+ * made from a store's records (store_cells_on_device), and expanded by ntsm_pca_expand, which writes the padding too
+ * (dev.expand_ms, HIP events) */
 int matrix_on_device(Device &dev, int device, uint64_t p, uint32_t n, const Source &src, ntsm_pca_times &tm)
 {
 	const uint32_t edge = (n + kTile - 1) / kTile;
@@ -339,25 +471,41 @@ int matrix_on_device(Device &dev, int device, uint64_t p, uint32_t n, const Sour
 	float ms = 0;
 	hipDeviceProp_t prop;
 	HIPCHK(hipGetDeviceProperties(&prop, device));
-	HIPCHK(dev.buf.alloc(&dev.cells, p * n));
 	HIPCHK(dev.buf.alloc(&dev.value, 2 * 65536));
 	HIPCHK(dev.buf.alloc(&dev.row_fill, p));
-	HIPCHK(hipMemcpy(dev.cells, src.cells, p * n * sizeof(uint16_t), hipMemcpyHostToDevice));
-	HIPCHK(hipMemcpy(dev.value, src.value, 2 * 65536 * sizeof(double), hipMemcpyHostToDevice));
-	HIPCHK(hipMemcpy(dev.row_fill, src.row_fill, p * sizeof(double), hipMemcpyHostToDevice));
-	HIPCHK(hipDeviceSynchronize());
-	tm.upload_ms = ms_since(t0);
+	if (src.db) {
+		/* the cells never leave the device; the 12 bytes per site of the tallies come down, every site's fill is what its
+		 * centre's text reads back as (the hand-over of `ntsmVCF --rotation`), and the codes 1, 2, 3 are 0, 0.5, 1 */
+		if (const int rc = store_cells_on_device(dev, p, n, src)) return rc;
+		const auto t1 = std::chrono::steady_clock::now();
+		std::vector<double> value(2 * 65536, std::numeric_limits<double>::quiet_NaN()), fill(p);
+		value[1] = 0.0; value[2] = 0.5; value[3] = 1.0;
+		for (uint64_t s = 0; s < p; ++s) fill[s] = ntsm::store_centre_value(dev.tallies[3 * s], dev.tallies[3 * s + 1], dev.tallies[3 * s + 2]);
+		HIPCHK(hipMemcpy(dev.value, value.data(), 2 * 65536 * sizeof(double), hipMemcpyHostToDevice));
+		HIPCHK(hipMemcpy(dev.row_fill, fill.data(), p * sizeof(double), hipMemcpyHostToDevice));
+		HIPCHK(hipDeviceSynchronize());
+		dev.st.fill_ms += ms_since(t1);
+		tm.upload_ms = dev.st.upload_ms;
+	} else {
+		dev.cell_ld = n;
+		HIPCHK(dev.buf.alloc(&dev.cells, p * n));
+		HIPCHK(hipMemcpy(dev.cells, src.cells, p * n * sizeof(uint16_t), hipMemcpyHostToDevice));
+		HIPCHK(hipMemcpy(dev.value, src.value, 2 * 65536 * sizeof(double), hipMemcpyHostToDevice));
+		HIPCHK(hipMemcpy(dev.row_fill, src.row_fill, p * sizeof(double), hipMemcpyHostToDevice));
+		HIPCHK(hipDeviceSynchronize());
+		tm.upload_ms = ms_since(t0);
+	}
 	/* a grid-stride walk over the rows, four per workgroup: 32 workgroups per compute unit keep every unit's store queue
 	 * fed, and a short buffer gets no more workgroups than it has rows */
 	const unsigned blocks = (unsigned) std::min<uint64_t>(dev.p_pad / 4, 32ull * (uint64_t) prop.multiProcessorCount);
 	HIPCHK(hipEventRecord(dev.ev[3], 0));
-	ntsm_pca_expand<<<dim3(blocks), dim3(256)>>>(dev.cells, dev.value, dev.row_fill, src.first_undef_cell, p, n, dev.p_pad,
+	ntsm_pca_expand<<<dim3(blocks), dim3(256)>>>(dev.cells, dev.value, dev.row_fill, src.first_undef_cell, p, n, dev.cell_ld, dev.p_pad,
 	    (uint32_t) dev.ld, dev.a);
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipEventRecord(dev.ev[4], 0));
 	HIPCHK(hipEventSynchronize(dev.ev[4]));
 	HIPCHK(hipEventElapsedTime(&ms, dev.ev[3], dev.ev[4]));
-	dev.expand_ms = ms;
+	dev.expand_ms = dev.st.expand_ms = ms;
 	return 0;
 }
 
@@ -422,9 +570,11 @@ int gram_of(int device, uint64_t p, uint32_t n, const Source &src, int centre, u
 	return 0;
 }
 
-/* the whole PCA of either source */
+/* the whole PCA of any source; tallies and store_times are a store's (given once the matrix is on the device, so a rank
+ * refusal has them too) */
 int run_of(int device, uint64_t p, uint32_t n, const Source &src, uint32_t d, uint32_t split, double *eigval, double *rot,
-		double *comp, uint32_t *bad_component, ntsm_pca_times *times, double *expand_ms)
+		double *comp, uint32_t *bad_component, ntsm_pca_times *times, double *expand_ms, uint32_t *tallies = nullptr,
+		ntsm_pca_store_times *store_times = nullptr)
 {
 	const Solver &sv = solver_bind();
 	if (!sv.ok) return NTSM_PCA_E_SOLVER_MISSING;
@@ -436,6 +586,8 @@ int run_of(int device, uint64_t p, uint32_t n, const Source &src, uint32_t d, ui
 	const uint32_t d_pad = (d + kProjComp - 1) / kProjComp * kProjComp;
 	std::vector<double> w(n), s(d_pad, 1.0);
 	if (const int rc = gram_on_device(dev, device, p, n, src, 1, split, tm)) return rc;
+	if (tallies) std::copy(dev.tallies.begin(), dev.tallies.end(), tallies);
+	if (store_times) *store_times = dev.st;
 
 	/* eigenpairs of G: dsyevd overwrites G with the eigenvectors (column-major), eigenvalues ascending in w */
 	HIPCHK(dev.buf.alloc(&dev.w, n));
@@ -523,6 +675,15 @@ Source cell_matrix(const uint16_t *cells, const double *value, const double *row
 	src.first_undef_cell = first_undef_cell;
 	return src;
 }
+Source store_matrix(const void *db_counts, uint64_t db_stride_bytes, uint32_t min_cov, uint32_t db_chunk)
+{
+	Source src;
+	src.db = db_counts;
+	src.db_stride = db_stride_bytes;
+	src.min_cov = min_cov;
+	src.db_chunk = db_chunk;
+	return src;
+}
 
 } // namespace
 
@@ -571,4 +732,29 @@ NTSM_PCA_EXPORT int ntsm_pca_run_cells(int device, uint64_t p, uint32_t n, const
 	const Source src = cell_matrix(cells, value, row_fill, first_undef_cell);
 	if (!args_ok(p, n, src) || !run_args_ok(p, n, d, eigval, rot, comp)) return NTSM_PCA_E_ARG;
 	return run_of(device, p, n, src, d, split, eigval, rot, comp, bad_component, times, expand_ms);
+}
+
+NTSM_PCA_EXPORT int ntsm_pca_store_cells(int device, const void *db_counts, uint64_t db_stride_bytes, uint32_t n, uint64_t n_sites,
+		uint32_t min_cov, uint32_t db_chunk, uint16_t *cells, uint32_t *tallies, ntsm_pca_store_times *store_times)
+{
+	const Source src = store_matrix(db_counts, db_stride_bytes, min_cov, db_chunk);
+	if (!args_ok(n_sites, n, src) || !cells || !tallies) return NTSM_PCA_E_ARG;
+	Device dev;
+	HIPCHK(hipSetDevice(device));
+	HIPCHK(dev.ev.create());
+	if (const int rc = store_cells_on_device(dev, n_sites, n, src)) return rc;
+	HIPCHK(hipMemcpy2D(cells, (size_t) n * sizeof(uint16_t), dev.cells, (size_t) dev.cell_ld * sizeof(uint16_t), (size_t) n * sizeof(uint16_t), n_sites,
+	    hipMemcpyDeviceToHost));
+	std::copy(dev.tallies.begin(), dev.tallies.end(), tallies);
+	if (store_times) *store_times = dev.st;
+	return 0;
+}
+
+NTSM_PCA_EXPORT int ntsm_pca_run_store(int device, const void *db_counts, uint64_t db_stride_bytes, uint32_t n, uint64_t n_sites,
+		uint32_t min_cov, uint32_t db_chunk, uint32_t d, uint32_t split, double *eigval, double *rot, double *comp, uint32_t *tallies,
+		uint32_t *bad_component, ntsm_pca_times *times, ntsm_pca_store_times *store_times)
+{
+	const Source src = store_matrix(db_counts, db_stride_bytes, min_cov, db_chunk);
+	if (!args_ok(n_sites, n, src) || !run_args_ok(n_sites, n, d, eigval, rot, comp) || !tallies) return NTSM_PCA_E_ARG;
+	return run_of(device, n_sites, n, src, d, split, eigval, rot, comp, bad_component, times, nullptr, tallies, store_times);
 }

@@ -160,3 +160,75 @@ def run_cells(cells, value, row_fill, d, first_undef_cell=None, split=0, device=
     if rc:
         raise RuntimeError("ntsm_pca_run_cells failed: %d" % rc)
     return eigval, rot, comp, times, ms.value
+
+
+# ---- the matrix from a cohort store (ntsmPCA --store)
+class StoreTimes(C.Structure):
+    _fields_ = [("upload_ms", C.c_double), ("genotype_ms", C.c_double), ("fill_ms", C.c_double), ("expand_ms", C.c_double),
+                ("chunks", C.c_uint32), ("chunk", C.c_uint32)]
+
+
+_STORE = [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32]
+lib.ntsm_pca_store_cells.restype = C.c_int
+lib.ntsm_pca_store_cells.argtypes = _STORE + [C.c_void_p, C.c_void_p, C.POINTER(StoreTimes)]
+lib.ntsm_pca_run_store.restype = C.c_int
+lib.ntsm_pca_run_store.argtypes = _STORE + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32),
+                                            C.POINTER(Times), C.POINTER(StoreTimes)]
+
+
+def store_value_table():
+    """The value of the cell codes of store_cells: float64 [2][65536] with [0][1..3] = 0, 0.5, 1 (NaN elsewhere)."""
+    value = np.full((2, 65536), np.nan, dtype=np.float64)
+    value[0, 1:4] = (0.0, 0.5, 1.0)
+    return value
+
+
+def _store(db, n):
+    """(address, stride, samples, sites, what keeps the memory alive) of db: uint32 [samples][sites][2], or anything with
+    .address / .stride / .n / .m (ntsm_amd.eval.Records: samples at a store's pitch); n: the first n samples, None = all."""
+    if not hasattr(db, "address"):
+        db = np.ascontiguousarray(db, dtype=np.uint32)
+        if db.ndim != 3 or db.shape[2] != 2:
+            raise ValueError("the samples are uint32 [samples][sites][2]")
+        address, stride, have, m = db.ctypes.data, 8 * db.shape[1], db.shape[0], db.shape[1]
+    else:
+        address, stride, have, m = db.address, db.stride, db.n, db.m
+    n = have if n is None else int(n)
+    if n > have:
+        raise ValueError("%d samples asked for, %d given" % (n, have))
+    return address, stride, n, m, db
+
+
+def store_cells(db, min_cov=1, db_chunk=0, n=None, device=0):
+    """The genotype step on its own.  Returns (cells uint16 [sites][n]: code + 1 = 1, 2, 3 for genotype 0, 0.5, 1 and
+    0 where the sample does not call the site; tallies uint32 [sites][3] = n_half, n_one, n_called; StoreTimes)."""
+    address, stride, n, m, keep = _store(db, n)
+    cells = np.zeros((m, n), dtype=np.uint16)
+    tallies = np.zeros((m, 3), dtype=np.uint32)
+    times = StoreTimes()
+    rc = lib.ntsm_pca_store_cells(device, address, stride, n, m, min_cov, db_chunk, cells.ctypes.data, tallies.ctypes.data, C.byref(times))
+    if rc:
+        raise RuntimeError("ntsm_pca_store_cells failed: %d" % rc)
+    return cells, tallies, times
+
+
+def run_store(db, d, min_cov=1, db_chunk=0, split=0, n=None, device=0):
+    """The whole PCA of the first n samples of db: (eigenvalues, rotation [sites][d], components [n][d], tallies
+    [sites][3], Times, StoreTimes) -- the same bits as run_cells on store_cells' cells with store_value_table() and the
+    fills of the tallies, in the same process, for every db_chunk."""
+    address, stride, n, m, keep = _store(db, n)
+    eigval = np.empty(max(d, 1), dtype=np.float64)
+    rot = np.empty((m, max(d, 1)), dtype=np.float64)
+    comp = np.empty((n, max(d, 1)), dtype=np.float64)
+    tallies = np.zeros((m, 3), dtype=np.uint32)
+    bad = C.c_uint32()
+    times, store_times = Times(), StoreTimes()
+    rc = lib.ntsm_pca_run_store(device, address, stride, n, m, min_cov, db_chunk, d, split, eigval.ctypes.data, rot.ctypes.data,
+                                comp.ctypes.data, tallies.ctypes.data, C.byref(bad), C.byref(times), C.byref(store_times))
+    if rc == E_RANK:
+        raise RankError(bad.value)
+    if rc == E_SOLVER_MISSING:
+        raise RuntimeError("rocSOLVER cannot be loaded (librocsolver.so.0, librocsolver.so)")
+    if rc:
+        raise RuntimeError("ntsm_pca_run_store failed: %d" % rc)
+    return eigval, rot, comp, tallies, times, store_times

@@ -9,7 +9,7 @@
 #                                                  PCA-guided search against one (--index / --near), and both runs over
 #                                                  the store's own samples (--within / --within-near), and one store
 #                                                  against another (--between) and the PCA-guided search between
-#                                                  two (--between-near)
+#                                                  two (--between-near), and the QC tables of a store (--qc)
 #   ntsm_amd/libntsm_vcf_hip.so, build/ntsmVCF     multi-sample VCF to PCA matrix + centre file (HIP library + CLI mirror);
 #                                                  with --rotation also the PCA, through libntsm_pca_hip.so
 #                                                  with --counts / --store the genotypes as counts files and cohort-store records
@@ -88,13 +88,15 @@ xlib:
 #   differs; the locus map and the band rule are host code that the library and the CLI share (host/eval_between.hpp)
 # + the PCA-guided search between two stores (--between-near): ntsm_eval_between_near.hip, the row remap of a store whose locus
 #   table differs in front of the projection and the listed-pair scorer; its candidate search is ntsm_eval_near.hip's kernels
+# + the QC tables of a store (--qc): ntsm_eval_profile.hip, one fused kernel over each chunk's dense rows; the chunk rule and the
+#   2-D copy are ntsm_eval_chunk.h's, the site table's text is host code (host/eval_qc.hpp)
 EVALSRC := $(CSRC)/ntsm_eval.hip $(CSRC)/ntsm_eval_pca.hip $(CSRC)/ntsm_eval_cross.hip $(CSRC)/ntsm_eval_near.hip $(CSRC)/ntsm_eval_within.hip \
-           $(CSRC)/ntsm_eval_between.hip $(CSRC)/ntsm_eval_between_near.hip
+           $(CSRC)/ntsm_eval_between.hip $(CSRC)/ntsm_eval_between_near.hip $(CSRC)/ntsm_eval_profile.hip
 ntsm_amd/libntsm_eval_hip.so: $(EVALSRC) $(CSRC)/ntsm_eval_score.h $(CSRC)/ntsm_eval_chunk.h $(CSRC)/ntsm_eval_pca.h $(CSRC)/ntsm_hip_scope.h $(CSRC)/xprec.h \
                               $(HOST)/eval_within.hpp $(HOST)/eval_between.hpp $(HOST)/eval_store.hpp include/ntsm_eval_hip.h
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -shared -o $@ $(EVALSRC)
 
-build/ntsmEval: $(HOST)/ntsm_eval_main.cpp $(HOST)/cli.hpp $(HOST)/eval_store.hpp $(HOST)/eval_index.hpp $(HOST)/eval_within.hpp $(HOST)/eval_between.hpp $(HOST)/crc32_fast.cpp $(HOST)/crc32_fast.hpp \
+build/ntsmEval: $(HOST)/ntsm_eval_main.cpp $(HOST)/cli.hpp $(HOST)/eval_store.hpp $(HOST)/eval_index.hpp $(HOST)/eval_qc.hpp $(HOST)/eval_within.hpp $(HOST)/eval_between.hpp $(HOST)/crc32_fast.cpp $(HOST)/crc32_fast.hpp \
                 $(HOST)/gz_stream.hpp $(CSRC)/xprec.h include/ntsm_eval_hip.h ntsm_amd/libntsm_eval_hip.so
 	@mkdir -p build
 	$(CXX) $(CXXFLAGS) -ffp-contract=off -o $@ $(HOST)/ntsm_eval_main.cpp $(HOST)/crc32_fast.cpp -Lntsm_amd -lntsm_eval_hip -lz \

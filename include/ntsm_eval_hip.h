@@ -258,6 +258,24 @@ int ntsm_eval_between_score_pairs(int device, const void *a_counts, uint64_t a_s
 		uint64_t b_stride_bytes, uint32_t n_b, uint32_t n_sites_a, uint32_t n_sites_b, const uint32_t *site_map, uint32_t min_cov, const uint32_t *pi,
 		const uint32_t *pk, uint64_t n_pairs, uint32_t chunk, ntsm_eval_record *out, ntsm_eval_cross_times *times);
 
+/* ---- The QC tables of a cohort store (ntsmEval --qc; ntsm_amd/csrc/ntsm_eval_profile.hip): what
+ * computeScoreSingle (src/CompareCounts.hpp:541-585) tallies per sample, and the same classes per site, in one pass over a
+ * mapped store.  The rule is calcHomHetMiss (:742-767) with strict > min_cov: both alleles above is a het, exactly one a hom,
+ * neither a miss.  db_counts / db_stride_bytes / db_chunk as for ntsm_eval_cross: one 2-D copy per chunk, the same chunk rule
+ * (at 8 * n_sites + 12 bytes per sample); one kernel reads each chunk once.
+ *   db_geno (may be NULL): [n_db][3] = hets, homs, miss per sample, value for value ntsm_eval_cross's and
+ *     ntsm_eval_project_store's db_geno on the same store.
+ *   site_tally (may be NULL): [n_sites][4] = homAT, homCG, het, miss per site: the number of samples of each class there, a
+ *     hom counted under the allele that is above min_cov.  The four sum to n_db at every site.
+ *   site_cov (may be NULL): [n_sites] = the sum over the samples of uint64(countAT) + uint64(countCG), raw: not masked by
+ *     min_cov, and never wrapped.
+ *   times (may be NULL): upload_ms the copies, cross_kernel_ms the kernel, download_ms the outputs' way back, chunks.
+ * All sums are integer sums: two calls give the same bits.
+ * Returns 0, -2 HIP error, -1 bad argument: a NULL db_counts the call needs, all three outputs NULL, a stride below
+ * 8 * n_sites or not a multiple of 4.  n_db == 0 or n_sites == 0: zeroed outputs, no device work. */
+int ntsm_eval_store_profile(int device, const void *db_counts, uint64_t db_stride_bytes, uint32_t n_db, uint32_t n_sites,
+		uint32_t min_cov, uint32_t db_chunk, uint32_t *db_geno, uint32_t *site_tally, uint64_t *site_cov, ntsm_eval_cross_times *times);
+
 #ifdef __cplusplus
 }
 #endif

@@ -105,6 +105,12 @@ int ntsm_host_format_counts(const ntsm_sites *s, const uint64_t *counts, uint64_
 int ntsm_host_format_summary(const ntsm_sites *s, const uint64_t *counts, uint64_t total_bases,
 		uint64_t total_kmers, uint64_t total_hits, char **out, size_t *len, uint64_t *covered);
 
+/* The per-site table of `ntsmEval --qc --sites-out` (ntsm_amd/csrc/host/eval_qc.hpp), header line included, for tests:
+ * locus[n_sites] IDs, tally [n_sites][4] = homAT, homCG, het, miss and site_cov [n_sites] as ntsm_eval_store_profile gives them
+ * (include/ntsm_eval_hip.h).  *out is freed with ntsm_host_free.  Returns 0, -1 for a NULL it needs. */
+int ntsm_host_site_table(const char *const *locus, uint32_t n_sites, const uint32_t *tally, const uint64_t *site_cov, uint64_t n_samples,
+		char **out, size_t *len);
+
 #ifdef __cplusplus
 }
 #endif

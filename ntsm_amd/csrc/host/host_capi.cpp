@@ -12,6 +12,7 @@
 #include "gz_stream.hpp"
 #include "pack2.hpp"
 #include "early_ingest.hpp"
+#include "eval_qc.hpp"
 #include "host_shape.hpp"
 #include "parallel_fastq.hpp"
 #include "parallel_gz_fastq.hpp"
@@ -375,6 +376,16 @@ int ntsm_host_format_summary(const ntsm_sites *s, const uint64_t *counts, uint64
 	std::vector<uint64_t> c(counts, counts + s->set.keys.size());
 	*out = dup_string(ntsm::info_summary(s->set, c, total_bases, total_kmers, total_hits), len);
 	if (covered) *covered = ntsm::sites_covered(s->set, c);
+	return 0;
+}
+
+int ntsm_host_site_table(const char *const *locus, uint32_t n_sites, const uint32_t *tally, const uint64_t *site_cov, uint64_t n_samples,
+		char **out, size_t *len)
+{
+	if (!out || !len || (n_sites && (!locus || !tally || !site_cov))) return -1;
+	std::string text = ntsm::eval_qc::kSiteHeader;
+	for (uint32_t s = 0; s < n_sites; ++s) ntsm::eval_qc::site_line(text, locus[s], tally + 4 * (size_t) s, site_cov[s], n_samples);
+	*out = dup_string(text, len);
 	return 0;
 }
 

@@ -22,7 +22,10 @@
  *                             B's projections from its own index where that serves, else ntsm_eval_project_store_mapped; then
  *                             ntsm_eval_between_candidates, ntsm_eval_between_rows for the search-all rows of A and
  *                             ntsm_eval_between_score_pairs for the rest
- * --within, --within-near, --between and --between-near read no counts file.  Not built, and refused: -b (the debug ground-truth mode) and -p without a
+ *   --qc STORE [-p ROT -n NORM] [--sites-out FILE]   computeScoreSingle's table (:541-585) with one row per sample of the store,
+ *                             and per-site tallies under the same rule: ntsm_eval_store_profile; the PC columns of -p from
+ *                             ntsm_eval_project_store
+ * --within, --within-near, --between, --between-near and --qc read no counts file.  Not built, and refused: -b (the debug ground-truth mode) and -p without a
  * normalization file (the reference dies in an assert).  Pinned to the reference: stdout equals, byte for byte, that of the
  * unmodified scoring class (oracle/ref_eval_driver.cpp -> oracle/_ref/ref_ntsmEval -t 1) and its recordings,
  * tests/test_eval_reference.py.
@@ -46,6 +49,7 @@
 #include "cli.hpp"
 #include "eval_between.hpp"
 #include "eval_index.hpp"
+#include "eval_qc.hpp"
 #include "eval_store.hpp"
 #include "eval_within.hpp"
 
@@ -69,6 +73,8 @@ struct Opt {                                 /* src/Options.h:44-55 */
 	unsigned betweenRows = 0;                /* --between-rows N: rows of A per band of --between, 0 = the band rule */
 	bool betweenRowsGiven = false;
 	std::string betweenNear;                 /* --between-near STORE_A; STORE_B is the one positional argument */
+	std::string qc, sitesOut;                /* --qc STORE: the QC table of the store's samples; --sites-out FILE: its per-site table */
+	bool sitesOutGiven = false;
 	bool minCovGiven = false, dimGiven = false;
 	bool onlyMerge = false;
 	unsigned dim = 20;                       /* src/Options.h:22, 35-39: the PCA search */
@@ -202,6 +208,16 @@ void printHelpDialog()
 	    "                             written over the same loci with the same matrices, else\n"
 	    "                             they are computed in the run. Not with -p, -n, -b, -e or\n"
 	    "                             -o.\n"
+	    "      --qc = STORE           The QC table of the single-file run with one row per sample\n"
+	    "                             of STORE, in store order: sample cov errorRate miss hom\n"
+	    "                             het, and with -p ROT -n NORM [-d] the PC columns. Every\n"
+	    "                             row ends in a newline (the single-file run prints its one\n"
+	    "                             row without one). Takes no FILES; reads and writes no\n"
+	    "                             STORE.pcaidx. -a, -s, -w and the radius flags have no\n"
+	    "                             effect. Not with -b, -e or -o.\n"
+	    "      --sites-out = FILE     With --qc: write one line per locus of STORE to FILE:\n"
+	    "                             #locusID called miss homAT homCG het freqAT hetObs hetExp\n"
+	    "                             meanCov, the genotypes by the scoring's rule at -c.\n"
 	    "Not in this build: -b (debug mode of the PCA search); the PCA-guided search (-p)\n"
 	    "against a store (--index and --near are that search); merging (-e) from a store.\n" << std::endl;
 	exit(EXIT_SUCCESS);
@@ -396,7 +412,7 @@ int scorePCA(const Counts &c, std::vector<Genotype> &g, const Opt &opt, ntsm_eva
 }
 
 constexpr int kOptPack = 1000, kOptAgainst = 1001, kOptIndex = 1002, kOptNear = 1003, kOptWithin = 1004, kOptWithinNear = 1005,
-              kOptWithinRows = 1006, kOptBetween = 1007, kOptBetweenRows = 1008, kOptBetweenNear = 1009;   /* long-only: no letter of the reference's option string is taken */
+              kOptWithinRows = 1006, kOptBetween = 1007, kOptBetweenRows = 1008, kOptBetweenNear = 1009, kOptQc = 1010, kOptSitesOut = 1011;   /* long-only: no letter of the reference's option string is taken */
 
 /* --pack STORE FILES...: no GPU */
 int packStore(const Counts &c, const Opt &opt)
@@ -983,6 +999,96 @@ int searchBetween(Opt &opt, const std::string &storeB, Clock::time_point t0)
 	return 0;
 }
 
+/* --sites-out FILE, opened before any GPU work and without touching what it holds: a file this run made is removed again
+ * unless the table gets written */
+struct SitesFile {
+	std::string path;
+	int fd = -1;
+	bool created = false, written = false;
+	~SitesFile()
+	{
+		if (fd >= 0) close(fd);
+		if (created && !written) unlink(path.c_str());
+	}
+	bool open(const std::string &name)
+	{
+		path = name;
+		struct stat sb;
+		created = stat(name.c_str(), &sb) != 0;
+		fd = ::open(name.c_str(), O_WRONLY | O_CREAT, 0644);
+		return fd >= 0;
+	}
+	bool write(const std::string &text)
+	{
+		written = ftruncate(fd, 0) == 0 && ntsm::eval_store::write_all(fd, text.data(), text.size(), 0);
+		return written;
+	}
+};
+
+/* --qc STORE [-p ROT -n NORM] [--sites-out FILE]: computeScoreSingle (:541-585) with one row per sample of the store -- the row
+ * the single-file run prints for a counts file whose loci and distinct columns are the store's --, each followed by "\n".  The
+ * tallies of the samples and, for --sites-out, of the sites come from one pass over the store (ntsm_eval_store_profile); the
+ * PC columns from ntsm_eval_project_store in the same run, STORE.pcaidx neither read nor written. */
+int qcStore(const Opt &opt, Clock::time_point t0)
+{
+	ntsm::eval_store::View store;
+	Counts c;
+	std::vector<long double> norm, rot;
+	SitesFile sites;
+	const auto tMap = Clock::now();
+	try {
+		openStore(opt.qc, 0, "scores", store, &c);
+		if (!opt.pca.empty()) loadPCA(opt, store.h.n_sites, norm, rot);
+		if (opt.sitesOutGiven && !sites.open(opt.sitesOut)) throw ntsm::eval_store::Error("cannot write " + opt.sitesOut);
+	} catch (const std::exception &e) {
+		ntsm::refuse(e.what());
+	}
+	const double mapMs = msSince(tMap);
+	const uint32_t n = (uint32_t) store.h.n_samples, m = store.h.n_sites;
+	if (opt.verbose > 1) std::cerr << "Mapped " << opt.qc << ". Providing only QC information for its " << n << " samples." << std::endl;
+	std::vector<uint32_t> geno((size_t) n * 3), tally(opt.sitesOutGiven ? (size_t) m * 4 : 0);
+	std::vector<uint64_t> siteCov(opt.sitesOutGiven ? m : 0);
+	ntsm_eval_cross_times times {}, projectTimes {};
+	int rc = ntsm_eval_store_profile(opt.device, store.counts(0), store.h.stride, n, m, opt.minCov, 0, geno.data(), opt.sitesOutGiven ? tally.data() : nullptr,
+			opt.sitesOutGiven ? siteCov.data() : nullptr, &times);
+	if (rc) return gpuFail("profiling the store", rc);
+	std::vector<double> cloud;
+	if (!opt.pca.empty()) {
+		cloud.assign((size_t) n * opt.dim, 0.0);
+		rc = ntsm_eval_project_store(opt.device, store.counts(0), store.h.stride, n, m, opt.minCov, norm.data(), rot.data(), opt.dim, 0, cloud.data(), nullptr,
+				&projectTimes);
+		if (rc) return gpuFail("projecting the store", rc);
+	}
+	const auto tPrint = Clock::now();
+	std::vector<Genotype> g;
+	appendStoreSamples(c, g, store, opt, [&](uint32_t d, Genotype &s) { s.hets = geno[3 * d]; s.homs = geno[3 * d + 1]; s.miss = geno[3 * d + 2]; });
+	std::string temp = "sample\tcov\terrorRate\tmiss\thom\thet";
+	if (!opt.pca.empty())
+		for (unsigned d = 1; d <= opt.dim; ++d) { temp += "\tPC"; temp += std::to_string(d); }
+	std::cout << temp << std::endl;
+	for (uint32_t i = 0; i < n; ++i) {
+		temp.clear();
+		temp += c.files[i]; temp += "\t"; temp += std::to_string(g[i].cov); temp += "\t"; temp += std::to_string(g[i].errorRate);
+		temp += "\t"; temp += std::to_string(g[i].miss); temp += "\t"; temp += std::to_string(g[i].homs); temp += "\t"; temp += std::to_string(g[i].hets);
+		for (unsigned d = 0; d < (opt.pca.empty() ? 0 : opt.dim); ++d) { temp += "\t"; temp += std::to_string(cloud[(size_t) i * opt.dim + d]); }
+		temp += "\n";
+		std::cout << temp;
+	}
+	std::cout.flush();
+	if (opt.sitesOutGiven) {
+		std::string text = ntsm::eval_qc::kSiteHeader;
+		for (uint32_t s = 0; s < m; ++s) ntsm::eval_qc::site_line(text, c.locus[s].c_str(), &tally[(size_t) s * 4], siteCov[s], n);
+		if (!sites.write(text)) { std::cerr << PROGRAM ": cannot write " << opt.sitesOut << std::endl; return 1; }
+	}
+	if (opt.verbose > 1)
+		std::cerr << "store qc: " << times.chunks << " chunks, map+load " << mapMs << " ms, upload " << times.upload_ms << " ms, profile kernel " << times.cross_kernel_ms
+		          << " ms, download " << times.download_ms << " ms, project " << projectTimes.upload_ms + projectTimes.prepare_kernel_ms + projectTimes.cross_kernel_ms
+		             + projectTimes.download_ms << " ms (upload " << projectTimes.upload_ms << " ms, projection kernel " << projectTimes.cross_kernel_ms
+		          << " ms), print " << msSince(tPrint) << " ms" << std::endl;
+	printTime(t0);
+	return 0;
+}
+
 /* what no store run goes with */
 void refuseDebugAndMerge(const Opt &opt, const char *mode)
 {
@@ -995,7 +1101,7 @@ void refuseDebugAndMerge(const Opt &opt, const char *mode)
 int main(int argc, char **argv)
 {
 	Opt opt;
-	bool die = false, storeMode = false, nearMode = false, withinMode = false, betweenMode = false, betweenNearMode = false;
+	bool die = false, storeMode = false, nearMode = false, withinMode = false, betweenMode = false, betweenNearMode = false, qcMode = false;
 	static struct option long_options[] = {
 		{ "score_thresh", required_argument, nullptr, 's' }, { "all", no_argument, nullptr, 'a' },
 		{ "min_cov", required_argument, nullptr, 'c' }, { "skew", required_argument, nullptr, 'w' },
@@ -1011,6 +1117,7 @@ int main(int argc, char **argv)
 		{ "within", required_argument, nullptr, kOptWithin }, { "within-near", required_argument, nullptr, kOptWithinNear },
 		{ "within-rows", required_argument, nullptr, kOptWithinRows }, { "between", required_argument, nullptr, kOptBetween },
 		{ "between-rows", required_argument, nullptr, kOptBetweenRows }, { "between-near", required_argument, nullptr, kOptBetweenNear },
+		{ "qc", required_argument, nullptr, kOptQc }, { "sites-out", required_argument, nullptr, kOptSitesOut },
 		{ nullptr, 0, nullptr, 0 } };
 	int ch;
 	while ((ch = getopt_long(argc, argv, "t:vhs:c:m:aw:g:p:n:d:r:e:o1:2:S:l:b:G:", long_options, nullptr)) != -1) {
@@ -1052,6 +1159,8 @@ int main(int argc, char **argv)
 				ntsm::refuse(std::string("--between-rows takes a number of rows of at least 1, not ") + optarg);
 			opt.betweenRowsGiven = true;
 			break;
+		case kOptQc: opt.qc = optarg; qcMode = true; break;
+		case kOptSitesOut: opt.sitesOut = optarg; opt.sitesOutGiven = true; break;
 		case '?': die = true; break;
 		default: break;                              /* m: read by the reference, without effect */
 		}
@@ -1059,6 +1168,10 @@ int main(int argc, char **argv)
 	Counts c;
 	while (optind < argc) c.files.emplace_back(argv[optind++]);
 	const char *sevenRuns = "--pack, --against, --index, --near, --within, --within-near and --between are seven runs: give one of them";
+	if (qcMode && (storeMode || nearMode || withinMode || betweenMode || betweenNearMode))
+		ntsm::refuse("--qc prints the QC tables of one store and is a run of its own: it goes with none of --pack, --against, --index, --near, --within, "
+		             "--within-near, --between and --between-near");
+	if (opt.sitesOutGiven && !qcMode) ntsm::refuse("--sites-out is the per-site table of --qc: give it with --qc STORE");
 	if (betweenNearMode) {                               /* --between-near: every refusal that needs no store, then the run */
 		if (storeMode || nearMode || withinMode || betweenMode)
 			ntsm::refuse("--pack, --against, --index, --near, --within, --within-near, --between and --between-near are eight runs: give one of them");
@@ -1096,6 +1209,18 @@ int main(int argc, char **argv)
 		return near ? searchWithin(opt, t0) : scoreWithin(opt, t0);
 	}
 	if (opt.withinRowsGiven) ntsm::refuse("--within-rows sets the bands of --within: give it with --within STORE");
+	if (qcMode) {                                        /* --qc: every refusal that needs no store, then the run */
+		if (!c.files.empty()) ntsm::refuse("--qc takes no input files: it prints the QC table of the samples of the store");
+		refuseDebugAndMerge(opt, "--qc");
+		if (!opt.pca.empty() || !opt.norm.empty()) {
+			if (opt.pca.empty()) ntsm::refuse("--qc takes -n only with -p: the centre belongs to the rotation of the PC columns");
+			if (!std::ifstream(opt.pca).good()) ntsm::refuse("--qc -p needs a readable rotation file");
+			if (opt.norm.empty() || !std::ifstream(opt.norm).good()) ntsm::refuse("--qc -p needs a readable normalization file (-n)");
+			if (opt.dim == 0) ntsm::refuse("a PCA search with -d 0 is not part of this build");
+		}
+		ntsm::try_help_if(die);
+		return qcStore(opt, Clock::now());
+	}
 	if (nearMode) {                                      /* --index and --near: every refusal that needs no store comes before any file is read */
 		const char *mode = opt.near.empty() ? "--index" : "--near";
 		if (storeMode || (!opt.index.empty() && !opt.near.empty())) ntsm::refuse("--pack, --against, --index and --near are four runs: give one of them");

@@ -1,6 +1,7 @@
 /*
  * ntsm_eval_chunk.h -- one chunk of a cohort store on the device, stated once for ntsm_eval_cross.hip (the dense rectangle),
- * ntsm_eval_near.hip (the projection of a store) and ntsm_eval_within.hip (the triangle, resident or streamed): the chunk
+ * ntsm_eval_near.hip (the projection of a store), ntsm_eval_within.hip (the triangle, resident or streamed) and
+ * ntsm_eval_profile.hip (the QC tallies; the chunk rule and the copy only): the chunk
  * rule; the kernels -- the genotype tallies of the chunk's samples over the dense [chunk sample][site][2] buffer and that
  * buffer's transpose to at / cg / term [site][chunk sample] --; and the step that stages a chunk: the 2-D copy from the
  * host pitch, those kernels, the wall clock and the events that time them.  Internal: not part of include/.  The kernels
@@ -108,16 +109,24 @@ static inline int add_interval(hipEvent_t e0, hipEvent_t e1, double *ms)
 }
 
 /* Samples first ... first + count - 1 of the store: one 2-D copy from the host pitch to d_raw [count][site][2], timed into
- * tm.upload_ms (added); then, between e0 and e1, with d_at the transpose to at / cg / term [site][count] and with d_geno
- * the tallies.  It waits for nothing: a caller adds the interval (e0, e1) to tm.prepare_kernel_ms once it has waited for e1
- * or for a later event of its own, so a walk over chunks keeps the one wait per chunk it has. */
-static inline int stage(const void *db, uint64_t stride, uint32_t first, uint32_t count, uint32_t n_sites, uint32_t min_cov, uint32_t *d_raw, uint32_t *d_at,
-		uint32_t *d_cg, double *d_term, uint32_t *d_geno, hipEvent_t e0, hipEvent_t e1, ntsm_eval_cross_times &tm)
+ * tm.upload_ms (added).  The whole of staging for a caller that reads the dense buffer itself (ntsm_eval_profile.hip). */
+static inline int upload(const void *db, uint64_t stride, uint32_t first, uint32_t count, uint32_t n_sites, uint32_t *d_raw, ntsm_eval_cross_times &tm)
 {
 	const uint64_t row_bytes = 8ull * n_sites;
 	const auto t = wall::now();
 	HIPCHK(hipMemcpy2D(d_raw, row_bytes, (const char *) db + (uint64_t) first * stride, stride, row_bytes, count, hipMemcpyHostToDevice));
 	tm.upload_ms += ms_since(t);
+	return 0;
+}
+
+/* That copy; then, between e0 and e1, with d_at the transpose to at / cg / term [site][count] and with d_geno the tallies.
+ * It waits for nothing: a caller adds the interval (e0, e1) to tm.prepare_kernel_ms once it has waited for e1 or for a later
+ * event of its own, so a walk over chunks keeps the one wait per chunk it has. */
+static inline int stage(const void *db, uint64_t stride, uint32_t first, uint32_t count, uint32_t n_sites, uint32_t min_cov, uint32_t *d_raw, uint32_t *d_at,
+		uint32_t *d_cg, double *d_term, uint32_t *d_geno, hipEvent_t e0, hipEvent_t e1, ntsm_eval_cross_times &tm)
+{
+	const int rc = upload(db, stride, first, count, n_sites, d_raw, tm);
+	if (rc) return rc;
 	HIPCHK(hipEventRecord(e0, 0));
 	if (d_at) {
 		launch_prepare(d_raw, count, n_sites, min_cov, d_at, d_cg, d_term);

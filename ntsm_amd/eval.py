@@ -1,6 +1,6 @@
 """ctypes plumbing for include/ntsm_eval_hip.h (all-pairs scoring of ntsmEval on the GPU, its PCA-guided search, queries and
-that search against a cohort store, the pairs inside a store, one store against another and the search between two); used by
-tests and tools.
+that search against a cohort store, the pairs inside a store, one store against another, the search between two and the QC
+tables of a store); used by tests and tools.
 Loaded on demand: `import ntsm_amd.eval`.  Fails loudly when libntsm_eval_hip.so has not been built."""
 import ctypes as C
 import os
@@ -527,3 +527,42 @@ def between_score_pairs(a, b, pi, pk, site_map=None, min_cov=1, chunk=0, device=
     if rc:
         raise RuntimeError("ntsm_eval_between_score_pairs failed: %d" % rc)
     return out, times
+
+
+# ---- the QC tables of a cohort store (ntsmEval --qc; include/ntsm_eval_hip.h: ntsm_eval_store_profile)
+lib.ntsm_eval_store_profile.restype = C.c_int
+lib.ntsm_eval_store_profile.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.POINTER(CrossTimes)]
+
+
+def store_profile(db, min_cov=1, db_chunk=0, device=0, geno=True, tally=True, cov=True):
+    """db: uint32 [n_db][n_sites][2] or Records.  Returns (geno [n_db][3] = hets, homs, miss per sample as cross()'s; tally
+    [n_sites][4] = homAT, homCG, het, miss per site; cov uint64 [n_sites] = the raw coverage sum per site; times).  An output
+    switched off is passed as NULL and returned as None."""
+    r = _records(db)
+    g = np.zeros((r.n, 3), dtype=np.uint32) if geno else None
+    t = np.zeros((r.m, 4), dtype=np.uint32) if tally else None
+    c = np.zeros(r.m, dtype=np.uint64) if cov else None
+    times = CrossTimes()
+    rc = lib.ntsm_eval_store_profile(device, r.address, r.stride, r.n, r.m, min_cov, db_chunk, *[None if a is None else a.ctypes.data for a in (g, t, c)],
+                                     C.byref(times))
+    if rc:
+        raise RuntimeError("ntsm_eval_store_profile failed: %d" % rc)
+    return g, t, c, times
+
+
+def site_table_text(locus, tally, cov, n_samples):
+    """The bytes of `ntsmEval --qc --sites-out` for these integers (ntsm_amd/csrc/host/eval_qc.hpp through libntsm_host.so):
+    locus: IDs; tally [n_sites][4]; cov [n_sites]."""
+    from .capi import HO
+    tally = np.ascontiguousarray(tally, dtype=np.uint32).reshape(-1, 4)
+    cov = np.ascontiguousarray(cov, dtype=np.uint64)
+    ids = (C.c_char_p * len(locus))(*[s.encode() for s in locus])
+    out, ln = C.c_void_p(), C.c_size_t()
+    rc = HO.ntsm_host_site_table(ids, len(locus), tally.ctypes.data_as(C.POINTER(C.c_uint32)), cov.ctypes.data_as(C.POINTER(C.c_uint64)), n_samples,
+                                 C.byref(out), C.byref(ln))
+    if rc:
+        raise RuntimeError("ntsm_host_site_table failed: %d" % rc)
+    data = C.string_at(out, ln.value)
+    HO.ntsm_host_free(out)
+    return data

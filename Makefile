@@ -9,7 +9,8 @@
 #                                                  PCA-guided search against one (--index / --near), and both runs over
 #                                                  the store's own samples (--within / --within-near), and one store
 #                                                  against another (--between) and the PCA-guided search between
-#                                                  two (--between-near), and the QC tables of a store (--qc)
+#                                                  two (--between-near), and the QC tables of a store (--qc), and the
+#                                                  cross-sample contamination check over one (--contam)
 #   ntsm_amd/libntsm_vcf_hip.so, build/ntsmVCF     multi-sample VCF to PCA matrix + centre file (HIP library + CLI mirror);
 #                                                  with --rotation also the PCA, through libntsm_pca_hip.so
 #                                                  with --counts / --store the genotypes as counts files and cohort-store records
@@ -90,13 +91,16 @@ xlib:
 #   table differs in front of the projection and the listed-pair scorer; its candidate search is ntsm_eval_near.hip's kernels
 # + the QC tables of a store (--qc): ntsm_eval_profile.hip, one fused kernel over each chunk's dense rows; the chunk rule and the
 #   2-D copy are ntsm_eval_chunk.h's, the site table's text is host code (host/eval_qc.hpp)
+# + the cross-sample contamination check over a store (--contam): ntsm_eval_contam.hip, the rectangle of ordered pairs (target,
+#   source) in integers; the chunk rule and the 2-D copy are ntsm_eval_chunk.h's, the band rule and both tables' text are host
+#   code (host/eval_contam.hpp)
 EVALSRC := $(CSRC)/ntsm_eval.hip $(CSRC)/ntsm_eval_pca.hip $(CSRC)/ntsm_eval_cross.hip $(CSRC)/ntsm_eval_near.hip $(CSRC)/ntsm_eval_within.hip \
-           $(CSRC)/ntsm_eval_between.hip $(CSRC)/ntsm_eval_between_near.hip $(CSRC)/ntsm_eval_profile.hip
+           $(CSRC)/ntsm_eval_between.hip $(CSRC)/ntsm_eval_between_near.hip $(CSRC)/ntsm_eval_profile.hip $(CSRC)/ntsm_eval_contam.hip
 ntsm_amd/libntsm_eval_hip.so: $(EVALSRC) $(CSRC)/ntsm_eval_score.h $(CSRC)/ntsm_eval_chunk.h $(CSRC)/ntsm_eval_pca.h $(CSRC)/ntsm_hip_scope.h $(CSRC)/xprec.h \
                               $(HOST)/eval_within.hpp $(HOST)/eval_between.hpp $(HOST)/eval_store.hpp include/ntsm_eval_hip.h
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -shared -o $@ $(EVALSRC)
 
-build/ntsmEval: $(HOST)/ntsm_eval_main.cpp $(HOST)/cli.hpp $(HOST)/eval_store.hpp $(HOST)/eval_index.hpp $(HOST)/eval_qc.hpp $(HOST)/eval_within.hpp $(HOST)/eval_between.hpp $(HOST)/crc32_fast.cpp $(HOST)/crc32_fast.hpp \
+build/ntsmEval: $(HOST)/ntsm_eval_main.cpp $(HOST)/cli.hpp $(HOST)/eval_store.hpp $(HOST)/eval_index.hpp $(HOST)/eval_qc.hpp $(HOST)/eval_contam.hpp $(HOST)/eval_within.hpp $(HOST)/eval_between.hpp $(HOST)/crc32_fast.cpp $(HOST)/crc32_fast.hpp \
                 $(HOST)/gz_stream.hpp $(CSRC)/xprec.h include/ntsm_eval_hip.h ntsm_amd/libntsm_eval_hip.so
 	@mkdir -p build
 	$(CXX) $(CXXFLAGS) -ffp-contract=off -o $@ $(HOST)/ntsm_eval_main.cpp $(HOST)/crc32_fast.cpp -Lntsm_amd -lntsm_eval_hip -lz \
@@ -136,6 +140,13 @@ between_near_check: build/eval_between_near_check
 build/eval_between_near_check: tools/eval_between_near_check.cpp $(HOST)/eval_between.hpp $(HOST)/eval_within.hpp $(HOST)/eval_store.hpp
 	@mkdir -p build
 	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ tools/eval_between_near_check.cpp
+
+# the band rule and the text of both tables of --contam likewise (tools/eval_contam_check.cpp; not part of `all`)
+contam_check: build/eval_contam_check
+	build/eval_contam_check
+build/eval_contam_check: tools/eval_contam_check.cpp $(HOST)/eval_contam.hpp include/ntsm_eval_hip.h
+	@mkdir -p build
+	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ tools/eval_contam_check.cpp
 
 # the host side of `ntsmCount --cohort` likewise: manifest parser, site lists, and the record builder against counts text +
 # --pack, byte for byte (tools/cohort_count_check.cpp; not part of `all`)
@@ -233,4 +244,4 @@ build/gather_bench: tools/gather_bench.hip
 clean:
 	rm -rf build ntsm_amd/*.so
 	$(MAKE) -C oracle clean
-.PHONY: all oracle_all ref_gpu_binding clean ablation abl_tab tab m12 xlib store_check index_check within_check between_check between_near_check cohort_check
+.PHONY: all oracle_all ref_gpu_binding clean ablation abl_tab tab m12 xlib store_check index_check within_check between_check between_near_check contam_check cohort_check

@@ -276,6 +276,45 @@ int ntsm_eval_between_score_pairs(int device, const void *a_counts, uint64_t a_s
 int ntsm_eval_store_profile(int device, const void *db_counts, uint64_t db_stride_bytes, uint32_t n_db, uint32_t n_sites,
 		uint32_t min_cov, uint32_t db_chunk, uint32_t *db_geno, uint32_t *site_tally, uint64_t *site_cov, ntsm_eval_cross_times *times);
 
+/* ---- The cross-sample contamination check over a cohort store (ntsmEval --contam; ntsm_amd/csrc/ntsm_eval_contam.hip; DESIGN.md
+ * section 9.7): the n_db x n_db rectangle of ordered pairs (target q, source d) of the store's own samples, in bands of rows.
+ * The reference has no such run; the contract is this text.  db_counts / db_stride_bytes / db_chunk as for ntsm_eval_cross; the
+ * mapping must outlive the session.  c = min_cov (strict >, as in the scoring), D = min_depth.
+ *
+ * A site with target counts (a, g) = (countAT, countCG): t = uint64(a) + uint64(g), m = min(a, g).  It is informative for q iff
+ *   t >= D and 4 * m < t, in 64 bits: the minor allele is below a quarter.  a == g is never informative, so the major allele
+ *   is AT iff a > g.  With x the source's count of q's minor allele there and y its count of q's major allele,
+ *   carries = x > c, has_major = y > c, and the site falls in
+ *     class 0, lack: !carries && has_major      class 1, het: carries && has_major      class 2, opp: carries && !has_major
+ *   or, with neither (a miss of d), is skipped for this pair.  In its class k: sites[k] += 1, minor[k] += m, depth[k] += t.
+ *   The diagonal (q, q) is a pair like any other.  Per target alone, over its informative sites: tally = (sites, sum of m, sum
+ *   of t).  All sums are integer sums: two calls give the same bits.
+ *
+ * ntsm_eval_contam_open: the store is resident when the chunk rule, asked at 16 bytes per sample and site (at, cg and the dense
+ *   copy they are transposed from), answers n_db: it is uploaded, transposed and tallied once, here.  Otherwise, or when a
+ *   non-zero db_chunk < n_db forces it, it is streamed: every _rows call uploads its band's rows and walks all n_db columns in
+ *   chunks of db_chunk; device memory is then O((n_rows + chunk) * n_sites + n_rows * n_db).
+ *   Returns 0, -2 HIP error, -1 bad argument, before any HIP call: a NULL it needs, a stride below 8 * n_sites or not a multiple
+ *   of 4.  n_db == 0 or n_sites == 0: a session without device work.
+ * ntsm_eval_contam_rows: targets row_first ... row_first + n_rows - 1 against every sample as a source.
+ *   out: [n_rows][n_db].  out[(q - row_first) * n_db + d] is the record of (q, d); pad is 0.
+ *   tally (may be NULL): [n_rows][3] = sites, minor reads, depth of each target of the band.
+ *   times (may be NULL): cross_kernel_ms is the rectangle kernel, prepare_kernel_ms the transposes and tallies; chunks counts
+ *     the column chunks this call uploaded, so it is 0 exactly when the store is resident; the first call on a resident store
+ *     also reports the upload and preparation of open.
+ *   Returns 0, -2, -1 (row_first + n_rows > n_db, n_rows == 0, a NULL it needs), the -1 before any HIP call.  n_sites == 0:
+ *   zeroed outputs, no device work; of n_db == 0 there is no range to take. */
+typedef struct ntsm_eval_contam_record { uint64_t minor[3], depth[3]; uint32_t sites[3], pad /* 0 */; } ntsm_eval_contam_record;  /* 64 bytes */
+typedef struct ntsm_eval_contam_session ntsm_eval_contam_session;
+int ntsm_eval_contam_open(int device, const void *db_counts, uint64_t db_stride_bytes, uint32_t n_db, uint32_t n_sites,
+		uint32_t min_cov, uint32_t min_depth, uint32_t db_chunk, ntsm_eval_contam_session **h);
+int ntsm_eval_contam_rows(ntsm_eval_contam_session *h, uint32_t row_first, uint32_t n_rows, ntsm_eval_contam_record *out,
+		uint64_t *tally, ntsm_eval_cross_times *times);
+void ntsm_eval_contam_close(ntsm_eval_contam_session *h);
+/* For measurements and tests only: force the rectangle kernel's workgroup width (64 or 256) and target group (1, 2 or 4) of later
+ * _rows calls in this process; 0 = the library's rule (ntsm_eval_cross's, inherited).  Returns 0, -1 for another value. */
+int ntsm_eval_contam_tune(uint32_t width, uint32_t target_group);
+
 #ifdef __cplusplus
 }
 #endif

@@ -111,6 +111,18 @@ int ntsm_host_format_summary(const ntsm_sites *s, const uint64_t *counts, uint64
 int ntsm_host_site_table(const char *const *locus, uint32_t n_sites, const uint32_t *tally, const uint64_t *site_cov, uint64_t n_samples,
 		char **out, size_t *len);
 
+/* The tables of `ntsmEval --contam` (ntsm_amd/csrc/host/eval_contam.hpp), for tests.  _rows: the lines of the band of targets
+ * row_first ... row_first + n_rows - 1 as stdout has them, without the header: names[n_db]; rec [n_rows][n_db] and tally
+ * [n_rows][3] as ntsm_eval_contam_rows gives them (include/ntsm_eval_hip.h; rec is an array of its 64-byte records); all,
+ * min_excess, min_explained = -a, --contam-min, --contam-explained.  _sample_table: the --samples-out file, header line included,
+ * tally [n_samples][3].  *out is freed with ntsm_host_free.  Both return 0, -1 for a NULL they need or a band past n_db.
+ * _band_rows: the band rule, the targets a band from row_first takes under `limit` records; 0 where there is no such row. */
+struct ntsm_eval_contam_record;
+int ntsm_host_contam_rows(const char *const *names, uint32_t n_db, uint32_t row_first, uint32_t n_rows, const struct ntsm_eval_contam_record *rec,
+		const uint64_t *tally, int all, double min_excess, double min_explained, char **out, size_t *len);
+int ntsm_host_contam_sample_table(const char *const *names, uint32_t n_samples, const uint64_t *tally, char **out, size_t *len);
+uint32_t ntsm_host_contam_band_rows(uint32_t row_first, uint32_t n_db, uint64_t limit);
+
 #ifdef __cplusplus
 }
 #endif

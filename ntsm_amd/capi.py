@@ -136,6 +136,10 @@ _sig(HO, "ntsm_host_format_counts", C.c_int, [C.c_void_p, u64p, C.c_uint64, C.PO
 _sig(HO, "ntsm_host_format_summary", C.c_int, [C.c_void_p, u64p, C.c_uint64, C.c_uint64, C.c_uint64,
                                                 C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), u64p])
 _sig(HO, "ntsm_host_site_table", C.c_int, [C.POINTER(C.c_char_p), C.c_uint32, u32p, u64p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)])
+_sig(HO, "ntsm_host_contam_rows", C.c_int, [C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, u64p, C.c_int, C.c_double, C.c_double,
+                                            C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)])
+_sig(HO, "ntsm_host_contam_sample_table", C.c_int, [C.POINTER(C.c_char_p), C.c_uint32, u64p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)])
+_sig(HO, "ntsm_host_contam_band_rows", C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint64])
 
 SY = synth_lib
 _sig(SY, "ntsm_synth_sites", C.c_int, [C.c_uint64, C.c_uint32, C.c_uint, u8p, C.c_char_p, u64p])

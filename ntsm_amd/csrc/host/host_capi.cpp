@@ -12,6 +12,7 @@
 #include "gz_stream.hpp"
 #include "pack2.hpp"
 #include "early_ingest.hpp"
+#include "eval_contam.hpp"
 #include "eval_qc.hpp"
 #include "host_shape.hpp"
 #include "parallel_fastq.hpp"
@@ -387,6 +388,30 @@ int ntsm_host_site_table(const char *const *locus, uint32_t n_sites, const uint3
 	for (uint32_t s = 0; s < n_sites; ++s) ntsm::eval_qc::site_line(text, locus[s], tally + 4 * (size_t) s, site_cov[s], n_samples);
 	*out = dup_string(text, len);
 	return 0;
+}
+
+int ntsm_host_contam_rows(const char *const *names, uint32_t n_db, uint32_t row_first, uint32_t n_rows, const ntsm_eval_contam_record *rec,
+		const uint64_t *tally, int all, double min_excess, double min_explained, char **out, size_t *len)
+{
+	if (!out || !len || (uint64_t) row_first + n_rows > n_db || (n_rows && (!names || !rec || !tally))) return -1;
+	std::string text;
+	ntsm::eval_contam::band_text(text, names, n_db, row_first, n_rows, rec, tally, all != 0, min_excess, min_explained);
+	*out = dup_string(text, len);
+	return 0;
+}
+
+int ntsm_host_contam_sample_table(const char *const *names, uint32_t n_samples, const uint64_t *tally, char **out, size_t *len)
+{
+	if (!out || !len || (n_samples && (!names || !tally))) return -1;
+	std::string text = ntsm::eval_contam::kSampleHeader;
+	for (uint32_t i = 0; i < n_samples; ++i) ntsm::eval_contam::sample_line(text, names[i], tally + 3 * (size_t) i);
+	*out = dup_string(text, len);
+	return 0;
+}
+
+uint32_t ntsm_host_contam_band_rows(uint32_t row_first, uint32_t n_db, uint64_t limit)
+{
+	return n_db == 0 || row_first >= n_db ? 0 : ntsm::eval_contam::band_rows(row_first, n_db, limit);
 }
 
 } // extern "C"

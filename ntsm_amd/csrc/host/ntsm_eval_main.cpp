@@ -25,7 +25,9 @@
  *   --qc STORE [-p ROT -n NORM] [--sites-out FILE]   computeScoreSingle's table (:541-585) with one row per sample of the store,
  *                             and per-site tallies under the same rule: ntsm_eval_store_profile; the PC columns of -p from
  *                             ntsm_eval_project_store
- * --within, --within-near, --between, --between-near and --qc read no counts file.  Not built, and refused: -b (the debug ground-truth mode) and -p without a
+ *   --contam STORE [--samples-out FILE]   is a sample a mixture, and of whom: every ordered pair (target, source) of the store,
+ *                             in bands of targets: ntsm_eval_contam_open / _rows; the table's text is eval_contam.hpp's
+ * --within, --within-near, --between, --between-near, --qc and --contam read no counts file.  Not built, and refused: -b (the debug ground-truth mode) and -p without a
  * normalization file (the reference dies in an assert).  Pinned to the reference: stdout equals, byte for byte, that of the
  * unmodified scoring class (oracle/ref_eval_driver.cpp -> oracle/_ref/ref_ntsmEval -t 1) and its recordings,
  * tests/test_eval_reference.py.
@@ -48,6 +50,7 @@
 #include "../../../include/ntsm_eval_hip.h"
 #include "cli.hpp"
 #include "eval_between.hpp"
+#include "eval_contam.hpp"
 #include "eval_index.hpp"
 #include "eval_qc.hpp"
 #include "eval_store.hpp"
@@ -75,6 +78,10 @@ struct Opt {                                 /* src/Options.h:44-55 */
 	std::string betweenNear;                 /* --between-near STORE_A; STORE_B is the one positional argument */
 	std::string qc, sitesOut;                /* --qc STORE: the QC table of the store's samples; --sites-out FILE: its per-site table */
 	bool sitesOutGiven = false;
+	std::string contam, samplesOut;          /* --contam STORE: the contamination check over the store; --samples-out FILE: its per-sample table */
+	unsigned contamDepth = ntsm::eval_contam::kMinDepth, contamRows = 0;   /* --contam-depth D; --contam-rows N: targets per band, 0 = the band rule */
+	double contamMin = ntsm::eval_contam::kMinExcess, contamExplained = ntsm::eval_contam::kMinExplained;   /* --contam-min X, --contam-explained Y */
+	bool samplesOutGiven = false, contamFlagGiven = false;
 	bool minCovGiven = false, dimGiven = false;
 	bool onlyMerge = false;
 	unsigned dim = 20;                       /* src/Options.h:22, 35-39: the PCA search */
@@ -218,6 +225,28 @@ void printHelpDialog()
 	    "      --sites-out = FILE     With --qc: write one line per locus of STORE to FILE:\n"
 	    "                             #locusID called miss homAT homCG het freqAT hetObs hetExp\n"
 	    "                             meanCov, the genotypes by the scoring's rule at -c.\n"
+	    "      --contam = STORE       Is a sample of STORE a mixture, and of which other sample?\n"
+	    "                             One row per ordered pair (sample, source) of the store:\n"
+	    "                             at the sites where the sample looks homozygous (minor\n"
+	    "                             allele below a quarter of at least --contam-depth reads)\n"
+	    "                             the share of minor-allele reads where the source lacks\n"
+	    "                             that allele (rateLack), has both (rateHet) or has only it\n"
+	    "                             (rateOpp); excess = rateOpp - rateLack; explained =\n"
+	    "                             1 - rateLack / the sample's rate over all such sites.\n"
+	    "                             Without -a only rows with excess >= --contam-min and\n"
+	    "                             explained >= --contam-explained. -c is the coverage above\n"
+	    "                             which the source carries an allele. Takes no FILES. Not\n"
+	    "                             with -p, -n, -b, -e or -o.\n"
+	    "      --contam-depth = INT   Least depth of a site of the sample [" << std::to_string(d.contamDepth) << "]\n"
+	    "      --contam-min = FLOAT   Least excess of a printed row [" << std::to_string(d.contamMin) << "]\n"
+	    "      --contam-explained = FLOAT\n"
+	    "                             Least explained share of a printed row [" << std::to_string(d.contamExplained) << "]\n"
+	    "                             Both defaults are conventions to override: they come from\n"
+	    "                             one simulation, not from real data.\n"
+	    "      --contam-rows = INT    Samples per band of --contam [0: as many as fit in 1 GiB\n"
+	    "                             of records]. For tests and measurements.\n"
+	    "      --samples-out = FILE   With --contam: write one line per sample of STORE to\n"
+	    "                             FILE: #sample sites minorReads depth rateAll.\n"
 	    "Not in this build: -b (debug mode of the PCA search); the PCA-guided search (-p)\n"
 	    "against a store (--index and --near are that search); merging (-e) from a store.\n" << std::endl;
 	exit(EXIT_SUCCESS);
@@ -334,6 +363,7 @@ template <typename H, void (*Close)(H *)> struct Handle {   /* closes the librar
 typedef Handle<ntsm_eval_session, ntsm_eval_close> Session;
 typedef Handle<ntsm_eval_within_session, ntsm_eval_within_close> WithinSession;
 typedef Handle<ntsm_eval_between_session, ntsm_eval_between_close> BetweenSession;
+typedef Handle<ntsm_eval_contam_session, ntsm_eval_contam_close> ContamSession;
 
 typedef std::chrono::steady_clock Clock;
 double msSince(Clock::time_point t) { return std::chrono::duration<double, std::milli>(Clock::now() - t).count(); }
@@ -412,7 +442,8 @@ int scorePCA(const Counts &c, std::vector<Genotype> &g, const Opt &opt, ntsm_eva
 }
 
 constexpr int kOptPack = 1000, kOptAgainst = 1001, kOptIndex = 1002, kOptNear = 1003, kOptWithin = 1004, kOptWithinNear = 1005,
-              kOptWithinRows = 1006, kOptBetween = 1007, kOptBetweenRows = 1008, kOptBetweenNear = 1009, kOptQc = 1010, kOptSitesOut = 1011;   /* long-only: no letter of the reference's option string is taken */
+              kOptWithinRows = 1006, kOptBetween = 1007, kOptBetweenRows = 1008, kOptBetweenNear = 1009, kOptQc = 1010, kOptSitesOut = 1011,
+              kOptContam = 1012, kOptContamDepth = 1013, kOptContamMin = 1014, kOptContamExplained = 1015, kOptContamRows = 1016, kOptSamplesOut = 1017;   /* long-only: no letter of the reference's option string is taken */
 
 /* --pack STORE FILES...: no GPU */
 int packStore(const Counts &c, const Opt &opt)
@@ -999,7 +1030,7 @@ int searchBetween(Opt &opt, const std::string &storeB, Clock::time_point t0)
 	return 0;
 }
 
-/* --sites-out FILE, opened before any GPU work and without touching what it holds: a file this run made is removed again
+/* --sites-out FILE (and --samples-out FILE of --contam), opened before any GPU work and without touching what it holds: a file this run made is removed again
  * unless the table gets written */
 struct SitesFile {
 	std::string path;
@@ -1089,6 +1120,67 @@ int qcStore(const Opt &opt, Clock::time_point t0)
 	return 0;
 }
 
+/* --contam STORE [-c N] [--contam-depth D] [--contam-min X] [--contam-explained Y] [-a] [--contam-rows N] [--samples-out FILE]:
+ * is a sample of the store a mixture, and of which other sample.  The rectangle of ordered pairs
+ * (target, source) comes in bands of targets (eval_contam.hpp's rule, or --contam-rows), printed band by band, each band's call
+ * bringing its targets' tallies; the rates, the filter and the text are that header's. */
+int contamStore(const Opt &opt, Clock::time_point t0)
+{
+	namespace ct = ntsm::eval_contam;
+	ntsm::eval_store::View store;
+	SitesFile samples;
+	const auto tMap = Clock::now();
+	try {
+		openStore(opt.contam, 0, "scores", store, nullptr);
+		if (opt.samplesOutGiven && !samples.open(opt.samplesOut)) throw ntsm::eval_store::Error("cannot write " + opt.samplesOut);
+	} catch (const std::exception &e) {
+		ntsm::refuse(e.what());
+	}
+	const double mapMs = msSince(tMap);
+	const uint32_t n = (uint32_t) store.h.n_samples, m = store.h.n_sites;
+	if (opt.verbose > 1) std::cerr << "Mapped " << opt.contam << ". Now checking its " << n << " samples against each other." << std::endl;
+	ContamSession session;
+	int rc = ntsm_eval_contam_open(opt.device, store.counts(0), store.h.stride, n, m, opt.minCov, opt.contamDepth, 0, &session.h);
+	if (rc) return gpuFail("opening the store", rc);
+	std::vector<std::string> nameOf(n);
+	std::vector<const char *> names(n);
+	for (uint32_t d = 0; d < n; ++d) { nameOf[d] = store.name(d); names[d] = nameOf[d].c_str(); }
+	std::vector<ntsm_eval_contam_record> rec;
+	std::vector<uint64_t> tally((size_t) n * 3);
+	ntsm_eval_cross_times sum {};
+	uint32_t bands = 0;
+	double printMs = 0;
+	std::string temp;
+	for (uint32_t first = 0; first < n; ++bands) {
+		const uint32_t rows = opt.contamRows ? std::min(opt.contamRows, n - first) : ct::band_rows(first, n, ct::kBandRecords);
+		rec.resize((size_t) rows * n);
+		ntsm_eval_cross_times times {};
+		rc = ntsm_eval_contam_rows(session.h, first, rows, rec.data(), tally.data() + (size_t) first * 3, &times);
+		if (rc) return gpuFail("checking the store", rc);
+		sum.upload_ms += times.upload_ms; sum.prepare_kernel_ms += times.prepare_kernel_ms; sum.cross_kernel_ms += times.cross_kernel_ms;
+		sum.download_ms += times.download_ms; sum.chunks += times.chunks;
+		const auto tPrint = Clock::now();
+		if (first == 0) std::cout << ct::kHeader;
+		temp.clear();
+		ct::band_text(temp, names.data(), n, first, rows, rec.data(), tally.data() + (size_t) first * 3, opt.all, opt.contamMin, opt.contamExplained);
+		std::cout << temp;
+		printMs += msSince(tPrint);
+		first += rows;
+	}
+	std::cout.flush();
+	if (opt.samplesOutGiven) {
+		std::string text = ct::kSampleHeader;
+		for (uint32_t i = 0; i < n; ++i) ct::sample_line(text, names[i], &tally[(size_t) i * 3]);
+		if (!samples.write(text)) { std::cerr << PROGRAM ": cannot write " << opt.samplesOut << std::endl; return 1; }
+	}
+	if (opt.verbose > 1)
+		std::cerr << "store contam: " << (sum.chunks ? "streamed" : "resident") << ", " << bands << " bands, " << sum.chunks << " chunks, map " << mapMs
+		          << " ms, upload " << sum.upload_ms << " ms, prepare " << sum.prepare_kernel_ms << " ms, rectangle kernel " << sum.cross_kernel_ms
+		          << " ms, download " << sum.download_ms << " ms, print " << printMs << " ms" << std::endl;
+	printTime(t0);
+	return 0;
+}
+
 /* what no store run goes with */
 void refuseDebugAndMerge(const Opt &opt, const char *mode)
 {
@@ -1101,7 +1193,7 @@ void refuseDebugAndMerge(const Opt &opt, const char *mode)
 int main(int argc, char **argv)
 {
 	Opt opt;
-	bool die = false, storeMode = false, nearMode = false, withinMode = false, betweenMode = false, betweenNearMode = false, qcMode = false;
+	bool die = false, storeMode = false, nearMode = false, withinMode = false, betweenMode = false, betweenNearMode = false, qcMode = false, contamMode = false;
 	static struct option long_options[] = {
 		{ "score_thresh", required_argument, nullptr, 's' }, { "all", no_argument, nullptr, 'a' },
 		{ "min_cov", required_argument, nullptr, 'c' }, { "skew", required_argument, nullptr, 'w' },
@@ -1118,6 +1210,9 @@ int main(int argc, char **argv)
 		{ "within-rows", required_argument, nullptr, kOptWithinRows }, { "between", required_argument, nullptr, kOptBetween },
 		{ "between-rows", required_argument, nullptr, kOptBetweenRows }, { "between-near", required_argument, nullptr, kOptBetweenNear },
 		{ "qc", required_argument, nullptr, kOptQc }, { "sites-out", required_argument, nullptr, kOptSitesOut },
+		{ "contam", required_argument, nullptr, kOptContam }, { "contam-depth", required_argument, nullptr, kOptContamDepth },
+		{ "contam-min", required_argument, nullptr, kOptContamMin }, { "contam-explained", required_argument, nullptr, kOptContamExplained },
+		{ "contam-rows", required_argument, nullptr, kOptContamRows }, { "samples-out", required_argument, nullptr, kOptSamplesOut },
 		{ nullptr, 0, nullptr, 0 } };
 	int ch;
 	while ((ch = getopt_long(argc, argv, "t:vhs:c:m:aw:g:p:n:d:r:e:o1:2:S:l:b:G:", long_options, nullptr)) != -1) {
@@ -1161,6 +1256,24 @@ int main(int argc, char **argv)
 			break;
 		case kOptQc: opt.qc = optarg; qcMode = true; break;
 		case kOptSitesOut: opt.sitesOut = optarg; opt.sitesOutGiven = true; break;
+		case kOptContam: opt.contam = optarg; contamMode = true; break;
+		case kOptContamDepth:
+			if (optarg[0] == '-' || !ntsm::read_whole(optarg, opt.contamDepth)) ntsm::refuse(std::string("--contam-depth takes a number of reads, not ") + optarg);
+			opt.contamFlagGiven = true;
+			break;
+		case kOptContamMin:
+			if (!ntsm::read_whole(optarg, opt.contamMin)) ntsm::refuse(std::string("--contam-min takes a number, not ") + optarg);
+			opt.contamFlagGiven = true;
+			break;
+		case kOptContamExplained:
+			if (!ntsm::read_whole(optarg, opt.contamExplained)) ntsm::refuse(std::string("--contam-explained takes a number, not ") + optarg);
+			opt.contamFlagGiven = true;
+			break;
+		case kOptContamRows:
+			if (optarg[0] == '-' || !ntsm::read_whole(optarg, opt.contamRows)) ntsm::refuse(std::string("--contam-rows takes a number of samples, not ") + optarg);
+			opt.contamFlagGiven = true;
+			break;
+		case kOptSamplesOut: opt.samplesOut = optarg; opt.samplesOutGiven = true; break;
 		case '?': die = true; break;
 		default: break;                              /* m: read by the reference, without effect */
 		}
@@ -1168,6 +1281,12 @@ int main(int argc, char **argv)
 	Counts c;
 	while (optind < argc) c.files.emplace_back(argv[optind++]);
 	const char *sevenRuns = "--pack, --against, --index, --near, --within, --within-near and --between are seven runs: give one of them";
+	if (contamMode && (storeMode || nearMode || withinMode || betweenMode || betweenNearMode || qcMode))
+		ntsm::refuse("--contam checks one store for cross-sample contamination and is a run of its own: it goes with none of --pack, --against, --index, "
+		             "--near, --within, --within-near, --between, --between-near and --qc");
+	if (opt.contamFlagGiven && !contamMode)
+		ntsm::refuse("--contam-depth, --contam-min, --contam-explained and --contam-rows belong to --contam: give them with --contam STORE");
+	if (opt.samplesOutGiven && !contamMode) ntsm::refuse("--samples-out is the per-sample table of --contam: give it with --contam STORE");
 	if (qcMode && (storeMode || nearMode || withinMode || betweenMode || betweenNearMode))
 		ntsm::refuse("--qc prints the QC tables of one store and is a run of its own: it goes with none of --pack, --against, --index, --near, --within, "
 		             "--within-near, --between and --between-near");
@@ -1209,6 +1328,13 @@ int main(int argc, char **argv)
 		return near ? searchWithin(opt, t0) : scoreWithin(opt, t0);
 	}
 	if (opt.withinRowsGiven) ntsm::refuse("--within-rows sets the bands of --within: give it with --within STORE");
+	if (contamMode) {                                    /* --contam: every refusal that needs no store, then the run */
+		if (!c.files.empty()) ntsm::refuse("--contam takes no input files: it checks the samples of the store against each other");
+		if (!opt.pca.empty() || !opt.norm.empty()) ntsm::refuse("--contam reads allele counts, not projections, and takes no -p and no -n");
+		refuseDebugAndMerge(opt, "--contam");
+		ntsm::try_help_if(die);
+		return contamStore(opt, Clock::now());
+	}
 	if (qcMode) {                                        /* --qc: every refusal that needs no store, then the run */
 		if (!c.files.empty()) ntsm::refuse("--qc takes no input files: it prints the QC table of the samples of the store");
 		refuseDebugAndMerge(opt, "--qc");

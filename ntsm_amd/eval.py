@@ -1,6 +1,6 @@
 """ctypes plumbing for include/ntsm_eval_hip.h (all-pairs scoring of ntsmEval on the GPU, its PCA-guided search, queries and
-that search against a cohort store, the pairs inside a store, one store against another, the search between two and the QC
-tables of a store); used by tests and tools.
+that search against a cohort store, the pairs inside a store, one store against another, the search between two, the QC
+tables of a store and the contamination check over one); used by tests and tools.
 Loaded on demand: `import ntsm_amd.eval`.  Fails loudly when libntsm_eval_hip.so has not been built."""
 import ctypes as C
 import os
@@ -566,3 +566,109 @@ def site_table_text(locus, tally, cov, n_samples):
     data = C.string_at(out, ln.value)
     HO.ntsm_host_free(out)
     return data
+
+
+# ---- the cross-sample contamination check over a cohort store (ntsmEval --contam; include/ntsm_eval_hip.h: ntsm_eval_contam_open ...
+# _tune).  Rows are targets, columns sources, both the store's samples.
+CONTAM_RECORD = np.dtype([("minor", "<u8", 3), ("depth", "<u8", 3), ("sites", "<u4", 3), ("pad", "<u4")])
+assert CONTAM_RECORD.itemsize == 64
+lib.ntsm_eval_contam_open.restype = C.c_int
+lib.ntsm_eval_contam_open.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+lib.ntsm_eval_contam_rows.restype = C.c_int
+lib.ntsm_eval_contam_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(CrossTimes)]
+lib.ntsm_eval_contam_close.restype = None
+lib.ntsm_eval_contam_close.argtypes = [C.c_void_p]
+lib.ntsm_eval_contam_tune.restype = C.c_int
+lib.ntsm_eval_contam_tune.argtypes = [C.c_uint32, C.c_uint32]
+
+
+def contam_tune(width, target_group):
+    """Force the workgroup width (64 or 256) and target group (1, 2 or 4) of later Contam.rows calls in this process; 0 = the
+    library's rule."""
+    rc = lib.ntsm_eval_contam_tune(width, target_group)
+    if rc:
+        raise ValueError("ntsm_eval_contam_tune(%r, %r) failed: %d" % (width, target_group, rc))
+
+
+class Contam:
+    """Every sample of a store as a target against every sample as a source (ntsm_eval_contam_open): db is uint32
+    [n_db][n_sites][2] or Records, which the session keeps alive.  db_chunk: 0 = resident if the store fits the device, else
+    streamed; a value below n_db streams the columns in chunks of it.  A context manager:
+    `with Contam(db) as s: rec, tally, times = s.rows(0, s.n)`."""
+
+    def __init__(self, db, min_cov=1, min_depth=8, db_chunk=0, device=0):
+        self.records = _records(db)
+        self.n, self.m = self.records.n, self.records.m
+        self.h = C.c_void_p()
+        rc = lib.ntsm_eval_contam_open(device, self.records.address, self.records.stride, self.n, self.m, min_cov, min_depth, db_chunk, C.byref(self.h))
+        if rc:
+            raise RuntimeError("ntsm_eval_contam_open failed: %d" % rc)
+
+    def rows(self, row_first, n_rows, tally=True):
+        """Targets row_first ... row_first + n_rows - 1 against every source: (records [n_rows, n] of CONTAM_RECORD; tally
+        uint64 [n_rows, 3] = sites, minor reads, depth of each target, or None when switched off (passed as NULL); times, a
+        CrossTimes (chunks == 0: the store is resident))."""
+        count = n_rows if 0 <= row_first and 0 <= n_rows and row_first + n_rows <= self.n else 0
+        out = np.zeros((count, self.n), dtype=CONTAM_RECORD)
+        t = np.zeros((count, 3), dtype=np.uint64) if tally else None
+        times = CrossTimes()
+        rc = lib.ntsm_eval_contam_rows(self.h, row_first, n_rows, out.ctypes.data, None if t is None else t.ctypes.data, C.byref(times))
+        if rc:
+            raise RuntimeError("ntsm_eval_contam_rows failed: %d" % rc)
+        return out, t, times
+
+    def close(self):
+        if self.h:
+            lib.ntsm_eval_contam_close(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+
+def _names(names):
+    return (C.c_char_p * len(names))(*[s.encode() for s in names])
+
+
+def _host_text(out, ln):
+    from .capi import HO
+    data = C.string_at(out, ln.value)
+    HO.ntsm_host_free(out)
+    return data
+
+
+def contam_rows_text(names, row_first, rec, tally, all_rows=False, min_excess=0.01, min_explained=0.5):
+    """The stdout lines of `ntsmEval --contam` for one band, without the header (ntsm_amd/csrc/host/eval_contam.hpp through
+    libntsm_host.so): names of all n samples; rec [n_rows][n] of CONTAM_RECORD and tally [n_rows][3] as Contam.rows gives them."""
+    from .capi import HO
+    rec = np.ascontiguousarray(rec, dtype=CONTAM_RECORD).reshape(-1, len(names))
+    tally = np.ascontiguousarray(tally, dtype=np.uint64).reshape(-1, 3)
+    out, ln = C.c_void_p(), C.c_size_t()
+    rc = HO.ntsm_host_contam_rows(_names(names), len(names), row_first, rec.shape[0], rec.ctypes.data, tally.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                  int(all_rows), min_excess, min_explained, C.byref(out), C.byref(ln))
+    if rc:
+        raise RuntimeError("ntsm_host_contam_rows failed: %d" % rc)
+    return _host_text(out, ln)
+
+
+def contam_sample_table_text(names, tally):
+    """The bytes of `ntsmEval --contam --samples-out` for these tallies [n][3], header line included."""
+    from .capi import HO
+    tally = np.ascontiguousarray(tally, dtype=np.uint64).reshape(-1, 3)
+    out, ln = C.c_void_p(), C.c_size_t()
+    rc = HO.ntsm_host_contam_sample_table(_names(names), len(names), tally.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(out), C.byref(ln))
+    if rc:
+        raise RuntimeError("ntsm_host_contam_sample_table failed: %d" % rc)
+    return _host_text(out, ln)
+
+
+def contam_band_rows(row_first, n_db, limit=(1 << 30) // 64):
+    """The band rule of --contam: the targets a band from row_first takes under `limit` records."""
+    from .capi import HO
+    return HO.ntsm_host_contam_band_rows(row_first, n_db, limit)

@@ -148,6 +148,14 @@ build/eval_contam_check: tools/eval_contam_check.cpp $(HOST)/eval_contam.hpp inc
 	@mkdir -p build
 	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ tools/eval_contam_check.cpp
 
+# the integer x87 add of the projection against the x87 itself likewise: every constructed class and 10^6 random operands, every
+# branch of ntsm_x87_acc reached (tests/xprec_check.cpp; not part of `all`)
+xprec_check: build/xprec_check
+	build/xprec_check 1000000 7
+build/xprec_check: tests/xprec_check.cpp $(CSRC)/xprec.h
+	@mkdir -p build
+	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ tests/xprec_check.cpp
+
 # the host side of `ntsmCount --cohort` likewise: manifest parser, site lists, and the record builder against counts text +
 # --pack, byte for byte (tools/cohort_count_check.cpp; not part of `all`)
 cohort_check: build/cohort_count_check
@@ -244,4 +252,4 @@ build/gather_bench: tools/gather_bench.hip
 clean:
 	rm -rf build ntsm_amd/*.so
 	$(MAKE) -C oracle clean
-.PHONY: all oracle_all ref_gpu_binding clean ablation abl_tab tab m12 xlib store_check index_check within_check between_check between_near_check contam_check cohort_check
+.PHONY: all oracle_all ref_gpu_binding clean ablation abl_tab tab m12 xlib store_check index_check within_check between_check between_near_check contam_check cohort_check xprec_check

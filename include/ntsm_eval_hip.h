@@ -51,7 +51,10 @@ int ntsm_eval_pairs(int device, const uint32_t *counts, uint32_t n_samples, uint
  *   each step acc = RN53(RN64(acc + RN64(v * rot[d][j]))), sites in order from +0.0 (x87 products and sums, a double
  *   accumulator).  The library's host code forms the products with real long double (a [site][dim][4] table: c = 0, 1/2,
  *   1 and the missing site's +0.0 * rot) and the device runs the sequential x87 add in integers (ntsm_amd/csrc/xprec.h),
- *   one lane per (sample, component).
+ *   one lane per (sample, component).  An accumulator that has overflowed stays where it is, as on the x87: from acc = +-inf
+ *   on, every finite product leaves it unchanged (inf +- finite = inf), so a component prints inf where the reference does.
+ *   Outside the promise: a table entry that is itself infinite or NaN (RN64(v * rot) beyond the x87 range, or rot not
+ *   finite), which the table has no encoding for, and a centre value with |norm[j]| beyond DBL_MAX.
  *
  * ntsm_eval_candidates: the pairs that computeScorePCA scores (:311-398), in its one-thread print order.  Rows i
  * ascending; a row with radius[i] < DBL_MAX takes every k with evalMetric(cloud[i], cloud[k]) < radius[i] (nanoflann's

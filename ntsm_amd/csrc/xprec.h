@@ -8,14 +8,24 @@
  * (x87 product and sum rounded to the 64-bit significand, then stored to a double).  The host computes the products with
  * real long double (ntsm_x64_from_ld); ntsm_x87_acc does the rest with integers: the two operands are aligned in a
  * 128-bit window with a sticky bit, added or subtracted, normalised by clz, rounded to 64 bits (RNE) and then to a double
- * (RNE, gradual underflow, overflow to infinity).  Correct for every finite input; the x87 exponent range is taken as
- * unbounded, which it is for every sum of a double and an x87 product of a double and a finite long double that does
- * not itself underflow the x87 range.  Plain C++: compiled by g++ for the CPU test (tests/test_eval_pca.py) and by hipcc
- * for the kernel.
+ * (RNE, gradual underflow, overflow to infinity).  Correct for every finite p and every acc: the x87 exponent range is taken
+ * as unbounded, which it is for every sum of a double and an x87 product of a double and a finite long double that does
+ * not itself underflow the x87 range.  An accumulator that has overflowed stays where it is, as on the x87: acc = +-inf or
+ * NaN is returned unchanged (inf +- finite = inf).  Outside the promise: a p that is itself infinite or NaN (ntsm_x64 has no
+ * encoding for one), i.e. RN64(v * rot) beyond the x87 range, and a centre value beyond DBL_MAX.  Plain C++: compiled by g++
+ * for the CPU test (tests/xprec_check.cpp through tests/test_eval_pca.py) and by hipcc for the kernel.
+ *
+ * NTSM_XP_COUNT(taken, branch) marks what nothing outside the function can see (the shift amount, the remainder, tie and carry of
+ * the RN64 step, the RN53 tie) for tests/xprec_check.cpp, which defines it before the include to count them; it expands
+ * to nothing everywhere else.
  */
 #ifndef NTSM_XPREC_H
 #define NTSM_XPREC_H
 #include <stdint.h>
+
+#ifndef NTSM_XP_COUNT
+#define NTSM_XP_COUNT(taken, branch)
+#endif
 
 #if defined(__HIPCC__)
 #define NTSM_XP_FN __host__ __device__ inline
@@ -50,6 +60,7 @@ NTSM_XP_FN double ntsm_xp_rn53(uint32_t sign, uint64_t sig, int e)
 	uint64_t q, rem, half;
 	if (shift == 64) { q = 0; rem = sig; half = 1ull << 63; }
 	else { q = sig >> shift; rem = sig & ((1ull << shift) - 1); half = 1ull << (shift - 1); }
+	NTSM_XP_COUNT(rem == half, rn53_tie);
 	if (rem > half || (rem == half && (q & 1))) ++q;
 	if (shift != 11) return ntsm_xp_bits_to_double(s | q);    /* subnormal (q == 2^52 is the smallest normal: the carry is the exponent) */
 	int be = e + 63 + 1023;
@@ -58,7 +69,7 @@ NTSM_XP_FN double ntsm_xp_rn53(uint32_t sign, uint64_t sig, int e)
 	return ntsm_xp_bits_to_double(s | ((uint64_t) be << 52) | (q & ((1ull << 52) - 1)));
 }
 
-/* RN53(RN64(acc + p)) for finite acc and p */
+/* RN53(RN64(acc + p)) for finite p; acc = +-inf or NaN comes back unchanged */
 NTSM_XP_FN double ntsm_x87_acc(double acc, ntsm_x64 p)
 {
 	uint64_t ab;
@@ -67,6 +78,7 @@ NTSM_XP_FN double ntsm_x87_acc(double acc, ntsm_x64 p)
 	const uint32_t be = (uint32_t) (ab >> 52) & 0x7ffu;
 	uint64_t ma = ab & ((1ull << 52) - 1), mb = p.sig;
 	int ea = -1074, eb = p.exp;
+	if (be == 0x7ffu) return acc;                                               /* inf +- finite = inf; NaN stays NaN */
 	if (be) { ma |= 1ull << 52; ea = (int) be - 1075; }
 	if (mb == 0) {
 		if (ma == 0) return ntsm_xp_bits_to_double((uint64_t) (sa & sb) << 63);   /* (-0) + (-0) = -0, else +0 */
@@ -95,12 +107,16 @@ NTSM_XP_FN double ntsm_x87_acc(double acc, ntsm_x64 p)
 	if (R == 0) return 0.0;                                                     /* exact cancellation: +0 */
 	const uint64_t rh = (uint64_t) (R >> 64), rl = (uint64_t) R;
 	const int n = rh ? ntsm_xp_clz64(rh) : 64 + ntsm_xp_clz64(rl);
+	NTSM_XP_COUNT(n >= 64, shift64);
+	NTSM_XP_COUNT(n > 64, shift65);                                             /* 65 at the most: 2^k against 2^k - 2^(k-64) */
 	R <<= n;
 	uint64_t hi = (uint64_t) (R >> 64);
 	const uint64_t lo = (uint64_t) R;
 	int e = ea + 1 - n;                                                         /* value = hi * 2^e (+ lo) */
+	NTSM_XP_COUNT(lo != 0, rn64_inexact);
+	NTSM_XP_COUNT(lo == (1ull << 63), rn64_tie);
 	if (lo > (1ull << 63) || (lo == (1ull << 63) && (hi & 1))) {               /* RN64 */
-		if (++hi == 0) { hi = 1ull << 63; ++e; }
+		if (++hi == 0) { hi = 1ull << 63; ++e; NTSM_XP_COUNT(true, rn64_carry); }
 	}
 	return ntsm_xp_rn53(sa, hi, e);
 }

@@ -57,6 +57,39 @@ def edge_samples():
     return s
 
 
+def write_pca_range(d, rng):
+    """norm.txt and rot.tsv for 12 sites and 4 components (the runs use three) whose values span the long double exponents
+    that a file can name and a double cannot hold.  Sites 0-3 have centres of -1.25 ... -2, so every call there gives
+    v >= 1.25.  PC1 starts with rotation values of 1.5e+308 -- the first covered site's product already overflows the double
+    accumulator to inf -- and goes on with -1.7e+308, which the inf has to survive; PC2 runs to -inf at sites 2-5 and then
+    meets +1.7e+308; PC3 sums products of a few e+306, huge but finite throughout; the last sites carry values near e-300."""
+    def digits(k):
+        return "".join(str(x) for x in rng.integers(0, 10, size=k).tolist())
+    norm = ["-1.5", "-1.25", "-1.75", "-2"] + ["0.%s" % digits(19) for _ in range(4)]
+    norm += ["2.5%se-300" % digits(12), "1.25e-5", "0.%s" % digits(19), "7.%se-301" % digits(15)]
+    rows = []
+    for j in range(12):
+        small = "%s%d.%se-300" % ("-" if j % 2 else "", 1 + j % 9, digits(18))
+        pc1 = "1.5%se+308" % digits(16) if j < 4 else "-1.7%se+308" % digits(16) if j < 8 else small
+        pc2 = small if j < 2 else "-1.6%se+308" % digits(16) if j < 6 else "1.7%se+308" % digits(16) if j < 10 else "3.%se+150" % digits(18)
+        pc3 = small if j == 8 else "%s%d.%se+306" % ("-" if j % 3 == 1 else "", 1 + j % 4, digits(18))
+        rows.append("rs%d\t%s\t%s\t%s\t%s.%se-2" % (j, pc1, pc2, pc3, 1 + j % 9, digits(19)))
+    with open(os.path.join(d, "norm.txt"), "w") as f:
+        f.write("".join(x + "\n" for x in norm))
+    with open(os.path.join(d, "rot.tsv"), "w") as f:
+        f.write("rsID\tPC1\tPC2\tPC3\tPC4\n" + "".join(r + "\n" for r in rows))
+
+
+def range_samples(rng):
+    """Six samples over 12 sites at depth 20; sample 3 lacks the first four sites (PC1 meets -1.7e+308 from +0.0), sample 4
+    lacks sites 2-5 (PC2 meets +1.7e+308 first), sample 5 lacks every site."""
+    s = random_samples(rng, 6, 12, depth=20.0)
+    s[3, :4] = 0
+    s[4, 2:6] = 0
+    s[5] = 0
+    return s
+
+
 def write_cohort(d, samples):
     names = []
     for i in range(samples.shape[0]):
@@ -74,12 +107,16 @@ def materialise(spec, d):
         s = random_samples(rng, spec["n"], spec["m"])
     elif spec["kind"] == "edge":
         s = edge_samples()
+    elif spec["kind"] == "pca_range":
+        s = range_samples(rng)
     else:
         assert spec["kind"] == "pca", spec
         s = spread(rng, spec["n"], spec["m"])
     names = write_cohort(d, s)
     if spec["kind"] == "pca":
         write_pca(Path(d), spec["m"], spec["components"], rng)
+    if spec["kind"] == "pca_range":
+        write_pca_range(d, rng)
     return s, names
 
 
@@ -93,6 +130,9 @@ PAIRS = dict(kind="random", seed=46, n=12, m=300)   # one pair scores under the 
 EDGE = dict(kind="edge", seed=14)
 PCA = dict(kind="pca", seed=33, n=33, m=96, components=3)
 PCA_ARGS = ["-p", "rot.tsv", "-n", "norm.txt", "-d", "2"]
+# single-file mode only: the QC row with its PC columns is the projection as printed, and no tree is built over an infinite cloud
+RANGE = dict(kind="pca_range", seed=36)
+RANGE_ARGS = ["-p", "rot.tsv", "-n", "norm.txt", "-d", "3"]
 # -S / -l: about the 15th and 60th percentile of the pair distances of the PCA cohort (make() checks that the three radii occur)
 # -s 3: without -a the default threshold leaves one row of this small cohort
 RADII = ["-S", "0.13", "-l", "0.31", "-r", "1", "-1", "0.05", "-2", "0.5", "-s", "3"]
@@ -110,6 +150,9 @@ CASES = [
     dict(name="pca_all", input=PCA, files=None, args=PCA_ARGS + ["-a"]),
     dict(name="pca_radii", input=PCA, files=None, args=PCA_ARGS + RADII),
     dict(name="pca_single", input=PCA, files=[6], args=PCA_ARGS + ["-a"]),
+    dict(name="pca_range_0", input=RANGE, files=[0], args=RANGE_ARGS),
+    dict(name="pca_range_3", input=RANGE, files=[3], args=RANGE_ARGS + ["-c", "2"]),
+    dict(name="pca_range_4", input=RANGE, files=[4], args=RANGE_ARGS),
 ]
 
 
@@ -133,7 +176,7 @@ def make():
     os.makedirs(OUT, exist_ok=True)
     for f in os.listdir(OUT):
         os.remove(os.path.join(OUT, f))
-    doc = []
+    doc, range_pcs = [], []
     for case in CASES:
         with tempfile.TemporaryDirectory() as d:
             _, names = materialise(case["input"], d)
@@ -142,6 +185,10 @@ def make():
             out = run_reference(case["args"], names, d)
             if case["name"] == "pca_radii":
                 assert len(radii_of(d, names, case["args"])) == 3 and out.count(b"\n") > 5
+            if case["name"].startswith("pca_range"):
+                pcs = out.split(b"\n")[1].split(b"\t")[6:]
+                assert len(pcs) == 3 and len(pcs[2]) > 300 and b"inf" not in pcs[2], pcs      # PC3: huge and finite
+                range_pcs.append(pcs[:2])
             rec = dict(case, stdout=case["name"] + ".out.gz", lines=out.count(b"\n"))
             with open(os.path.join(OUT, rec["stdout"]), "wb") as fh:
                 fh.write(gzip.compress(out, mtime=0))
@@ -151,6 +198,7 @@ def make():
                     fh.write(gzip.compress(open(os.path.join(d, case["merge"]), "rb").read(), mtime=0))
             doc.append(rec)
             print("%-16s %6d bytes %4d lines" % (case["name"], len(out), rec["lines"]))
+    assert [b"inf", b"-inf"] in range_pcs and len({tuple(p) for p in range_pcs}) == len(range_pcs), range_pcs
     with open(os.path.join(OUT, "cases.json"), "w") as fh:
         json.dump(dict(recorded_with="oracle/_ref/ref_ntsmEval -t 1 (oracle/ref_eval_driver.cpp around the unmodified "
                                      "src/CompareCounts.hpp), relative file names, cwd = the data directory",

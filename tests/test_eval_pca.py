@@ -7,7 +7,10 @@ its recordings, byte for byte.  What the tests of this file pin is (CPU) the int
 CLI's refusals and flag errors; (GPU) the projection and the candidate list against tests/eval_pca_restatement.cpp, an
 independent restatement written from the reference text and compiled here with real long double, the listed-pair scoring
 against ntsm_eval_pairs, and the CLI's stdout against text assembled from the restatement and the all-pairs oracle
-(oracle/ntsm_eval_oracle.c)."""
+(oracle/ntsm_eval_oracle.c).  The rotation files of write_pca keep the x87 add in a narrow regime (small exponent gaps, no
+cancellation, carry, underflow or overflow), so the device build of the add also gets the operand classes of
+tests/xprec_check.cpp as table entries, against real x87 arithmetic, and the candidate search gets hand-made clouds at the
+edges of the double range."""
 import math
 import os
 import subprocess
@@ -170,15 +173,167 @@ def cohort(rng, n, m, missing=(0.0, 0.03, 0.2, 0.6)):
     return s
 
 
+# ---------------------------------------------------------------------------------------------------- the x87 add's operand classes
+# tests/xprec_check.cpp writes its cases; the GPU test feeds them to ntsm_eval_project, whose lane (sample i, component d)
+# computes ntsm_x87_acc over the sites that sample i covers: with norm = 0 and a site called 1.0 the table entry is rot[d][j]
+# itself, so the sites (lead-in, acc, p) give ntsm_x87_acc(ntsm_x87_acc(lead-in result, acc), p).
+X87_RECORD = np.dtype([("acc", "<f8"), ("p", np.longdouble), ("want", "<f8")])
+X87_PER_CLASS = 2000
+X87_NOT_DUMPED = "nan_acc"                       # no finite table entry leads to a NaN accumulator: the host check alone has that class
+X87_BRANCHES = {"p_zero", "acc_zero", "swap", "subtraction", "gap_ge_64", "gap_ge_128", "exact_cancellation", "shift_ge_64", "shift_gt_64", "rn64_tie",
+                "rn64_carry_out", "rn53_tie_after_rn64", "subnormal_result", "underflow_to_zero", "overflow", "nonfinite_acc"}
+COVERED, HALF, MISSING_SITE = (5, 0), (5, 5), (0, 0)        # counts that min_cov = 1 calls 1.0, 0.5 and missing
+
+
+def parse_x87_report(text):
+    """The "class NAME COUNT" and "branch NAME COUNT" lines of xprec_check as two dicts (classes in the file's order)."""
+    classes, branches = {}, {}
+    for line in text.splitlines():
+        w = line.split()
+        if len(w) == 3 and w[0] in ("class", "branch"):
+            (classes if w[0] == "class" else branches)[w[1]] = int(w[2])
+    return classes, branches
+
+
+@pytest.fixture(scope="module")
+def x87_cases(tmp_path_factory):
+    """(records, class of each record, classes, branches) of `xprec_check dump FILE X87_PER_CLASS 7`, built and run once."""
+    d = tmp_path_factory.mktemp("x87")
+    exe = gxx(d, "xprec_check.cpp", "xprec_check")
+    p = subprocess.run([exe, "dump", str(d / "cases.bin"), str(X87_PER_CLASS), "7"], capture_output=True, text=True)
+    assert p.returncode == 0 and p.stdout.startswith("ok "), p.stdout[-2000:]
+    print(p.stdout)
+    classes, branches = parse_x87_report(p.stdout)
+    rec = np.fromfile(str(d / "cases.bin"), dtype=X87_RECORD)
+    return rec, np.repeat(np.arange(len(classes)), list(classes.values())), classes, branches
+
+
+def assert_x87_is_numpy_longdouble():
+    """numpy's long double is the x87 format and its sums round twice: to 64 bits, then to the double."""
+    assert X87_RECORD.itemsize == 32 and np.finfo(np.longdouble).nmant == 63
+    witness = np.float64(np.longdouble(1.0) + (np.longdouble(2.0) ** -53 + np.longdouble(2.0) ** -64))
+    assert witness.view(np.uint64) == np.float64(1.0).view(np.uint64)
+    assert np.float64(1.0) + np.float64(2.0 ** -53 + 2.0 ** -64) == np.float64(1.0000000000000002)
+
+
+def x87_fold(v, rot):
+    """The reference's projection in real x87 arithmetic: v double [n][m] (call - norm, or +0.0 for a missing site), rot long
+    double [dim][m]; acc = double(acc + (long double) v[j] * rot[d][j]) in site order, a store to double after every add."""
+    acc = np.zeros((v.shape[0], rot.shape[0]), dtype=np.float64)
+    with np.errstate(all="ignore"):
+        for j in range(v.shape[1]):
+            prod = v[:, j, None].astype(np.longdouble) * rot[None, :, j]
+            acc = (acc.astype(np.longdouble) + prod).astype(np.float64)
+    return acc
+
+
+def x87_chain(*entries):
+    """x87_fold of one lane over sites called 1.0 with norm = 0: the table entries are rot's values themselves."""
+    acc = np.zeros(entries[0].shape, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        for e in entries:
+            acc = (acc.astype(np.longdouble) + e).astype(np.float64)
+    return acc
+
+
+def x87_sites(cases):
+    """The three table entries (lead-in, acc, p) whose chain from +0.0 is the case, as long doubles shaped like `cases`: a
+    lead-in of +0 leaves +0; acc = -0.0 needs the lead-in -2^-1100, which rounds to -0.0 where (+0) + (-0) would give +0; an
+    infinite acc is reached as the overflow of 1.7e308 + 1.7e308 of its sign."""
+    acc = cases["acc"]
+    lead = np.zeros(acc.shape, dtype=np.longdouble)
+    site = acc.astype(np.longdouble)
+    lead[(acc == 0) & np.signbit(acc)] = -np.longdouble(2.0) ** -1100
+    big = np.copysign(1.7e308, acc[np.isinf(acc)]).astype(np.longdouble)
+    lead[np.isinf(acc)], site[np.isinf(acc)] = big, big
+    assert np.isfinite(lead).all() and np.isfinite(site).all() and np.isfinite(cases["p"]).all()
+    return lead, site, cases["p"]
+
+
+def x87_block_layout(cases, n, dim):
+    """Sample i is covered at its own sites 3 i ... 3 i + 2 alone, and lane (i, d) runs case i * dim + d there; every other
+    site is missing for it, a product of +-0 with the sign of rot.  Returns (counts, rot, expected, cases): expected is the
+    fold of the lane's own three sites, and where that is a zero, of the zeros that follow: -0 survives only -0 products;
+    cases [n][dim] are the records as the lanes got them (the input repeated where it is shorter than n * dim)."""
+    cases = np.resize(cases, n * dim).reshape(n, dim)
+    counts = np.zeros((n, 3 * n, 2), dtype=np.uint32)
+    for s in range(3):
+        counts[np.arange(n), 3 * np.arange(n) + s] = COVERED
+    sites = x87_sites(cases)
+    rot = np.ascontiguousarray(np.stack(sites, axis=-1).transpose(1, 0, 2).reshape(dim, 3 * n))
+    own = x87_chain(*sites)
+    neg_tail = np.ones((dim, 3 * n + 3), dtype=bool)                          # neg_tail[d][j]: every site from j on has a negative rot
+    neg_tail[:, :3 * n] = np.logical_and.accumulate(np.signbit(rot)[:, ::-1], axis=1)[:, ::-1]
+    stays_negative = np.signbit(own) & neg_tail[:, 3 * np.arange(1, n + 1)].T
+    expected = np.where(own == 0, np.where(stays_negative, -0.0, 0.0), own)
+    return counts, rot, expected, cases
+
+
+def x87_wave_layout(cases, n, rng):
+    """Every sample is covered at the same three sites, called 1.0 or 0.5 (sample 0: 1.0 throughout), and component d is case
+    d: all lanes of a wave run the full add at once, on operands that differ by factors of two.  expected is each lane's own
+    fold."""
+    call = rng.integers(1, 3, size=(n, 3))
+    call[0] = 2
+    counts = np.where((call == 2)[:, :, None], np.array(COVERED, dtype=np.uint32), np.array(HALF, dtype=np.uint32)).astype(np.uint32)
+    rot = np.ascontiguousarray(np.stack(x87_sites(cases), axis=-1))
+    return counts, rot, x87_fold(call * 0.5, rot)
+
+
+def same_double_bits(got, want):
+    """Bit for bit; a NaN only has to be a NaN."""
+    both_nan = np.isnan(got) & np.isnan(want)
+    return (got.view(np.uint64) == want.view(np.uint64)) | both_nan
+
+
 # ---------------------------------------------------------------------------------------------------- CPU
 def test_x87_add_helper_matches_the_x87(tmp_path):
     """ntsm_x87_acc(acc, p) = RN53(RN64(acc + p)), bit for bit against g++'s long double on x86-64: 10^7 random operands
     plus constructed cases (ties at bit 64 and at bit 53 after RN64, exact cancellation, exponent gaps -130 ... +130, signed
-    zeros, subnormal results, overflow) -- tests/xprec_check.cpp."""
+    zeros, subnormal results, overflow, a carry out of the RN64 increment, an accumulator that is already infinite or NaN) --
+    tests/xprec_check.cpp.  The program counts the branches of ntsm_x87_acc that its cases take and fails on one that none
+    takes."""
     exe = gxx(tmp_path, "xprec_check.cpp", "xprec_check")
     p = subprocess.run([exe, "10000000", "7"], capture_output=True, text=True)
     assert p.returncode == 0 and p.stdout.startswith("ok "), p.stdout[-2000:]
-    assert int(p.stdout.split()[1]) > 10000000
+    assert int(p.stdout.split()[1]) > 12000000
+    classes, branches = parse_x87_report(p.stdout)
+    assert X87_BRANCHES <= set(branches) and all(v > 0 for v in branches.values()), branches
+    assert len(classes) == 13 and all(v >= 200 for v in classes.values()), classes
+
+
+def test_x87_add_helper_under_the_host_sanitizers():
+    """tests/xprec_check.cpp as `make xprec_check` builds it, a program of its own under -fsanitize=address,undefined: every
+    constructed class and 10^6 random operands, run once."""
+    subprocess.run(["make", "-s", "build/xprec_check"], cwd=ROOT, check=True, stdout=subprocess.DEVNULL)
+    p = subprocess.run([os.path.join(ROOT, "build", "xprec_check"), "1000000", "7"], capture_output=True, text=True)
+    assert p.returncode == 0 and p.stdout.startswith("ok ") and p.stderr == "", (p.stdout[-600:], p.stderr[-600:])
+    assert int(p.stdout.split()[1]) > 3000000
+
+
+def test_x87_dumped_cases_cover_every_class_and_branch(x87_cases):
+    """The conditions on the input of test_projection_runs_the_x87_add_on_every_operand_class, without a device: every class
+    but NaN gives at least 1,000 cases, the written cases alone take every branch, numpy's long double folds every case's
+    three sites to the x87's own result, and the block layout's expected values are the fold of the whole site sequence."""
+    rec, cls, classes, branches = x87_cases
+    assert_x87_is_numpy_longdouble()
+    dumped = {k: v for k, v in classes.items() if k != X87_NOT_DUMPED}
+    assert classes[X87_NOT_DUMPED] == 0 and len(dumped) == 12 and min(dumped.values()) >= 1000, classes
+    assert len(rec) == sum(dumped.values()) == len(cls)
+    assert X87_BRANCHES <= set(branches) and all(v > 0 for v in branches.values()), branches
+    assert not np.isnan(rec["acc"]).any() and np.isinf(rec["acc"]).sum() >= 1000
+    chain = x87_chain(*x87_sites(rec))
+    bad = np.flatnonzero(chain.view(np.uint64) != rec["want"].view(np.uint64))
+    assert bad.size == 0, (bad[:5].tolist(), rec[bad[:5]], chain[bad[:5]])
+    zeros, spread = np.flatnonzero(rec["want"] == 0)[:150], np.arange(0, len(rec), 97)
+    for n, dim in ((37, 11), (5, 60)):                                       # zero results with a tail, and in the last sample without
+        counts, rot, expected, cases = x87_block_layout(rec[np.concatenate([spread[:n * dim - 150], zeros])], n, dim)
+        v = np.where(counts[:, :, 0] > 0, 1.0, 0.0)
+        assert np.array_equal(x87_fold(v, rot).view(np.uint64), expected.view(np.uint64))
+        assert np.array_equal(expected[-1].view(np.uint64), cases["want"][-1].view(np.uint64))     # the last sample has no tail
+        nz = cases["want"] != 0
+        assert np.array_equal(expected[nz].view(np.uint64), cases["want"][nz].view(np.uint64))
+        assert (np.signbit(expected) & (expected == 0)).any() and ((expected == 0) & np.signbit(cases["want"]) & ~np.signbit(expected)).any()
 
 
 def test_pca_cli_refusals_and_flag_errors(tmp_path):
@@ -243,6 +398,101 @@ def test_projection_equals_restatement_bits(tmp_path, restatement):
         if n > 4:
             assert np.array_equal(got[0].view(np.uint64), got[n - 1].view(np.uint64))
         assert ms >= 0
+
+
+@pytest.mark.gpu
+def test_projection_runs_the_x87_add_on_every_operand_class(x87_cases):
+    """The device build of ntsm_x87_acc on the operand classes that no rotation file of the other tests reaches: the cases
+    that tests/xprec_check.cpp dumps (12 classes of 2,000: signed zeros, cancellation, exponent gaps to +-130, ties at bit 64
+    and at bit 53 after RN64, subnormal results, overflow, the carry out of the RN64 increment, an infinite accumulator,
+    four random kinds; every branch of the function taken) through ntsm_eval_project, compared by bits with real x87
+    arithmetic -- the dumped result, which is g++'s long double, and numpy's long double fold of each lane's sites.
+    Block layout: lane (i, d) meets its case at sample i's own three sites and +-0 products elsewhere, so the lanes of a
+    wave take different branches at one step; n = 256, 300 (a second workgroup of 44 lanes) and 65.  Wave layout: all
+    samples covered at the same three sites with calls 1.0 or 0.5, so every lane of a wave runs the full add at once; n = 70
+    (a wave of six live lanes) and 257."""
+    import ntsm_amd.eval as ev
+    rec, cls, classes, branches = x87_cases
+    assert_x87_is_numpy_longdouble()
+    names = list(classes)
+    print({k: v for k, v in branches.items()})
+    assert classes[X87_NOT_DUMPED] == 0 and all(v >= 1000 for k, v in classes.items() if k != X87_NOT_DUMPED), classes
+    assert X87_BRANCHES <= set(branches) and all(v > 0 for v in branches.values()), branches
+    compared, first = 0, 0
+    plan = [(256, 64), (300, 24), (65, 8)]
+    while first < len(rec):
+        n, dim = plan[0]
+        plan = plan[1:] + plan[:1]
+        idx = np.resize(np.arange(first, min(first + n * dim, len(rec))), n * dim).reshape(n, dim)
+        counts, rot, expected, cases = x87_block_layout(rec[idx.ravel()], n, dim)
+        got, _ = ev.project(counts, np.zeros(3 * n, dtype=np.longdouble), rot, min_cov=1)
+        bad = np.argwhere(~same_double_bits(got, expected))
+        assert bad.size == 0, ("block", n, dim, [(names[cls[idx[i, d]]], cases[i, d], got[i, d], expected[i, d]) for i, d in bad[:5]])
+        last_or_nonzero = (cases["want"] != 0) | (np.arange(n) == n - 1)[:, None]          # no tail of zeros changes these
+        assert np.array_equal(got[last_or_nonzero].view(np.uint64), cases["want"][last_or_nonzero].view(np.uint64))
+        compared += min(n * dim, len(rec) - first)
+        first += n * dim
+    assert compared == len(rec)
+    rng = np.random.default_rng(26)
+    for n, pick in ((70, np.arange(len(rec))), (257, np.arange(0, len(rec), 5))):
+        counts, rot, expected = x87_wave_layout(rec[pick], n, rng)
+        got, _ = ev.project(counts, np.zeros(3, dtype=np.longdouble), rot, min_cov=1)
+        assert got.shape == expected.shape == (n, len(pick))
+        bad = np.argwhere(~same_double_bits(got, expected))
+        assert bad.size == 0, ("wave", n, [(names[cls[pick[d]]], rec[pick[d]], counts[i, :, 1].tolist(), got[i, d], expected[i, d]) for i, d in bad[:5]])
+        assert np.array_equal(got[0].view(np.uint64), rec["want"][pick].view(np.uint64))    # sample 0 is the case itself
+
+
+def edge_cloud(rng, n, dim, families):
+    """A finite cloud at the edges of the double range, one family per row: 0 coordinates near +-1e200 (their squares
+    overflow), 1 +-DBL_MAX (the subtraction itself overflows), 2 near +-1e-200 with some near 1e-160 (squares that underflow
+    to zero or to a subnormal), 3 signed zeros, 4 ordinary values, 5 a coordinate of each kind."""
+    def coords(f, size):
+        sign = rng.choice([-1.0, 1.0], size=size)
+        return {0: sign * rng.integers(1, 10, size=size) * 1e200,
+                1: sign * DBL_MAX,
+                2: sign * rng.integers(1, 4, size=size) * np.where(rng.random(size) < 0.2, 1e-160, 1e-200),
+                3: sign * 0.0,
+                4: rng.integers(-3, 4, size=size) * 0.5}[f]
+    cloud = np.empty((n, dim))
+    for i in range(n):
+        f = families[i % len(families)]
+        cloud[i] = coords(f, dim) if f < 5 else [coords(int(g), 1)[0] for g in rng.integers(0, 5, size=dim)]
+    assert np.isfinite(cloud).all()
+    return cloud
+
+
+@pytest.mark.gpu
+def test_candidates_at_the_edges_of_the_double_range(tmp_path, restatement):
+    """eval_metric, calc_distance and the selection on hand-made finite clouds against the restatement, order, k and the bits
+    of dist: squares and differences that overflow (metric +inf: a radius row takes nothing, a search-all row everything with
+    dist inf), squares that underflow (exact ties at metric 0, ordered by k, and subnormal metrics), +0.0 against -0.0, and
+    ordinary values among them; dim 1 / 3 / 4 / 5 / 8 (the four-wide loop and its tail), n 2 / 65 / 257, radii that mix
+    finite values down to 1e-300 with DBL_MAX."""
+    import ntsm_amd.eval as ev
+    rng = np.random.default_rng(27)
+    seen_inf = seen_zero = seen_subnormal = 0
+    for n in (2, 65, 257):
+        sess = ev.Session(np.full((n, 1, 2), 7, dtype=np.uint32), 1)
+        for dim in (1, 3, 4, 5, 8):
+            for families in ([(0,), (1,), (2,), (3,), (0, 1), (2, 3), (4, 0)] if n == 2 else [(0, 1, 2, 3, 4, 5, 2, 3, 2)]):
+                cloud = edge_cloud(rng, n, dim, families)
+                if families == (1,):
+                    cloud[1] = -cloud[0]                                     # DBL_MAX against -DBL_MAX in every coordinate
+                if families == (3,):
+                    cloud[1] = -cloud[0]                                     # +0.0 against -0.0
+                for radii in ((DBL_MAX, 1.0, 1e-300, 4.0, 1e300, 1e-300, DBL_MAX), (1e-300, 1e300), (DBL_MAX,)):
+                    radius = np.array([radii[(i * 5 + dim) % len(radii)] for i in range(n)])
+                    want = rs_candidates(restatement, tmp_path, cloud, radius)
+                    pi, pk, dist, _ = sess.candidates(cloud, radius)
+                    got = list(zip(pi.tolist(), pk.tolist(), dist.tolist()))
+                    assert same_list(got, want), (n, dim, families, radii, len(got), len(want), got[:5], want[:5])
+                    assert np.array_equal(np.array([w[2] for w in want], dtype=np.float64).view(np.uint64), dist.view(np.uint64))
+                    seen_inf += int(np.isinf(dist).sum())
+                    seen_zero += int((dist == 0).sum())
+                    seen_subnormal += int(((dist > 0) & (dist < 2.2250738585072014e-308)).sum())
+        sess.close()
+    assert seen_inf > 1000 and seen_zero > 1000 and seen_subnormal > 100, (seen_inf, seen_zero, seen_subnormal)
 
 
 @pytest.mark.gpu

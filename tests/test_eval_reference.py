@@ -416,15 +416,20 @@ def test_recordings_equal_oracle_and_restatement(tmp_path, restatement, case):
     dim, kw = pca_kw(case["args"])
     if len(names) == 1:
         s, _ = make_eval.materialise(case["input"], str(tmp_path))
-        cloud = restated_cloud(restatement, tmp_path, s, dim)
-        assert single_pca_text(tmp_path, names[0], cloud[case["files"][0]]) == out
+        cloud = restated_cloud(restatement, tmp_path, s, dim, min_cov=kw.get("min_cov", 1))
+        assert single_pca_text(tmp_path, names[0], cloud[case["files"][0]], min_cov=kw.get("min_cov", 1)) == out
     else:
         assert pca_expected(restatement, tmp_path, names, case["args"])[0] == out
 
 
 def test_recordings_cover_what_they_should():
     by = {c["name"]: c for c in RECORDED}
-    assert {"pairs_all", "pairs_all_c0", "pairs_all_c3_w1", "pairs_default", "single", "merge", "pca_all", "pca_radii", "pca_single"} <= set(by)
+    assert {"pairs_all", "pairs_all_c0", "pairs_all_c3_w1", "pairs_default", "single", "merge", "pca_all", "pca_radii", "pca_single", "pca_range_0",
+            "pca_range_3", "pca_range_4"} <= set(by)
+    # rotation values to e+308: an accumulator that overflows to inf and then meets -1.7e+308, one at -inf, one huge and finite
+    pcs = [gzip.open(os.path.join(GOLD, by[k]["stdout"])).read().split(b"\n")[1].split(b"\t")[6:] for k in ("pca_range_0", "pca_range_3", "pca_range_4")]
+    assert pcs[0][:2] == [b"inf", b"-inf"] and pcs[1][1] == b"inf" and pcs[2][0] == b"inf"
+    assert all(len(p) == 3 and len(p[2]) > 300 and b"inf" not in p[2] for p in pcs) and len(pcs[1][0]) > 300 and len(pcs[2][1]) > 300
     assert by["pairs_all"]["lines"] == 1 + 12 * 11 // 2 and by["pairs_default"]["lines"] >= 2 and by["pca_radii"]["lines"] > 5
     files = set(os.listdir(GOLD))
     assert files == {"cases.json"} | {c["stdout"] for c in RECORDED} | {c["merge_out"] for c in RECORDED if c.get("merge_out")}

@@ -10,7 +10,8 @@
 #                                                  the store's own samples (--within / --within-near), and one store
 #                                                  against another (--between) and the PCA-guided search between
 #                                                  two (--between-near), and the QC tables of a store (--qc), and the
-#                                                  cross-sample contamination check over one (--contam)
+#                                                  cross-sample contamination check over one (--contam), and the
+#                                                  parent-parent-child trios in one (--trios)
 #   ntsm_amd/libntsm_vcf_hip.so, build/ntsmVCF     multi-sample VCF to PCA matrix + centre file (HIP library + CLI mirror);
 #                                                  with --rotation also the PCA, through libntsm_pca_hip.so
 #                                                  with --counts / --store the genotypes as counts files and cohort-store records
@@ -94,13 +95,17 @@ xlib:
 # + the cross-sample contamination check over a store (--contam): ntsm_eval_contam.hip, the rectangle of ordered pairs (target,
 #   source) in integers; the chunk rule and the 2-D copy are ntsm_eval_chunk.h's, the band rule and both tables' text are host
 #   code (host/eval_contam.hpp)
+# + parent-parent-child trios in a store (--trios): ntsm_eval_trio.hip, bit-planes of genotype classes and popcount kernels over
+#   site words; the chunk rule and the 2-D copy are ntsm_eval_chunk.h's, the candidate rule, the batches, the pedigree and the
+#   text are host code (host/eval_trio.hpp)
 EVALSRC := $(CSRC)/ntsm_eval.hip $(CSRC)/ntsm_eval_pca.hip $(CSRC)/ntsm_eval_cross.hip $(CSRC)/ntsm_eval_near.hip $(CSRC)/ntsm_eval_within.hip \
-           $(CSRC)/ntsm_eval_between.hip $(CSRC)/ntsm_eval_between_near.hip $(CSRC)/ntsm_eval_profile.hip $(CSRC)/ntsm_eval_contam.hip
+           $(CSRC)/ntsm_eval_between.hip $(CSRC)/ntsm_eval_between_near.hip $(CSRC)/ntsm_eval_profile.hip $(CSRC)/ntsm_eval_contam.hip \
+           $(CSRC)/ntsm_eval_trio.hip
 ntsm_amd/libntsm_eval_hip.so: $(EVALSRC) $(CSRC)/ntsm_eval_score.h $(CSRC)/ntsm_eval_chunk.h $(CSRC)/ntsm_eval_pca.h $(CSRC)/ntsm_hip_scope.h $(CSRC)/xprec.h \
                               $(HOST)/eval_within.hpp $(HOST)/eval_between.hpp $(HOST)/eval_store.hpp include/ntsm_eval_hip.h
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -shared -o $@ $(EVALSRC)
 
-build/ntsmEval: $(HOST)/ntsm_eval_main.cpp $(HOST)/cli.hpp $(HOST)/eval_store.hpp $(HOST)/eval_index.hpp $(HOST)/eval_qc.hpp $(HOST)/eval_contam.hpp $(HOST)/eval_within.hpp $(HOST)/eval_between.hpp $(HOST)/crc32_fast.cpp $(HOST)/crc32_fast.hpp \
+build/ntsmEval: $(HOST)/ntsm_eval_main.cpp $(HOST)/cli.hpp $(HOST)/eval_store.hpp $(HOST)/eval_index.hpp $(HOST)/eval_qc.hpp $(HOST)/eval_contam.hpp $(HOST)/eval_trio.hpp $(HOST)/eval_within.hpp $(HOST)/eval_between.hpp $(HOST)/crc32_fast.cpp $(HOST)/crc32_fast.hpp \
                 $(HOST)/gz_stream.hpp $(CSRC)/xprec.h include/ntsm_eval_hip.h ntsm_amd/libntsm_eval_hip.so
 	@mkdir -p build
 	$(CXX) $(CXXFLAGS) -ffp-contract=off -o $@ $(HOST)/ntsm_eval_main.cpp $(HOST)/crc32_fast.cpp -Lntsm_amd -lntsm_eval_hip -lz \
@@ -147,6 +152,14 @@ contam_check: build/eval_contam_check
 build/eval_contam_check: tools/eval_contam_check.cpp $(HOST)/eval_contam.hpp include/ntsm_eval_hip.h
 	@mkdir -p build
 	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ tools/eval_contam_check.cpp
+
+# the candidate rule, the batch cutter, the pedigree parser, the name matcher, the row text and both runs of --trios over a model
+# of the device likewise (tools/eval_trio_check.cpp; not part of `all`)
+trio_check: build/eval_trio_check
+	build/eval_trio_check
+build/eval_trio_check: tools/eval_trio_check.cpp $(HOST)/eval_trio.hpp $(HOST)/eval_contam.hpp include/ntsm_eval_hip.h
+	@mkdir -p build
+	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ tools/eval_trio_check.cpp
 
 # the integer x87 add of the projection against the x87 itself likewise: every constructed class and 10^6 random operands, every
 # branch of ntsm_x87_acc reached (tests/xprec_check.cpp; not part of `all`)
@@ -252,4 +265,4 @@ build/gather_bench: tools/gather_bench.hip
 clean:
 	rm -rf build ntsm_amd/*.so
 	$(MAKE) -C oracle clean
-.PHONY: all oracle_all ref_gpu_binding clean ablation abl_tab tab m12 xlib store_check index_check within_check between_check between_near_check contam_check cohort_check xprec_check
+.PHONY: all oracle_all ref_gpu_binding clean ablation abl_tab tab m12 xlib store_check index_check within_check between_check between_near_check contam_check trio_check cohort_check xprec_check

@@ -318,6 +318,64 @@ void ntsm_eval_contam_close(ntsm_eval_contam_session *h);
  * _rows calls in this process; 0 = the library's rule (ntsm_eval_cross's, inherited).  Returns 0, -1 for another value. */
 int ntsm_eval_contam_tune(uint32_t width, uint32_t target_group);
 
+/* ---- Parent-parent-child trios in a cohort store (ntsmEval --trios; ntsm_amd/csrc/ntsm_eval_trio.hip):
+ * which samples form a trio, and do the trios of a pedigree hold.  The reference has no such run; the contract is this text.
+ * db_counts / db_stride_bytes / db_chunk as for ntsm_eval_cross.  All accumulated quantities are integers: two calls of any
+ * entry give the same bytes.
+ *
+ * The genotype rule of this run.  c = min_cov (strict >, as everywhere in the scoring), D = min_depth.  For a sample's cell
+ *   (a, g) = (countAT, countCG): A = a > c, G = g > c, t = uint64(a) + uint64(g), and the cell is
+ *     het    A && G                  (not depth-gated: both alleles were seen above the cut)
+ *     homAT  A && !G && t >= D
+ *     homCG  !A && G && t >= D
+ *     miss   everything else
+ *   called = het | homAT | homCG.  With D = 0 this is the classing of calcHomHetMiss / calcRelatedness (src/CompareCounts.hpp:
+ *   1144-1196).  D is there because at low depth a het site shows one allele only and looks like a Mendelian error.
+ * A duo (x, y), symmetric: called = the sites where both are called, opp = the sites where one is homAT and the other homCG.
+ *   The diagonal is a pair like any other: called = the sample's called sites, opp = 0.
+ * A trio (child k; parents x, y), over the sites where all three are called: called += 1; err_hom += 1 when the child is homAT
+ *   and x or y is homCG, or the child is homCG and x or y is homAT; err_het += 1 when the child is het and x, y are both homAT
+ *   or both homCG.  In bit-planes, 0 / 1 / 2 = homAT / het / homCG:
+ *     cl = called_K & called_X & called_Y
+ *     eh = cl & ((K0 & (X2 | Y2)) | (K2 & (X0 | Y0)))
+ *     et = cl & K1 & ((X0 & Y0) | (X2 & Y2))
+ *   The two error classes are disjoint; the record is symmetric in x and y and not in the child; pad is 0.
+ *
+ * ntsm_eval_trio_open: streams the store once, in chunks of db_chunk samples (0 = the chunk rule, asked at what a staged chunk
+ *   holds beside the planes: 8 * n_sites bytes per sample), and builds the three planes hom_at, het, hom_cg, one bit per sample
+ *   and site, on the device.  The planes are always resident (3 * ceil(n_sites / 64) * 8 bytes per sample); the counts go back
+ *   before open returns.  The mapping need not outlive the call.
+ *   geno (may be NULL): [n_db][4] = homAT, het, homCG, miss of each sample under this rule; the four sum to n_sites.
+ *   times (may be NULL): upload_ms the copies, prepare_kernel_ms the plane and geno kernels, download_ms geno's way back,
+ *     chunks the chunks uploaded.
+ *   Returns 0, -2 HIP error, -1 bad argument, before any HIP call: a NULL it needs, a stride below 8 * n_sites or not a
+ *   multiple of 4.  n_db == 0 or n_sites == 0: a session without device work (geno zeroed).
+ * ntsm_eval_trio_duos: rows row_first ... row_first + n_rows - 1 against every sample: out [n_rows][n_db],
+ *   out[(x - row_first) * n_db + y] the duo (x, y).  kernel_ms (may be NULL): the rectangle kernel, from HIP events.
+ *   Returns 0, -2, -1 (row_first + n_rows > n_db, n_rows == 0, a NULL it needs), the -1 before any HIP call.  n_sites == 0:
+ *   zeroed records; of n_db == 0 there is no range to take.
+ * ntsm_eval_trio_score: trio lists in CSR form.  Entry i, i < n_children, has the child child[i] and the candidate list
+ *   cand[offset[i] ... offset[i + 1]) of length k_i; its k_i (k_i - 1) / 2 records are the pairs of list positions p < q, p
+ *   ascending and q ascending inside p, the record of (p, q) being the trio (child[i]; cand[offset[i] + p], cand[offset[i] + q]);
+ *   they start at out[sum over j < i of k_j (k_j - 1) / 2].  Lists need not be sorted and may repeat a sample; a child may
+ *   appear in several entries; lists of length 0 or 1 give no records.  offset: [n_children + 1].  kernel_ms (may be NULL).
+ *   Returns 0, -2, -1 before any HIP call: a NULL it needs, an index >= n_db, a candidate equal to its entry's child, a
+ *   decreasing offset, offset[0] != 0.  n_children == 0: nothing to do, returns 0.  n_sites == 0: zeroed records. */
+typedef struct ntsm_eval_trio_duo { uint32_t called, opp; } ntsm_eval_trio_duo;   /* 8 bytes */
+typedef struct ntsm_eval_trio_record { uint32_t called, err_hom, err_het, pad /* 0 */; } ntsm_eval_trio_record;   /* 16 bytes */
+typedef struct ntsm_eval_trio_session ntsm_eval_trio_session;
+int ntsm_eval_trio_open(int device, const void *db_counts, uint64_t db_stride_bytes, uint32_t n_db, uint32_t n_sites, uint32_t min_cov,
+		uint32_t min_depth, uint32_t db_chunk, uint32_t *geno, ntsm_eval_cross_times *times, ntsm_eval_trio_session **h);
+int ntsm_eval_trio_duos(ntsm_eval_trio_session *h, uint32_t row_first, uint32_t n_rows, ntsm_eval_trio_duo *out, double *kernel_ms);
+int ntsm_eval_trio_score(ntsm_eval_trio_session *h, const uint32_t *child, const uint64_t *offset, const uint32_t *cand, uint32_t n_children,
+		ntsm_eval_trio_record *out, double *kernel_ms);
+void ntsm_eval_trio_close(ntsm_eval_trio_session *h);
+/* For measurements and tests only: force the workgroup width (64 or 256) of later _duos and _score calls in this process: the
+ * duo kernel's workgroup, and the trio kernel's tile for every list (64 threads: the 16 x 16 tile, 256 threads: the 64 x 64
+ * tile); 0 = the library's rule (duo: ntsm_eval_cross's, inherited; trio: the small tile for lists of up to 16).  Returns 0, -1
+ * for another value. */
+int ntsm_eval_trio_tune(uint32_t width);
+
 #ifdef __cplusplus
 }
 #endif

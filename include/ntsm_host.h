@@ -123,6 +123,31 @@ int ntsm_host_contam_rows(const char *const *names, uint32_t n_db, uint32_t row_
 int ntsm_host_contam_sample_table(const char *const *names, uint32_t n_samples, const uint64_t *tally, char **out, size_t *len);
 uint32_t ntsm_host_contam_band_rows(uint32_t row_first, uint32_t n_db, uint64_t limit);
 
+/* The host side of `ntsmEval --trios` (ntsm_amd/csrc/host/eval_trio.hpp), for tests; records as include/ntsm_eval_hip.h has them.
+ * _rows: the lines of n_rows evaluated triples (child[i]; pa[i], pb[i]), indices into names[n_names], with their trio records
+ *   and the duo records (child, parentA) and (child, parentB), without the header.  ped != 0: every line, with its verdict;
+ *   else the search's print rule under all, min_called, max_rate.  0, -1 for a NULL it needs or an index >= n_names.
+ * _ped_parse: the complete trios of a pedigree file's text as samples of names[], *trios [*n_trios][3] = child, father,
+ *   mother in file order; *comments and *founders (may be NULL) = the skipped lines.  0; 1 for a refusal, its sentence in
+ *   *error; -1 for a NULL it needs.  *trios and *error are freed with ntsm_host_free.
+ * _match: the sample an ID names (stored name, then basename, then the basename without _counts.txt / .counts.txt / .txt),
+ *   -1 where none does, -2 where more than one does at the first level any does, -3 for a NULL.
+ * _candidates: the candidate parents of `child` out of its duo row [n_db], in store order, into out [n_db]; returns how many,
+ *   -1 for a NULL it needs.
+ * _batches: lists of lengths k[n] cut into batches of at most `limit` records, the batches' ends into ends [n] and their
+ *   number into *n_ends; returns n, or the position of a list that alone exceeds the limit, or SIZE_MAX for a NULL k.
+ * The band rule of the duo rectangle is ntsm_host_contam_band_rows, asked at 2^27 records (1 GiB of 8 bytes). */
+struct ntsm_eval_trio_record;
+struct ntsm_eval_trio_duo;
+int ntsm_host_trio_rows(const char *const *names, uint32_t n_names, size_t n_rows, const uint32_t *child, const uint32_t *pa, const uint32_t *pb,
+		const struct ntsm_eval_trio_record *rec, const struct ntsm_eval_trio_duo *da, const struct ntsm_eval_trio_duo *db, int ped, int all,
+		uint32_t min_called, double max_rate, char **out, size_t *len);
+int ntsm_host_trio_ped_parse(const char *text, size_t text_len, const char *const *names, uint32_t n_names, uint32_t **trios, size_t *n_trios,
+		uint64_t *comments, uint64_t *founders, char **error, size_t *error_len);
+int64_t ntsm_host_trio_match(const char *const *names, uint32_t n_names, const char *id);
+int64_t ntsm_host_trio_candidates(const struct ntsm_eval_trio_duo *row, uint32_t n_db, uint32_t child, uint32_t min_called, double max_duo, uint32_t *out);
+size_t ntsm_host_trio_batches(const uint32_t *k, size_t n, uint64_t limit, size_t *ends, size_t *n_ends);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,7 @@
 #include "early_ingest.hpp"
 #include "eval_contam.hpp"
 #include "eval_qc.hpp"
+#include "eval_trio.hpp"
 #include "host_shape.hpp"
 #include "parallel_fastq.hpp"
 #include "parallel_gz_fastq.hpp"
@@ -412,6 +413,65 @@ int ntsm_host_contam_sample_table(const char *const *names, uint32_t n_samples, 
 uint32_t ntsm_host_contam_band_rows(uint32_t row_first, uint32_t n_db, uint64_t limit)
 {
 	return n_db == 0 || row_first >= n_db ? 0 : ntsm::eval_contam::band_rows(row_first, n_db, limit);
+}
+
+int ntsm_host_trio_rows(const char *const *names, uint32_t n_names, size_t n_rows, const uint32_t *child, const uint32_t *pa, const uint32_t *pb,
+		const ntsm_eval_trio_record *rec, const ntsm_eval_trio_duo *da, const ntsm_eval_trio_duo *db, int ped, int all, uint32_t min_called, double max_rate,
+		char **out, size_t *len)
+{
+	if (!out || !len || (n_rows && (!names || !child || !pa || !pb || !rec || !da || !db))) return -1;
+	for (size_t i = 0; i < n_rows; ++i)
+		if (child[i] >= n_names || pa[i] >= n_names || pb[i] >= n_names) return -1;
+	std::string text;
+	ntsm::eval_trio::rows_text(text, names, n_rows, child, pa, pb, rec, da, db, ped != 0, all != 0, min_called, max_rate);
+	*out = dup_string(text, len);
+	return 0;
+}
+
+int ntsm_host_trio_ped_parse(const char *text, size_t text_len, const char *const *names, uint32_t n_names, uint32_t **trios, size_t *n_trios,
+		uint64_t *comments, uint64_t *founders, char **error, size_t *error_len)
+{
+	if ((!text && text_len) || (!names && n_names) || !trios || !n_trios || !error || !error_len) return -1;
+	*trios = nullptr; *n_trios = 0; *error = nullptr; *error_len = 0;
+	try {
+		const ntsm::eval_trio::Ped ped = ntsm::eval_trio::parse_ped(std::string(text ? text : "", text_len));
+		const std::vector<ntsm::eval_trio::PedTrio> t = ntsm::eval_trio::resolve(ped, std::vector<std::string>(names, names + n_names));
+		*trios = (uint32_t *) malloc((t.size() ? t.size() : 1) * 3 * sizeof(uint32_t));
+		if (!*trios) return -1;
+		for (size_t i = 0; i < t.size(); ++i) { (*trios)[3 * i] = t[i].child; (*trios)[3 * i + 1] = t[i].father; (*trios)[3 * i + 2] = t[i].mother; }
+		*n_trios = t.size();
+		if (comments) *comments = ped.comments;
+		if (founders) *founders = ped.founders;
+	} catch (const ntsm::eval_trio::Error &e) {
+		*error = dup_string(e.what(), error_len);
+		return 1;
+	}
+	return 0;
+}
+
+int64_t ntsm_host_trio_match(const char *const *names, uint32_t n_names, const char *id)
+{
+	if ((!names && n_names) || !id) return -3;
+	return ntsm::eval_trio::match_name(std::vector<std::string>(names, names + n_names), id);
+}
+
+int64_t ntsm_host_trio_candidates(const ntsm_eval_trio_duo *row, uint32_t n_db, uint32_t child, uint32_t min_called, double max_duo, uint32_t *out)
+{
+	if (n_db && (!row || !out)) return -1;                                        /* out holds n_db entries: as many as there can be */
+	std::vector<uint32_t> list;
+	ntsm::eval_trio::candidates(row, n_db, child, min_called, max_duo, list);
+	std::copy(list.begin(), list.end(), out);
+	return (int64_t) list.size();
+}
+
+size_t ntsm_host_trio_batches(const uint32_t *k, size_t n, uint64_t limit, size_t *ends, size_t *n_ends)
+{
+	if (n && !k) return (size_t) -1;
+	std::vector<size_t> e;
+	const size_t bad = ntsm::eval_trio::cut_batches(k, n, limit, e);
+	if (ends) std::copy(e.begin(), e.end(), ends);
+	if (n_ends) *n_ends = e.size();
+	return bad;
 }
 
 } // extern "C"

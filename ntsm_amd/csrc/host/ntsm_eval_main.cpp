@@ -27,7 +27,10 @@
  *                             ntsm_eval_project_store
  *   --contam STORE [--samples-out FILE]   is a sample a mixture, and of whom: every ordered pair (target, source) of the store,
  *                             in bands of targets: ntsm_eval_contam_open / _rows; the table's text is eval_contam.hpp's
- * --within, --within-near, --between, --between-near, --qc and --contam read no counts file.  Not built, and refused: -b (the debug ground-truth mode) and -p without a
+ *   --trios STORE [--ped FILE]   which samples form a parent-parent-child trio, or do a pedigree's trios hold: bit-planes of
+ *                             genotype classes on the device: ntsm_eval_trio_open / _duos / _score; the runs and the text are
+ *                             eval_trio.hpp's
+ * --within, --within-near, --between, --between-near, --qc, --contam and --trios read no counts file.  Not built, and refused: -b (the debug ground-truth mode) and -p without a
  * normalization file (the reference dies in an assert).  Pinned to the reference: stdout equals, byte for byte, that of the
  * unmodified scoring class (oracle/ref_eval_driver.cpp -> oracle/_ref/ref_ntsmEval -t 1) and its recordings,
  * tests/test_eval_reference.py.
@@ -54,6 +57,7 @@
 #include "eval_index.hpp"
 #include "eval_qc.hpp"
 #include "eval_store.hpp"
+#include "eval_trio.hpp"
 #include "eval_within.hpp"
 
 #define PROGRAM "ntsmEval"
@@ -82,6 +86,10 @@ struct Opt {                                 /* src/Options.h:44-55 */
 	unsigned contamDepth = ntsm::eval_contam::kMinDepth, contamRows = 0;   /* --contam-depth D; --contam-rows N: targets per band, 0 = the band rule */
 	double contamMin = ntsm::eval_contam::kMinExcess, contamExplained = ntsm::eval_contam::kMinExplained;   /* --contam-min X, --contam-explained Y */
 	bool samplesOutGiven = false, contamFlagGiven = false;
+	std::string trios, ped;                  /* --trios STORE: parent-child trios in the store; --ped FILE: the trios to check instead of a search */
+	unsigned trioDepth = ntsm::eval_trio::kMinDepth, trioCalled = ntsm::eval_trio::kMinCalled;   /* --trio-depth D, --trio-called M */
+	double trioMax = ntsm::eval_trio::kMaxRate, trioDuo = ntsm::eval_trio::kMaxDuo;              /* --trio-max X, --trio-duo Y */
+	bool trioExhaustive = false, trioFlagGiven = false, pedGiven = false;
 	bool minCovGiven = false, dimGiven = false;
 	bool onlyMerge = false;
 	unsigned dim = 20;                       /* src/Options.h:22, 35-39: the PCA search */
@@ -247,6 +255,36 @@ void printHelpDialog()
 	    "                             of records]. For tests and measurements.\n"
 	    "      --samples-out = FILE   With --contam: write one line per sample of STORE to\n"
 	    "                             FILE: #sample sites minorReads depth rateAll.\n"
+	    "      --trios = STORE        Which samples of STORE form a parent-parent-child trio?\n"
+	    "                             A site of a sample is het when both alleles are above -c,\n"
+	    "                             homozygous when one is and the site has at least\n"
+	    "                             --trio-depth reads, else missing. A sample is a candidate\n"
+	    "                             parent of a child when they share at least --trio-called\n"
+	    "                             called sites and are opposite homozygotes at no more than\n"
+	    "                             --trio-duo of them. One row per child and pair of its\n"
+	    "                             candidates: child parentA parentB called errHom errHet\n"
+	    "                             rate calledA oppA calledB oppB, the Mendelian errors over\n"
+	    "                             the sites all three are called at. Without -a only rows\n"
+	    "                             with called >= --trio-called and rate <= --trio-max.\n"
+	    "                             Takes no FILES. Not with -p, -n, -b, -e or -o.\n"
+	    "      --trio-depth = INT     Least depth of a homozygous site [" << std::to_string(d.trioDepth) << "]\n"
+	    "      --trio-max = FLOAT     Largest error rate of a printed trio [" << std::to_string(d.trioMax) << "]\n"
+	    "      --trio-duo = FLOAT     Largest opposite-homozygote rate of a candidate parent\n"
+	    "                             [" << std::to_string(d.trioDuo) << "]\n"
+	    "      --trio-called = INT    Least called sites of a candidate and of a printed trio\n"
+	    "                             [" << std::to_string(d.trioCalled) << "]\n"
+	    "                             All four defaults are conventions to override: they come\n"
+	    "                             from one simulation, not from real data.\n"
+	    "      --trio-exhaustive      With --trios: every pair of other samples is tried for\n"
+	    "                             every child, without the candidate step.\n"
+	    "      --ped = FILE           With --trios: no search. Check the trios of the six-column\n"
+	    "                             pedigree FILE (columns 2-4: individual, father, mother;\n"
+	    "                             lines with a 0 parent are skipped). An ID names the sample\n"
+	    "                             whose stored name, basename, or basename without\n"
+	    "                             _counts.txt, .counts.txt or .txt it equals. One row per\n"
+	    "                             trio in file order, with a last column verdict: lowcov\n"
+	    "                             (called < --trio-called), ok (rate <= --trio-max) or fail.\n"
+	    "                             Not with -a or --trio-exhaustive.\n"
 	    "Not in this build: -b (debug mode of the PCA search); the PCA-guided search (-p)\n"
 	    "against a store (--index and --near are that search); merging (-e) from a store.\n" << std::endl;
 	exit(EXIT_SUCCESS);
@@ -364,6 +402,7 @@ typedef Handle<ntsm_eval_session, ntsm_eval_close> Session;
 typedef Handle<ntsm_eval_within_session, ntsm_eval_within_close> WithinSession;
 typedef Handle<ntsm_eval_between_session, ntsm_eval_between_close> BetweenSession;
 typedef Handle<ntsm_eval_contam_session, ntsm_eval_contam_close> ContamSession;
+typedef Handle<ntsm_eval_trio_session, ntsm_eval_trio_close> TrioSession;
 
 typedef std::chrono::steady_clock Clock;
 double msSince(Clock::time_point t) { return std::chrono::duration<double, std::milli>(Clock::now() - t).count(); }
@@ -443,7 +482,8 @@ int scorePCA(const Counts &c, std::vector<Genotype> &g, const Opt &opt, ntsm_eva
 
 constexpr int kOptPack = 1000, kOptAgainst = 1001, kOptIndex = 1002, kOptNear = 1003, kOptWithin = 1004, kOptWithinNear = 1005,
               kOptWithinRows = 1006, kOptBetween = 1007, kOptBetweenRows = 1008, kOptBetweenNear = 1009, kOptQc = 1010, kOptSitesOut = 1011,
-              kOptContam = 1012, kOptContamDepth = 1013, kOptContamMin = 1014, kOptContamExplained = 1015, kOptContamRows = 1016, kOptSamplesOut = 1017;   /* long-only: no letter of the reference's option string is taken */
+              kOptContam = 1012, kOptContamDepth = 1013, kOptContamMin = 1014, kOptContamExplained = 1015, kOptContamRows = 1016, kOptSamplesOut = 1017,
+              kOptTrios = 1018, kOptTrioDepth = 1019, kOptTrioMax = 1020, kOptTrioDuo = 1021, kOptTrioCalled = 1022, kOptTrioExhaustive = 1023, kOptPed = 1024;   /* long-only: no letter of the reference's option string is taken */
 
 /* --pack STORE FILES...: no GPU */
 int packStore(const Counts &c, const Opt &opt)
@@ -1181,6 +1221,81 @@ int contamStore(const Opt &opt, Clock::time_point t0)
 	return 0;
 }
 
+/* --trios STORE [-c N] [--trio-depth D] [--trio-max X] [--trio-duo Y] [--trio-called M] [--trio-exhaustive] [-a] [--ped FILE]:
+ * which samples of the store form a parent-parent-child trio, or whether a pedigree's trios hold.  The
+ * runs, their rules and the text are eval_trio.hpp's; this opens the store and the session and hands it the library's two entry
+ * points.  Every refusal -- the store, the pedigree, its IDs -- comes before the session is opened. */
+int trioStore(const Opt &opt, Clock::time_point t0)
+{
+	namespace tr = ntsm::eval_trio;
+	ntsm::eval_store::View store;
+	std::vector<std::string> nameOf;
+	std::vector<tr::PedTrio> pedTrios;
+	tr::Ped ped;
+	const auto tMap = Clock::now();
+	try {
+		openStore(opt.trios, 0, "scores", store, nullptr);
+		if (store.h.n_samples < 3) throw tr::Error(opt.trios + " holds fewer than 3 samples: there is no trio to look for");
+		nameOf.resize(store.h.n_samples);
+		for (uint32_t d = 0; d < nameOf.size(); ++d) nameOf[d] = store.name(d);
+		if (opt.pedGiven) {
+			std::ifstream fh(opt.ped);
+			struct stat sb;
+			if (!fh.good() || stat(opt.ped.c_str(), &sb) != 0 || !S_ISREG(sb.st_mode)) throw tr::Error("cannot read the pedigree file " + opt.ped);
+			std::stringstream text;
+			text << fh.rdbuf();
+			ped = tr::parse_ped(text.str());
+			pedTrios = tr::resolve(ped, nameOf);
+		}
+	} catch (const std::exception &e) {
+		ntsm::refuse(e.what());
+	}
+	const double mapMs = msSince(tMap);
+	const uint32_t n = (uint32_t) store.h.n_samples, m = store.h.n_sites;
+	if (opt.verbose > 0 && opt.pedGiven)
+		std::cerr << "Read " << pedTrios.size() << " trios from " << opt.ped << "; skipped " << ped.comments << " comment lines and " << ped.founders
+		          << " lines without both parents" << std::endl;
+	if (opt.verbose > 1) std::cerr << "Mapped " << opt.trios << ". Now looking for trios among its " << n << " samples." << std::endl;
+	TrioSession session;
+	ntsm_eval_cross_times open {};
+	int rc = ntsm_eval_trio_open(opt.device, store.counts(0), store.h.stride, n, m, opt.minCov, opt.trioDepth, 0, nullptr, &open, &session.h);
+	if (rc) return gpuFail("opening the store", rc);
+	double duoMs = 0, scoreMs = 0, duoCallMs = 0, scoreCallMs = 0, printMs = 0;
+	tr::Device dev;
+	dev.duos = [&](uint32_t first, uint32_t rows, ntsm_eval_trio_duo *out) {
+		const auto t = Clock::now();
+		double ms = 0;
+		const int r = ntsm_eval_trio_duos(session.h, first, rows, out, &ms);
+		duoMs += ms; duoCallMs += msSince(t);
+		return r;
+	};
+	dev.score = [&](const uint32_t *child, const uint64_t *offset, const uint32_t *cand, uint32_t count, ntsm_eval_trio_record *out) {
+		const auto t = Clock::now();
+		double ms = 0;
+		const int r = ntsm_eval_trio_score(session.h, child, offset, cand, count, out, &ms);
+		scoreMs += ms; scoreCallMs += msSince(t);
+		return r;
+	};
+	const tr::Sink sink = [&](const std::string &text) { const auto t = Clock::now(); std::cout << text; printMs += msSince(t); };
+	tr::Cuts cuts;
+	cuts.min_called = opt.trioCalled; cuts.max_rate = opt.trioMax; cuts.max_duo = opt.trioDuo; cuts.all = opt.all; cuts.exhaustive = opt.trioExhaustive;
+	tr::Stats st;
+	try {
+		rc = opt.pedGiven ? tr::pedigree(dev, nameOf, pedTrios, cuts, sink, st) : tr::search(dev, nameOf, cuts, sink, st);
+	} catch (const tr::Error &e) {
+		ntsm::refuse(e.what());
+	}
+	if (rc) return gpuFail("looking for trios", rc);
+	std::cout.flush();
+	if (opt.verbose > 1)
+		std::cerr << "store trios: planes " << 3ull * ((m + 63ull) / 64) * 8 * n << " bytes, " << open.chunks << " chunks, " << st.bands << " duo bands, "
+		          << st.children << " children with 2 or more candidates, " << st.triples << " triples, " << st.rows << " rows, map " << mapMs << " ms, upload "
+		          << open.upload_ms << " ms, plane kernel " << open.prepare_kernel_ms << " ms, duo " << duoCallMs << " ms (kernel " << duoMs << " ms), score "
+		          << scoreCallMs << " ms (kernel " << scoreMs << " ms), print " << printMs << " ms" << std::endl;
+	printTime(t0);
+	return 0;
+}
+
 /* what no store run goes with */
 void refuseDebugAndMerge(const Opt &opt, const char *mode)
 {
@@ -1193,7 +1308,7 @@ void refuseDebugAndMerge(const Opt &opt, const char *mode)
 int main(int argc, char **argv)
 {
 	Opt opt;
-	bool die = false, storeMode = false, nearMode = false, withinMode = false, betweenMode = false, betweenNearMode = false, qcMode = false, contamMode = false;
+	bool die = false, storeMode = false, nearMode = false, withinMode = false, betweenMode = false, betweenNearMode = false, qcMode = false, contamMode = false, trioMode = false;
 	static struct option long_options[] = {
 		{ "score_thresh", required_argument, nullptr, 's' }, { "all", no_argument, nullptr, 'a' },
 		{ "min_cov", required_argument, nullptr, 'c' }, { "skew", required_argument, nullptr, 'w' },
@@ -1213,6 +1328,10 @@ int main(int argc, char **argv)
 		{ "contam", required_argument, nullptr, kOptContam }, { "contam-depth", required_argument, nullptr, kOptContamDepth },
 		{ "contam-min", required_argument, nullptr, kOptContamMin }, { "contam-explained", required_argument, nullptr, kOptContamExplained },
 		{ "contam-rows", required_argument, nullptr, kOptContamRows }, { "samples-out", required_argument, nullptr, kOptSamplesOut },
+		{ "trios", required_argument, nullptr, kOptTrios }, { "trio-depth", required_argument, nullptr, kOptTrioDepth },
+		{ "trio-max", required_argument, nullptr, kOptTrioMax }, { "trio-duo", required_argument, nullptr, kOptTrioDuo },
+		{ "trio-called", required_argument, nullptr, kOptTrioCalled }, { "trio-exhaustive", no_argument, nullptr, kOptTrioExhaustive },
+		{ "ped", required_argument, nullptr, kOptPed },
 		{ nullptr, 0, nullptr, 0 } };
 	int ch;
 	while ((ch = getopt_long(argc, argv, "t:vhs:c:m:aw:g:p:n:d:r:e:o1:2:S:l:b:G:", long_options, nullptr)) != -1) {
@@ -1274,6 +1393,25 @@ int main(int argc, char **argv)
 			opt.contamFlagGiven = true;
 			break;
 		case kOptSamplesOut: opt.samplesOut = optarg; opt.samplesOutGiven = true; break;
+		case kOptTrios: opt.trios = optarg; trioMode = true; break;
+		case kOptTrioDepth:
+			if (optarg[0] == '-' || !ntsm::read_whole(optarg, opt.trioDepth)) ntsm::refuse(std::string("--trio-depth takes a number of reads, not ") + optarg);
+			opt.trioFlagGiven = true;
+			break;
+		case kOptTrioCalled:
+			if (optarg[0] == '-' || !ntsm::read_whole(optarg, opt.trioCalled)) ntsm::refuse(std::string("--trio-called takes a number of sites, not ") + optarg);
+			opt.trioFlagGiven = true;
+			break;
+		case kOptTrioMax:
+			if (!ntsm::read_whole(optarg, opt.trioMax) || !std::isfinite(opt.trioMax)) ntsm::refuse(std::string("--trio-max takes a number, not ") + optarg);
+			opt.trioFlagGiven = true;
+			break;
+		case kOptTrioDuo:
+			if (!ntsm::read_whole(optarg, opt.trioDuo) || !std::isfinite(opt.trioDuo)) ntsm::refuse(std::string("--trio-duo takes a number, not ") + optarg);
+			opt.trioFlagGiven = true;
+			break;
+		case kOptTrioExhaustive: opt.trioExhaustive = true; opt.trioFlagGiven = true; break;
+		case kOptPed: opt.ped = optarg; opt.pedGiven = true; break;
 		case '?': die = true; break;
 		default: break;                              /* m: read by the reference, without effect */
 		}
@@ -1281,6 +1419,11 @@ int main(int argc, char **argv)
 	Counts c;
 	while (optind < argc) c.files.emplace_back(argv[optind++]);
 	const char *sevenRuns = "--pack, --against, --index, --near, --within, --within-near and --between are seven runs: give one of them";
+	if (trioMode && (storeMode || nearMode || withinMode || betweenMode || betweenNearMode || qcMode || contamMode))
+		ntsm::refuse("--trios looks for parent-child trios in one store and is a run of its own: it goes with none of --pack, --against, --index, --near, "
+		             "--within, --within-near, --between, --between-near, --qc and --contam");
+	if ((opt.trioFlagGiven || opt.pedGiven) && !trioMode)
+		ntsm::refuse("--trio-depth, --trio-max, --trio-duo, --trio-called, --trio-exhaustive and --ped belong to --trios: give them with --trios STORE");
 	if (contamMode && (storeMode || nearMode || withinMode || betweenMode || betweenNearMode || qcMode))
 		ntsm::refuse("--contam checks one store for cross-sample contamination and is a run of its own: it goes with none of --pack, --against, --index, "
 		             "--near, --within, --within-near, --between, --between-near and --qc");
@@ -1328,6 +1471,15 @@ int main(int argc, char **argv)
 		return near ? searchWithin(opt, t0) : scoreWithin(opt, t0);
 	}
 	if (opt.withinRowsGiven) ntsm::refuse("--within-rows sets the bands of --within: give it with --within STORE");
+	if (trioMode) {                                      /* --trios: every refusal that needs no store, then the run */
+		if (!c.files.empty()) ntsm::refuse("--trios takes no input files: it looks for trios among the samples of the store");
+		if (!opt.pca.empty() || !opt.norm.empty()) ntsm::refuse("--trios reads allele counts, not projections, and takes no -p and no -n");
+		refuseDebugAndMerge(opt, "--trios");
+		if (opt.pedGiven && opt.trioExhaustive) ntsm::refuse("--ped checks the trios of a pedigree and searches nothing: it does not go with --trio-exhaustive");
+		if (opt.pedGiven && opt.all) ntsm::refuse("--ped prints every trio of the pedigree with its verdict: it does not go with -a");
+		ntsm::try_help_if(die);
+		return trioStore(opt, Clock::now());
+	}
 	if (contamMode) {                                    /* --contam: every refusal that needs no store, then the run */
 		if (!c.files.empty()) ntsm::refuse("--contam takes no input files: it checks the samples of the store against each other");
 		if (!opt.pca.empty() || !opt.norm.empty()) ntsm::refuse("--contam reads allele counts, not projections, and takes no -p and no -n");

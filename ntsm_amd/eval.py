@@ -1,6 +1,6 @@
 """ctypes plumbing for include/ntsm_eval_hip.h (all-pairs scoring of ntsmEval on the GPU, its PCA-guided search, queries and
 that search against a cohort store, the pairs inside a store, one store against another, the search between two, the QC
-tables of a store and the contamination check over one); used by tests and tools.
+tables of a store, the contamination check over one and the trios in one); used by tests and tools.
 Loaded on demand: `import ntsm_amd.eval`.  Fails loudly when libntsm_eval_hip.so has not been built."""
 import ctypes as C
 import os
@@ -672,3 +672,144 @@ def contam_band_rows(row_first, n_db, limit=(1 << 30) // 64):
     """The band rule of --contam: the targets a band from row_first takes under `limit` records."""
     from .capi import HO
     return HO.ntsm_host_contam_band_rows(row_first, n_db, limit)
+
+
+# ---- parent-parent-child trios in a cohort store (ntsmEval --trios; include/ntsm_eval_hip.h: ntsm_eval_trio_open ... _tune).
+TRIO_DUO = np.dtype([("called", "<u4"), ("opp", "<u4")])
+TRIO_RECORD = np.dtype([("called", "<u4"), ("err_hom", "<u4"), ("err_het", "<u4"), ("pad", "<u4")])
+assert TRIO_DUO.itemsize == 8 and TRIO_RECORD.itemsize == 16
+lib.ntsm_eval_trio_open.restype = C.c_int
+lib.ntsm_eval_trio_open.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(CrossTimes),
+                                    C.POINTER(C.c_void_p)]
+lib.ntsm_eval_trio_duos.restype = C.c_int
+lib.ntsm_eval_trio_duos.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_double)]
+lib.ntsm_eval_trio_score.restype = C.c_int
+lib.ntsm_eval_trio_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_double)]
+lib.ntsm_eval_trio_close.restype = None
+lib.ntsm_eval_trio_close.argtypes = [C.c_void_p]
+lib.ntsm_eval_trio_tune.restype = C.c_int
+lib.ntsm_eval_trio_tune.argtypes = [C.c_uint32]
+
+
+def trio_tune(width):
+    """Force the workgroup width (64 or 256) of later Trio.duos and Trio.score calls in this process; 0 = the library's rule."""
+    rc = lib.ntsm_eval_trio_tune(width)
+    if rc:
+        raise ValueError("ntsm_eval_trio_tune(%r) failed: %d" % (width, rc))
+
+
+class Trio:
+    """The genotype bit-planes of a store on the device (ntsm_eval_trio_open): db is uint32 [n_db][n_sites][2] or Records, read
+    once, here.  geno: uint32 [n_db, 4] = homAT, het, homCG, miss, or None when switched off (passed as NULL); times: the
+    CrossTimes of open.  A context manager: `with Trio(db) as s: duo, ms = s.duos(0, s.n)`."""
+
+    def __init__(self, db, min_cov=1, min_depth=8, db_chunk=0, device=0, geno=True):
+        records = _records(db)
+        self.n, self.m = records.n, records.m
+        self.h = C.c_void_p()
+        self.geno = np.zeros((self.n, 4), dtype=np.uint32) if geno else None
+        self.times = CrossTimes()
+        rc = lib.ntsm_eval_trio_open(device, records.address, records.stride, self.n, self.m, min_cov, min_depth, db_chunk,
+                                     None if self.geno is None else self.geno.ctypes.data, C.byref(self.times), C.byref(self.h))
+        if rc:
+            raise RuntimeError("ntsm_eval_trio_open failed: %d" % rc)
+
+    def duos(self, row_first, n_rows):
+        """Rows row_first ... row_first + n_rows - 1 against every sample: (records [n_rows, n] of TRIO_DUO, kernel ms)."""
+        count = n_rows if 0 <= row_first and 0 <= n_rows and row_first + n_rows <= self.n else 0
+        out = np.zeros((count, self.n), dtype=TRIO_DUO)
+        ms = C.c_double()
+        rc = lib.ntsm_eval_trio_duos(self.h, row_first, n_rows, out.ctypes.data, C.byref(ms))
+        if rc:
+            raise RuntimeError("ntsm_eval_trio_duos failed: %d" % rc)
+        return out, ms.value
+
+    def score(self, children, lists):
+        """The trios of every entry (children[i]; every pair of positions p < q of lists[i]), in CSR order: (records of
+        TRIO_RECORD, kernel ms)."""
+        child = np.ascontiguousarray(children, dtype=np.uint32)
+        offset = np.zeros(len(lists) + 1, dtype=np.uint64)
+        offset[1:] = np.cumsum([len(l) for l in lists], dtype=np.uint64)
+        cand = np.ascontiguousarray(np.concatenate([np.asarray(l, dtype=np.uint32) for l in lists]) if len(lists) else [], dtype=np.uint32)
+        out = np.zeros(sum(len(l) * (len(l) - 1) // 2 for l in lists), dtype=TRIO_RECORD)
+        ms = C.c_double()
+        rc = lib.ntsm_eval_trio_score(self.h, child.ctypes.data, offset.ctypes.data, cand.ctypes.data, len(lists), out.ctypes.data, C.byref(ms))
+        if rc:
+            raise RuntimeError("ntsm_eval_trio_score failed: %d" % rc)
+        return out, ms.value
+
+    def close(self):
+        if self.h:
+            lib.ntsm_eval_trio_close(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+
+def _u32(a):
+    a = np.ascontiguousarray(a, dtype=np.uint32)
+    return a, a.ctypes.data_as(C.POINTER(C.c_uint32))
+
+
+def trio_rows_text(names, child, pa, pb, rec, da, db, ped=False, all_rows=False, min_called=200, max_rate=0.02):
+    """The stdout lines of `ntsmEval --trios` for these evaluated triples, without the header (ntsm_amd/csrc/host/eval_trio.hpp
+    through libntsm_host.so): child, pa, pb index names; rec of TRIO_RECORD; da, db of TRIO_DUO = (child, parentA), (child, parentB)."""
+    from .capi import HO
+    (child, cp), (pa, ap), (pb, bp) = _u32(child), _u32(pa), _u32(pb)
+    rec = np.ascontiguousarray(rec, dtype=TRIO_RECORD)
+    da, db = np.ascontiguousarray(da, dtype=TRIO_DUO), np.ascontiguousarray(db, dtype=TRIO_DUO)
+    out, ln = C.c_void_p(), C.c_size_t()
+    rc = HO.ntsm_host_trio_rows(_names(names), len(names), len(child), cp, ap, bp, rec.ctypes.data, da.ctypes.data, db.ctypes.data, int(ped), int(all_rows),
+                                min_called, max_rate, C.byref(out), C.byref(ln))
+    if rc:
+        raise RuntimeError("ntsm_host_trio_rows failed: %d" % rc)
+    return _host_text(out, ln)
+
+
+def trio_ped_parse(text, names):
+    """The complete trios of a pedigree file's bytes as samples of names: ([(child, father, mother), ...], comment lines skipped,
+    lines with a 0 parent skipped); a refusal raises ValueError with its sentence."""
+    from .capi import HO
+    trios, n, err, err_len = C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_size_t()
+    comments, founders = C.c_uint64(), C.c_uint64()
+    rc = HO.ntsm_host_trio_ped_parse(text, len(text), _names(names), len(names), C.byref(trios), C.byref(n), C.byref(comments), C.byref(founders),
+                                     C.byref(err), C.byref(err_len))
+    if rc == 1:
+        raise ValueError(_host_text(err, err_len).decode())
+    if rc:
+        raise RuntimeError("ntsm_host_trio_ped_parse failed: %d" % rc)
+    flat = np.ctypeslib.as_array(C.cast(trios, C.POINTER(C.c_uint32)), shape=(max(n.value, 1) * 3,))[:n.value * 3].copy()
+    HO.ntsm_host_free(trios)
+    return [tuple(int(v) for v in flat[3 * i:3 * i + 3]) for i in range(n.value)], comments.value, founders.value
+
+
+def trio_match(names, sample_id):
+    """The sample an ID of a pedigree names: its index, -1 where none matches, -2 where the first matching level is ambiguous."""
+    from .capi import HO
+    return HO.ntsm_host_trio_match(_names(names), len(names), sample_id.encode())
+
+
+def trio_candidates(row, child, min_called=200, max_duo=0.02):
+    """The candidate parents of `child` out of its duo row (TRIO_DUO [n_db]), in store order."""
+    from .capi import HO
+    row = np.ascontiguousarray(row, dtype=TRIO_DUO)
+    out = np.zeros(max(len(row), 1), dtype=np.uint32)
+    n = HO.ntsm_host_trio_candidates(row.ctypes.data, len(row), child, min_called, max_duo, out.ctypes.data_as(C.POINTER(C.c_uint32)))
+    return out[:n].tolist()
+
+
+def trio_batches(lengths, limit=(1 << 30) // 16):
+    """The batch cutter of --trios: (the ends of the batches, None), or (None, the position of a list that alone exceeds limit)."""
+    from .capi import HO
+    k, kp = _u32(lengths)
+    ends = (C.c_size_t * max(len(k), 1))()
+    n_ends = C.c_size_t()
+    bad = HO.ntsm_host_trio_batches(kp, len(k), limit, ends, C.byref(n_ends))
+    return (list(ends[:n_ends.value]), None) if bad == len(k) else (None, bad)

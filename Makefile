@@ -98,10 +98,13 @@ xlib:
 # + parent-parent-child trios in a store (--trios): ntsm_eval_trio.hip, bit-planes of genotype classes and popcount kernels over
 #   site words; the chunk rule and the 2-D copy are ntsm_eval_chunk.h's, the candidate rule, the batches, the pedigree and the
 #   text are host code (host/eval_trio.hpp)
+# + what those store paths share on the host side of their HIP calls: ntsm_eval_chunk.h also states the check of a store argument,
+#   the launch rule of the row-group kernels (cross, contam, the trio duo kernel) and the timed launch; ntsm_eval_band.h states the
+#   band session of --within, --between and --contam once: the holding of a store's columns, resident or streamed, and the band walk
 EVALSRC := $(CSRC)/ntsm_eval.hip $(CSRC)/ntsm_eval_pca.hip $(CSRC)/ntsm_eval_cross.hip $(CSRC)/ntsm_eval_near.hip $(CSRC)/ntsm_eval_within.hip \
            $(CSRC)/ntsm_eval_between.hip $(CSRC)/ntsm_eval_between_near.hip $(CSRC)/ntsm_eval_profile.hip $(CSRC)/ntsm_eval_contam.hip \
            $(CSRC)/ntsm_eval_trio.hip
-ntsm_amd/libntsm_eval_hip.so: $(EVALSRC) $(CSRC)/ntsm_eval_score.h $(CSRC)/ntsm_eval_chunk.h $(CSRC)/ntsm_eval_pca.h $(CSRC)/ntsm_hip_scope.h $(CSRC)/xprec.h \
+ntsm_amd/libntsm_eval_hip.so: $(EVALSRC) $(CSRC)/ntsm_eval_score.h $(CSRC)/ntsm_eval_chunk.h $(CSRC)/ntsm_eval_band.h $(CSRC)/ntsm_eval_pca.h $(CSRC)/ntsm_hip_scope.h $(CSRC)/xprec.h \
                               $(HOST)/eval_within.hpp $(HOST)/eval_between.hpp $(HOST)/eval_store.hpp include/ntsm_eval_hip.h
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -shared -o $@ $(EVALSRC)
 

@@ -780,6 +780,13 @@ int searchNear(Counts &c, Opt &opt, Clock::time_point t0)
 	return routeAndScore(c, g, opt, store, radius, cand, route, mapMs, projectMs, searchMs, t0);
 }
 
+/* one band's times added to a run's */
+void addTimes(ntsm_eval_cross_times &sum, const ntsm_eval_cross_times &t)
+{
+	sum.upload_ms += t.upload_ms; sum.prepare_kernel_ms += t.prepare_kernel_ms; sum.cross_kernel_ms += t.cross_kernel_ms;
+	sum.download_ms += t.download_ms; sum.chunks += t.chunks;
+}
+
 /* --within STORE: computeScore's rows (:591-624) over the store's samples in store order -- the stdout of the all-to-all run
  * over their files at one thread -- without reading a counts file.  The triangle comes in bands of rows (eval_within.hpp's
  * rule, or --within-rows), printed band by band, which is the reference's order; the first band's call brings every
@@ -816,8 +823,7 @@ int scoreWithin(const Opt &opt, Clock::time_point t0)
 		ntsm_eval_cross_times times {};
 		rc = ntsm_eval_within_rows(session.h, first, rows, rec.data(), first == 0 ? geno.data() : nullptr, &times);
 		if (rc) return gpuFail("scoring the store", rc);
-		sum.upload_ms += times.upload_ms; sum.prepare_kernel_ms += times.prepare_kernel_ms; sum.cross_kernel_ms += times.cross_kernel_ms;
-		sum.download_ms += times.download_ms; sum.chunks += times.chunks;
+		addTimes(sum, times);
 		const auto tPrint = Clock::now();
 		if (first == 0) {
 			appendStoreSamples(c, g, store, opt, [&](uint32_t d, Genotype &s) { s.hets = geno[3 * d]; s.homs = geno[3 * d + 1]; s.miss = geno[3 * d + 2]; });
@@ -917,8 +923,7 @@ int scoreBetween(const Opt &opt, const std::string &storeB, Clock::time_point t0
 		ntsm_eval_cross_times times {};
 		rc = ntsm_eval_between_rows(session.h, first, rows, rec.data(), genoA.data(), first == 0 ? genoB.data() : nullptr, &times);
 		if (rc) return gpuFail("scoring the stores", rc);
-		sum.upload_ms += times.upload_ms; sum.prepare_kernel_ms += times.prepare_kernel_ms; sum.cross_kernel_ms += times.cross_kernel_ms;
-		sum.download_ms += times.download_ms; sum.chunks += times.chunks;
+		addTimes(sum, times);
 		const auto tPrint = Clock::now();
 		if (first == 0) {
 			appendStoreSamples(c, g, b, opt, [&](uint32_t d, Genotype &s) { s.hets = genoB[3 * d]; s.homs = genoB[3 * d + 1]; s.miss = genoB[3 * d + 2]; });
@@ -1197,8 +1202,7 @@ int contamStore(const Opt &opt, Clock::time_point t0)
 		ntsm_eval_cross_times times {};
 		rc = ntsm_eval_contam_rows(session.h, first, rows, rec.data(), tally.data() + (size_t) first * 3, &times);
 		if (rc) return gpuFail("checking the store", rc);
-		sum.upload_ms += times.upload_ms; sum.prepare_kernel_ms += times.prepare_kernel_ms; sum.cross_kernel_ms += times.cross_kernel_ms;
-		sum.download_ms += times.download_ms; sum.chunks += times.chunks;
+		addTimes(sum, times);
 		const auto tPrint = Clock::now();
 		if (first == 0) std::cout << ct::kHeader;
 		temp.clear();

@@ -19,7 +19,9 @@
  *
  * Holdings.  B is resident when the chunk rule, asked at 24 bytes per sample and site of A, answers n_b: staged once at
  * open, the dense third released again.  Otherwise every _rows call walks B in chunks of b_chunk.  A's band is always
- * uploaded and transposed by the _rows call into a buffer of its own pitch.  One stream, no overlap.
+ * uploaded and transposed by the _rows call into a buffer of its own pitch.  The holding, the staging of a band's rows and
+ * the walk are ntsm_eval_band.h's; what is here: the kernels, the launch, B's stager and the bytes per sample.  One stream,
+ * no overlap.
  */
 #include <hip/hip_runtime.h>
 
@@ -27,20 +29,23 @@
 #include <cstdint>
 #include <cstring>
 #include <memory>
-#include <vector>
 
 #include "../../include/ntsm_eval_hip.h"
 #include "host/eval_between.hpp"
 #define NTSM_HIP_TAG "ntsm_eval_between"
-#include "ntsm_eval_chunk.h"
+#include "ntsm_eval_band.h"
 #include "ntsm_eval_score.h"
 #include "ntsm_hip_scope.h"
 
 namespace {
 
+using ntsm_eval_band::Staged;
+using ntsm_eval_band::Window;
 using ntsm_eval_chunk::kThreads;
 using ntsm_eval_chunk::kTile;
 using ntsm_eval_chunk::ms_since;
+using ntsm_eval_chunk::timed_copy;
+using ntsm_eval_chunk::valid_store;
 using ntsm_eval_chunk::wall;
 constexpr int kTI = 4;                       /* rows of A per workgroup, as in ntsm_eval.hip */
 constexpr uint32_t kLacks = ntsm::eval_between::kLacks;
@@ -125,72 +130,66 @@ __global__ __launch_bounds__(kThreads) void ntsm_eval_between_tally_kernel(const
 	if (threadIdx.x < 3) geno[(uint64_t) blockIdx.x * 3 + threadIdx.x] = sum[threadIdx.x];
 }
 
-/* a window of transposed samples on the device */
-struct Window { const uint32_t *at, *cg; const double *term; uint32_t pitch, count; };
-
-/* the pairs of the rows with the columns into d_out [rows.count][out_pitch] from column col_first on, timed into *ms (added) */
-int launch_between(const Window &rows, const Window &cols, uint32_t n_sites, uint32_t min_cov, ntsm_eval_record *d_out, uint64_t out_pitch, uint32_t col_first,
-		hipEvent_t e0, hipEvent_t e1, double *ms)
+/* the pairs of the rows with the columns into d_out [rows.count][out_pitch] from column cols.first on, timed into *ms (added) */
+int launch_between(const Window &rows, const Window &cols, uint32_t n_sites, uint32_t min_cov, ntsm_eval_record *d_out, uint64_t out_pitch, hipEvent_t e0,
+		hipEvent_t e1, double *ms)
 {
 	/* 256 threads, unlike ntsm_eval_cross and ntsm_eval_within: on 1,024 rows x 4,096 columns x 96,287 sites they take 777 ms
 	 * against 817 ms for 64 (three alternating runs each, spreads 11 and 14 ms).  A launch of at most
 	 * 256 columns keeps one-wave workgroups: a wider one would only add waves that compute clamped copies.  Nothing between
 	 * 256 and 4,096 columns has been measured.  ntsm_eval_between_tune forces either width. */
 	const unsigned bt = g_width ? g_width : cols.count > 256 ? 256 : 64;
-	HIPCHK(hipEventRecord(e0, 0));
-	for (uint32_t y0 = 0; y0 < rows.count; y0 += kMaxGridY * kTI) {             /* a grid's second dimension ends at 65,535 */
-		const uint32_t yn = std::min<uint32_t>(rows.count - y0, kMaxGridY * kTI);
-		hipLaunchKernelGGL(ntsm_eval_between_kernel, dim3((cols.count + bt - 1) / bt, (yn + kTI - 1) / kTI), dim3(bt), 0, 0, rows.at + y0, rows.cg + y0,
-				rows.term + y0, rows.pitch, yn, cols.at, cols.cg, cols.term, cols.pitch, cols.count, n_sites, min_cov, d_out + (uint64_t) y0 * out_pitch + col_first,
-				out_pitch);
-		HIPCHK(hipGetLastError());
-	}
-	HIPCHK(hipEventRecord(e1, 0));
-	HIPCHK(hipEventSynchronize(e1));
-	return ntsm_eval_chunk::add_interval(e0, e1, ms);
+	return ntsm_eval_chunk::timed(e0, e1, ms, [&] {
+		for (uint32_t y0 = 0; y0 < rows.count; y0 += kMaxGridY * kTI) {             /* a grid's second dimension ends at 65,535 */
+			const uint32_t yn = std::min<uint32_t>(rows.count - y0, kMaxGridY * kTI);
+			hipLaunchKernelGGL(ntsm_eval_between_kernel, dim3((cols.count + bt - 1) / bt, (yn + kTI - 1) / kTI), dim3(bt), 0, 0, rows.at + y0, rows.cg + y0,
+					rows.term + y0, rows.pitch, yn, cols.at, cols.cg, cols.term, cols.pitch, cols.count, n_sites, min_cov,
+					d_out + (uint64_t) y0 * out_pitch + cols.first, out_pitch);
+			HIPCHK(hipGetLastError());
+		}
+		return 0;
+	});
 }
 
 }  // namespace
 
 struct ntsm_eval_between_session {
-	int device = 0;
 	const char *a = nullptr, *b = nullptr;
 	uint64_t a_stride = 0, b_stride = 0;
 	uint32_t n_a = 0, n_b = 0, n_sites_a = 0, n_sites_b = 0, min_cov = 0;
-	uint32_t chunk = 0;                      /* samples of B per pass */
-	bool resident = false, device_work = false;
-	ntsm_hip::Buffers buf;
-	ntsm_hip::Events<2> ev;
-	/* B over A's sites: resident, all of it [site][n_b]; streamed, one chunk [site][chunk]; with its staging, tallies and map */
-	uint32_t *d_at = nullptr, *d_cg = nullptr, *d_raw = nullptr, *d_geno = nullptr, *d_map = nullptr;
-	double *d_term = nullptr;
-	std::vector<uint32_t> geno;              /* resident: [n_b][3], taken at open */
-	ntsm_eval_cross_times open_times {};     /* resident: the upload and preparation of open, reported by the first _rows call */
+	ntsm_eval_band::Holding<uint32_t> hold;  /* B over A's sites as columns, with its hets, homs, miss; its buffers hold the map too */
+	uint32_t *d_map = nullptr;
 
-	/* Samples first ... first + count - 1 of B over A's sites into d_at / d_cg / d_term [site][count] and, with `tallies`,
-	 * d_geno; waits for it and adds its times to tm.  Identical tables: ntsm_eval_chunk::stage as it is. */
-	int stage_b(uint32_t first, uint32_t count, bool tallies, ntsm_eval_cross_times &tm)
+	/* A's rows: ntsm_eval_chunk.h's staging of a window as it is */
+	auto stager_a()
 	{
-		if (!d_map) {
-			const int rc = ntsm_eval_chunk::stage(b, b_stride, first, count, n_sites_a, min_cov, d_raw, d_at, d_cg, d_term, tallies ? d_geno : nullptr, ev[0], ev[1], tm);
-			if (rc) return rc;
-		} else {
+		return [this](uint32_t first, uint32_t count, const Staged<uint32_t> &to, bool tallies, ntsm_eval_cross_times &tm) {
+			return ntsm_eval_band::stage_scored(a, a_stride, first, count, n_sites_a, min_cov, to, tallies, hold.ev[0], hold.ev[1], tm);
+		};
+	}
+
+	/* B's samples over A's sites.  Identical tables: as A's.  Mapped: the 2-D copy of B's own n_sites_b-wide rows, then this
+	 * file's gathering transpose and tallies. */
+	auto stager_b()
+	{
+		return [this](uint32_t first, uint32_t count, const Staged<uint32_t> &to, bool tallies, ntsm_eval_cross_times &tm) {
+			if (!d_map) return ntsm_eval_band::stage_scored(b, b_stride, first, count, n_sites_a, min_cov, to, tallies, hold.ev[0], hold.ev[1], tm);
 			const uint64_t row_bytes = 8ull * n_sites_b;
 			const auto t = wall::now();
-			if (row_bytes) HIPCHK(hipMemcpy2D(d_raw, row_bytes, b + (uint64_t) first * b_stride, b_stride, row_bytes, count, hipMemcpyHostToDevice));
+			if (row_bytes) HIPCHK(hipMemcpy2D(to.raw, row_bytes, b + (uint64_t) first * b_stride, b_stride, row_bytes, count, hipMemcpyHostToDevice));
 			tm.upload_ms += ms_since(t);
-			HIPCHK(hipEventRecord(ev[0], 0));
-			hipLaunchKernelGGL(ntsm_eval_between_prepare_kernel, dim3((n_sites_a + kTile - 1) / kTile, (count + kTile - 1) / kTile), dim3(kThreads), 0, 0,
-					(const uint2 *) d_raw, d_map, count, n_sites_a, n_sites_b, min_cov, d_at, d_cg, d_term);
-			HIPCHK(hipGetLastError());
-			if (tallies) {
-				hipLaunchKernelGGL(ntsm_eval_between_tally_kernel, dim3(count), dim3(kThreads), 0, 0, (const uint2 *) d_raw, d_map, n_sites_a, n_sites_b, min_cov, d_geno);
+			return ntsm_eval_chunk::timed(hold.ev[0], hold.ev[1], &tm.prepare_kernel_ms, [&] {
+				hipLaunchKernelGGL(ntsm_eval_between_prepare_kernel, dim3((n_sites_a + kTile - 1) / kTile, (count + kTile - 1) / kTile), dim3(kThreads), 0, 0,
+						(const uint2 *) to.raw, d_map, count, n_sites_a, n_sites_b, min_cov, to.at, to.cg, to.term);
 				HIPCHK(hipGetLastError());
-			}
-			HIPCHK(hipEventRecord(ev[1], 0));
-		}
-		HIPCHK(hipEventSynchronize(ev[1]));
-		return ntsm_eval_chunk::add_interval(ev[0], ev[1], &tm.prepare_kernel_ms);
+				if (tallies) {
+					hipLaunchKernelGGL(ntsm_eval_between_tally_kernel, dim3(count), dim3(kThreads), 0, 0, (const uint2 *) to.raw, d_map, n_sites_a, n_sites_b, min_cov,
+							to.tally);
+					HIPCHK(hipGetLastError());
+				}
+				return 0;
+			});
+		};
 	}
 };
 
@@ -206,53 +205,28 @@ extern "C" int ntsm_eval_between_open(int device, const void *a_counts, uint64_t
 {
 	if (!h) return -1;
 	*h = nullptr;
-	if ((!a_counts && n_a && n_sites_a) || a_stride_bytes < 8ull * n_sites_a || a_stride_bytes % 4) return -1;
-	if ((!b_counts && n_b && n_sites_b) || b_stride_bytes < 8ull * n_sites_b || b_stride_bytes % 4) return -1;
+	if (!valid_store(a_counts, a_stride_bytes, n_a, n_sites_a) || !valid_store(b_counts, b_stride_bytes, n_b, n_sites_b)) return -1;
 	if (site_map ? !ntsm::eval_between::valid_map(site_map, n_sites_a, n_sites_b) : n_sites_a != n_sites_b) return -1;
 	std::unique_ptr<ntsm_eval_between_session> s(new ntsm_eval_between_session);
-	s->device = device;
 	s->a = (const char *) a_counts; s->a_stride = a_stride_bytes; s->n_a = n_a; s->n_sites_a = n_sites_a;
 	s->b = (const char *) b_counts; s->b_stride = b_stride_bytes; s->n_b = n_b; s->n_sites_b = n_sites_b;
 	s->min_cov = min_cov;
 	if (n_a == 0 || n_b == 0 || n_sites_a == 0) { *h = s.release(); return 0; }   /* nothing to score: no device work, here or in _rows */
 
-	HIPCHK(hipSetDevice(device));
-	s->device_work = true;
-	size_t free_b = 0, total_b = 0;
-	if (b_chunk == 0) HIPCHK(hipMemGetInfo(&free_b, &total_b));
 	/* 24 bytes per sample and site of A: the transposed 16 and the dense 8 (a map that leaves sites of B unnamed may make the dense third the larger) */
-	s->chunk = ntsm_eval_chunk::samples_per_pass(b_chunk, n_b, free_b, 16ull * n_sites_a + 8ull * std::max(n_sites_a, n_sites_b) + 12, 0);
-	s->resident = s->chunk == n_b;
-	const uint64_t cells = (uint64_t) s->chunk * n_sites_a;
-	HIPCHK(s->ev.create());
-	HIPCHK(s->buf.alloc(&s->d_at, cells));
-	HIPCHK(s->buf.alloc(&s->d_cg, cells));
-	HIPCHK(s->buf.alloc(&s->d_term, cells));
-	HIPCHK(s->buf.alloc(&s->d_geno, (uint64_t) s->chunk * 3));
-	HIPCHK(s->buf.alloc(&s->d_raw, (uint64_t) s->chunk * n_sites_b * 2));
+	int rc = s->hold.open(device, n_b, n_sites_a, n_sites_b, b_chunk, 16ull * n_sites_a + 8ull * std::max(n_sites_a, n_sites_b) + 12, true, true);
+	if (rc) return rc;
 	if (site_map) {
-		HIPCHK(s->buf.alloc(&s->d_map, n_sites_a));
-		const auto t = wall::now();
-		HIPCHK(hipMemcpy(s->d_map, site_map, (size_t) n_sites_a * sizeof(uint32_t), hipMemcpyHostToDevice));
-		s->open_times.upload_ms += ms_since(t);
+		HIPCHK(s->hold.b.alloc(&s->d_map, n_sites_a));
+		if ((rc = timed_copy(s->d_map, site_map, (size_t) n_sites_a * sizeof(uint32_t), hipMemcpyHostToDevice, &s->hold.open_times.upload_ms)) != 0) return rc;
 	}
-	if (s->resident) {
-		const int rc = s->stage_b(0, n_b, true, s->open_times);
-		if (rc) return rc;
-		s->geno.resize((size_t) n_b * 3);
-		const auto t = wall::now();
-		HIPCHK(hipMemcpy(s->geno.data(), s->d_geno, s->geno.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-		s->open_times.download_ms += ms_since(t);
-		HIPCHK(s->buf.release(&s->d_raw));                                       /* the dense third goes back before the records need room */
-	}
+	if ((rc = s->hold.fill(s->stager_b())) != 0) return rc;
 	*h = s.release();
 	return 0;
 }
 
 extern "C" void ntsm_eval_between_close(ntsm_eval_between_session *h)
 {
-	if (!h) return;
-	if (h->device_work) (void) hipSetDevice(h->device);                          /* a session without device work touches no device here either */
 	delete h;
 }
 
@@ -265,59 +239,22 @@ extern "C" int ntsm_eval_between_rows(ntsm_eval_between_session *h, uint32_t row
 	const uint32_t n_b = h->n_b, n_sites = h->n_sites_a, min_cov = h->min_cov;
 	const uint64_t records = (uint64_t) n_rows * n_b;
 	if (!out && records) return -1;
-	if (!h->device_work) {
+	if (!h->hold.device_work) {
 		if (records) memset(out, 0, records * sizeof(ntsm_eval_record));
 		if (a_geno && n_rows) memset(a_geno, 0, (size_t) n_rows * 3 * sizeof(uint32_t));
 		if (b_geno && n_b) memset(b_geno, 0, (size_t) n_b * 3 * sizeof(uint32_t));
 		return 0;
 	}
-	HIPCHK(hipSetDevice(h->device));
-	ntsm_hip::Buffers b;                                                          /* this call's: the records and the band's rows */
-	ntsm_eval_record *d_out;
-	uint32_t *d_rraw, *d_rat, *d_rcg, *d_rgeno;
-	double *d_rterm;
-	const uint64_t rcells = (uint64_t) n_rows * n_sites;
-	HIPCHK(b.alloc(&d_out, records));
-	HIPCHK(b.alloc(&d_rat, rcells));
-	HIPCHK(b.alloc(&d_rcg, rcells));
-	HIPCHK(b.alloc(&d_rterm, rcells));
-	HIPCHK(b.alloc(&d_rgeno, (uint64_t) n_rows * 3));
-	HIPCHK(b.alloc(&d_rraw, rcells * 2));
-	ntsm_eval_cross_times tm = h->open_times;
-	h->open_times = ntsm_eval_cross_times {};
-	int rc = ntsm_eval_chunk::stage(h->a, h->a_stride, row_first, n_rows, n_sites, min_cov, d_rraw, d_rat, d_rcg, d_rterm, a_geno ? d_rgeno : nullptr, h->ev[0],
-			h->ev[1], tm);
+	HIPCHK(hipSetDevice(h->hold.device));
+	ntsm_hip::Buffers b;                                                          /* this call's: the band's rows, always staged: they are A's */
+	ntsm_eval_cross_times tm = h->hold.take_open_times();
+	Window rows;
+	int rc = ntsm_eval_band::stage_rows(b, row_first, n_rows, n_sites, true, a_geno, h->stager_a(), tm, rows);
 	if (rc) return rc;
-	HIPCHK(hipEventSynchronize(h->ev[1]));
-	if ((rc = ntsm_eval_chunk::add_interval(h->ev[0], h->ev[1], &tm.prepare_kernel_ms)) != 0) return rc;
-	HIPCHK(b.release(&d_rraw));
-	if (a_geno) {
-		const auto t = wall::now();
-		HIPCHK(hipMemcpy(a_geno, d_rgeno, (size_t) n_rows * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-		tm.download_ms += ms_since(t);
-	}
-	const Window rows { d_rat, d_rcg, d_rterm, n_rows, n_rows };
-	if (h->resident) {
-		const Window cols { h->d_at, h->d_cg, h->d_term, n_b, n_b };
-		if ((rc = launch_between(rows, cols, n_sites, min_cov, d_out, n_b, 0, h->ev[0], h->ev[1], &tm.cross_kernel_ms)) != 0) return rc;
-		if (b_geno) memcpy(b_geno, h->geno.data(), h->geno.size() * sizeof(uint32_t));
-	} else {
-		for (uint32_t c0 = 0; c0 < n_b; c0 += h->chunk) {
-			const uint32_t cn = std::min(h->chunk, n_b - c0);
-			if ((rc = h->stage_b(c0, cn, b_geno != nullptr, tm)) != 0) return rc;
-			const Window cols { h->d_at, h->d_cg, h->d_term, cn, cn };
-			if ((rc = launch_between(rows, cols, n_sites, min_cov, d_out, n_b, c0, h->ev[0], h->ev[1], &tm.cross_kernel_ms)) != 0) return rc;
-			if (b_geno) {
-				const auto t = wall::now();
-				HIPCHK(hipMemcpy(b_geno + (size_t) c0 * 3, h->d_geno, (size_t) cn * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-				tm.download_ms += ms_since(t);
-			}
-			tm.chunks++;
-		}
-	}
-	const auto t = wall::now();
-	HIPCHK(hipMemcpy(out, d_out, records * sizeof(ntsm_eval_record), hipMemcpyDeviceToHost));
-	tm.download_ms += ms_since(t);
+	rc = h->hold.walk(0, records, out, b_geno, h->stager_b(), [&](const Window &cols, ntsm_eval_record *d_out) {
+		return launch_between(rows, cols, n_sites, min_cov, d_out, n_b, h->hold.ev[0], h->hold.ev[1], &tm.cross_kernel_ms);
+	}, tm);
+	if (rc) return rc;
 	if (times) *times = tm;
 	return 0;
 }

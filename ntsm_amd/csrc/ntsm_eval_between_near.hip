@@ -48,6 +48,7 @@ constexpr uint32_t kLacks = ntsm::eval_between::kLacks;
 constexpr uint32_t kMaxGridY = 65535;
 
 using ntsm_eval_chunk::add_interval;
+using ntsm_eval_chunk::valid_store;
 using ntsm_eval_chunk::ms_since;
 using ntsm_eval_chunk::wall;
 
@@ -72,12 +73,7 @@ void launch_remap(const uint32_t *src, const uint32_t *site_map, const uint32_t 
 			site_map, dst_row, n_rows, n_sites_a, n_sites_b, (uint2 *) dst);
 }
 
-/* what both entry points ask of their stores and map (ntsm_eval_between_open's rules) */
-bool stores_fit(const void *counts, uint64_t stride, uint32_t n, uint32_t n_sites)
-{
-	return !(!counts && n && n_sites) && stride >= 8ull * n_sites && stride % 4 == 0;
-}
-
+/* what both entry points ask of their map (ntsm_eval_between_open's rule) */
 bool map_fits(const uint32_t *site_map, uint32_t n_sites_a, uint32_t n_sites_b)
 {
 	return site_map ? ntsm::eval_between::valid_map(site_map, n_sites_a, n_sites_b) : n_sites_a == n_sites_b;
@@ -110,7 +106,7 @@ extern "C" int ntsm_eval_project_store_mapped(int device, const void *b_counts, 
 		return ntsm_eval_project_store(device, b_counts, b_stride_bytes, n_b, n_sites_a, min_cov, norm, rot, dim, b_chunk, cloud, b_geno, times);
 	}
 	if (times) *times = ntsm_eval_cross_times {};
-	if (!stores_fit(b_counts, b_stride_bytes, n_b, n_sites_b) || (n_sites_a && (!norm || (dim && !rot))) || (!cloud && n_b && dim)) return -1;
+	if (!valid_store(b_counts, b_stride_bytes, n_b, n_sites_b) || (n_sites_a && (!norm || (dim && !rot))) || (!cloud && n_b && dim)) return -1;
 	if (!map_fits(site_map, n_sites_a, n_sites_b)) return -1;
 	if (n_b && dim) memset(cloud, 0, (size_t) n_b * dim * sizeof(double));
 	if (b_geno && n_b) memset(b_geno, 0, (size_t) n_b * 3 * sizeof(uint32_t));
@@ -181,7 +177,7 @@ extern "C" int ntsm_eval_between_score_pairs(int device, const void *a_counts, u
 		const uint32_t *pk, uint64_t n_pairs, uint32_t chunk_arg, ntsm_eval_record *out, ntsm_eval_cross_times *times)
 {
 	if (times) *times = ntsm_eval_cross_times {};
-	if (!stores_fit(a_counts, a_stride_bytes, n_a, n_sites_a) || !stores_fit(b_counts, b_stride_bytes, n_b, n_sites_b)) return -1;
+	if (!valid_store(a_counts, a_stride_bytes, n_a, n_sites_a) || !valid_store(b_counts, b_stride_bytes, n_b, n_sites_b)) return -1;
 	if ((n_pairs && (!pi || !pk || !out)) || chunk_arg == 1 || !map_fits(site_map, n_sites_a, n_sites_b)) return -1;
 	const uint64_t n64 = (uint64_t) n_a + n_b;
 	if (n64 > UINT32_MAX) return -1;

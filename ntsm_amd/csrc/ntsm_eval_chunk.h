@@ -4,8 +4,10 @@
  * ntsm_eval_profile.hip (the QC tallies; the chunk rule and the copy only): the chunk
  * rule; the kernels -- the genotype tallies of the chunk's samples over the dense [chunk sample][site][2] buffer and that
  * buffer's transpose to at / cg / term [site][chunk sample] --; and the step that stages a chunk: the 2-D copy from the
- * host pitch, those kernels, the wall clock and the events that time them.  Internal: not part of include/.  The kernels
- * have internal linkage; each translation unit that includes this file carries its own copy, and names itself first
+ * host pitch, those kernels, the wall clock and the events that time them.  Also what every store path repeats around its HIP
+ * calls, whether it holds a band (ntsm_eval_band.h, which builds on this file) or not (ntsm_eval_trio.hip): the check of a store
+ * argument, the launch rule of the kernels with a wave-uniform row group, the timed launch and the timed copy.  Internal: not
+ * part of include/.  The kernels have internal linkage; each translation unit that includes this file carries its own copy, and names itself first
  * (NTSM_HIP_TAG, ntsm_hip_scope.h).
  */
 #ifndef NTSM_EVAL_CHUNK_H
@@ -96,8 +98,41 @@ inline uint32_t samples_per_pass(uint32_t db_chunk, uint32_t n_db, size_t free_b
 	return std::min(chunk, n_db);
 }
 
+/* what every entry point asks of a store argument: n samples of n_sites sites each, [site][2] uint32 at a pitch of `stride` bytes */
+inline bool valid_store(const void *counts, uint64_t stride, uint32_t n, uint32_t n_sites)
+{
+	return !(!counts && n && n_sites) && stride >= 8ull * n_sites && stride % 4 == 0;
+}
+
+/* Workgroup width and row group of one launch of a kernel that puts the columns across the lanes and a group of 1, 2 or 4 rows on
+ * the wave-uniform side (ntsm_eval_cross.hip, ntsm_eval_contam.hip, the duo kernel of ntsm_eval_trio.hip).  A lane's walk over the
+ * sites is sequential, so the only parallelism is across pairs: the widest group whose launch still puts a wave on every SIMD wins
+ * (each column value loaded is used `group` times); a rectangle too small for that takes single rows, which at least spreads what
+ * there is.  One-wave workgroups at every size: measured 4 to 5 % faster than 256 threads on 1 and 8 queries against 4,096 samples
+ * with the cross kernel and not measured again for the other two (sections 9.7, 9.8).  forced_width and
+ * forced_group are the caller's _tune values, 0 = this rule. */
+constexpr uint64_t kFillWaves = 1024;        /* one wave on every SIMD of the 256 CUs */
+inline void launch_shape(uint32_t n_rows, uint32_t n_cols, uint32_t forced_width, uint32_t forced_group, uint32_t &width, uint32_t &group)
+{
+	width = forced_width ? forced_width : 64;
+	const uint64_t waves = (n_cols + 63) / 64;
+	group = 1;
+	for (uint32_t t = 4; t > 1; t /= 2)
+		if (t / 2 < n_rows && waves * ((n_rows + t - 1) / t) >= kFillWaves) { group = t; break; }
+	if (forced_group) group = forced_group;
+}
+
 typedef std::chrono::steady_clock wall;
 static inline double ms_since(wall::time_point t) { return std::chrono::duration<double, std::milli>(wall::now() - t).count(); }
+
+/* one hipMemcpy, its wall time added to *ms */
+static inline int timed_copy(void *dst, const void *src, size_t bytes, hipMemcpyKind kind, double *ms)
+{
+	const auto t = wall::now();
+	HIPCHK(hipMemcpy(dst, src, bytes, kind));
+	*ms += ms_since(t);
+	return 0;
+}
 
 /* the interval between two events that have completed, added to *ms */
 static inline int add_interval(hipEvent_t e0, hipEvent_t e1, double *ms)
@@ -106,6 +141,18 @@ static inline int add_interval(hipEvent_t e0, hipEvent_t e1, double *ms)
 	HIPCHK(hipEventElapsedTime(&f, e0, e1));
 	*ms += f;
 	return 0;
+}
+
+/* The timed launch: e0, what `launches` starts on the null stream, e1, the wait for e1, and the interval added to *ms.  `launches`
+ * returns 0 or the failure of its own check of hipGetLastError. */
+template <typename Launches> static inline int timed(hipEvent_t e0, hipEvent_t e1, double *ms, Launches &&launches)
+{
+	HIPCHK(hipEventRecord(e0, 0));
+	const int rc = launches();
+	if (rc) return rc;
+	HIPCHK(hipEventRecord(e1, 0));
+	HIPCHK(hipEventSynchronize(e1));
+	return add_interval(e0, e1, ms);
 }
 
 /* Samples first ... first + count - 1 of the store: one 2-D copy from the host pitch to d_raw [count][site][2], timed into

@@ -16,30 +16,28 @@
  * Two ways of holding the store, as ntsm_eval_within.hip has them.  Resident: the store fits the chunk rule at 16 bytes per
  * sample and site (at and cg, and the dense copy the transpose reads); it is uploaded, transposed and tallied once at open and
  * a band's rows are an offset into the columns' arrays.  Streamed: each call uploads and transposes its band's rows (pitch =
- * n_rows) and walks all n_db columns in chunks.  The chunk rule and the 2-D copy are ntsm_eval_chunk.h's; the transpose is
- * this file's, since that header's also writes the 8-byte term plane of the scoring, which nothing reads here.  The
- * per-target tallies come from one workgroup per row over the dense copy.  One stream, no overlap.
+ * n_rows) and walks all n_db columns in chunks.  The holding, the band's rows and the walk are ntsm_eval_band.h's; the chunk
+ * rule, the 2-D copy and the launch rule are ntsm_eval_chunk.h's; the transpose is this file's, since that header's also
+ * writes the 8-byte term plane of the scoring, which nothing reads here.  The per-target tallies come from one workgroup per
+ * row over the dense copy.  One stream, no overlap.
  */
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <memory>
-#include <vector>
 
 #include "../../include/ntsm_eval_hip.h"
 #define NTSM_HIP_TAG "ntsm_eval_contam"
-#include "ntsm_eval_chunk.h"
+#include "ntsm_eval_band.h"
 #include "ntsm_hip_scope.h"
 
 namespace {
 
+using ntsm_eval_band::Staged;
+using ntsm_eval_band::Window;
 using ntsm_eval_chunk::kThreads;
 using ntsm_eval_chunk::kTile;
-using ntsm_eval_chunk::ms_since;
-using ntsm_eval_chunk::wall;
-constexpr uint64_t kFillWaves = 1024;        /* one wave on every SIMD of the 256 CUs, as ntsm_eval_cross.hip */
 
 uint32_t g_width = 0, g_target_group = 0;    /* ntsm_eval_contam_tune */
 
@@ -149,74 +147,50 @@ template <int TQ> __global__ __launch_bounds__(kThreads) void ntsm_eval_contam_k
 	}
 }
 
-/* Workgroup width and target group of one launch: ntsm_eval_cross.hip's rule, inherited and not measured again for this
- * kernel -- one-wave workgroups, and the widest group of targets whose launch still puts a wave on
- * every SIMD. */
-void launch_shape(uint32_t n_rows, uint32_t n_cols, uint32_t &width, uint32_t &tq)
-{
-	width = g_width ? g_width : 64;
-	const uint64_t waves = (n_cols + 63) / 64;
-	tq = 1;
-	for (uint32_t t = 4; t > 1; t /= 2)
-		if (t / 2 < n_rows && waves * ((n_rows + t - 1) / t) >= kFillWaves) { tq = t; break; }
-	if (g_target_group) tq = g_target_group;
-}
-
-/* a window of transposed samples on the device */
-struct Window { const uint32_t *at, *cg; uint32_t pitch, count; };
-
-/* the band's rows against the window's columns, into columns col_first ... of d_out [rows.count][n_db]; timed into *ms (added) */
-int launch_contam(const Window &rows, const Window &cols, uint32_t col_first, uint32_t n_db, uint32_t n_sites, uint32_t min_cov, uint32_t min_depth,
-		ntsm_eval_contam_record *d_out, hipEvent_t e0, hipEvent_t e1, double *ms)
+/* The band's rows against the window's columns, into columns cols.first ... of d_out [rows.count][n_db]; timed into *ms (added).
+ * Width and target group: ntsm_eval_chunk.h's launch rule, inherited and not measured again for this kernel. */
+int launch_contam(const Window &rows, const Window &cols, uint32_t n_db, uint32_t n_sites, uint32_t min_cov, uint32_t min_depth, ntsm_eval_contam_record *d_out,
+		hipEvent_t e0, hipEvent_t e1, double *ms)
 {
 	uint32_t width, tq;
-	launch_shape(rows.count, cols.count, width, tq);
+	ntsm_eval_chunk::launch_shape(rows.count, cols.count, g_width, g_target_group, width, tq);
 	const dim3 grid((cols.count + width - 1) / width, (rows.count + tq - 1) / tq);
 	auto kernel = tq == 4 ? ntsm_eval_contam_kernel<4> : tq == 2 ? ntsm_eval_contam_kernel<2> : ntsm_eval_contam_kernel<1>;
-	HIPCHK(hipEventRecord(e0, 0));
-	hipLaunchKernelGGL(kernel, grid, dim3(width), 0, 0, rows.at, rows.cg, rows.pitch, rows.count, cols.at, cols.cg, cols.pitch, cols.count, n_sites, min_cov,
-			min_depth, d_out + col_first, (uint64_t) n_db);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(e1, 0));
-	HIPCHK(hipEventSynchronize(e1));
-	return ntsm_eval_chunk::add_interval(e0, e1, ms);
-}
-
-/* Samples first ... first + count - 1 of the store: ntsm_eval_chunk::upload to d_raw, the transpose to d_at / d_cg [site][count]
- * and, with d_tally, the tallies [count][3]; the kernels timed into tm.prepare_kernel_ms (added) */
-int stage(const char *db, uint64_t stride, uint32_t first, uint32_t count, uint32_t n_sites, uint32_t min_depth, uint32_t *d_raw, uint32_t *d_at, uint32_t *d_cg,
-		unsigned long long *d_tally, hipEvent_t e0, hipEvent_t e1, ntsm_eval_cross_times &tm)
-{
-	const int rc = ntsm_eval_chunk::upload(db, stride, first, count, n_sites, d_raw, tm);
-	if (rc) return rc;
-	HIPCHK(hipEventRecord(e0, 0));
-	hipLaunchKernelGGL(ntsm_eval_contam_transpose_kernel, dim3((n_sites + kTile - 1) / kTile, (count + kTile - 1) / kTile), dim3(kThreads), 0, 0,
-			(const uint2 *) d_raw, count, n_sites, d_at, d_cg);
-	HIPCHK(hipGetLastError());
-	if (d_tally) {
-		hipLaunchKernelGGL(ntsm_eval_contam_tally_kernel, dim3(count), dim3(kThreads), 0, 0, (const uint2 *) d_raw, n_sites, min_depth, d_tally);
+	return ntsm_eval_chunk::timed(e0, e1, ms, [&] {
+		hipLaunchKernelGGL(kernel, grid, dim3(width), 0, 0, rows.at, rows.cg, rows.pitch, rows.count, cols.at, cols.cg, cols.pitch, cols.count, n_sites, min_cov,
+				min_depth, d_out + cols.first, (uint64_t) n_db);
 		HIPCHK(hipGetLastError());
-	}
-	HIPCHK(hipEventRecord(e1, 0));
-	HIPCHK(hipEventSynchronize(e1));
-	return ntsm_eval_chunk::add_interval(e0, e1, &tm.prepare_kernel_ms);
+		return 0;
+	});
 }
 
 }  // namespace
 
 struct ntsm_eval_contam_session {
-	int device = 0;
 	const char *db = nullptr;
 	uint64_t stride = 0;
 	uint32_t n_db = 0, n_sites = 0, min_cov = 0, min_depth = 0;
-	uint32_t chunk = 0;                      /* columns per pass of a streamed store */
-	bool resident = false;
-	ntsm_hip::Buffers b;
-	ntsm_hip::Events<2> ev;
-	/* resident: the whole store [site][n_db]; streamed: one chunk of columns [site][chunk] with its staging */
-	uint32_t *d_at = nullptr, *d_cg = nullptr, *d_raw = nullptr;
-	std::vector<uint64_t> tally;             /* resident: [n_db][3], taken at open */
-	ntsm_eval_cross_times open_times {};     /* resident: the upload and preparation of open, reported by the first _rows call */
+	ntsm_eval_band::Holding<uint64_t> hold;  /* the store's samples as columns; their tallies are read as targets, by row */
+
+	/* ntsm_eval_chunk::upload, then this file's transpose (no term plane) and, with `tallies`, its tallies */
+	auto stager()
+	{
+		return [this](uint32_t first, uint32_t count, const Staged<uint64_t> &to, bool tallies, ntsm_eval_cross_times &tm) {
+			const int rc = ntsm_eval_chunk::upload(db, stride, first, count, n_sites, to.raw, tm);
+			if (rc) return rc;
+			return ntsm_eval_chunk::timed(hold.ev[0], hold.ev[1], &tm.prepare_kernel_ms, [&] {
+				hipLaunchKernelGGL(ntsm_eval_contam_transpose_kernel, dim3((n_sites + kTile - 1) / kTile, (count + kTile - 1) / kTile), dim3(kThreads), 0, 0,
+						(const uint2 *) to.raw, count, n_sites, to.at, to.cg);
+				HIPCHK(hipGetLastError());
+				if (tallies) {
+					hipLaunchKernelGGL(ntsm_eval_contam_tally_kernel, dim3(count), dim3(kThreads), 0, 0, (const uint2 *) to.raw, n_sites, min_depth,
+							(unsigned long long *) to.tally);
+					HIPCHK(hipGetLastError());
+				}
+				return 0;
+			});
+		};
+	}
 };
 
 extern "C" int ntsm_eval_contam_tune(uint32_t width, uint32_t target_group)
@@ -232,45 +206,23 @@ extern "C" int ntsm_eval_contam_open(int device, const void *db_counts, uint64_t
 {
 	if (!h) return -1;
 	*h = nullptr;
-	if ((!db_counts && n_db && n_sites) || db_stride_bytes < 8ull * n_sites || db_stride_bytes % 4) return -1;
+	if (!ntsm_eval_chunk::valid_store(db_counts, db_stride_bytes, n_db, n_sites)) return -1;
 	std::unique_ptr<ntsm_eval_contam_session> s(new ntsm_eval_contam_session);
-	s->device = device;
 	s->db = (const char *) db_counts;
 	s->stride = db_stride_bytes;
 	s->n_db = n_db; s->n_sites = n_sites; s->min_cov = min_cov; s->min_depth = min_depth;
 	if (n_db == 0 || n_sites == 0) { *h = s.release(); return 0; }                /* nothing to sum: no device work, here or in _rows */
 
-	const uint64_t row_bytes = 8ull * n_sites;
-	HIPCHK(hipSetDevice(device));
-	size_t free_b = 0, total_b = 0;
-	if (db_chunk == 0) HIPCHK(hipMemGetInfo(&free_b, &total_b));
-	s->chunk = ntsm_eval_chunk::samples_per_pass(db_chunk, n_db, free_b, 2 * row_bytes + 3 * sizeof(uint64_t), 0);
-	s->resident = s->chunk == n_db;
-	const uint64_t cells = (uint64_t) s->chunk * n_sites;
-	HIPCHK(s->ev.create());
-	HIPCHK(s->b.alloc(&s->d_at, cells));
-	HIPCHK(s->b.alloc(&s->d_cg, cells));
-	HIPCHK(s->b.alloc(&s->d_raw, cells * 2));
-	if (s->resident) {
-		ntsm_hip::Buffers b;
-		unsigned long long *d_tally;
-		HIPCHK(b.alloc(&d_tally, (uint64_t) n_db * 3));
-		const int rc = stage(s->db, s->stride, 0, n_db, n_sites, min_depth, s->d_raw, s->d_at, s->d_cg, d_tally, s->ev[0], s->ev[1], s->open_times);
-		if (rc) return rc;
-		s->tally.resize((size_t) n_db * 3);
-		const auto t = wall::now();
-		HIPCHK(hipMemcpy(s->tally.data(), d_tally, s->tally.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-		s->open_times.download_ms += ms_since(t);
-		HIPCHK(s->b.release(&s->d_raw));                                         /* the staging half goes back before the records need room */
-	}
+	/* 16 bytes per sample and site: at and cg, and the dense copy the transpose reads; and the tallies.  A streamed walk takes
+	 * none per chunk: the tallies are the targets', staged with a band's rows. */
+	int rc = s->hold.open(device, n_db, n_sites, n_sites, db_chunk, 2 * 8ull * n_sites + 3 * sizeof(uint64_t), false, false);
+	if (rc || (rc = s->hold.fill(s->stager())) != 0) return rc;
 	*h = s.release();
 	return 0;
 }
 
 extern "C" void ntsm_eval_contam_close(ntsm_eval_contam_session *h)
 {
-	if (!h) return;
-	if (h->d_at) (void) hipSetDevice(h->device);                                 /* a session without device work touches no device here either */
 	delete h;
 }
 
@@ -281,53 +233,21 @@ extern "C" int ntsm_eval_contam_rows(ntsm_eval_contam_session *h, uint32_t row_f
 	if (!h || !out || n_rows == 0 || (uint64_t) row_first + n_rows > h->n_db) return -1;
 	const uint32_t n_db = h->n_db, n_sites = h->n_sites;
 	const uint64_t records = (uint64_t) n_rows * n_db;
-	if (n_sites == 0) {                                                          /* n_db == 0 has no range to take */
+	if (!h->hold.device_work) {                                                  /* no site; n_db == 0 has no range to take */
 		memset(out, 0, records * sizeof(ntsm_eval_contam_record));
 		if (tally) memset(tally, 0, (size_t) n_rows * 3 * sizeof(uint64_t));
 		return 0;
 	}
-	HIPCHK(hipSetDevice(h->device));
-	ntsm_hip::Buffers b;                                                          /* this call's: the records and, streamed, the band's rows */
-	ntsm_eval_contam_record *d_out;
-	HIPCHK(b.alloc(&d_out, records));
-	ntsm_eval_cross_times tm = h->open_times;
-	h->open_times = ntsm_eval_cross_times {};
-	if (h->resident) {
-		const Window rows { h->d_at + row_first, h->d_cg + row_first, n_db, n_rows };
-		const Window cols { h->d_at, h->d_cg, n_db, n_db };
-		const int rc = launch_contam(rows, cols, 0, n_db, n_sites, h->min_cov, h->min_depth, d_out, h->ev[0], h->ev[1], &tm.cross_kernel_ms);
-		if (rc) return rc;
-		if (tally) memcpy(tally, h->tally.data() + (size_t) row_first * 3, (size_t) n_rows * 3 * sizeof(uint64_t));
-	} else {
-		uint32_t *d_rraw, *d_rat, *d_rcg;
-		unsigned long long *d_tally;
-		const uint64_t rcells = (uint64_t) n_rows * n_sites;
-		HIPCHK(b.alloc(&d_rat, rcells));
-		HIPCHK(b.alloc(&d_rcg, rcells));
-		HIPCHK(b.alloc(&d_tally, (uint64_t) n_rows * 3));
-		HIPCHK(b.alloc(&d_rraw, rcells * 2));
-		int rc = stage(h->db, h->stride, row_first, n_rows, n_sites, h->min_depth, d_rraw, d_rat, d_rcg, tally ? d_tally : nullptr, h->ev[0], h->ev[1], tm);
-		if (rc) return rc;
-		if (tally) {
-			const auto t = wall::now();
-			HIPCHK(hipMemcpy(tally, d_tally, (size_t) n_rows * 3 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-			tm.download_ms += ms_since(t);
-		}
-		HIPCHK(b.release(&d_rraw));
-		const Window rows { d_rat, d_rcg, n_rows, n_rows };
-		for (uint32_t c0 = 0; c0 < n_db; c0 += h->chunk) {
-			const uint32_t cn = std::min(h->chunk, n_db - c0);
-			rc = stage(h->db, h->stride, c0, cn, n_sites, h->min_depth, h->d_raw, h->d_at, h->d_cg, nullptr, h->ev[0], h->ev[1], tm);
-			if (rc) return rc;
-			const Window cols { h->d_at, h->d_cg, cn, cn };
-			rc = launch_contam(rows, cols, c0, n_db, n_sites, h->min_cov, h->min_depth, d_out, h->ev[0], h->ev[1], &tm.cross_kernel_ms);
-			if (rc) return rc;
-			tm.chunks++;
-		}
-	}
-	const auto t = wall::now();
-	HIPCHK(hipMemcpy(out, d_out, records * sizeof(ntsm_eval_contam_record), hipMemcpyDeviceToHost));
-	tm.download_ms += ms_since(t);
+	HIPCHK(hipSetDevice(h->hold.device));
+	ntsm_hip::Buffers b;                                                          /* this call's: streamed, the band's rows */
+	ntsm_eval_cross_times tm = h->hold.take_open_times();
+	Window rows;
+	int rc = h->hold.band_rows(b, row_first, n_rows, tally, h->stager(), tm, rows);
+	if (rc) return rc;
+	rc = h->hold.walk(0, records, out, nullptr, h->stager(), [&](const Window &cols, ntsm_eval_contam_record *d_out) {
+		return launch_contam(rows, cols, n_db, n_sites, h->min_cov, h->min_depth, d_out, h->hold.ev[0], h->hold.ev[1], &tm.cross_kernel_ms);
+	}, tm);
+	if (rc) return rc;
 	if (times) *times = tm;
 	return 0;
 }

@@ -32,7 +32,6 @@
 namespace {
 
 using ntsm_eval_chunk::kThreads;
-constexpr uint64_t kFillWaves = 1024;        /* one wave on every SIMD of the 256 CUs */
 
 uint32_t g_width = 0, g_query_group = 0;     /* ntsm_eval_cross_tune */
 
@@ -60,21 +59,6 @@ template <int TQ> __global__ __launch_bounds__(kThreads) void ntsm_eval_cross_ke
 		if (q0 + k < n_q) out[(uint64_t) (q0 + k) * out_pitch + d] = acc[k].record();
 }
 
-/* Workgroup width and query group of one launch.  A lane's walk over the sites is sequential, so the only parallelism is
- * across pairs: the widest query group whose launch still puts a wave on every SIMD wins (each database value loaded is used
- * TQ times); a rectangle too small for that takes single queries, which at least spreads what there is.  One-wave workgroups
- * at every size: measured 4 to 5 % faster than 256 threads on 1 and 8 queries against 4,096 samples,
- * so unlike ntsm_eval.hip there is no width switch; 256 is reachable through ntsm_eval_cross_tune only. */
-void launch_shape(uint32_t n_q, uint32_t n_d, uint32_t &width, uint32_t &tq)
-{
-	width = g_width ? g_width : 64;
-	const uint64_t waves = (n_d + 63) / 64;
-	tq = 1;
-	for (uint32_t t = 4; t > 1; t /= 2)
-		if (t / 2 < n_q && waves * ((n_q + t - 1) / t) >= kFillWaves) { tq = t; break; }
-	if (g_query_group) tq = g_query_group;
-}
-
 }  // namespace
 
 extern "C" int ntsm_eval_cross_tune(uint32_t width, uint32_t query_group)
@@ -90,8 +74,7 @@ extern "C" int ntsm_eval_cross(int device, const uint32_t *q_counts, uint32_t n_
 		ntsm_eval_record *out, uint32_t *db_geno, ntsm_eval_cross_times *times)
 {
 	if (times) *times = ntsm_eval_cross_times {};
-	if ((!q_counts && n_q && n_sites) || (!db_counts && n_db && n_sites) || (!out && n_q && n_db)) return -1;
-	if (db_stride_bytes < 8ull * n_sites || db_stride_bytes % 4) return -1;
+	if ((!q_counts && n_q && n_sites) || !ntsm_eval_chunk::valid_store(db_counts, db_stride_bytes, n_db, n_sites) || (!out && n_q && n_db)) return -1;
 	if (n_q && n_db) memset(out, 0, (size_t) n_q * n_db * sizeof(ntsm_eval_record));
 	if (db_geno && n_db) memset(db_geno, 0, (size_t) n_db * 3 * sizeof(uint32_t));
 	if (n_q == 0 || n_db == 0 || n_sites == 0) return 0;
@@ -124,30 +107,30 @@ extern "C" int ntsm_eval_cross(int device, const uint32_t *q_counts, uint32_t n_
 	using ntsm_eval_chunk::ms_since;
 	using ntsm_eval_chunk::wall;
 	ntsm_eval_cross_times tm {};
-	auto t = wall::now();
-	HIPCHK(hipMemcpy(d_q, q_counts, qcells * 2 * sizeof(uint32_t), hipMemcpyHostToDevice));
-	tm.upload_ms += ms_since(t);
-	HIPCHK(hipEventRecord(ev[0], 0));
-	ntsm_eval_chunk::launch_prepare(d_q, n_q, n_sites, min_cov, d_qat, d_qcg, d_qterm);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(ev[1], 0));
-	HIPCHK(hipEventSynchronize(ev[1]));
-	int rc = ntsm_eval_chunk::add_interval(ev[0], ev[1], &tm.prepare_kernel_ms);
+	int rc = ntsm_eval_chunk::timed_copy(d_q, q_counts, qcells * 2 * sizeof(uint32_t), hipMemcpyHostToDevice, &tm.upload_ms);
+	if (rc) return rc;
+	rc = ntsm_eval_chunk::timed(ev[0], ev[1], &tm.prepare_kernel_ms, [&] {
+		ntsm_eval_chunk::launch_prepare(d_q, n_q, n_sites, min_cov, d_qat, d_qcg, d_qterm);
+		HIPCHK(hipGetLastError());
+		return 0;
+	});
 	if (rc) return rc;
 
 	for (uint32_t c0 = 0; c0 < n_db; c0 += chunk) {
 		const uint32_t cn = std::min(chunk, n_db - c0);
 		rc = ntsm_eval_chunk::stage(db_counts, db_stride_bytes, c0, cn, n_sites, min_cov, d_raw, d_at, d_cg, d_term, db_geno ? d_geno : nullptr, ev[0], ev[1], tm);
 		if (rc) return rc;
+		/* ntsm_eval_chunk.h's launch rule, measured on this kernel: unlike ntsm_eval.hip no width switch;
+		 * 256 threads are reachable through ntsm_eval_cross_tune only */
 		uint32_t width, tq;
-		launch_shape(n_q, cn, width, tq);
+		ntsm_eval_chunk::launch_shape(n_q, cn, g_width, g_query_group, width, tq);
 		const dim3 grid((cn + width - 1) / width, (n_q + tq - 1) / tq);
 		auto kernel = tq == 4 ? ntsm_eval_cross_kernel<4> : tq == 2 ? ntsm_eval_cross_kernel<2> : ntsm_eval_cross_kernel<1>;
 		hipLaunchKernelGGL(kernel, grid, dim3(width), 0, 0, d_qat, d_qcg, d_qterm, n_q, d_at, d_cg, d_term, cn, n_sites, min_cov, d_out, chunk);
 		HIPCHK(hipGetLastError());
 		HIPCHK(hipEventRecord(ev[2], 0));
 		HIPCHK(hipEventSynchronize(ev[2]));
-		t = wall::now();
+		const auto t = wall::now();
 		HIPCHK(hipMemcpy2D(out + c0, (size_t) n_db * sizeof(ntsm_eval_record), d_out, (size_t) chunk * sizeof(ntsm_eval_record),
 				(size_t) cn * sizeof(ntsm_eval_record), n_q, hipMemcpyDeviceToHost));
 		if (db_geno) HIPCHK(hipMemcpy(db_geno + (uint64_t) c0 * 3, d_geno, (size_t) cn * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost));

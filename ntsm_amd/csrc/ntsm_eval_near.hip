@@ -188,8 +188,7 @@ extern "C" int ntsm_eval_project_store(int device, const void *db_counts, uint64
 		ntsm_eval_cross_times *times)
 {
 	if (times) *times = ntsm_eval_cross_times {};
-	if ((!db_counts && n_db && n_sites) || (n_sites && (!norm || (dim && !rot))) || (!cloud && n_db && dim)) return -1;
-	if (db_stride_bytes < 8ull * n_sites || db_stride_bytes % 4) return -1;
+	if (!ntsm_eval_chunk::valid_store(db_counts, db_stride_bytes, n_db, n_sites) || (n_sites && (!norm || (dim && !rot))) || (!cloud && n_db && dim)) return -1;
 	if (n_db && dim) memset(cloud, 0, (size_t) n_db * dim * sizeof(double));     /* no site: inner_product of nothing */
 	if (db_geno && n_db) memset(db_geno, 0, (size_t) n_db * 3 * sizeof(uint32_t));
 	if (n_db == 0 || n_sites == 0) return 0;
@@ -311,8 +310,7 @@ extern "C" int ntsm_eval_cross_score_pairs(int device, const uint32_t *q_counts,
 		ntsm_eval_record *out, ntsm_eval_cross_times *times)
 {
 	if (times) *times = ntsm_eval_cross_times {};
-	if ((!q_counts && n_q && n_sites) || (!db_counts && n_db && n_sites) || (n_pairs && (!pi || !pk || !out))) return -1;
-	if (db_stride_bytes < 8ull * n_sites || db_stride_bytes % 4) return -1;
+	if ((!q_counts && n_q && n_sites) || !ntsm_eval_chunk::valid_store(db_counts, db_stride_bytes, n_db, n_sites) || (n_pairs && (!pi || !pk || !out))) return -1;
 	const uint64_t n = (uint64_t) n_q + n_db;
 	if (n > UINT32_MAX) return -1;
 	for (uint64_t p = 0; p < n_pairs; ++p)
@@ -391,8 +389,7 @@ extern "C" int ntsm_eval_store_score_pairs(int device, const void *db_counts, ui
 		ntsm_eval_record *out, ntsm_eval_cross_times *times)
 {
 	if (times) *times = ntsm_eval_cross_times {};
-	if ((!db_counts && n_db && n_sites) || (n_pairs && (!pi || !pk || !out)) || db_chunk == 1) return -1;
-	if (db_stride_bytes < 8ull * n_sites || db_stride_bytes % 4) return -1;
+	if (!ntsm_eval_chunk::valid_store(db_counts, db_stride_bytes, n_db, n_sites) || (n_pairs && (!pi || !pk || !out)) || db_chunk == 1) return -1;
 	for (uint64_t p = 0; p < n_pairs; ++p)
 		if (pi[p] >= n_db || pk[p] >= n_db || pi[p] == pk[p]) return -1;
 	if (n_pairs == 0) return 0;

@@ -98,8 +98,7 @@ extern "C" int ntsm_eval_store_profile(int device, const void *db_counts, uint64
 		uint32_t min_cov, uint32_t db_chunk, uint32_t *db_geno, uint32_t *site_tally, uint64_t *site_cov, ntsm_eval_cross_times *times)
 {
 	if (times) *times = ntsm_eval_cross_times {};
-	if ((!db_counts && n_db && n_sites) || (!db_geno && !site_tally && !site_cov)) return -1;
-	if (db_stride_bytes < 8ull * n_sites || db_stride_bytes % 4) return -1;
+	if (!ntsm_eval_chunk::valid_store(db_counts, db_stride_bytes, n_db, n_sites) || (!db_geno && !site_tally && !site_cov)) return -1;
 	if (db_geno && n_db) memset(db_geno, 0, (size_t) n_db * 3 * sizeof(uint32_t));
 	if (site_tally && n_sites) memset(site_tally, 0, (size_t) n_sites * 4 * sizeof(uint32_t));
 	if (site_cov && n_sites) memset(site_cov, 0, (size_t) n_sites * sizeof(uint64_t));

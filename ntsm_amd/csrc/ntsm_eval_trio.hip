@@ -42,9 +42,7 @@
 namespace {
 
 using ntsm_eval_chunk::kThreads;
-using ntsm_eval_chunk::ms_since;
-using ntsm_eval_chunk::wall;
-constexpr uint64_t kFillWaves = 1024;        /* one wave on every SIMD of the 256 CUs, as ntsm_eval_cross.hip */
+using ntsm_eval_chunk::timed;
 constexpr int kSlab = 8;                     /* site words per LDS slab of the trio kernel */
 constexpr uint32_t kShortList = 16;          /* lists up to this long take the one-wave tile */
 constexpr uint32_t kMaxGridY = 65535;
@@ -229,17 +227,6 @@ template <int TX, int RB> __global__ __launch_bounds__(TX * TX) void ntsm_eval_t
 		}
 }
 
-/* Workgroup width and row group of one duo launch: ntsm_eval_cross.hip's rule, inherited and not measured again for this kernel
- *  -- one-wave workgroups, and the widest group of rows whose launch still puts a wave on every SIMD. */
-void duo_shape(uint32_t n_rows, uint32_t n_cols, uint32_t &width, uint32_t &tq)
-{
-	width = g_width ? g_width : 64;
-	const uint64_t waves = (n_cols + 63) / 64;
-	tq = 1;
-	for (uint32_t t = 4; t > 1; t /= 2)
-		if (t / 2 < n_rows && waves * ((n_rows + t - 1) / t) >= kFillWaves) { tq = t; break; }
-}
-
 /* the tile edge an entry's list takes: the library's rule, or the forced width (64 threads: 16, 256 threads: 64) */
 uint32_t tile_of(uint32_t k) { return g_width ? (g_width == 64 ? 16u : 64u) : k <= kShortList ? 16u : 64u; }
 
@@ -266,7 +253,7 @@ extern "C" int ntsm_eval_trio_open(int device, const void *db_counts, uint64_t d
 	if (times) *times = ntsm_eval_cross_times {};
 	if (!h) return -1;
 	*h = nullptr;
-	if ((!db_counts && n_db && n_sites) || db_stride_bytes < 8ull * n_sites || db_stride_bytes % 4) return -1;
+	if (!ntsm_eval_chunk::valid_store(db_counts, db_stride_bytes, n_db, n_sites)) return -1;
 	std::unique_ptr<ntsm_eval_trio_session> s(new ntsm_eval_trio_session);
 	s->device = device;
 	s->n_db = n_db; s->n_sites = n_sites;
@@ -290,15 +277,15 @@ extern "C" int ntsm_eval_trio_open(int device, const void *db_counts, uint64_t d
 	HIPCHK(b.alloc(&d_raw, (uint64_t) chunk * n_sites * 2));
 	for (uint32_t first = 0; first < n_db; first += chunk) {
 		const uint32_t count = std::min(chunk, n_db - first);
-		const int rc = ntsm_eval_chunk::upload(db_counts, db_stride_bytes, first, count, n_sites, d_raw, tm);
+		int rc = ntsm_eval_chunk::upload(db_counts, db_stride_bytes, first, count, n_sites, d_raw, tm);
 		if (rc) return rc;
-		HIPCHK(hipEventRecord(s->ev[0], 0));
-		hipLaunchKernelGGL(ntsm_eval_trio_planes_kernel, dim3((count + 63) / 64 * n_words), dim3(kThreads), 0, 0, (const uint2 *) d_raw, count, n_sites, min_cov,
-				min_depth, first, n_db, n_words, s->d_planes);
-		HIPCHK(hipGetLastError());
-		HIPCHK(hipEventRecord(s->ev[1], 0));
-		HIPCHK(hipEventSynchronize(s->ev[1]));                                     /* the next chunk overwrites d_raw */
-		if (ntsm_eval_chunk::add_interval(s->ev[0], s->ev[1], &tm.prepare_kernel_ms)) return NTSM_HIP_FAIL;
+		rc = timed(s->ev[0], s->ev[1], &tm.prepare_kernel_ms, [&] {                  /* it waits: the next chunk overwrites d_raw */
+			hipLaunchKernelGGL(ntsm_eval_trio_planes_kernel, dim3((count + 63) / 64 * n_words), dim3(kThreads), 0, 0, (const uint2 *) d_raw, count, n_sites, min_cov,
+					min_depth, first, n_db, n_words, s->d_planes);
+			HIPCHK(hipGetLastError());
+			return 0;
+		});
+		if (rc) return rc;
 		tm.chunks++;
 	}
 	if (geno) {
@@ -306,15 +293,12 @@ extern "C" int ntsm_eval_trio_open(int device, const void *db_counts, uint64_t d
 		HIPCHK(b.alloc(&d_geno, (uint64_t) n_db * 4));
 		HIPCHK(hipMemset(d_geno, 0, (size_t) n_db * 4 * sizeof(uint32_t)));
 		const uint32_t per = std::max(64u, (n_words + kMaxGridY - 1) / kMaxGridY);
-		HIPCHK(hipEventRecord(s->ev[0], 0));
-		hipLaunchKernelGGL(ntsm_eval_trio_geno_kernel, dim3((n_db + 63) / 64, (n_words + per - 1) / per), dim3(kThreads), 0, 0, s->d_planes, n_db, n_words, per, d_geno);
-		HIPCHK(hipGetLastError());
-		HIPCHK(hipEventRecord(s->ev[1], 0));
-		HIPCHK(hipEventSynchronize(s->ev[1]));
-		if (ntsm_eval_chunk::add_interval(s->ev[0], s->ev[1], &tm.prepare_kernel_ms)) return NTSM_HIP_FAIL;
-		const auto t = wall::now();
-		HIPCHK(hipMemcpy(geno, d_geno, (size_t) n_db * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-		tm.download_ms += ms_since(t);
+		int rc = timed(s->ev[0], s->ev[1], &tm.prepare_kernel_ms, [&] {
+			hipLaunchKernelGGL(ntsm_eval_trio_geno_kernel, dim3((n_db + 63) / 64, (n_words + per - 1) / per), dim3(kThreads), 0, 0, s->d_planes, n_db, n_words, per, d_geno);
+			HIPCHK(hipGetLastError());
+			return 0;
+		});
+		if (rc || (rc = ntsm_eval_chunk::timed_copy(geno, d_geno, (size_t) n_db * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, &tm.download_ms)) != 0) return rc;
 		for (uint32_t d = 0; d < n_db; ++d) geno[4ull * d + 3] = n_sites - (geno[4ull * d] + geno[4ull * d + 1] + geno[4ull * d + 2]);
 	}
 	if (times) *times = tm;
@@ -343,20 +327,21 @@ extern "C" int ntsm_eval_trio_duos(ntsm_eval_trio_session *h, uint32_t row_first
 	ntsm_hip::Buffers b;
 	ntsm_eval_trio_duo *d_out;
 	HIPCHK(b.alloc(&d_out, records));
+	/* ntsm_eval_chunk.h's launch rule, inherited and not measured again for this kernel; no forced group */
 	uint32_t width, tq;
-	duo_shape(n_rows, n_db, width, tq);
+	ntsm_eval_chunk::launch_shape(n_rows, n_db, g_width, 0, width, tq);
 	auto kernel = tq == 4 ? ntsm_eval_trio_duo_kernel<4> : tq == 2 ? ntsm_eval_trio_duo_kernel<2> : ntsm_eval_trio_duo_kernel<1>;
 	double ms = 0;
-	HIPCHK(hipEventRecord(h->ev[0], 0));
-	for (uint32_t r = 0; r < n_rows; r += kMaxGridY * tq) {                        /* one launch, unless the band has more row groups than a grid's y takes */
-		const uint32_t rows = std::min(kMaxGridY * tq, n_rows - r);
-		hipLaunchKernelGGL(kernel, dim3((n_db + width - 1) / width, (rows + tq - 1) / tq), dim3(width), 0, 0, h->d_planes, n_db, h->n_words, row_first + r, rows,
-				d_out + (uint64_t) r * n_db);
-		HIPCHK(hipGetLastError());
-	}
-	HIPCHK(hipEventRecord(h->ev[1], 0));
-	HIPCHK(hipEventSynchronize(h->ev[1]));
-	if (ntsm_eval_chunk::add_interval(h->ev[0], h->ev[1], &ms)) return NTSM_HIP_FAIL;
+	const int rc = timed(h->ev[0], h->ev[1], &ms, [&] {
+		for (uint32_t r = 0; r < n_rows; r += kMaxGridY * tq) {                    /* one launch, unless the band has more row groups than a grid's y takes */
+			const uint32_t rows = std::min(kMaxGridY * tq, n_rows - r);
+			hipLaunchKernelGGL(kernel, dim3((n_db + width - 1) / width, (rows + tq - 1) / tq), dim3(width), 0, 0, h->d_planes, n_db, h->n_words, row_first + r, rows,
+					d_out + (uint64_t) r * n_db);
+			HIPCHK(hipGetLastError());
+		}
+		return 0;
+	});
+	if (rc) return rc;
 	HIPCHK(hipMemcpy(out, d_out, records * sizeof(ntsm_eval_trio_duo), hipMemcpyDeviceToHost));
 	if (kernel_ms) *kernel_ms = ms;
 	return 0;
@@ -412,20 +397,20 @@ extern "C" int ntsm_eval_trio_score(ntsm_eval_trio_session *h, const uint32_t *c
 		if (!items[t].empty()) HIPCHK(hipMemcpy(d_items[t], items[t].data(), items[t].size() * sizeof(Item), hipMemcpyHostToDevice));
 	}
 	double ms = 0;
-	HIPCHK(hipEventRecord(h->ev[0], 0));
 	const uint64_t kSlice = 1u << 30;                                              /* work items per launch: below a grid's x */
-	for (int t = 0; t < 2; ++t)
-		for (uint64_t i0 = 0; i0 < items[t].size(); i0 += kSlice) {
-			const uint32_t n = (uint32_t) std::min<uint64_t>(kSlice, items[t].size() - i0);
-			if (t == 0)
-				hipLaunchKernelGGL((ntsm_eval_trio_kernel<8, 2>), dim3(n), dim3(64), 0, 0, h->d_planes, h->n_db, h->n_words, d_entries, d_items[t] + i0, d_cand, d_out);
-			else
-				hipLaunchKernelGGL((ntsm_eval_trio_kernel<16, 4>), dim3(n), dim3(256), 0, 0, h->d_planes, h->n_db, h->n_words, d_entries, d_items[t] + i0, d_cand, d_out);
-			HIPCHK(hipGetLastError());
-		}
-	HIPCHK(hipEventRecord(h->ev[1], 0));
-	HIPCHK(hipEventSynchronize(h->ev[1]));
-	if (ntsm_eval_chunk::add_interval(h->ev[0], h->ev[1], &ms)) return NTSM_HIP_FAIL;
+	const int rc = timed(h->ev[0], h->ev[1], &ms, [&] {
+		for (int t = 0; t < 2; ++t)
+			for (uint64_t i0 = 0; i0 < items[t].size(); i0 += kSlice) {
+				const uint32_t n = (uint32_t) std::min<uint64_t>(kSlice, items[t].size() - i0);
+				if (t == 0)
+					hipLaunchKernelGGL((ntsm_eval_trio_kernel<8, 2>), dim3(n), dim3(64), 0, 0, h->d_planes, h->n_db, h->n_words, d_entries, d_items[t] + i0, d_cand, d_out);
+				else
+					hipLaunchKernelGGL((ntsm_eval_trio_kernel<16, 4>), dim3(n), dim3(256), 0, 0, h->d_planes, h->n_db, h->n_words, d_entries, d_items[t] + i0, d_cand, d_out);
+				HIPCHK(hipGetLastError());
+			}
+		return 0;
+	});
+	if (rc) return rc;
 	HIPCHK(hipMemcpy(out, d_out, records * sizeof(ntsm_eval_trio_record), hipMemcpyDeviceToHost));
 	if (kernel_ms) *kernel_ms = ms;
 	return 0;

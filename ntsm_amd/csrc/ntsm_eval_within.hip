@@ -15,28 +15,27 @@
  * into the same arrays.  Streamed: each call uploads and transposes its band's rows into a buffer of their own (pitch =
  * n_rows) and walks the columns row_first ... n_db - 1 in chunks of db_chunk, as ntsm_eval_cross walks a store; the columns
  * before row_first never leave the host.  The chunk rule and the staging of a window (copy, transpose, tallies) are
- * ntsm_eval_chunk.h's.  One stream, no overlap.
+ * ntsm_eval_chunk.h's; the holding, the band's rows and the walk over the columns are ntsm_eval_band.h's.  What is here: the
+ * kernel, its launch, and the 24 bytes per sample and site.  One stream, no overlap.
  */
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <memory>
-#include <vector>
 
 #include "../../include/ntsm_eval_hip.h"
 #include "host/eval_within.hpp"
 #define NTSM_HIP_TAG "ntsm_eval_within"
-#include "ntsm_eval_chunk.h"
+#include "ntsm_eval_band.h"
 #include "ntsm_eval_score.h"
 #include "ntsm_hip_scope.h"
 
 namespace {
 
+using ntsm_eval_band::Staged;
+using ntsm_eval_band::Window;
 using ntsm_eval_chunk::kThreads;
-using ntsm_eval_chunk::ms_since;
-using ntsm_eval_chunk::wall;
 namespace band = ntsm::eval_within;
 constexpr int kTI = 4;                       /* rows i per workgroup, as in ntsm_eval.hip */
 
@@ -74,9 +73,6 @@ __global__ __launch_bounds__(kThreads) void ntsm_eval_within_kernel(const uint32
 	}
 }
 
-/* a window of transposed samples on the device */
-struct Window { const uint32_t *at, *cg; const double *term; uint32_t pitch, first, count; };
-
 /* the pairs of the rows' samples with the columns' samples, timed into *ms (added) */
 int launch_within(const Window &rows, const Window &cols, uint32_t n_db, uint32_t n_sites, uint32_t min_cov, ntsm_eval_record *d_out, uint64_t out_base,
 		hipEvent_t e0, hipEvent_t e1, double *ms)
@@ -86,41 +82,29 @@ int launch_within(const Window &rows, const Window &cols, uint32_t n_db, uint32_
 	 * 4,096 x 96,287 sites, 64 threads take 2,412 ms against 2,954 ms for 256 (three runs each, spreads 47 and 46 ms; DESIGN.md
 	 * section 9.3), as ntsm_eval_cross found for the rectangle.  256 is reachable through ntsm_eval_within_tune only. */
 	const unsigned bt = g_width ? g_width : 64;
-	HIPCHK(hipEventRecord(e0, 0));
-	hipLaunchKernelGGL(ntsm_eval_within_kernel, dim3((cols.count + bt - 1) / bt, (rows.count + kTI - 1) / kTI), dim3(bt), 0, 0, rows.at, rows.cg, rows.term,
-			rows.pitch, rows.first, rows.count, cols.at, cols.cg, cols.term, cols.pitch, cols.first, cols.count, n_db, n_sites, min_cov, d_out, out_base);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(e1, 0));
-	HIPCHK(hipEventSynchronize(e1));
-	return ntsm_eval_chunk::add_interval(e0, e1, ms);
-}
-
-/* ntsm_eval_chunk::stage and the wait for it: the pair kernel's launch records the same two events next */
-int stage(const char *db, uint64_t stride, uint32_t first, uint32_t count, uint32_t n_sites, uint32_t min_cov, uint32_t *d_raw, uint32_t *d_at, uint32_t *d_cg,
-		double *d_term, uint32_t *d_geno, hipEvent_t e0, hipEvent_t e1, ntsm_eval_cross_times &tm)
-{
-	const int rc = ntsm_eval_chunk::stage(db, stride, first, count, n_sites, min_cov, d_raw, d_at, d_cg, d_term, d_geno, e0, e1, tm);
-	if (rc) return rc;
-	HIPCHK(hipEventSynchronize(e1));
-	return ntsm_eval_chunk::add_interval(e0, e1, &tm.prepare_kernel_ms);
+	return ntsm_eval_chunk::timed(e0, e1, ms, [&] {
+		hipLaunchKernelGGL(ntsm_eval_within_kernel, dim3((cols.count + bt - 1) / bt, (rows.count + kTI - 1) / kTI), dim3(bt), 0, 0, rows.at, rows.cg, rows.term,
+				rows.pitch, rows.first, rows.count, cols.at, cols.cg, cols.term, cols.pitch, cols.first, cols.count, n_db, n_sites, min_cov, d_out, out_base);
+		HIPCHK(hipGetLastError());
+		return 0;
+	});
 }
 
 }  // namespace
 
 struct ntsm_eval_within_session {
-	int device = 0;
 	const char *db = nullptr;
 	uint64_t stride = 0;
 	uint32_t n_db = 0, n_sites = 0, min_cov = 0;
-	uint32_t chunk = 0;                      /* columns per pass of a streamed store */
-	bool resident = false;
-	ntsm_hip::Buffers b;
-	ntsm_hip::Events<2> ev;
-	/* resident: the whole store [site][n_db]; streamed: one chunk of columns [site][chunk] with its staging and tallies */
-	uint32_t *d_at = nullptr, *d_cg = nullptr, *d_raw = nullptr, *d_geno = nullptr;
-	double *d_term = nullptr;
-	std::vector<uint32_t> geno;              /* resident: [n_db][3], taken at open */
-	ntsm_eval_cross_times open_times {};     /* resident: the upload and preparation of open, reported by the first _rows call */
+	ntsm_eval_band::Holding<uint32_t> hold;  /* the store's samples as columns, with their hets, homs, miss */
+
+	/* ntsm_eval_chunk.h's staging of a window, for the columns and for a streamed band's rows */
+	auto stager()
+	{
+		return [this](uint32_t first, uint32_t count, const Staged<uint32_t> &to, bool tallies, ntsm_eval_cross_times &tm) {
+			return ntsm_eval_band::stage_scored(db, stride, first, count, n_sites, min_cov, to, tallies, hold.ev[0], hold.ev[1], tm);
+		};
+	}
 };
 
 extern "C" int ntsm_eval_within_tune(uint32_t width)
@@ -135,44 +119,22 @@ extern "C" int ntsm_eval_within_open(int device, const void *db_counts, uint64_t
 {
 	if (!h) return -1;
 	*h = nullptr;
-	if ((!db_counts && n_db && n_sites) || db_stride_bytes < 8ull * n_sites || db_stride_bytes % 4) return -1;
+	if (!ntsm_eval_chunk::valid_store(db_counts, db_stride_bytes, n_db, n_sites)) return -1;
 	std::unique_ptr<ntsm_eval_within_session> s(new ntsm_eval_within_session);
-	s->device = device;
 	s->db = (const char *) db_counts;
 	s->stride = db_stride_bytes;
 	s->n_db = n_db; s->n_sites = n_sites; s->min_cov = min_cov;
 	if (n_db < 2 || n_sites == 0) { *h = s.release(); return 0; }                /* nothing to score: no device work, here or in _rows */
 
-	const uint64_t row_bytes = 8ull * n_sites;
-	HIPCHK(hipSetDevice(device));
-	size_t free_b = 0, total_b = 0;
-	if (db_chunk == 0) HIPCHK(hipMemGetInfo(&free_b, &total_b));
-	s->chunk = ntsm_eval_chunk::samples_per_pass(db_chunk, n_db, free_b, 3 * row_bytes + 12, 0);
-	s->resident = s->chunk == n_db;
-	const uint64_t cells = (uint64_t) s->chunk * n_sites;
-	HIPCHK(s->ev.create());
-	HIPCHK(s->b.alloc(&s->d_at, cells));
-	HIPCHK(s->b.alloc(&s->d_cg, cells));
-	HIPCHK(s->b.alloc(&s->d_term, cells));
-	HIPCHK(s->b.alloc(&s->d_geno, (uint64_t) s->chunk * 3));
-	HIPCHK(s->b.alloc(&s->d_raw, cells * 2));
-	if (s->resident) {
-		const int rc = stage(s->db, s->stride, 0, n_db, n_sites, min_cov, s->d_raw, s->d_at, s->d_cg, s->d_term, s->d_geno, s->ev[0], s->ev[1], s->open_times);
-		if (rc) return rc;
-		s->geno.resize((size_t) n_db * 3);
-		const auto t = wall::now();
-		HIPCHK(hipMemcpy(s->geno.data(), s->d_geno, s->geno.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-		s->open_times.download_ms += ms_since(t);
-		HIPCHK(s->b.release(&s->d_raw));                                         /* the staging third goes back before the records need room */
-	}
+	/* 24 bytes per sample and site (what ntsm_eval_pairs holds): the transposed 16 and the dense 8; and the tallies */
+	int rc = s->hold.open(device, n_db, n_sites, n_sites, db_chunk, 3 * 8ull * n_sites + 12, true, true);
+	if (rc || (rc = s->hold.fill(s->stager())) != 0) return rc;
 	*h = s.release();
 	return 0;
 }
 
 extern "C" void ntsm_eval_within_close(ntsm_eval_within_session *h)
 {
-	if (!h) return;
-	if (h->d_at) (void) hipSetDevice(h->device);                                 /* a session without device work touches no device here either */
 	delete h;
 }
 
@@ -184,54 +146,23 @@ extern "C" int ntsm_eval_within_rows(ntsm_eval_within_session *h, uint32_t row_f
 	const uint32_t n_db = h->n_db, n_sites = h->n_sites, min_cov = h->min_cov;
 	const uint64_t records = band::band_records(row_first, n_rows, n_db), base = band::band_base(row_first, n_db);
 	if (!out && records) return -1;
-	if (n_db < 2 || n_sites == 0) {
+	if (!h->hold.device_work) {
 		if (records) memset(out, 0, records * sizeof(ntsm_eval_record));
 		if (db_geno) memset(db_geno + (size_t) row_first * 3, 0, (size_t) (n_db - row_first) * 3 * sizeof(uint32_t));
 		return 0;
 	}
-	HIPCHK(hipSetDevice(h->device));
-	ntsm_hip::Buffers b;                                                          /* this call's: the records and, streamed, the band's rows */
-	ntsm_eval_record *d_out;
-	HIPCHK(b.alloc(&d_out, records));
-	ntsm_eval_cross_times tm = h->open_times;
-	h->open_times = ntsm_eval_cross_times {};
-	const uint32_t n_cols = n_db - row_first;
-	if (h->resident) {
-		const Window rows { h->d_at + row_first, h->d_cg + row_first, h->d_term + row_first, n_db, row_first, n_rows };
-		const Window cols { rows.at, rows.cg, rows.term, n_db, row_first, n_cols };
-		const int rc = launch_within(rows, cols, n_db, n_sites, min_cov, d_out, base, h->ev[0], h->ev[1], &tm.cross_kernel_ms);
-		if (rc) return rc;
-		if (db_geno) memcpy(db_geno + (size_t) row_first * 3, h->geno.data() + (size_t) row_first * 3, (size_t) n_cols * 3 * sizeof(uint32_t));
-	} else {
-		uint32_t *d_rraw, *d_rat, *d_rcg;
-		double *d_rterm;
-		const uint64_t rcells = (uint64_t) n_rows * n_sites;
-		HIPCHK(b.alloc(&d_rat, rcells));
-		HIPCHK(b.alloc(&d_rcg, rcells));
-		HIPCHK(b.alloc(&d_rterm, rcells));
-		HIPCHK(b.alloc(&d_rraw, rcells * 2));
-		int rc = stage(h->db, h->stride, row_first, n_rows, n_sites, min_cov, d_rraw, d_rat, d_rcg, d_rterm, nullptr, h->ev[0], h->ev[1], tm);
-		if (rc) return rc;
-		HIPCHK(b.release(&d_rraw));
-		const Window rows { d_rat, d_rcg, d_rterm, n_rows, row_first, n_rows };
-		for (uint32_t c0 = row_first; c0 < n_db; c0 += h->chunk) {
-			const uint32_t cn = std::min(h->chunk, n_db - c0);
-			rc = stage(h->db, h->stride, c0, cn, n_sites, min_cov, h->d_raw, h->d_at, h->d_cg, h->d_term, db_geno ? h->d_geno : nullptr, h->ev[0], h->ev[1], tm);
-			if (rc) return rc;
-			const Window cols { h->d_at, h->d_cg, h->d_term, cn, c0, cn };
-			rc = launch_within(rows, cols, n_db, n_sites, min_cov, d_out, base, h->ev[0], h->ev[1], &tm.cross_kernel_ms);
-			if (rc) return rc;
-			if (db_geno) {
-				const auto t = wall::now();
-				HIPCHK(hipMemcpy(db_geno + (size_t) c0 * 3, h->d_geno, (size_t) cn * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-				tm.download_ms += ms_since(t);
-			}
-			tm.chunks++;
-		}
-	}
-	const auto t = wall::now();
-	if (records) HIPCHK(hipMemcpy(out, d_out, records * sizeof(ntsm_eval_record), hipMemcpyDeviceToHost));
-	tm.download_ms += ms_since(t);
+	HIPCHK(hipSetDevice(h->hold.device));
+	ntsm_hip::Buffers b;                                                          /* this call's: streamed, the band's rows */
+	ntsm_eval_cross_times tm = h->hold.take_open_times();
+	Window rows;
+	int rc = h->hold.band_rows(b, row_first, n_rows, nullptr, h->stager(), tm, rows);
+	if (rc) return rc;
+	/* the columns before row_first pair with no row of the band: a streamed store leaves them on the host */
+	rc = h->hold.walk(row_first, records, out, db_geno, h->stager(), [&](const Window &cols, ntsm_eval_record *d_out) {
+		return launch_within(rows, cols, n_db, n_sites, min_cov, d_out, base, h->hold.ev[0], h->hold.ev[1], &tm.cross_kernel_ms);
+	}, tm);
+	if (rc) return rc;
 	if (times) *times = tm;
 	return 0;
 }
+

@@ -11,7 +11,8 @@
 #                                                  against another (--between) and the PCA-guided search between
 #                                                  two (--between-near), and the QC tables of a store (--qc), and the
 #                                                  cross-sample contamination check over one (--contam), and the
-#                                                  parent-parent-child trios in one (--trios)
+#                                                  parent-parent-child trios in one (--trios), and the site-pair LD
+#                                                  and prune over one (--ld)
 #   ntsm_amd/libntsm_vcf_hip.so, build/ntsmVCF     multi-sample VCF to PCA matrix + centre file (HIP library + CLI mirror);
 #                                                  with --rotation also the PCA, through libntsm_pca_hip.so
 #                                                  with --counts / --store the genotypes as counts files and cohort-store records
@@ -98,17 +99,21 @@ xlib:
 # + parent-parent-child trios in a store (--trios): ntsm_eval_trio.hip, bit-planes of genotype classes and popcount kernels over
 #   site words; the chunk rule and the 2-D copy are ntsm_eval_chunk.h's, the candidate rule, the batches, the pedigree and the
 #   text are host code (host/eval_trio.hpp)
+# + site-pair LD over a store (--ld): ntsm_eval_ld.hip, bit-planes with the samples along the bits and a popcount GEMM over
+#   sites x sites; the genotype rule is ntsm_eval_geno.h's, shared with --trios; the chunk rule and the 2-D copy are
+#   ntsm_eval_chunk.h's; the moments and r^2 (compiled for the device too), the band rule, the text and the prune are host code
+#   (host/eval_ld.hpp)
 # + what those store paths share on the host side of their HIP calls: ntsm_eval_chunk.h also states the check of a store argument,
 #   the launch rule of the row-group kernels (cross, contam, the trio duo kernel) and the timed launch; ntsm_eval_band.h states the
 #   band session of --within, --between and --contam once: the holding of a store's columns, resident or streamed, and the band walk
 EVALSRC := $(CSRC)/ntsm_eval.hip $(CSRC)/ntsm_eval_pca.hip $(CSRC)/ntsm_eval_cross.hip $(CSRC)/ntsm_eval_near.hip $(CSRC)/ntsm_eval_within.hip \
            $(CSRC)/ntsm_eval_between.hip $(CSRC)/ntsm_eval_between_near.hip $(CSRC)/ntsm_eval_profile.hip $(CSRC)/ntsm_eval_contam.hip \
-           $(CSRC)/ntsm_eval_trio.hip
-ntsm_amd/libntsm_eval_hip.so: $(EVALSRC) $(CSRC)/ntsm_eval_score.h $(CSRC)/ntsm_eval_chunk.h $(CSRC)/ntsm_eval_band.h $(CSRC)/ntsm_eval_pca.h $(CSRC)/ntsm_hip_scope.h $(CSRC)/xprec.h \
+           $(CSRC)/ntsm_eval_trio.hip $(CSRC)/ntsm_eval_ld.hip
+ntsm_amd/libntsm_eval_hip.so: $(EVALSRC) $(CSRC)/ntsm_eval_geno.h $(HOST)/eval_ld.hpp $(CSRC)/ntsm_eval_score.h $(CSRC)/ntsm_eval_chunk.h $(CSRC)/ntsm_eval_band.h $(CSRC)/ntsm_eval_pca.h $(CSRC)/ntsm_hip_scope.h $(CSRC)/xprec.h \
                               $(HOST)/eval_within.hpp $(HOST)/eval_between.hpp $(HOST)/eval_store.hpp include/ntsm_eval_hip.h
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -shared -o $@ $(EVALSRC)
 
-build/ntsmEval: $(HOST)/ntsm_eval_main.cpp $(HOST)/cli.hpp $(HOST)/eval_store.hpp $(HOST)/eval_index.hpp $(HOST)/eval_qc.hpp $(HOST)/eval_contam.hpp $(HOST)/eval_trio.hpp $(HOST)/eval_within.hpp $(HOST)/eval_between.hpp $(HOST)/crc32_fast.cpp $(HOST)/crc32_fast.hpp \
+build/ntsmEval: $(HOST)/ntsm_eval_main.cpp $(HOST)/cli.hpp $(HOST)/eval_store.hpp $(HOST)/eval_index.hpp $(HOST)/eval_qc.hpp $(HOST)/eval_contam.hpp $(HOST)/eval_trio.hpp $(HOST)/eval_ld.hpp $(HOST)/eval_within.hpp $(HOST)/eval_between.hpp $(HOST)/crc32_fast.cpp $(HOST)/crc32_fast.hpp \
                 $(HOST)/gz_stream.hpp $(CSRC)/xprec.h include/ntsm_eval_hip.h ntsm_amd/libntsm_eval_hip.so
 	@mkdir -p build
 	$(CXX) $(CXXFLAGS) -ffp-contract=off -o $@ $(HOST)/ntsm_eval_main.cpp $(HOST)/crc32_fast.cpp -Lntsm_amd -lntsm_eval_hip -lz \
@@ -163,6 +168,14 @@ trio_check: build/eval_trio_check
 build/eval_trio_check: tools/eval_trio_check.cpp $(HOST)/eval_trio.hpp $(HOST)/eval_contam.hpp include/ntsm_eval_hip.h
 	@mkdir -p build
 	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ tools/eval_trio_check.cpp
+
+# the moments and r^2, the band rule and its halving, the row text and the prune of --ld over a model of the device likewise
+# (tools/eval_ld_check.cpp; not part of `all`)
+ld_check: build/eval_ld_check
+	build/eval_ld_check
+build/eval_ld_check: tools/eval_ld_check.cpp $(HOST)/eval_ld.hpp include/ntsm_eval_hip.h
+	@mkdir -p build
+	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ tools/eval_ld_check.cpp
 
 # the integer x87 add of the projection against the x87 itself likewise: every constructed class and 10^6 random operands, every
 # branch of ntsm_x87_acc reached (tests/xprec_check.cpp; not part of `all`)
@@ -268,4 +281,4 @@ build/gather_bench: tools/gather_bench.hip
 clean:
 	rm -rf build ntsm_amd/*.so
 	$(MAKE) -C oracle clean
-.PHONY: all oracle_all ref_gpu_binding clean ablation abl_tab tab m12 xlib store_check index_check within_check between_check between_near_check contam_check trio_check cohort_check xprec_check
+.PHONY: all oracle_all ref_gpu_binding clean ablation abl_tab tab m12 xlib store_check index_check within_check between_check between_near_check contam_check trio_check ld_check cohort_check xprec_check

@@ -376,6 +376,60 @@ void ntsm_eval_trio_close(ntsm_eval_trio_session *h);
  * for another value. */
 int ntsm_eval_trio_tune(uint32_t width);
 
+/* ---- Site-pair LD over a cohort store (ntsmEval --ld; ntsm_amd/csrc/ntsm_eval_ld.hip): the transpose of
+ * the trio question -- bit-planes with the samples along the bits, and a popcount GEMM over sites x sites.  The reference has no
+ * such run; the contract is this text.  db_counts / db_stride_bytes / db_chunk as for ntsm_eval_cross.  All accumulated quantities
+ * are integers: two calls of any entry give the same bytes.
+ *
+ * Classes.  c = min_cov, D = min_depth; a cell's class is "the genotype rule of this run" of the trio section above, unchanged
+ *   (one function for both libraries: ntsm_amd/csrc/ntsm_eval_geno.h).  Dosage x = 0 for homAT, 1 for het, 2 for homCG.
+ * Per site s, as sets of samples: H_s = het, G_s = homCG, C_s = called.
+ * The record of the ordered site pair (s, t), eight counts of samples:
+ *     n  = |C_s & C_t|   hs = |H_s & C_t|   gs = |G_s & C_t|   ht = |C_s & H_t|   gt = |C_s & G_t|
+ *     hh = |H_s & H_t|   hg = |(H_s & G_t) | (G_s & H_t)|      gg = |G_s & G_t|
+ *   The two sets under hg are disjoint.  The record of (t, s) is that of (s, t) with hs <-> ht and gs <-> gt.  The diagonal is a
+ *   pair like any other.
+ * Moments, in int64, exact for n_db <= 2^24 (a larger store is refused):
+ *     Sx = hs + 2 gs   Sy = ht + 2 gt   Sxx = hs + 4 gs   Syy = ht + 4 gt   Sxy = hh + 2 hg + 4 gg
+ *     cov = n Sxy - Sx Sy    vx = n Sxx - Sx^2    vy = n Syy - Sy^2
+ * r^2 is undefined when n < min_called, vx == 0 or vy == 0; else it is the double (double(cov) * double(cov)) / (double(vx) *
+ *   double(vy)): two multiplications and one division, each rounded once (no contraction).  r^2 <= 1.0.  dir is + when cov > 0,
+ *   else -.  The expressions are ntsm_amd/csrc/host/eval_ld.hpp's, which the device's test of a pair compiles too.
+ * A pair is selected when s < t, r^2 is defined and r^2 >= r2_min.
+ *
+ * ntsm_eval_ld_open: streams the store once, in chunks of db_chunk samples (0 = the chunk rule, asked at 8 * n_sites bytes per
+ *   sample), and builds three planes het, hom_cg, called as [plane][sample word][site] uint64 on the device: a word holds 64
+ *   samples, the site index is fastest, bits past n_db in the last word are zero.  The planes are always resident
+ *   (3 * ceil(n_db / 64) * 8 bytes per site); the counts go back before open returns.  The mapping need not outlive the call.
+ *   site_geno (may be NULL): [n_sites][4] = het, homCG, called, homAT of each site: the number of samples of each class there.
+ *   times (may be NULL): upload_ms the copies, prepare_kernel_ms the plane and site_geno kernels, download_ms site_geno's way
+ *     back, chunks the chunks uploaded.
+ *   Returns 0, -2 HIP error, -1 bad argument, before any HIP call: a NULL it needs, a stride below 8 * n_sites or not a multiple
+ *   of 4, n_db > 2^24.  n_db == 0 or n_sites == 0: a session without device work (site_geno zeroed).
+ * ntsm_eval_ld_rows: the dense records of sites row_first ... row_first + n_rows - 1 against every site: out [n_rows][n_sites],
+ *   out[(s - row_first) * n_sites + t] the record of (s, t).  kernel_ms (may be NULL): the rectangle kernel, from HIP events.
+ *   Returns 0, -2, -1 (row_first + n_rows > n_sites, n_rows == 0, a NULL it needs), the -1 before any HIP call.  n_db == 0: zeroed
+ *   records; of n_sites == 0 there is no range to take.
+ * ntsm_eval_ld_select: the selected pairs (a, b) with row_first <= a < row_first + n_rows and a < b < n_sites, sorted by (a, b).
+ *   Only tiles on or above the diagonal are evaluated, the test runs on the device and no dense rectangle is written.
+ *   cap: the pairs out_pairs holds (out_pairs may be NULL when cap is 0).  *n_found is always the true total.  Returns 0; 1 when
+ *   *n_found > cap, out_pairs then unspecified; -2; -1 as _rows, and for a non-finite r2_min or a NULL n_found.  n_db == 0:
+ *   nothing is selected. */
+typedef struct ntsm_eval_ld_record { uint32_t n, hs, gs, ht, gt, hh, hg, gg; } ntsm_eval_ld_record;   /* 32 bytes */
+typedef struct ntsm_eval_ld_pair { uint32_t a, b; ntsm_eval_ld_record rec; } ntsm_eval_ld_pair;   /* 40 bytes */
+#define NTSM_EVAL_LD_MAX_SAMPLES (1u << 24)
+typedef struct ntsm_eval_ld_session ntsm_eval_ld_session;
+int ntsm_eval_ld_open(int device, const void *db_counts, uint64_t db_stride_bytes, uint32_t n_db, uint32_t n_sites, uint32_t min_cov,
+		uint32_t min_depth, uint32_t db_chunk, uint32_t *site_geno, ntsm_eval_cross_times *times, ntsm_eval_ld_session **h);
+int ntsm_eval_ld_rows(ntsm_eval_ld_session *h, uint32_t row_first, uint32_t n_rows, ntsm_eval_ld_record *out, double *kernel_ms);
+int ntsm_eval_ld_select(ntsm_eval_ld_session *h, uint32_t row_first, uint32_t n_rows, uint32_t min_called, double r2_min, uint64_t cap,
+		ntsm_eval_ld_pair *out_pairs, uint64_t *n_found, double *kernel_ms);
+void ntsm_eval_ld_close(ntsm_eval_ld_session *h);
+/* For measurements and tests only: force the register block of the rectangle kernel -- rows x columns of pairs per lane, one of
+ * 2 x 2, 4 x 2 and 2 x 4, which with 16 x 16 lanes is a tile of 32 x 32, 64 x 32 or 32 x 64 sites -- of later _rows and _select
+ * calls in this process; (0, 0) = the library's rule (2 x 2).  Returns 0, -1 for another value. */
+int ntsm_eval_ld_tune(uint32_t block_rows, uint32_t block_cols);
+
 #ifdef __cplusplus
 }
 #endif

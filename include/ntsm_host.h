@@ -148,6 +148,23 @@ int64_t ntsm_host_trio_match(const char *const *names, uint32_t n_names, const c
 int64_t ntsm_host_trio_candidates(const struct ntsm_eval_trio_duo *row, uint32_t n_db, uint32_t child, uint32_t min_called, double max_duo, uint32_t *out);
 size_t ntsm_host_trio_batches(const uint32_t *k, size_t n, uint64_t limit, size_t *ends, size_t *n_ends);
 
+/* The host side of `ntsmEval --ld` (ntsm_amd/csrc/host/eval_ld.hpp), for tests; records as include/ntsm_eval_hip.h has them.
+ * _r2: the moments of a record into moments [4] = n, cov, vx, vy (may be NULL); 1 and *r2 where r^2 is defined at min_called,
+ *   0 where it is not (*r2 untouched), -1 for a NULL record.
+ * _rows: the lines of these pairs in their order, locus[n_sites] the store's IDs, without the header.  0, -1 for a NULL it
+ *   needs or an index >= n_sites.
+ * _prune: kept [n_sites] = 1 / 0 after these pairs, which are in (a, b) order: b is dropped when the pair is selected at
+ *   (min_called, r2_min) and a is kept.  0, -1.
+ * _bands: the band walk over a model of the device that selects row_pairs[a] pairs in row a: every call's first row, rows and
+ *   return (0, or 1 = more than the capacity) into calls [max_calls][3]; stats [3] (may be NULL) = bands, re-runs, pairs.
+ *   Returns the number of calls, -1 for a NULL it needs. */
+struct ntsm_eval_ld_record;
+struct ntsm_eval_ld_pair;
+int ntsm_host_ld_r2(const struct ntsm_eval_ld_record *rec, uint32_t min_called, int64_t *moments, double *r2);
+int ntsm_host_ld_rows(const char *const *locus, uint32_t n_sites, const struct ntsm_eval_ld_pair *pairs, uint64_t n_pairs, char **out, size_t *len);
+int ntsm_host_ld_prune(uint32_t n_sites, const struct ntsm_eval_ld_pair *pairs, uint64_t n_pairs, uint32_t min_called, double r2_min, uint8_t *kept);
+int64_t ntsm_host_ld_bands(const uint64_t *row_pairs, uint32_t n_sites, uint64_t budget, uint32_t *calls, size_t max_calls, uint64_t *stats);
+
 #ifdef __cplusplus
 }
 #endif

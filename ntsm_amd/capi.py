@@ -147,6 +147,10 @@ _sig(HO, "ntsm_host_trio_ped_parse", C.c_int, [C.c_char_p, C.c_size_t, C.POINTER
 _sig(HO, "ntsm_host_trio_match", C.c_int64, [C.POINTER(C.c_char_p), C.c_uint32, C.c_char_p])
 _sig(HO, "ntsm_host_trio_candidates", C.c_int64, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, u32p])
 _sig(HO, "ntsm_host_trio_batches", C.c_size_t, [u32p, C.c_size_t, C.c_uint64, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)])
+_sig(HO, "ntsm_host_ld_r2", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_int64), C.POINTER(C.c_double)])
+_sig(HO, "ntsm_host_ld_rows", C.c_int, [C.POINTER(C.c_char_p), C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)])
+_sig(HO, "ntsm_host_ld_prune", C.c_int, [C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_double, C.c_void_p])
+_sig(HO, "ntsm_host_ld_bands", C.c_int64, [u64p, C.c_uint32, C.c_uint64, u32p, C.c_size_t, u64p])
 
 SY = synth_lib
 _sig(SY, "ntsm_synth_sites", C.c_int, [C.c_uint64, C.c_uint32, C.c_uint, u8p, C.c_char_p, u64p])

@@ -13,6 +13,7 @@
 #include "pack2.hpp"
 #include "early_ingest.hpp"
 #include "eval_contam.hpp"
+#include "eval_ld.hpp"
 #include "eval_qc.hpp"
 #include "eval_trio.hpp"
 #include "host_shape.hpp"
@@ -472,6 +473,58 @@ size_t ntsm_host_trio_batches(const uint32_t *k, size_t n, uint64_t limit, size_
 	if (ends) std::copy(e.begin(), e.end(), ends);
 	if (n_ends) *n_ends = e.size();
 	return bad;
+}
+
+int ntsm_host_ld_r2(const ntsm_eval_ld_record *rec, uint32_t min_called, int64_t *moments, double *r2)
+{
+	if (!rec) return -1;
+	const ntsm::eval_ld::Moments m = ntsm::eval_ld::moments_of(*rec);
+	if (moments) { moments[0] = m.n; moments[1] = m.cov; moments[2] = m.vx; moments[3] = m.vy; }
+	if (!ntsm::eval_ld::r2_defined(m, min_called)) return 0;
+	if (r2) *r2 = ntsm::eval_ld::r2_of(m);
+	return 1;
+}
+
+int ntsm_host_ld_rows(const char *const *locus, uint32_t n_sites, const ntsm_eval_ld_pair *pairs, uint64_t n_pairs, char **out, size_t *len)
+{
+	if (!out || !len || (n_pairs && (!locus || !pairs))) return -1;
+	for (uint64_t i = 0; i < n_pairs; ++i)
+		if (pairs[i].a >= n_sites || pairs[i].b >= n_sites) return -1;
+	std::string text;
+	ntsm::eval_ld::rows_text(text, locus, pairs, n_pairs);
+	*out = dup_string(text, len);
+	return 0;
+}
+
+int ntsm_host_ld_prune(uint32_t n_sites, const ntsm_eval_ld_pair *pairs, uint64_t n_pairs, uint32_t min_called, double r2_min, uint8_t *kept)
+{
+	if ((n_sites && !kept) || (n_pairs && !pairs)) return -1;
+	for (uint64_t i = 0; i < n_pairs; ++i)
+		if (pairs[i].a >= n_sites || pairs[i].b >= n_sites) return -1;
+	ntsm::eval_ld::Prune prune(n_sites);
+	prune.add(pairs, n_pairs, min_called, r2_min);
+	std::copy(prune.kept.begin(), prune.kept.end(), kept);
+	return 0;
+}
+
+int64_t ntsm_host_ld_bands(const uint64_t *row_pairs, uint32_t n_sites, uint64_t budget, uint32_t *calls, size_t max_calls, uint64_t *stats)
+{
+	if ((n_sites && !row_pairs) || (max_calls && !calls)) return -1;
+	size_t n_calls = 0;
+	ntsm::eval_ld::Device dev;
+	dev.select = [&](uint32_t first, uint32_t rows, uint64_t cap, ntsm_eval_ld_pair *, uint64_t *found) {
+		*found = 0;
+		for (uint32_t r = 0; r < rows; ++r) *found += row_pairs[first + r];
+		const int rc = *found > cap;
+		if (n_calls < max_calls) { calls[3 * n_calls] = first; calls[3 * n_calls + 1] = rows; calls[3 * n_calls + 2] = (uint32_t) rc; }
+		++n_calls;
+		return rc;
+	};
+	ntsm::eval_ld::Stats st;
+	const int rc = ntsm::eval_ld::walk(dev, n_sites, budget, [](const ntsm_eval_ld_pair *, uint64_t) {}, st);
+	if (rc) return -2;
+	if (stats) { stats[0] = st.bands; stats[1] = st.reruns; stats[2] = st.pairs; }
+	return (int64_t) n_calls;
 }
 
 } // extern "C"

@@ -30,7 +30,10 @@
  *   --trios STORE [--ped FILE]   which samples form a parent-parent-child trio, or do a pedigree's trios hold: bit-planes of
  *                             genotype classes on the device: ntsm_eval_trio_open / _duos / _score; the runs and the text are
  *                             eval_trio.hpp's
- * --within, --within-near, --between, --between-near, --qc, --contam and --trios read no counts file.  Not built, and refused: -b (the debug ground-truth mode) and -p without a
+ *   --ld STORE [--ld-prune FILE]   which pairs of sites are in linkage disequilibrium, and which sites does a prune keep:
+ *                             bit-planes with the samples along the bits on the device: ntsm_eval_ld_open / _select; the
+ *                             moments, the band walk, the text and the prune are eval_ld.hpp's
+ * --within, --within-near, --between, --between-near, --qc, --contam, --trios and --ld read no counts file.  Not built, and refused: -b (the debug ground-truth mode) and -p without a
  * normalization file (the reference dies in an assert).  Pinned to the reference: stdout equals, byte for byte, that of the
  * unmodified scoring class (oracle/ref_eval_driver.cpp -> oracle/_ref/ref_ntsmEval -t 1) and its recordings,
  * tests/test_eval_reference.py.
@@ -55,6 +58,7 @@
 #include "eval_between.hpp"
 #include "eval_contam.hpp"
 #include "eval_index.hpp"
+#include "eval_ld.hpp"
 #include "eval_qc.hpp"
 #include "eval_store.hpp"
 #include "eval_trio.hpp"
@@ -90,6 +94,10 @@ struct Opt {                                 /* src/Options.h:44-55 */
 	unsigned trioDepth = ntsm::eval_trio::kMinDepth, trioCalled = ntsm::eval_trio::kMinCalled;   /* --trio-depth D, --trio-called M */
 	double trioMax = ntsm::eval_trio::kMaxRate, trioDuo = ntsm::eval_trio::kMaxDuo;              /* --trio-max X, --trio-duo Y */
 	bool trioExhaustive = false, trioFlagGiven = false, pedGiven = false;
+	std::string ld, ldPrune;                 /* --ld STORE: site-pair LD over the store; --ld-prune FILE: the IDs of the sites a prune keeps */
+	unsigned ldDepth = ntsm::eval_ld::kMinDepth, ldCalled = ntsm::eval_ld::kMinCalled;   /* --ld-depth D, --ld-called M */
+	double ldMin = ntsm::eval_ld::kMinR2;    /* --ld-min T */
+	bool ldFlagGiven = false, ldPruneGiven = false;
 	bool minCovGiven = false, dimGiven = false;
 	bool onlyMerge = false;
 	unsigned dim = 20;                       /* src/Options.h:22, 35-39: the PCA search */
@@ -285,6 +293,23 @@ void printHelpDialog()
 	    "                             trio in file order, with a last column verdict: lowcov\n"
 	    "                             (called < --trio-called), ok (rate <= --trio-max) or fail.\n"
 	    "                             Not with -a or --trio-exhaustive.\n"
+	    "      --ld = STORE           Which pairs of sites of STORE are in linkage disequilibrium?\n"
+	    "                             Classes as for --trios, gated by --ld-depth; dosage 0 / 1 /\n"
+	    "                             2 = homAT / het / homCG; r2 is the squared correlation of\n"
+	    "                             the dosages over the samples called at both sites,\n"
+	    "                             undefined below --ld-called such samples or where a site\n"
+	    "                             does not vary among them. One row per pair of sites in\n"
+	    "                             store order with r2 >= --ld-min: siteA siteB n r2 dir, dir\n"
+	    "                             the sign of the covariance. With -a every pair with a\n"
+	    "                             defined r2. Takes no FILES. Not with -p, -n, -b, -e or -o.\n"
+	    "      --ld-depth = INT       Least depth of a homozygous site [" << std::to_string(d.ldDepth) << " reads]\n"
+	    "      --ld-min = FLOAT       Least r2 of a printed pair [" << std::to_string(d.ldMin) << "]\n"
+	    "      --ld-called = INT      Least samples called at both sites [" << std::to_string(d.ldCalled) << " samples]\n"
+	    "                             All three defaults are conventions to override.\n"
+	    "      --ld-prune = FILE      With --ld: write the IDs of the sites a greedy prune keeps\n"
+	    "                             to FILE, one per line: in store order a site is dropped\n"
+	    "                             when it pairs at r2 >= --ld-min with an earlier kept site\n"
+	    "                             (also under -a).\n"
 	    "Not in this build: -b (debug mode of the PCA search); the PCA-guided search (-p)\n"
 	    "against a store (--index and --near are that search); merging (-e) from a store.\n" << std::endl;
 	exit(EXIT_SUCCESS);
@@ -403,6 +428,7 @@ typedef Handle<ntsm_eval_within_session, ntsm_eval_within_close> WithinSession;
 typedef Handle<ntsm_eval_between_session, ntsm_eval_between_close> BetweenSession;
 typedef Handle<ntsm_eval_contam_session, ntsm_eval_contam_close> ContamSession;
 typedef Handle<ntsm_eval_trio_session, ntsm_eval_trio_close> TrioSession;
+typedef Handle<ntsm_eval_ld_session, ntsm_eval_ld_close> LdSession;
 
 typedef std::chrono::steady_clock Clock;
 double msSince(Clock::time_point t) { return std::chrono::duration<double, std::milli>(Clock::now() - t).count(); }
@@ -483,7 +509,8 @@ int scorePCA(const Counts &c, std::vector<Genotype> &g, const Opt &opt, ntsm_eva
 constexpr int kOptPack = 1000, kOptAgainst = 1001, kOptIndex = 1002, kOptNear = 1003, kOptWithin = 1004, kOptWithinNear = 1005,
               kOptWithinRows = 1006, kOptBetween = 1007, kOptBetweenRows = 1008, kOptBetweenNear = 1009, kOptQc = 1010, kOptSitesOut = 1011,
               kOptContam = 1012, kOptContamDepth = 1013, kOptContamMin = 1014, kOptContamExplained = 1015, kOptContamRows = 1016, kOptSamplesOut = 1017,
-              kOptTrios = 1018, kOptTrioDepth = 1019, kOptTrioMax = 1020, kOptTrioDuo = 1021, kOptTrioCalled = 1022, kOptTrioExhaustive = 1023, kOptPed = 1024;   /* long-only: no letter of the reference's option string is taken */
+              kOptTrios = 1018, kOptTrioDepth = 1019, kOptTrioMax = 1020, kOptTrioDuo = 1021, kOptTrioCalled = 1022, kOptTrioExhaustive = 1023, kOptPed = 1024,
+              kOptLd = 1025, kOptLdDepth = 1026, kOptLdMin = 1027, kOptLdCalled = 1028, kOptLdPrune = 1029;   /* long-only: no letter of the reference's option string is taken */
 
 /* --pack STORE FILES...: no GPU */
 int packStore(const Counts &c, const Opt &opt)
@@ -1300,6 +1327,73 @@ int trioStore(const Opt &opt, Clock::time_point t0)
 	return 0;
 }
 
+/* --ld STORE [-c N] [--ld-depth D] [--ld-min T] [--ld-called M] [--ld-prune FILE] [-a]: which pairs of sites of the store are
+ * in linkage disequilibrium, and which sites a prune keeps.  The band walk, the text and the prune are
+ * eval_ld.hpp's; this opens the store and the session and hands the walk the library's selection.  Every refusal comes before the
+ * session is opened.  NTSM_LD_PAIR_BUDGET (tests): the pairs of one call, in place of 1 GiB of them. */
+int ldStore(const Opt &opt, Clock::time_point t0)
+{
+	namespace ld = ntsm::eval_ld;
+	ntsm::eval_store::View store;
+	SitesFile prunedFile;
+	const auto tMap = Clock::now();
+	try {
+		openStore(opt.ld, 0, "scores", store, nullptr);
+		if (store.h.n_samples < 2) throw ld::Error(opt.ld + " holds fewer than 2 samples: no site varies among them");
+		if (store.h.n_samples > NTSM_EVAL_LD_MAX_SAMPLES) throw ld::Error(opt.ld + " holds more than 16777216 samples: the moments of --ld are exact up to there");
+		if (store.h.n_sites < 2) throw ld::Error(opt.ld + " holds fewer than 2 sites: there is no pair of sites");
+		if (opt.ldPruneGiven && !prunedFile.open(opt.ldPrune)) throw ld::Error("cannot write " + opt.ldPrune);
+	} catch (const std::exception &e) {
+		ntsm::refuse(e.what());
+	}
+	const double mapMs = msSince(tMap);
+	const uint32_t n = (uint32_t) store.h.n_samples, m = store.h.n_sites;
+	uint64_t budget = ld::kPairBudget;
+	if (const char *b = getenv("NTSM_LD_PAIR_BUDGET")) budget = strtoull(b, nullptr, 10);
+	if (opt.verbose > 1) std::cerr << "Mapped " << opt.ld << ". Now comparing its " << m << " sites over " << n << " samples." << std::endl;
+	LdSession session;
+	ntsm_eval_cross_times open {};
+	int rc = ntsm_eval_ld_open(opt.device, store.counts(0), store.h.stride, n, m, opt.minCov, opt.ldDepth, 0, nullptr, &open, &session.h);
+	if (rc) return gpuFail("opening the store", rc);
+	std::vector<const char *> locus(m);
+	for (uint32_t s = 0; s < m; ++s) locus[s] = store.locus[s].c_str();
+	double kernelMs = 0, callMs = 0, printMs = 0;
+	const double cut = opt.all ? 0.0 : opt.ldMin;                                  /* r2 >= 0 wherever it is defined */
+	ld::Device dev;
+	dev.select = [&](uint32_t first, uint32_t rows, uint64_t cap, ntsm_eval_ld_pair *out, uint64_t *found) {
+		const auto t = Clock::now();
+		double ms = 0;
+		const int r = ntsm_eval_ld_select(session.h, first, rows, opt.ldCalled, cut, cap, out, found, &ms);
+		kernelMs += ms; callMs += msSince(t);
+		return r;
+	};
+	ld::Prune prune(m);
+	bool headed = false;
+	std::string text;
+	ld::Stats st;
+	rc = ld::walk(dev, m, budget, [&](const ntsm_eval_ld_pair *pairs, uint64_t count) {
+		const auto t = Clock::now();
+		text.clear();
+		if (!headed) { text = ld::kHeader; headed = true; }
+		ld::rows_text(text, locus.data(), pairs, count);
+		std::cout << text;
+		if (opt.ldPruneGiven) prune.add(pairs, count, opt.ldCalled, opt.ldMin);
+		printMs += msSince(t);
+	}, st);
+	if (rc) return gpuFail("comparing the sites", rc);
+	std::cout.flush();
+	if (opt.ldPruneGiven && !prunedFile.write(prune.text(locus.data()))) { std::cerr << PROGRAM ": cannot write " << opt.ldPrune << std::endl; return 1; }
+	if (opt.verbose > 1) {
+		std::cerr << "store ld: planes " << 3ull * ((n + 63ull) / 64) * 8 * m << " bytes, " << open.chunks << " chunks, " << st.bands << " bands, " << st.reruns
+		          << " re-runs, " << st.pairs << " pairs";
+		if (opt.ldPruneGiven) std::cerr << ", " << prune.n_kept() << " kept sites";
+		std::cerr << ", map " << mapMs << " ms, upload " << open.upload_ms << " ms, plane kernel " << open.prepare_kernel_ms << " ms, select " << callMs
+		          << " ms (kernel " << kernelMs << " ms), print " << printMs << " ms" << std::endl;
+	}
+	printTime(t0);
+	return 0;
+}
+
 /* what no store run goes with */
 void refuseDebugAndMerge(const Opt &opt, const char *mode)
 {
@@ -1312,7 +1406,7 @@ void refuseDebugAndMerge(const Opt &opt, const char *mode)
 int main(int argc, char **argv)
 {
 	Opt opt;
-	bool die = false, storeMode = false, nearMode = false, withinMode = false, betweenMode = false, betweenNearMode = false, qcMode = false, contamMode = false, trioMode = false;
+	bool die = false, storeMode = false, nearMode = false, withinMode = false, betweenMode = false, betweenNearMode = false, qcMode = false, contamMode = false, trioMode = false, ldMode = false;
 	static struct option long_options[] = {
 		{ "score_thresh", required_argument, nullptr, 's' }, { "all", no_argument, nullptr, 'a' },
 		{ "min_cov", required_argument, nullptr, 'c' }, { "skew", required_argument, nullptr, 'w' },
@@ -1336,6 +1430,8 @@ int main(int argc, char **argv)
 		{ "trio-max", required_argument, nullptr, kOptTrioMax }, { "trio-duo", required_argument, nullptr, kOptTrioDuo },
 		{ "trio-called", required_argument, nullptr, kOptTrioCalled }, { "trio-exhaustive", no_argument, nullptr, kOptTrioExhaustive },
 		{ "ped", required_argument, nullptr, kOptPed },
+		{ "ld", required_argument, nullptr, kOptLd }, { "ld-depth", required_argument, nullptr, kOptLdDepth }, { "ld-min", required_argument, nullptr, kOptLdMin },
+		{ "ld-called", required_argument, nullptr, kOptLdCalled }, { "ld-prune", required_argument, nullptr, kOptLdPrune },
 		{ nullptr, 0, nullptr, 0 } };
 	int ch;
 	while ((ch = getopt_long(argc, argv, "t:vhs:c:m:aw:g:p:n:d:r:e:o1:2:S:l:b:G:", long_options, nullptr)) != -1) {
@@ -1416,6 +1512,20 @@ int main(int argc, char **argv)
 			break;
 		case kOptTrioExhaustive: opt.trioExhaustive = true; opt.trioFlagGiven = true; break;
 		case kOptPed: opt.ped = optarg; opt.pedGiven = true; break;
+		case kOptLd: opt.ld = optarg; ldMode = true; break;
+		case kOptLdDepth:
+			if (optarg[0] == '-' || !ntsm::read_whole(optarg, opt.ldDepth)) ntsm::refuse(std::string("--ld-depth takes a number of reads, not ") + optarg);
+			opt.ldFlagGiven = true;
+			break;
+		case kOptLdCalled:
+			if (optarg[0] == '-' || !ntsm::read_whole(optarg, opt.ldCalled)) ntsm::refuse(std::string("--ld-called takes a number of samples, not ") + optarg);
+			opt.ldFlagGiven = true;
+			break;
+		case kOptLdMin:
+			if (!ntsm::read_whole(optarg, opt.ldMin) || !std::isfinite(opt.ldMin)) ntsm::refuse(std::string("--ld-min takes a number, not ") + optarg);
+			opt.ldFlagGiven = true;
+			break;
+		case kOptLdPrune: opt.ldPrune = optarg; opt.ldPruneGiven = true; opt.ldFlagGiven = true; break;
 		case '?': die = true; break;
 		default: break;                              /* m: read by the reference, without effect */
 		}
@@ -1423,6 +1533,10 @@ int main(int argc, char **argv)
 	Counts c;
 	while (optind < argc) c.files.emplace_back(argv[optind++]);
 	const char *sevenRuns = "--pack, --against, --index, --near, --within, --within-near and --between are seven runs: give one of them";
+	if (ldMode && (storeMode || nearMode || withinMode || betweenMode || betweenNearMode || qcMode || contamMode || trioMode))
+		ntsm::refuse("--ld compares the sites of one store and is a run of its own: it goes with none of --pack, --against, --index, --near, --within, "
+		             "--within-near, --between, --between-near, --qc, --contam and --trios");
+	if (opt.ldFlagGiven && !ldMode) ntsm::refuse("--ld-depth, --ld-min, --ld-called and --ld-prune belong to --ld: give them with --ld STORE");
 	if (trioMode && (storeMode || nearMode || withinMode || betweenMode || betweenNearMode || qcMode || contamMode))
 		ntsm::refuse("--trios looks for parent-child trios in one store and is a run of its own: it goes with none of --pack, --against, --index, --near, "
 		             "--within, --within-near, --between, --between-near, --qc and --contam");
@@ -1475,6 +1589,13 @@ int main(int argc, char **argv)
 		return near ? searchWithin(opt, t0) : scoreWithin(opt, t0);
 	}
 	if (opt.withinRowsGiven) ntsm::refuse("--within-rows sets the bands of --within: give it with --within STORE");
+	if (ldMode) {                                        /* --ld: every refusal that needs no store, then the run */
+		if (!c.files.empty()) ntsm::refuse("--ld takes no input files: it compares the sites of the store");
+		if (!opt.pca.empty() || !opt.norm.empty()) ntsm::refuse("--ld reads allele counts, not projections, and takes no -p and no -n");
+		refuseDebugAndMerge(opt, "--ld");
+		ntsm::try_help_if(die);
+		return ldStore(opt, Clock::now());
+	}
 	if (trioMode) {                                      /* --trios: every refusal that needs no store, then the run */
 		if (!c.files.empty()) ntsm::refuse("--trios takes no input files: it looks for trios among the samples of the store");
 		if (!opt.pca.empty() || !opt.norm.empty()) ntsm::refuse("--trios reads allele counts, not projections, and takes no -p and no -n");

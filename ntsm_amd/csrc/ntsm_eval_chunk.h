@@ -5,7 +5,7 @@
  * rule; the kernels -- the genotype tallies of the chunk's samples over the dense [chunk sample][site][2] buffer and that
  * buffer's transpose to at / cg / term [site][chunk sample] --; and the step that stages a chunk: the 2-D copy from the
  * host pitch, those kernels, the wall clock and the events that time them.  Also what every store path repeats around its HIP
- * calls, whether it holds a band (ntsm_eval_band.h, which builds on this file) or not (ntsm_eval_trio.hip): the check of a store
+ * calls, whether it holds a band (ntsm_eval_band.h, which builds on this file) or not (ntsm_eval_trio.hip, ntsm_eval_ld.hip): the check of a store
  * argument, the launch rule of the kernels with a wave-uniform row group, the timed launch and the timed copy.  Internal: not
  * part of include/.  The kernels have internal linkage; each translation unit that includes this file carries its own copy, and names itself first
  * (NTSM_HIP_TAG, ntsm_hip_scope.h).

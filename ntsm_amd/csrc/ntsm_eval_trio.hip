@@ -37,6 +37,7 @@
 #include "../../include/ntsm_eval_hip.h"
 #define NTSM_HIP_TAG "ntsm_eval_trio"
 #include "ntsm_eval_chunk.h"
+#include "ntsm_eval_geno.h"
 #include "ntsm_hip_scope.h"
 
 namespace {
@@ -48,15 +49,6 @@ constexpr uint32_t kShortList = 16;          /* lists up to this long take the o
 constexpr uint32_t kMaxGridY = 65535;
 
 uint32_t g_width = 0;                        /* ntsm_eval_trio_tune */
-
-/* the genotype rule of this run (include/ntsm_eval_hip.h): 0 homAT, 1 het, 2 homCG, 3 miss */
-__device__ __host__ inline int class_of(uint32_t a, uint32_t g, uint32_t min_cov, uint32_t min_depth)
-{
-	const bool A = a > min_cov, G = g > min_cov;
-	if (A && G) return 1;
-	if (A == G || (uint64_t) a + (uint64_t) g < min_depth) return 3;
-	return A ? 0 : 2;
-}
 
 /* counts [count][site][2] (dense) -> words `word` of samples first ... first + count - 1 in planes [3][n_words][n_db].
  * grid (tiles of 64 samples * n_words), word fastest; wave v of the workgroup takes samples v * 16 ... v * 16 + 15 of its tile. */
@@ -72,7 +64,7 @@ __global__ __launch_bounds__(kThreads) void ntsm_eval_trio_planes_kernel(const u
 		int cls = 3;
 		if (s < count && site < n_sites) {
 			const uint2 c = counts[(uint64_t) s * n_sites + site];
-			cls = class_of(c.x, c.y, min_cov, min_depth);
+			cls = ntsm_eval_class_of(c.x, c.y, min_cov, min_depth);                 /* the genotype rule, shared with --ld: ntsm_eval_geno.h */
 		}
 		const uint64_t b0 = __ballot(cls == 0), b1 = __ballot(cls == 1), b2 = __ballot(cls == 2);
 		if (lane == 0) { tile[0][r] = b0; tile[1][r] = b1; tile[2][r] = b2; }

@@ -1,6 +1,6 @@
 """ctypes plumbing for include/ntsm_eval_hip.h (all-pairs scoring of ntsmEval on the GPU, its PCA-guided search, queries and
 that search against a cohort store, the pairs inside a store, one store against another, the search between two, the QC
-tables of a store, the contamination check over one and the trios in one); used by tests and tools.
+tables of a store, the contamination check over one, the trios in one and the site-pair LD over one); used by tests and tools.
 Loaded on demand: `import ntsm_amd.eval`.  Fails loudly when libntsm_eval_hip.so has not been built."""
 import ctypes as C
 import os
@@ -813,3 +813,128 @@ def trio_batches(lengths, limit=(1 << 30) // 16):
     n_ends = C.c_size_t()
     bad = HO.ntsm_host_trio_batches(kp, len(k), limit, ends, C.byref(n_ends))
     return (list(ends[:n_ends.value]), None) if bad == len(k) else (None, bad)
+
+
+# ---- site-pair LD over a cohort store (ntsmEval --ld; include/ntsm_eval_hip.h: ntsm_eval_ld_open ... _tune).
+LD_RECORD = np.dtype([(f, "<u4") for f in ("n", "hs", "gs", "ht", "gt", "hh", "hg", "gg")])
+LD_PAIR = np.dtype([("a", "<u4"), ("b", "<u4"), ("rec", LD_RECORD)])
+assert LD_RECORD.itemsize == 32 and LD_PAIR.itemsize == 40
+lib.ntsm_eval_ld_open.restype = C.c_int
+lib.ntsm_eval_ld_open.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(CrossTimes),
+                                  C.POINTER(C.c_void_p)]
+lib.ntsm_eval_ld_rows.restype = C.c_int
+lib.ntsm_eval_ld_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_double)]
+lib.ntsm_eval_ld_select.restype = C.c_int
+lib.ntsm_eval_ld_select.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+lib.ntsm_eval_ld_close.restype = None
+lib.ntsm_eval_ld_close.argtypes = [C.c_void_p]
+lib.ntsm_eval_ld_tune.restype = C.c_int
+lib.ntsm_eval_ld_tune.argtypes = [C.c_uint32, C.c_uint32]
+
+
+def ld_tune(block_rows, block_cols):
+    """Force the register block (2 x 2, 4 x 2 or 2 x 4 pairs per lane) of later Ld.rows and Ld.select calls in this process;
+    (0, 0) = the library's rule."""
+    rc = lib.ntsm_eval_ld_tune(block_rows, block_cols)
+    if rc:
+        raise ValueError("ntsm_eval_ld_tune(%r, %r) failed: %d" % (block_rows, block_cols, rc))
+
+
+class Ld:
+    """The genotype bit-planes of a store on the device, samples along the bits (ntsm_eval_ld_open): db is uint32
+    [n_db][n_sites][2] or Records, read once, here.  site_geno: uint32 [n_sites, 4] = het, homCG, called, homAT, or None when
+    switched off (passed as NULL); times: the CrossTimes of open.  A context manager: `with Ld(db) as s: rec, ms = s.rows(0, s.m)`."""
+
+    def __init__(self, db, min_cov=1, min_depth=8, db_chunk=0, device=0, site_geno=True):
+        records = _records(db)
+        self.n, self.m = records.n, records.m
+        self.h = C.c_void_p()
+        self.site_geno = np.zeros((self.m, 4), dtype=np.uint32) if site_geno else None
+        self.times = CrossTimes()
+        rc = lib.ntsm_eval_ld_open(device, records.address, records.stride, self.n, self.m, min_cov, min_depth, db_chunk,
+                                   None if self.site_geno is None else self.site_geno.ctypes.data, C.byref(self.times), C.byref(self.h))
+        if rc:
+            raise RuntimeError("ntsm_eval_ld_open failed: %d" % rc)
+
+    def rows(self, row_first, n_rows):
+        """Sites row_first ... row_first + n_rows - 1 against every site: (records [n_rows, m] of LD_RECORD, kernel ms)."""
+        count = n_rows if 0 <= row_first and 0 <= n_rows and row_first + n_rows <= self.m else 0
+        out = np.zeros((count, self.m), dtype=LD_RECORD)
+        ms = C.c_double()
+        rc = lib.ntsm_eval_ld_rows(self.h, row_first, n_rows, out.ctypes.data, C.byref(ms))
+        if rc:
+            raise RuntimeError("ntsm_eval_ld_rows failed: %d" % rc)
+        return out, ms.value
+
+    def select(self, row_first, n_rows, min_called=20, r2_min=0.5, cap=None):
+        """The selected pairs (a, b), a in the band, a < b, sorted: (return code 0 or 1, pairs of LD_PAIR -- empty on 1 --, the
+        true number found, kernel ms).  cap None: as many as the band can hold."""
+        if cap is None:
+            cap = max(n_rows, 0) * self.m
+        out = np.zeros(max(cap, 1), dtype=LD_PAIR)
+        found, ms = C.c_uint64(), C.c_double()
+        rc = lib.ntsm_eval_ld_select(self.h, row_first, n_rows, min_called, r2_min, cap, out.ctypes.data, C.byref(found), C.byref(ms))
+        if rc not in (0, 1):
+            raise RuntimeError("ntsm_eval_ld_select failed: %d" % rc)
+        return rc, out[:0 if rc else found.value].copy(), found.value, ms.value
+
+    def close(self):
+        if self.h:
+            lib.ntsm_eval_ld_close(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+
+def ld_r2(rec, min_called=20):
+    """The moments and r^2 of one LD_RECORD through libntsm_host.so: ((n, cov, vx, vy), r2 or None where it is undefined)."""
+    from .capi import HO
+    rec = np.ascontiguousarray(rec, dtype=LD_RECORD).reshape(1)
+    mom, r2 = (C.c_int64 * 4)(), C.c_double()
+    rc = HO.ntsm_host_ld_r2(rec.ctypes.data, min_called, mom, C.byref(r2))
+    if rc < 0:
+        raise RuntimeError("ntsm_host_ld_r2 failed: %d" % rc)
+    return tuple(mom), (r2.value if rc else None)
+
+
+def ld_rows_text(locus, pairs):
+    """The stdout lines of `ntsmEval --ld` for these LD_PAIRs, in their order, without the header."""
+    from .capi import HO
+    pairs = np.ascontiguousarray(pairs, dtype=LD_PAIR)
+    out, ln = C.c_void_p(), C.c_size_t()
+    rc = HO.ntsm_host_ld_rows(_names(locus), len(locus), pairs.ctypes.data, len(pairs), C.byref(out), C.byref(ln))
+    if rc:
+        raise RuntimeError("ntsm_host_ld_rows failed: %d" % rc)
+    return _host_text(out, ln)
+
+
+def ld_prune(n_sites, pairs, min_called=20, r2_min=0.5):
+    """The prune of --ld over LD_PAIRs in (a, b) order: a bool array [n_sites], True = kept."""
+    from .capi import HO
+    pairs = np.ascontiguousarray(pairs, dtype=LD_PAIR)
+    kept = np.zeros(max(n_sites, 1), dtype=np.uint8)
+    rc = HO.ntsm_host_ld_prune(n_sites, pairs.ctypes.data, len(pairs), min_called, r2_min, kept.ctypes.data)
+    if rc:
+        raise RuntimeError("ntsm_host_ld_prune failed: %d" % rc)
+    return kept[:n_sites].astype(bool)
+
+
+def ld_bands(row_pairs, budget=(1 << 30) // 40):
+    """The band walk of --ld over a model device that selects row_pairs[a] pairs in row a: ([(first, rows, return), ...] of
+    every call, (bands, re-runs, pairs))."""
+    from .capi import HO
+    rp = np.ascontiguousarray(row_pairs, dtype=np.uint64)
+    room = 4 * len(rp) + 64
+    calls = np.zeros((room, 3), dtype=np.uint32)
+    stats = (C.c_uint64 * 3)()
+    n = HO.ntsm_host_ld_bands(rp.ctypes.data_as(C.POINTER(C.c_uint64)), len(rp), budget, calls.ctypes.data_as(C.POINTER(C.c_uint32)), room, stats)
+    if n < 0 or n > room:
+        raise RuntimeError("ntsm_host_ld_bands failed: %d" % n)
+    return [tuple(int(v) for v in c) for c in calls[:n]], tuple(stats)

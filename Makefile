@@ -113,7 +113,7 @@ ntsm_amd/libntsm_eval_hip.so: $(EVALSRC) $(CSRC)/ntsm_eval_geno.h $(HOST)/eval_l
                               $(HOST)/eval_within.hpp $(HOST)/eval_between.hpp $(HOST)/eval_store.hpp include/ntsm_eval_hip.h
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -shared -o $@ $(EVALSRC)
 
-build/ntsmEval: $(HOST)/ntsm_eval_main.cpp $(HOST)/cli.hpp $(HOST)/eval_store.hpp $(HOST)/eval_index.hpp $(HOST)/eval_qc.hpp $(HOST)/eval_contam.hpp $(HOST)/eval_trio.hpp $(HOST)/eval_ld.hpp $(HOST)/eval_within.hpp $(HOST)/eval_between.hpp $(HOST)/crc32_fast.cpp $(HOST)/crc32_fast.hpp \
+build/ntsmEval: $(HOST)/ntsm_eval_main.cpp $(HOST)/eval_cli_args.hpp $(HOST)/eval_cli_rows.hpp $(HOST)/cli.hpp $(HOST)/eval_store.hpp $(HOST)/eval_index.hpp $(HOST)/eval_qc.hpp $(HOST)/eval_contam.hpp $(HOST)/eval_trio.hpp $(HOST)/eval_ld.hpp $(HOST)/eval_within.hpp $(HOST)/eval_between.hpp $(HOST)/crc32_fast.cpp $(HOST)/crc32_fast.hpp \
                 $(HOST)/gz_stream.hpp $(CSRC)/xprec.h include/ntsm_eval_hip.h ntsm_amd/libntsm_eval_hip.so
 	@mkdir -p build
 	$(CXX) $(CXXFLAGS) -ffp-contract=off -o $@ $(HOST)/ntsm_eval_main.cpp $(HOST)/crc32_fast.cpp -Lntsm_amd -lntsm_eval_hip -lz \

@@ -60,7 +60,40 @@ def _ld_ptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_longdouble))
 
 
-class Session:
+class _Handle:
+    """A library session: `h` is its handle, `close=` in the class statement the name of the library function that frees it
+    (a subclass of a session class that gives none keeps its parent's).  A context manager; closing twice, or what was never
+    opened, does nothing."""
+    h = None
+
+    def __init_subclass__(cls, close=None, **kwargs):
+        super().__init_subclass__(**kwargs)
+        if close:
+            cls._close = close
+
+    def close(self):
+        if self.h:
+            getattr(lib, self._close)(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+
+def _tune(name, *args):
+    """The library's tuning call `name` with args; a value it does not take is a ValueError"""
+    rc = getattr(lib, name)(*args)
+    if rc:
+        raise ValueError("%s(%s) failed: %d" % (name, ", ".join("%r" % (a,) for a in args), rc))
+
+
+class Session(_Handle, close="ntsm_eval_close"):
     """One run's counts on the device (ntsm_eval_open): uint32 [n_samples][n_sites][2], uploaded once."""
 
     def __init__(self, counts, min_cov=1, device=0):
@@ -118,14 +151,6 @@ class Session:
         if rc:
             raise RuntimeError("ntsm_eval_score_pairs failed: %d" % rc)
         return out, ms.value
-
-    def close(self):
-        if self.h:
-            lib.ntsm_eval_close(self.h)
-            self.h = None
-
-    def __del__(self):
-        self.close()
 
 
 def project(counts, norm, rot, min_cov=1, device=0):
@@ -315,12 +340,10 @@ lib.ntsm_eval_store_score_pairs.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c
 
 def within_tune(width):
     """Force the workgroup width (64 or 256) of later Within.rows calls in this process; 0 = the library's rule."""
-    rc = lib.ntsm_eval_within_tune(width)
-    if rc:
-        raise ValueError("ntsm_eval_within_tune(%r) failed: %d" % (width, rc))
+    _tune("ntsm_eval_within_tune", width)
 
 
-class Within:
+class Within(_Handle, close="ntsm_eval_within_close"):
     """The pairs of a store's samples with each other (ntsm_eval_within_open): db is uint32 [n_db][n_sites][2] or Records,
     which the session keeps alive.  db_chunk: 0 = resident if the store fits the device, else streamed; a value below n_db
     streams the columns in chunks of it.  A context manager: `with Within(db) as w: rec, geno, times = w.rows(0, w.n)`."""
@@ -346,20 +369,6 @@ class Within:
         if rc:
             raise RuntimeError("ntsm_eval_within_rows failed: %d" % rc)
         return out, geno, times
-
-    def close(self):
-        if self.h:
-            lib.ntsm_eval_within_close(self.h)
-            self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        self.close()
 
 
 def store_score_pairs(db, pi, pk, min_cov=1, db_chunk=0, device=0):
@@ -393,12 +402,10 @@ lib.ntsm_eval_between_tune.argtypes = [C.c_uint32]
 
 def between_tune(width):
     """Force the workgroup width (64 or 256) of later Between.rows calls in this process; 0 = the library's rule."""
-    rc = lib.ntsm_eval_between_tune(width)
-    if rc:
-        raise ValueError("ntsm_eval_between_tune(%r) failed: %d" % (width, rc))
+    _tune("ntsm_eval_between_tune", width)
 
 
-class Between:
+class Between(_Handle, close="ntsm_eval_between_close"):
     """The samples of store A against those of store B (ntsm_eval_between_open): a and b are uint32 [n][n_sites][2] or Records,
     which the session keeps alive.  site_map: uint32 [n_sites_a], the index among B's sites of each site of A, LACKS where B
     has none; None = identical tables.  b_chunk: 0 = B resident if it fits the device, else streamed; a value below n_b
@@ -427,20 +434,6 @@ class Between:
         if rc:
             raise RuntimeError("ntsm_eval_between_rows failed: %d" % rc)
         return out, a_geno, b_geno, times
-
-    def close(self):
-        if self.h:
-            lib.ntsm_eval_between_close(self.h)
-            self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        self.close()
 
 
 # ---- the PCA-guided search between two stores (ntsmEval --between-near; ntsm_eval_project_store_mapped, ntsm_eval_between_candidates,
@@ -585,12 +578,10 @@ lib.ntsm_eval_contam_tune.argtypes = [C.c_uint32, C.c_uint32]
 def contam_tune(width, target_group):
     """Force the workgroup width (64 or 256) and target group (1, 2 or 4) of later Contam.rows calls in this process; 0 = the
     library's rule."""
-    rc = lib.ntsm_eval_contam_tune(width, target_group)
-    if rc:
-        raise ValueError("ntsm_eval_contam_tune(%r, %r) failed: %d" % (width, target_group, rc))
+    _tune("ntsm_eval_contam_tune", width, target_group)
 
 
-class Contam:
+class Contam(_Handle, close="ntsm_eval_contam_close"):
     """Every sample of a store as a target against every sample as a source (ntsm_eval_contam_open): db is uint32
     [n_db][n_sites][2] or Records, which the session keeps alive.  db_chunk: 0 = resident if the store fits the device, else
     streamed; a value below n_db streams the columns in chunks of it.  A context manager:
@@ -616,20 +607,6 @@ class Contam:
         if rc:
             raise RuntimeError("ntsm_eval_contam_rows failed: %d" % rc)
         return out, t, times
-
-    def close(self):
-        if self.h:
-            lib.ntsm_eval_contam_close(self.h)
-            self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        self.close()
 
 
 def _names(names):
@@ -693,12 +670,10 @@ lib.ntsm_eval_trio_tune.argtypes = [C.c_uint32]
 
 def trio_tune(width):
     """Force the workgroup width (64 or 256) of later Trio.duos and Trio.score calls in this process; 0 = the library's rule."""
-    rc = lib.ntsm_eval_trio_tune(width)
-    if rc:
-        raise ValueError("ntsm_eval_trio_tune(%r) failed: %d" % (width, rc))
+    _tune("ntsm_eval_trio_tune", width)
 
 
-class Trio:
+class Trio(_Handle, close="ntsm_eval_trio_close"):
     """The genotype bit-planes of a store on the device (ntsm_eval_trio_open): db is uint32 [n_db][n_sites][2] or Records, read
     once, here.  geno: uint32 [n_db, 4] = homAT, het, homCG, miss, or None when switched off (passed as NULL); times: the
     CrossTimes of open.  A context manager: `with Trio(db) as s: duo, ms = s.duos(0, s.n)`."""
@@ -737,20 +712,6 @@ class Trio:
         if rc:
             raise RuntimeError("ntsm_eval_trio_score failed: %d" % rc)
         return out, ms.value
-
-    def close(self):
-        if self.h:
-            lib.ntsm_eval_trio_close(self.h)
-            self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        self.close()
 
 
 def _u32(a):
@@ -835,12 +796,10 @@ lib.ntsm_eval_ld_tune.argtypes = [C.c_uint32, C.c_uint32]
 def ld_tune(block_rows, block_cols):
     """Force the register block (2 x 2, 4 x 2 or 2 x 4 pairs per lane) of later Ld.rows and Ld.select calls in this process;
     (0, 0) = the library's rule."""
-    rc = lib.ntsm_eval_ld_tune(block_rows, block_cols)
-    if rc:
-        raise ValueError("ntsm_eval_ld_tune(%r, %r) failed: %d" % (block_rows, block_cols, rc))
+    _tune("ntsm_eval_ld_tune", block_rows, block_cols)
 
 
-class Ld:
+class Ld(_Handle, close="ntsm_eval_ld_close"):
     """The genotype bit-planes of a store on the device, samples along the bits (ntsm_eval_ld_open): db is uint32
     [n_db][n_sites][2] or Records, read once, here.  site_geno: uint32 [n_sites, 4] = het, homCG, called, homAT, or None when
     switched off (passed as NULL); times: the CrossTimes of open.  A context manager: `with Ld(db) as s: rec, ms = s.rows(0, s.m)`."""
@@ -877,20 +836,6 @@ class Ld:
         if rc not in (0, 1):
             raise RuntimeError("ntsm_eval_ld_select failed: %d" % rc)
         return rc, out[:0 if rc else found.value].copy(), found.value, ms.value
-
-    def close(self):
-        if self.h:
-            lib.ntsm_eval_ld_close(self.h)
-            self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        self.close()
 
 
 def ld_r2(rec, min_called=20):

@@ -49,7 +49,7 @@ using ntsm_eval_chunk::valid_store;
 using ntsm_eval_chunk::wall;
 constexpr int kTI = 4;                       /* rows of A per workgroup, as in ntsm_eval.hip */
 constexpr uint32_t kLacks = ntsm::eval_between::kLacks;
-constexpr uint32_t kMaxGridY = 65535;
+using ntsm_eval_chunk::kMaxGridY;
 
 uint32_t g_width = 0;                        /* ntsm_eval_between_tune */
 
@@ -83,11 +83,11 @@ __global__ __launch_bounds__(kThreads) void ntsm_eval_between_kernel(const uint3
  * prepare_kernel with the read side gathered.  Lanes run along A's sites of one sample, so the reads are coalesced wherever
  * the map is locally monotone; the writes run along the samples of one site and are always coalesced. */
 __global__ __launch_bounds__(kThreads) void ntsm_eval_between_prepare_kernel(const uint2 *__restrict__ counts, const uint32_t *__restrict__ site_map,
-		uint32_t n_samples, uint32_t n_sites_a, uint32_t n_sites_b, uint32_t min_cov, uint32_t *__restrict__ at, uint32_t *__restrict__ cg,
+		uint32_t n_samples, uint32_t n_sites_a, uint32_t n_sites_b, uint32_t min_cov, uint32_t s_first, uint32_t *__restrict__ at, uint32_t *__restrict__ cg,
 		double *__restrict__ term)
 {
 	__shared__ uint2 tile[kTile][kTile + 1];
-	const uint32_t m0 = blockIdx.x * kTile, s0 = blockIdx.y * kTile;
+	const uint32_t m0 = blockIdx.x * kTile, s0 = s_first + blockIdx.y * kTile;
 	const uint32_t lo = threadIdx.x % kTile, hi = threadIdx.x / kTile;
 	const uint32_t from = m0 + lo < n_sites_a ? site_map[m0 + lo] : kLacks;      /* this lane's site of B in the first phase */
 	for (uint32_t r = hi; r < (uint32_t) kTile; r += kThreads / kTile) {
@@ -179,8 +179,10 @@ struct ntsm_eval_between_session {
 			if (row_bytes) HIPCHK(hipMemcpy2D(to.raw, row_bytes, b + (uint64_t) first * b_stride, b_stride, row_bytes, count, hipMemcpyHostToDevice));
 			tm.upload_ms += ms_since(t);
 			return ntsm_eval_chunk::timed(hold.ev[0], hold.ev[1], &tm.prepare_kernel_ms, [&] {
-				hipLaunchKernelGGL(ntsm_eval_between_prepare_kernel, dim3((n_sites_a + kTile - 1) / kTile, (count + kTile - 1) / kTile), dim3(kThreads), 0, 0,
-						(const uint2 *) to.raw, d_map, count, n_sites_a, n_sites_b, min_cov, to.at, to.cg, to.term);
+				ntsm_eval_chunk::for_grid_y_slices(((uint64_t) count + kTile - 1) / kTile, [&](uint64_t tile, uint32_t tiles) {
+					hipLaunchKernelGGL(ntsm_eval_between_prepare_kernel, dim3((n_sites_a + kTile - 1) / kTile, tiles), dim3(kThreads), 0, 0, (const uint2 *) to.raw, d_map,
+							count, n_sites_a, n_sites_b, min_cov, (uint32_t) (tile * kTile), to.at, to.cg, to.term);
+				});
 				HIPCHK(hipGetLastError());
 				if (tallies) {
 					hipLaunchKernelGGL(ntsm_eval_between_tally_kernel, dim3(count), dim3(kThreads), 0, 0, (const uint2 *) to.raw, d_map, n_sites_a, n_sites_b, min_cov,

@@ -27,13 +27,14 @@ namespace ntsm_eval_chunk {
 
 constexpr int kThreads = 256;
 constexpr int kTile = 64;                    /* the transpose moves 64 samples x 64 sites per workgroup */
+constexpr uint32_t kMaxGridY = 65535;        /* a grid's second dimension ends here (hipDeviceAttributeMaxGridDimY) */
 
-/* counts [sample][site][2] (dense) -> at / cg / term [site][sample] */
+/* counts [sample][site][2] (dense) -> at / cg / term [site][sample]; grid (tiles of sites, tiles of samples from sample s_first on) */
 static __global__ __launch_bounds__(kThreads) void prepare_kernel(const uint2 *__restrict__ counts, uint32_t n_samples, uint32_t n_sites,
-		uint32_t min_cov, uint32_t *__restrict__ at, uint32_t *__restrict__ cg, double *__restrict__ term)
+		uint32_t min_cov, uint32_t s_first, uint32_t *__restrict__ at, uint32_t *__restrict__ cg, double *__restrict__ term)
 {
 	__shared__ uint2 tile[kTile][kTile + 1];
-	const uint32_t m0 = blockIdx.x * kTile, s0 = blockIdx.y * kTile;
+	const uint32_t m0 = blockIdx.x * kTile, s0 = s_first + blockIdx.y * kTile;
 	const uint32_t lo = threadIdx.x % kTile, hi = threadIdx.x / kTile;              /* hi: 0 ... 3 */
 	for (uint32_t r = hi; r < (uint32_t) kTile; r += kThreads / kTile) {             /* lanes along the sites of one sample */
 		const uint32_t s = s0 + r, site = m0 + lo;
@@ -74,11 +75,20 @@ static __global__ __launch_bounds__(kThreads) void tally_kernel(const uint2 *__r
 	if (threadIdx.x < 3) geno[(uint64_t) blockIdx.x * 3 + threadIdx.x] = sum[threadIdx.x];
 }
 
+/* A launch whose grid.y grows with a caller's count goes out in slices of at most kMaxGridY: each(first, count)
+ * starts the launch of groups first ... first + count - 1 of n_groups. */
+template <typename Each> inline void for_grid_y_slices(uint64_t n_groups, Each &&each)
+{
+	for (uint64_t g = 0; g < n_groups; g += kMaxGridY) each(g, (uint32_t) std::min<uint64_t>(kMaxGridY, n_groups - g));
+}
+
 /* the launches; the caller checks hipGetLastError */
 inline void launch_prepare(const uint32_t *counts, uint32_t n_samples, uint32_t n_sites, uint32_t min_cov, uint32_t *at, uint32_t *cg, double *term)
 {
-	hipLaunchKernelGGL(prepare_kernel, dim3((n_sites + kTile - 1) / kTile, (n_samples + kTile - 1) / kTile), dim3(kThreads), 0, 0,
-			(const uint2 *) counts, n_samples, n_sites, min_cov, at, cg, term);
+	for_grid_y_slices(((uint64_t) n_samples + kTile - 1) / kTile, [&](uint64_t tile, uint32_t tiles) {
+		hipLaunchKernelGGL(prepare_kernel, dim3((n_sites + kTile - 1) / kTile, tiles), dim3(kThreads), 0, 0, (const uint2 *) counts, n_samples, n_sites, min_cov,
+				(uint32_t) (tile * kTile), at, cg, term);
+	});
 }
 
 inline void launch_tally(const uint32_t *counts, uint32_t n_samples, uint32_t n_sites, uint32_t min_cov, uint32_t *geno)

@@ -43,10 +43,10 @@ uint32_t g_width = 0, g_target_group = 0;    /* ntsm_eval_contam_tune */
 
 /* counts [sample][site][2] (dense) -> at / cg [site][sample]: ntsm_eval_chunk::prepare_kernel without the term plane */
 __global__ __launch_bounds__(kThreads) void ntsm_eval_contam_transpose_kernel(const uint2 *__restrict__ counts, uint32_t n_samples, uint32_t n_sites,
-		uint32_t *__restrict__ at, uint32_t *__restrict__ cg)
+		uint32_t s_first, uint32_t *__restrict__ at, uint32_t *__restrict__ cg)
 {
 	__shared__ uint2 tile[kTile][kTile + 1];
-	const uint32_t m0 = blockIdx.x * kTile, s0 = blockIdx.y * kTile;
+	const uint32_t m0 = blockIdx.x * kTile, s0 = s_first + blockIdx.y * kTile;
 	const uint32_t lo = threadIdx.x % kTile, hi = threadIdx.x / kTile;              /* hi: 0 ... 3 */
 	for (uint32_t r = hi; r < (uint32_t) kTile; r += kThreads / kTile) {             /* lanes along the sites of one sample */
 		const uint32_t s = s0 + r, site = m0 + lo;
@@ -179,8 +179,10 @@ struct ntsm_eval_contam_session {
 			const int rc = ntsm_eval_chunk::upload(db, stride, first, count, n_sites, to.raw, tm);
 			if (rc) return rc;
 			return ntsm_eval_chunk::timed(hold.ev[0], hold.ev[1], &tm.prepare_kernel_ms, [&] {
-				hipLaunchKernelGGL(ntsm_eval_contam_transpose_kernel, dim3((n_sites + kTile - 1) / kTile, (count + kTile - 1) / kTile), dim3(kThreads), 0, 0,
-						(const uint2 *) to.raw, count, n_sites, to.at, to.cg);
+				ntsm_eval_chunk::for_grid_y_slices(((uint64_t) count + kTile - 1) / kTile, [&](uint64_t tile, uint32_t tiles) {
+					hipLaunchKernelGGL(ntsm_eval_contam_transpose_kernel, dim3((n_sites + kTile - 1) / kTile, tiles), dim3(kThreads), 0, 0, (const uint2 *) to.raw, count,
+							n_sites, (uint32_t) (tile * kTile), to.at, to.cg);
+				});
 				HIPCHK(hipGetLastError());
 				if (tallies) {
 					hipLaunchKernelGGL(ntsm_eval_contam_tally_kernel, dim3(count), dim3(kThreads), 0, 0, (const uint2 *) to.raw, n_sites, min_depth,

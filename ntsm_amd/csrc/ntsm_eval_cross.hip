@@ -35,13 +35,13 @@ using ntsm_eval_chunk::kThreads;
 
 uint32_t g_width = 0, g_query_group = 0;     /* ntsm_eval_cross_tune */
 
-/* grid (chunk samples / blockDim.x, queries / TQ); out [n_q][out_pitch], the chunk's sample d at column d */
+/* grid (chunk samples / blockDim.x, groups of TQ queries from query q_first on); out [n_q][out_pitch], the chunk's sample d at column d */
 template <int TQ> __global__ __launch_bounds__(kThreads) void ntsm_eval_cross_kernel(const uint32_t *__restrict__ qat, const uint32_t *__restrict__ qcg,
-		const double *__restrict__ qterm, uint32_t n_q, const uint32_t *__restrict__ at, const uint32_t *__restrict__ cg,
+		const double *__restrict__ qterm, uint32_t n_q, uint32_t q_first, const uint32_t *__restrict__ at, const uint32_t *__restrict__ cg,
 		const double *__restrict__ term, uint32_t n_d, uint32_t n_sites, uint32_t min_cov, ntsm_eval_record *__restrict__ out, uint32_t out_pitch)
 {
 	const uint32_t d = blockIdx.x * blockDim.x + threadIdx.x;
-	const uint32_t q0 = blockIdx.y * TQ;
+	const uint32_t q0 = q_first + blockIdx.y * TQ;
 	const uint32_t dc = d < n_d ? d : n_d - 1;                                   /* lanes past the end compute a copy of the last sample, not stored */
 	uint32_t q[TQ];
 #pragma unroll
@@ -124,9 +124,11 @@ extern "C" int ntsm_eval_cross(int device, const uint32_t *q_counts, uint32_t n_
 		 * 256 threads are reachable through ntsm_eval_cross_tune only */
 		uint32_t width, tq;
 		ntsm_eval_chunk::launch_shape(n_q, cn, g_width, g_query_group, width, tq);
-		const dim3 grid((cn + width - 1) / width, (n_q + tq - 1) / tq);
 		auto kernel = tq == 4 ? ntsm_eval_cross_kernel<4> : tq == 2 ? ntsm_eval_cross_kernel<2> : ntsm_eval_cross_kernel<1>;
-		hipLaunchKernelGGL(kernel, grid, dim3(width), 0, 0, d_qat, d_qcg, d_qterm, n_q, d_at, d_cg, d_term, cn, n_sites, min_cov, d_out, chunk);
+		ntsm_eval_chunk::for_grid_y_slices(((uint64_t) n_q + tq - 1) / tq, [&](uint64_t group, uint32_t groups) {   /* one launch up to 65,535 query groups */
+			hipLaunchKernelGGL(kernel, dim3((cn + width - 1) / width, groups), dim3(width), 0, 0, d_qat, d_qcg, d_qterm, n_q, (uint32_t) (group * tq), d_at, d_cg, d_term,
+					cn, n_sites, min_cov, d_out, chunk);
+		});
 		HIPCHK(hipGetLastError());
 		HIPCHK(hipEventRecord(ev[2], 0));
 		HIPCHK(hipEventSynchronize(ev[2]));
